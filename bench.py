@@ -8,8 +8,17 @@ A "step" is one pass of the whole hot path (H2D of the reads -> seed search -> l
 SW + edit verify -> hit gather -> D2H of the hits) over one batch of synthetic reads handed over in
 host memory, as SURVEY.md 8(d) defines the metric; the index is resident in HBM, replicated per GPU,
 and reads shard across ranks with no collective on the data path (weak scaling: every rank processes
-its own batch of the same size).  The device-resident rate of the same kernels is reported beside it
-(`device_resident`).  Rank 0 prints ONE JSON line.
+its own batch of the same size).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything beside the headline runs
+with --full only: the device-resident rate of the same kernels (`device_resident`), the other verification
+order, reads in pageable memory, the per-stage kernel times and the roofline, and the CPU oracle's rate and
+parity on a sample of the reads (in --mode chunks: the oracle and the mtsv-collapse leg).
+
+--dump-outputs DIR writes the hits of the last timed step (what the caller of the step receives) as
+DIR/*.npy in float64: every field of the hits of a fixed, seeded sample of the reads, their hit counts and
+the total number of hits.  The inputs are a pure function of the arguments, so two builds can be compared
+file by file.
 
 Default workload = the configuration BASELINE.json's metric is quoted on: config2.
 Workloads (BASELINE.json configs; generators of SURVEY.md 8(d), seeds fixed):
@@ -37,6 +46,68 @@ WORKLOADS = {
 }
 SEED_DB = 0x6D747376
 PEAK_HBM_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+HIT_FIELDS = ("read", "tax_id", "gi", "edit", "strand", "offset")
+DUMP_SEED = 0x64756D70
+DUMP_SAMPLE_READS = 1 << 19
+DUMP_BUDGET_BYTES = 60 << 20  # all files of --dump-outputs together (under 64 MB)
+
+
+def hip_check(rc, what):
+    if rc != 0:
+        raise SystemExit(f"bench: {what} failed (HIP error {rc})")
+
+
+def hip_sync(device):
+    """hipDeviceSynchronize on `device`, through the HIP runtime libmtsv_amd.so is linked against (a one-GPU run
+    does not import torch)"""
+    import mtsv_tools_amd as M
+    hip_check(M.lib().hipSetDevice(device), "hipSetDevice")
+    hip_check(M.lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+
+
+def gpu_pci_bus_id(device):
+    import ctypes
+
+    import mtsv_tools_amd as M
+    buf = ctypes.create_string_buffer(64)
+    hip_check(M.lib().hipDeviceGetPCIBusId(buf, len(buf), device), "hipDeviceGetPCIBusId")
+    return buf.value.decode().lower()
+
+
+def copy_hits(out_p, n):
+    """the hit array the caller of a step receives, copied out of the library's buffer (which the caller still frees)"""
+    import ctypes
+
+    import mtsv_tools_amd as M
+    if n == 0:
+        return np.zeros(0, dtype=M.HIT_DTYPE)
+    raw = (ctypes.c_ubyte * (n * M.HIT_DTYPE.itemsize)).from_address(out_p.value)
+    return np.frombuffer(raw, dtype=M.HIT_DTYPE).copy()
+
+
+def dump_outputs(dirname, hits, n_reads):
+    """--dump-outputs: the hits of a fixed, seeded sample of the reads (all of them when they fit), field by field,
+    in float64 (every value is an integer below 2^53); returns {file name: bytes}"""
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    sample = np.sort(rng.choice(n_reads, size=min(n_reads, DUMP_SAMPLE_READS), replace=False))
+    read = hits["read"].astype(np.int64)
+    per_read = np.bincount(read, minlength=n_reads)[sample]
+    # whole reads only: keep the sampled reads (in read order) whose hits fit in the budget
+    fit = (DUMP_BUDGET_BYTES - 8 * 2 * len(sample) - 4096) // (8 * len(HIT_FIELDS))
+    keep = int(np.searchsorted(np.cumsum(per_read), fit, side="right"))
+    sample, per_read = sample[:keep], per_read[:keep]
+    in_sample = np.zeros(n_reads, dtype=bool)
+    in_sample[sample] = True
+    sel = hits[in_sample[read]]
+    files = {"sample_reads": sample, "sample_hits_per_read": per_read, "n_hits": np.array([len(hits)])}
+    files.update({f"hits_{f}": sel[f] for f in HIT_FIELDS})
+    written = {}
+    for name, a in files.items():
+        path = os.path.join(dirname, name + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        written[name + ".npy"] = os.path.getsize(path)
+    return written
 
 
 def algorithmic_bytes(ctr, n_reads):
@@ -103,29 +174,35 @@ def main_chunks(args):
     import ctypes
     import subprocess
 
-    import torch
-    import torch.distributed as dist
-
     import mtsv_tools_amd as M
     from mtsv_tools_amd import _lib as L
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if not torch.cuda.is_available() or M.device_count() < 1:
+    if M.device_count() < 1:
         sys.exit("bench.py needs a HIP device: libmtsv_amd has no CPU path")
     shared_gpu = os.environ.get("MTSV_BENCH_SHARE_GPU") == "1"
     if shared_gpu:
         local_rank = 0
-    torch.cuda.set_device(local_rank)
     if world > 1:
+        import torch
+        import torch.distributed as dist
+
+        if not torch.cuda.is_available():
+            sys.exit("bench.py needs a HIP device: libmtsv_amd has no CPU path")
+        torch.cuda.set_device(local_rank)
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo" if shared_gpu else "nccl", **({} if shared_gpu else {"device_id": torch.device("cuda", local_rank)}))
+    else:
+        hip_check(M.lib().hipSetDevice(local_rank), "hipSetDevice")
 
     def barrier():
         if world > 1:
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
+        else:
+            hip_sync(local_rank)
 
     n_taxa, gis, seq_len, n_reads, read_len = CHUNK_SPEC
     if args.reads:
@@ -174,7 +251,17 @@ def main_chunks(args):
     pinned = M.HostBuffer(len(bases))
     pinned.array[:] = bases
     bases_p, off_p = pinned.array.ctypes.data, off.ctypes.data
-    HIT_FIELDS = ("read", "tax_id", "gi", "edit", "strand", "offset")
+    untimed = [0.0]  # seconds spent copying the kept hits out inside a timed step
+
+    def finish(out_p, out_n, keep):
+        """free the step's hits; with keep, first copy them out (untimed: the caller receives the hits in place)"""
+        hits = None
+        if keep:
+            t_k = time.perf_counter()
+            hits = copy_hits(out_p, out_n.value)
+            untimed[0] += time.perf_counter() - t_k
+        M.lib().mtsv_hits_free(out_p)
+        return hits
 
     if world == 1:
         handles = (ctypes.c_void_p * n_chunks)(*[chunks[c].h for c in range(n_chunks)])
@@ -184,9 +271,7 @@ def main_chunks(args):
             out_p, out_n = ctypes.c_void_p(), ctypes.c_uint64()
             L._check(M.lib().mtsv_bin_batch_chunks(handles, devs, n_chunks, bases_p, off_p, n_reads, ctypes.byref(params),
                                                    ctypes.byref(out_p), ctypes.byref(out_n)))
-            if keep:
-                return L._hits_from(out_p, out_n.value)
-            M.lib().mtsv_hits_free(out_p)
+            return finish(out_p, out_n, keep)
     else:
         slice_reads = M.bin_batch_slice_reads(n_reads)
         hb = M.Batch(chunks[rank], local_rank, min(n_reads, slice_reads), min(len(bases), slice_reads * (read_len + 8)))
@@ -195,65 +280,70 @@ def main_chunks(args):
             L._check(M.lib().mtsv_batch_run_host(hb.h, bases_p, off_p, n_reads, ctypes.byref(params)))
             out_p, out_n = ctypes.c_void_p(), ctypes.c_uint64()
             L._check(M.lib().mtsv_batch_download(hb.h, ctypes.byref(out_p), ctypes.byref(out_n)))
-            if keep:
-                return L._hits_from(out_p, out_n.value)
-            M.lib().mtsv_hits_free(out_p)
+            return finish(out_p, out_n, keep)
 
+    keep_last = args.full or args.dump_outputs is not None
     for _ in range(args.warmup):
         step()
     barrier()
     t0 = time.perf_counter()
     each_ms = []
-    for _ in range(args.steps):
+    hits = None
+    for i in range(args.steps):
         t_s = time.perf_counter()
-        step()
-        each_ms.append(round((time.perf_counter() - t_s) * 1e3, 2))
+        u0 = untimed[0]
+        out = step(keep=keep_last and i == args.steps - 1)
+        each_ms.append(round((time.perf_counter() - t_s - (untimed[0] - u0)) * 1e3, 2))
+        if out is not None:
+            hits = out  # the last timed step's: what the dump, the checks and the collapse leg look at
     barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - untimed[0]
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if shared_gpu else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    hits = step(keep=True)  # untimed: what the checks and the collapse leg look at
+    dumped = dump_outputs(args.dump_outputs, hits, n_reads) if args.dump_outputs and rank == 0 else None
 
-    # ---- parity on a sample of the reads (every (n/ns)-th read, so that every chunk's reads are in it) ----
-    ns = min(args.cpu_sample // 4, n_reads)
-    idx = (np.arange(ns, dtype=np.int64) * (n_reads // ns))
-    sample = bases.reshape(n_reads, read_len)[idx].reshape(-1)
-    soff = (np.arange(ns + 1, dtype=np.uint64) * read_len)
-    remap = np.full(n_reads, -1, dtype=np.int64)
-    remap[idx] = np.arange(ns)
-    mine_sample = hits[remap[hits["read"].astype(np.int64)] >= 0].copy()
-    mine_sample["read"] = remap[mine_sample["read"].astype(np.int64)]
-    parity, cpu, collapse = "not checked", None, None
-    gathered = [mine_sample]
-    if world > 1:
-        gathered = [None] * world if rank == 0 else None
-        dist.gather_object(mine_sample, gathered, dst=0)
-        # the reference's workflow: a results file per chunk, merged by mtsv-collapse
-        ids = [f"r{i}" for i in range(n_reads)] if n_reads <= 2_000_000 else None
-        if ids is not None:
-            res = f"/tmp/mtsv_bench_config5_results_{rank}.txt"
-            open(res, "w").write(M.format_results(hits, ids, False))
-            dist.barrier()
-            if rank == 0:
-                t0 = time.perf_counter()
-                subprocess.check_call([os.path.join(ROOT, "mtsv_tools_amd", "bin", "mtsv-collapse"), "-o", "/tmp/mtsv_bench_config5_collapsed.txt"]
-                                      + [f"/tmp/mtsv_bench_config5_results_{r}.txt" for r in range(world)])
-                collapse = {"collapse_s": time.perf_counter() - t0, "files": world,
-                            "lines": sum(1 for _ in open("/tmp/mtsv_bench_config5_collapsed.txt"))}
-    if rank == 0 and not args.no_cpu_baseline:
-        from oracle import oracle as O
-        got = merge_by_read(gathered) if world > 1 else mine_sample
-        cores = max(1, min(ncpu, args.cpu_threads or 16))
-        t0 = time.perf_counter()
-        per = [O.Index.read(paths[c]).bin_batch(sample, soff, O.default_params(), threads=cores)[0] for c in range(n_chunks)]
-        dt = time.perf_counter() - t0
-        want = merge_by_read(per)
-        same = len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in HIT_FIELDS)
-        parity = f"{'identical' if same else 'MISMATCH'} on {ns} sampled reads x {n_chunks} chunks ({len(want)} merged hits)"
-        cpu = {"value": ns / dt, "unit": "reads/s", "cores": cores, "kind": "port", "host": host_description(),
-               "sample": f"{ns} reads (every {n_reads // ns}-th) against all {n_chunks} chunks one after the other, oracle/libmtsv_oracle.so, {cores} OpenMP threads, {dt:.1f} s"}
+    parity, cpu, collapse = "not checked (--full)", None, None
+    if args.full:
+        # ---- parity on a sample of the reads (every (n/ns)-th read, so that every chunk's reads are in it) ----
+        ns = min(args.cpu_sample // 4, n_reads)
+        idx = (np.arange(ns, dtype=np.int64) * (n_reads // ns))
+        sample = bases.reshape(n_reads, read_len)[idx].reshape(-1)
+        soff = (np.arange(ns + 1, dtype=np.uint64) * read_len)
+        remap = np.full(n_reads, -1, dtype=np.int64)
+        remap[idx] = np.arange(ns)
+        mine_sample = hits[remap[hits["read"].astype(np.int64)] >= 0].copy()
+        mine_sample["read"] = remap[mine_sample["read"].astype(np.int64)]
+        parity = "not checked"
+        gathered = [mine_sample]
+        if world > 1:
+            gathered = [None] * world if rank == 0 else None
+            dist.gather_object(mine_sample, gathered, dst=0)
+            # the reference's workflow: a results file per chunk, merged by mtsv-collapse
+            ids = [f"r{i}" for i in range(n_reads)] if n_reads <= 2_000_000 else None
+            if ids is not None:
+                res = f"/tmp/mtsv_bench_config5_results_{rank}.txt"
+                open(res, "w").write(M.format_results(hits, ids, False))
+                dist.barrier()
+                if rank == 0:
+                    t0 = time.perf_counter()
+                    subprocess.check_call([os.path.join(ROOT, "mtsv_tools_amd", "bin", "mtsv-collapse"), "-o", "/tmp/mtsv_bench_config5_collapsed.txt"]
+                                          + [f"/tmp/mtsv_bench_config5_results_{r}.txt" for r in range(world)])
+                    collapse = {"collapse_s": time.perf_counter() - t0, "files": world,
+                                "lines": sum(1 for _ in open("/tmp/mtsv_bench_config5_collapsed.txt"))}
+        if rank == 0 and not args.no_cpu_baseline:
+            from oracle import oracle as O
+            got = merge_by_read(gathered) if world > 1 else mine_sample
+            cores = max(1, min(ncpu, args.cpu_threads or 16))
+            t0 = time.perf_counter()
+            per = [O.Index.read(paths[c]).bin_batch(sample, soff, O.default_params(), threads=cores)[0] for c in range(n_chunks)]
+            dt = time.perf_counter() - t0
+            want = merge_by_read(per)
+            same = len(got) == len(want) and all(np.array_equal(got[f], want[f]) for f in HIT_FIELDS)
+            parity = f"{'identical' if same else 'MISMATCH'} on {ns} sampled reads x {n_chunks} chunks ({len(want)} merged hits)"
+            cpu = {"value": ns / dt, "unit": "reads/s", "cores": cores, "kind": "port", "host": host_description(),
+                   "sample": f"{ns} reads (every {n_reads // ns}-th) against all {n_chunks} chunks one after the other, oracle/libmtsv_oracle.so, {cores} OpenMP threads, {dt:.1f} s"}
     if world > 1:
         dist.barrier()
     if rank == 0:
@@ -272,8 +362,9 @@ def main_chunks(args):
                           "mode": "chunks (SURVEY 8(e) Mode B)", "chunks": n_chunks, "reads_per_step": n_reads, "read_len": read_len,
                           "chunk_symbols": info["n"], "chunk_hbm_bytes": info["device_bytes"], "chunk_kmer_k": info.get("kmer_k"),
                           "parallelism": f"{n_chunks} database chunks x {world} GPU(s), reads broadcast, hits merged per read; no collective on the data path"},
-               "n_hits_merged": int(len(hits)) if world == 1 else None, "collapse": collapse,
-               "cpu_baseline": cpu, "parity": parity, "setup_s": {"chunk_build": t_build}}
+               "n_hits_merged": int(len(hits)) if world == 1 and hits is not None else None, "collapse": collapse,
+               "cpu_baseline": cpu, "parity": parity, "setup_s": {"chunk_build": t_build}, "full": args.full,
+               "dump_outputs": dumped}
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
@@ -303,7 +394,14 @@ def main():
                     help="reads (default): BASELINE configs 1-4, index replicated per GPU, reads sharded.  chunks: BASELINE config 5, "
                          "the database in chunks (one per GPU), every chunk sees every read, hits merged per read")
     ap.add_argument("--chunks", type=int, default=8, help="--mode chunks on one GPU: database chunks, all resident on that GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what lies beside the headline: device-resident rate, the other verification order, "
+                         "pageable input, per-stage kernel times, roofline, CPU oracle rate and parity (--mode chunks: oracle "
+                         "parity and the mtsv-collapse leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hits of the last timed step to DIR/*.npy (float64; a fixed, seeded sample of the reads)")
     args = ap.parse_args()
+    t_start = time.time()
     if args.mode == "chunks":
         return main_chunks(args)
 
@@ -315,37 +413,42 @@ def main():
             sys.exit("launch N>1 with: python -m torch.distributed.run --nnodes=1 --nproc-per-node N bench.py --gpus N")
         args.gpus = world
 
-    import torch
-    import torch.distributed as dist
-
     import mtsv_tools_amd as M
 
-    if not torch.cuda.is_available() or M.device_count() < 1:
+    if M.device_count() < 1:
         sys.exit("bench.py needs a HIP device: libmtsv_amd has no CPU path")
     # rehearsal knob: several ranks sharing one GPU (gloo; NCCL refuses duplicate devices) to exercise
     # the rank logic on a one-GPU box.  Never set by the driver.
     shared_gpu = os.environ.get("MTSV_BENCH_SHARE_GPU") == "1"
     if shared_gpu:
         local_rank = 0
-    torch.cuda.set_device(local_rank)
-    if world > 1:
+    if world > 1:  # torch only for the ranks' plumbing: a one-GPU run talks to the library alone
+        import torch
+        import torch.distributed as dist
+
+        if not torch.cuda.is_available():
+            sys.exit("bench.py needs a HIP device: libmtsv_amd has no CPU path")
+        torch.cuda.set_device(local_rank)
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if shared_gpu:
             dist.init_process_group("gloo")
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+    else:
+        hip_check(M.lib().hipSetDevice(local_rank), "hipSetDevice")
 
     def barrier():
         if world > 1:
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
+        else:
+            hip_sync(local_rank)
 
     # Host threads of a rank (uploaders, lanes, staging copies) stay on the NUMA node of their GPU: on a
     # two-socket node eight ranks staging 25 GB/s each should not cross the socket interconnect.  Best effort.
     affinity = None
     try:
-        pr = torch.cuda.get_device_properties(local_rank)
-        bdf = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
+        bdf = gpu_pci_bus_id(local_rank)
         node = int(open(f"/sys/bus/pci/devices/{bdf}/numa_node").read())
         if node >= 0 and os.environ.get("MTSV_BENCH_NO_AFFINITY") != "1":
             cpus = set()
@@ -356,7 +459,7 @@ def main():
             if cpus:
                 os.sched_setaffinity(0, cpus)
                 affinity = f"NUMA node {node} of GPU {bdf} ({len(cpus)} CPUs)"
-    except Exception:
+    except (Exception, SystemExit):
         pass
 
     # The library packs the reads to 4-bit codes on the host before they cross PCIe when the process has the CPUs for it
@@ -377,8 +480,13 @@ def main():
     build_threads = max(4, min(32, ncpu // max(1, world) if world > 1 else ncpu))
 
     # ---- index: rank 0 builds + writes the MG-index file, every rank loads it (drop-in format) ----
+    # A plain one-GPU run that finds no file keeps the index it built in memory instead: the same index, without
+    # writing and re-reading 10 GB (the file is what other ranks, the CPU oracle of --full and later runs read).
+    keep_built = world == 1 and not args.full and not args.resident_only
     t0 = time.time()
     index_cached = False
+    ixb = None
+    t_write = None
     if rank == 0:
         # the synthetic database is a pure function of (workload, SEED_DB): reuse a file left by an
         # earlier run on this box (the loader re-validates every invariant of the file anyway)
@@ -394,13 +502,17 @@ def main():
                 M.set_build_device(local_rank)
             ixb = M.MGIndex.synth(SEED_DB, n_taxa, gis, seq_len, threads=min(32, ncpu))
             M.set_build_device(-1)
-            ixb.write(idx_path + ".tmp")
-            ixb.close()
-            os.replace(idx_path + ".tmp", idx_path)
+            if not keep_built:
+                t_w = time.time()
+                ixb.write(idx_path + ".tmp")
+                ixb.close()
+                ixb = None
+                os.replace(idx_path + ".tmp", idx_path)
+                t_write = time.time() - t_w
     t_build = time.time() - t0
     barrier()
     t0 = time.time()
-    ix = M.MGIndex.load(idx_path)
+    ix = ixb if ixb is not None else M.MGIndex.load(idx_path)
     t_load = time.time() - t0
     t0 = time.time()
     ix.to_device(local_rank, args.dev_flags)
@@ -412,7 +524,6 @@ def main():
     from mtsv_tools_amd import _lib as L
     bases, off = M.synth_reads(ix, seed=1000 + rank, n_reads=n_reads, read_len=read_len)
     params = M.default_params()
-    HIT_FIELDS = ("read", "tax_id", "gi", "edit", "strand", "offset")
 
     def same_hits(a, b):
         return len(a) == len(b) and all(np.array_equal(a[f], b[f]) for f in HIT_FIELDS)
@@ -462,49 +573,111 @@ def main():
     bases_p, off_p = (pinned.array if pinned else bases).ctypes.data, off.ctypes.data
 
     split = [0.0, 0.0, 0.0]  # seconds inside mtsv_batch_run_host / mtsv_batch_download / mtsv_hits_free over the timed steps
+    untimed = [0.0]  # seconds spent copying the kept hits out inside a timed step
 
     def host_step(keep=False):
+        """one step; with keep, the hits the caller receives are copied out before they are freed (the copy untimed)"""
         t_a = time.perf_counter()
         L._check(M.lib().mtsv_batch_run_host(hb.h, bases_p, off_p, n_reads, ctypes.byref(params)))
         t_b = time.perf_counter()
         out_p, out_n = ctypes.c_void_p(), ctypes.c_uint64()
         L._check(M.lib().mtsv_batch_download(hb.h, ctypes.byref(out_p), ctypes.byref(out_n)))
         t_c = time.perf_counter()
+        hits = None
         if keep:
-            return L._hits_from(out_p, out_n.value)  # copies, then frees
+            hits = copy_hits(out_p, out_n.value)
+            untimed[0] += time.perf_counter() - t_c
+        t_f = time.perf_counter()
         M.lib().mtsv_hits_free(out_p)
         t_d = time.perf_counter()
         split[0] += t_b - t_a
         split[1] += t_c - t_b
-        split[2] += t_d - t_c
-        return None
+        split[2] += t_d - t_f
+        return hits
 
+    t_setup = time.time() - t_start
+    keep_last = args.full or args.dump_outputs is not None
     for _ in range(args.warmup):
         host_step()
     barrier()
     split[:] = [0.0, 0.0, 0.0]
+    untimed[0] = 0.0
     t0 = time.perf_counter()
     host_stage = None
     each_ms = []
-    for _ in range(args.steps):
+    hits = None
+    for i in range(args.steps):
         t_s = time.perf_counter()
-        host_step()
-        each_ms.append(round((time.perf_counter() - t_s) * 1e3, 2))
-        sth = hb.stats()
-        if host_stage is None:
-            host_stage = dict(sth["stage_ms"])
-        else:
-            for k, v in sth["stage_ms"].items():
-                host_stage[k] += v
+        u0 = untimed[0]
+        out = host_step(keep=keep_last and i == args.steps - 1)
+        each_ms.append(round((time.perf_counter() - t_s - (untimed[0] - u0)) * 1e3, 2))
+        if out is not None:
+            hits = out  # the last timed step's: what --dump-outputs writes and the checks of --full look at
+        if args.full:
+            sth = hb.stats()
+            if host_stage is None:
+                host_stage = dict(sth["stage_ms"])
+            else:
+                for k, v in sth["stage_ms"].items():
+                    host_stage[k] += v
     barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - untimed[0]
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if shared_gpu else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = dump_outputs(args.dump_outputs, hits, n_reads) if args.dump_outputs and rank == 0 else None
     st_host = hb.stats()
     split_timed = list(split)  # (the pageable leg below calls host_step again)
-    hits = host_step(keep=True)  # untimed: the hits the parity checks below look at
+    value = n_reads * args.steps * world / elapsed
+    step_ms = elapsed / args.steps * 1e3
+    line = {
+        "metric": "reads/sec (whole node), 150bp reads vs MG-index",
+        "value": value,
+        "unit": "reads/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": step_ms,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32/i16",
+        "data": "synthetic",
+        "value_region": "SURVEY 8(d): wall clock over host bases in -> host hits out through the C ABI (mtsv_batch_run_host + "
+                        "mtsv_batch_download = mtsv_bin_batch on a warm workspace), H2D of reads and D2H of hits included; "
+                        "index load/upload excluded",
+        "timed_calls_ms_per_step": {"mtsv_batch_run_host": split_timed[0] / args.steps * 1e3, "mtsv_batch_download": split_timed[1] / args.steps * 1e3,
+                                    "mtsv_hits_free": split_timed[2] / args.steps * 1e3},
+        "step_ms_each": each_ms,
+        "host_input": "ordinary (pageable) memory" if args.pageable_input else "page-locked memory from mtsv_host_alloc",
+        "host_transfer": ({"form": "4-bit codes, packed on the host chunk by chunk (csrc/host_pack.cpp), expanded by k_unpack",
+                           "pack_threads": M.lib().mtsv_host_pack_threads()} if M.lib().mtsv_host_pack_threads()
+                          else {"form": "plain bytes (MTSV_H2D_PLAIN, or fewer than nine CPUs to pack with), k_normalise on the device",
+                                "pack_threads": 0}),
+        "config": {"workload": f"{args.workload}: {desc}", "reads_per_gpu_per_step": n_reads, "read_len": read_len,
+                   "index_symbols": info["n"], "index_file_bytes": info["file_bytes"] or None,
+                   "index_hbm_bytes": info["device_bytes"], "dev_flags": args.dev_flags, "workspace_reads": min(n_reads, slice_reads),
+                   "host_cpu_affinity": affinity,
+                   "verify_mode": ["reference (SW prefilter + edit distance per verified candidate)", "edit_first"][args.verify_mode],
+                   "parallelism": f"reads sharded x{world}, index replicated, no collective"},
+        "setup_s": {"index_build": t_build, "index_file_reused": index_cached, "index_write": t_write, "index_load": t_load,
+                    "index_pack_upload_accel": t_upload, "until_warmup": t_setup},
+        "full": args.full,
+        "dump_outputs": dumped,
+    }
+    if not args.full:  # a plain run: the headline only
+        hb.close()
+        if pinned is not None:
+            pinned.close()
+        if rank == 0:
+            line["parity"] = "not checked (--full)"
+            print(json.dumps(line))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     pageable = None
     if pinned is not None and not args.no_extras and rank == 0:
         bases_p = bases.ctypes.data
@@ -583,9 +756,6 @@ def main():
                   f"workspace (MTSV_LANES=1); the timed steps ran {st_host.get('n_lanes', 1)} overlapping lanes over host slices")
     overlapped = {"n_lanes": st_host.get("n_lanes", 1), "stage_ms_summed_over_lanes_per_step": {k: v / args.steps for k, v in host_stage.items()}}
 
-    value = n_reads * args.steps * world / elapsed
-    step_ms = elapsed / args.steps * 1e3
-
     # ---- CPU baseline + algorithmic-byte counters from the oracle on a bounded sample ----
     cpu = None
     ctr_per = None
@@ -614,8 +784,7 @@ def main():
         oix.bin_batch(bases[: ns4 * read_len], off[: ns4 + 1], O.default_params(), threads=4)
         cpu["value_4_threads"] = ns4 / (time.perf_counter() - t0)
         g = hits[hits["read"] < ns]
-        same = len(g) == len(ohits) and all(np.array_equal(g[f], ohits[f]) for f in
-                                            ("read", "tax_id", "gi", "edit", "strand", "offset"))
+        same = len(g) == len(ohits) and all(np.array_equal(g[f], ohits[f]) for f in HIT_FIELDS)
         parity = f"{'identical' if same else 'MISMATCH'} on {ns} sampled reads ({len(ohits)} hits)"
 
     if "MISMATCH" in parity:
@@ -700,38 +869,10 @@ def main():
             hbm["measured_traffic_source"] = {"file": "profiles/hbm_traffic.json", "from_profile_of_commit": prof.get("commit"), "how": prof.get("source")}
         roof["survey_8d"] = hbm
 
-    out = {
-        "metric": "reads/sec (whole node), 150bp reads vs MG-index",
-        "value": value,
-        "unit": "reads/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": step_ms,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32/i16",
-        "data": "synthetic",
-        "value_region": "SURVEY 8(d): wall clock over host bases in -> host hits out through the C ABI (mtsv_batch_run_host + "
-                        "mtsv_batch_download = mtsv_bin_batch on a warm workspace), H2D of reads and D2H of hits included; "
-                        "index load/upload excluded",
-        "timed_calls_ms_per_step": {"mtsv_batch_run_host": split_timed[0] / args.steps * 1e3, "mtsv_batch_download": split_timed[1] / args.steps * 1e3,
-                                    "mtsv_hits_free": split_timed[2] / args.steps * 1e3},
-        "step_ms_each": each_ms,
+    out = dict(line)
+    out.update({
         "device_resident": resident,
-        "host_input": "ordinary (pageable) memory" if args.pageable_input else "page-locked memory from mtsv_host_alloc",
-        "host_transfer": ({"form": "4-bit codes, packed on the host chunk by chunk (csrc/host_pack.cpp), expanded by k_unpack",
-                           "pack_threads": M.lib().mtsv_host_pack_threads()} if M.lib().mtsv_host_pack_threads()
-                          else {"form": "plain bytes (MTSV_H2D_PLAIN, or fewer than nine CPUs to pack with), k_normalise on the device",
-                                "pack_threads": 0}),
         "pageable_input": pageable,
-        "config": {"workload": f"{args.workload}: {desc}", "reads_per_gpu_per_step": n_reads, "read_len": read_len,
-                   "index_symbols": info["n"], "index_file_bytes": os.path.getsize(idx_path),
-                   "index_hbm_bytes": info["device_bytes"], "dev_flags": args.dev_flags, "workspace_reads": min(n_reads, slice_reads),
-                   "host_cpu_affinity": affinity,
-                   "verify_mode": ["reference (SW prefilter + edit distance per verified candidate)", "edit_first"][args.verify_mode],
-                   "parallelism": f"reads sharded x{world}, index replicated, no collective"},
         "roofline": roof,
         "cpu_baseline": cpu,
         "stage_ms": stage_ms,
@@ -743,8 +884,7 @@ def main():
                                                  "n_sw_bound_refuted", "myers_columns")},
         "parity": parity,
         "other_verify_order": alt,
-        "setup_s": {"index_build": t_build, "index_file_reused": index_cached, "index_load": t_load, "index_pack_upload_accel": t_upload},
-    }
+    })
     print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -5,6 +5,9 @@
                       into oracle/_ref/libssw_ref.so by oracle/Makefile), called exactly as
                       ssw/src/lib.rs:36-84 does, for seeded (read, window) pairs incl. N's and reads
                       of 254+ bases (word kernel).  Needs the upstream checkout; data only.
+  ssw_live_golden.json
+                      score1 of the same library for the pairs of helpers.ssw_live_pairs() (stored
+                      as scores + a digest of the inputs, which the generator recreates).
   e2e_db.fasta / e2e_reads.txt / e2e_*.results
                       a small seeded database + reads and the result lines of the CPU oracle for
                       default and stress parameters (the reference holds no end-to-end vector:
@@ -56,6 +59,10 @@ def main():
         sys.exit("oracle/_ref/libssw_ref.so missing: run `make -C oracle ref` where /root/reference exists")
     with open(os.path.join(HERE, "ssw_golden.json"), "w") as f:
         json.dump(ssw_vectors(), f, separators=(",", ":"))
+    pairs = helpers.ssw_live_pairs()
+    with open(os.path.join(HERE, "ssw_live_golden.json"), "w") as f:
+        json.dump({"inputs_sha256": helpers.pairs_digest(pairs),
+                   "scores": [O.ref_ssw_scores(read, [w])[0] for read, w in pairs]}, f, separators=(",", ":"))
 
     entries, gene, unit = helpers.tricky_db(seed=7)
     with open(os.path.join(HERE, "e2e_db.fasta"), "w") as f:

@@ -1,6 +1,7 @@
 """Shared generators for the test-suite: adversarial databases and read sets that reach the
 order-dependent corners of the reference's hot loop (duplicate TaxIds, tie-breaking in the stable
 rank sort, merged windows, seed thinning, bin-boundary clipping, N handling)."""
+import hashlib
 import random
 
 import numpy as np
@@ -66,6 +67,29 @@ def tricky_db(seed=7):
     entries.append((1, 8, rnd_seq(rng, 19)))
     rng.shuffle(entries)
     return entries, gene, unit
+
+
+def ssw_live_pairs():
+    """seeded (read, window) pairs of lengths 40..320 (the word kernel from 254 on), a third of them with N's: the
+    inputs of tests/golden/ssw_live_golden.json"""
+    rng = random.Random(99)
+    pairs = []
+    for L in (40, 100, 150, 253, 254, 320):
+        for it in range(60):
+            w = rnd_seq(rng, L + rng.randrange(0, 70), b"ACGTN" if it % 3 == 0 else b"ACGT")
+            st = rng.randrange(0, max(1, len(w) - L + 1))
+            read = mutate(rng, w[st:st + L], rng.randrange(0, L // 4)) if it % 2 else rnd_seq(rng, L)
+            if len(read) < 30:
+                continue
+            pairs.append((read, w))
+    return pairs
+
+
+def pairs_digest(pairs):
+    h = hashlib.sha256()
+    for read, w in pairs:
+        h.update(read + b"|" + w + b"\n")
+    return h.hexdigest()
 
 
 def reads_to_batch(reads):

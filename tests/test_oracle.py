@@ -75,17 +75,19 @@ def test_ssw_emulation_matches_golden_vectors_from_reference_ssw_c():
     assert n_word >= 10  # the word-kernel path is exercised
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built (needs the upstream checkout)")
 def test_ssw_emulation_matches_compiled_reference_live():
-    rng = random.Random(99)
-    for L in (40, 100, 150, 253, 254, 320):
-        for it in range(60):
-            w = helpers.rnd_seq(rng, L + rng.randrange(0, 70), b"ACGTN" if it % 3 == 0 else b"ACGT")
-            st = rng.randrange(0, max(1, len(w) - L + 1))
-            read = helpers.mutate(rng, w[st:st + L], rng.randrange(0, L // 4)) if it % 2 else helpers.rnd_seq(rng, L)
-            if len(read) < 30:
-                continue
-            assert O.ssw_score(read, w) == O.ref_ssw_scores(read, [w])[0]
+    """the reference's ssw.c on seeded pairs: the scores it gave them (stored in tests/golden), and the compiled
+    library itself wherever oracle/_ref is built"""
+    pairs = helpers.ssw_live_pairs()
+    gold = json.load(open(os.path.join(GOLD, "ssw_live_golden.json")))
+    assert helpers.pairs_digest(pairs) == gold["inputs_sha256"], "the generator no longer makes the stored scores' inputs"
+    assert len(pairs) == len(gold["scores"]) > 300
+    live = O.ref_available()
+    for (read, w), want in zip(pairs, gold["scores"]):
+        got = O.ssw_score(read, w)
+        assert got == want, (read, w)
+        if live:
+            assert got == O.ref_ssw_scores(read, [w])[0], (read, w)
 
 
 def test_edit_within_tolerance_implies_sw_over_threshold():
