@@ -7,6 +7,7 @@
 //     steps of FMIndex::backward_search (call site src/index.rs:305) become one 8-byte gather.
 // Both hold exactly the values the reference's primitives would compute; results are unchanged.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -105,6 +106,27 @@ __global__ void k_kmer_level(DevIndexView ix, const uint2* __restrict__ prev, ui
         }
         cur[t] = make_uint2(lo, hi);
     }
+}
+
+// singleton entries of the finished table -> their text position and the two symbols in front of it
+// (dev_layout.hpp).  The table is in k-mer order, which is SA order: lo grows with t, so the sa_full and rank-block
+// reads stream; only the text byte is a random read.
+__global__ void k_kmer_tag(DevIndexView ix, uint2* __restrict__ tab, uint64_t total, unsigned long long* __restrict__ n_tagged) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint32_t mine = 0;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+        const uint2 iv = tab[t];
+        if (iv.y != iv.x + 1) continue;
+        const uint32_t lo = iv.x;
+        const uint32_t p = ix.sa_full[lo];
+        const LoadedBlock b = load_block(ix.blocks, lo >> kBlockShift);
+        const uint32_t c1 = block_code(b, lo & (kBlockRows - 1));  // text[p-1], or '$' when p == 0
+        const uint32_t c2 = p >= 2 ? ix.text[p - 2] : 7u;
+        tab[t] = kmer_tag_entry(p, c1, c2);
+        mine++;
+    }
+    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(n_tagged, (unsigned long long)mine);
 }
 
 template <class F>
@@ -336,6 +358,33 @@ std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint3
         di->bytes += entries * 8;
         v.kmer_tab = di->d_kmer;
         v.kmer_k = k;
+        // singleton k-mers carry their text position (full SA only: the sampled-SA mode keeps its LF-walk locate)
+        const char* kp = getenv("MTSV_KMER_POS");
+        if (v.sa_full && !(kp && atoi(kp) == 0)) {
+            unsigned long long* d_n = nullptr;
+            HIP_CHECK(hipMalloc((void**)&d_n, sizeof(unsigned long long)));
+            HIP_CHECK(hipMemset(d_n, 0, sizeof(unsigned long long)));
+            hipEvent_t t0, t1;
+            HIP_CHECK(hipEventCreate(&t0));
+            HIP_CHECK(hipEventCreate(&t1));
+            HIP_CHECK(hipEventRecord(t0, 0));
+            hipLaunchKernelGGL(k_kmer_tag, dim3((uint32_t)std::min<uint64_t>((entries + 255) / 256, 1u << 16)), dim3(256), 0, 0, v,
+                               di->d_kmer, entries, d_n);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipEventRecord(t1, 0));
+            unsigned long long n_tagged = 0;
+            HIP_CHECK(hipMemcpy(&n_tagged, d_n, sizeof(n_tagged), hipMemcpyDeviceToHost));
+            float ms = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+            (void)hipEventDestroy(t0);
+            (void)hipEventDestroy(t1);
+            (void)hipFree(d_n);
+            if (getenv("MTSV_TRACE"))
+                fprintf(stderr, "[upload] kmer table k=%u: %llu tagged entries of %llu (%.1f ms)\n", k, n_tagged,
+                        (unsigned long long)entries, ms);
+        } else if (getenv("MTSV_TRACE")) {
+            fprintf(stderr, "[upload] kmer table k=%u: 0 tagged entries of %llu (0.0 ms)\n", k, (unsigned long long)entries);
+        }
     }
     HIP_CHECK(hipEventRecord(e1, 0));
     HIP_CHECK(hipEventSynchronize(e1));

@@ -52,9 +52,28 @@ struct DevIndexView {
     uint32_t n_bins;
     const uint32_t* bin_lut;    // bin_lut[p >> bin_lut_shift] = first bin whose end > (p >> shift) << shift
     uint32_t bin_lut_shift;
-    const uint2* kmer_tab;      // [4^kmer_k] SA interval (lo, hi) of every ACGT k-mer, or nullptr
+    const uint2* kmer_tab;      // [4^kmer_k] SA interval (lo, hi) of every ACGT k-mer (or its tagged position), or nullptr
     uint32_t kmer_k;
 };
+
+// k-mer table entries.  An ordinary entry is the SA interval (x, y) = (lo, hi), hi <= n < 0xFFFFFF00.  With the
+// full SA resident, the entry of a k-mer that occurs exactly once (hi == lo + 1) holds its text position instead:
+//     x = p = SA[lo]
+//     y = kKmerTag | c1 | c2 << 3,  c1 = text[p-1] (= BWT[lo]; the sentinel code 5 when p == 0),
+//                                   c2 = text[p-2] (7 when p < 2: matches no read symbol)
+// Extending a singleton by symbol a matches iff a == c1, and the extended seed sits at p - 1: a seed that finds
+// such an entry needs no rank step and no SA gather.  Every reader of the table tests the tag first.
+constexpr uint32_t kKmerTag = 0xFFFFFF00u;
+__host__ __device__ inline bool kmer_tagged(uint2 e) { return (e.y & kKmerTag) == kKmerTag; }
+__host__ __device__ inline uint32_t kmer_tag_c1(uint2 e) { return e.y & 7u; }
+__host__ __device__ inline uint32_t kmer_tag_c2(uint2 e) { return (e.y >> 3) & 7u; }
+__host__ __device__ inline uint2 kmer_tag_entry(uint32_t p, uint32_t c1, uint32_t c2) {
+    return make_uint2(p, kKmerTag | c1 | (c2 << 3));
+}
+
+// seed_cnt value of a seed slot that resolved to one hit whose text position is known (seed_lo holds it).  No
+// interval count reaches it (n < 0xFFFFFF00).
+constexpr uint32_t kSeedAtPos = 0xFFFFFFFFu;
 
 // binner.rs:88-100 as symbol codes: A/a C/c G/g T/t, everything else (incl. N/n) -> N
 __host__ __device__ inline uint32_t base_code(uint8_t b) {

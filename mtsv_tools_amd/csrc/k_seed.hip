@@ -85,6 +85,7 @@ __device__ inline void search_slot(const DevIndexView& ix, const uint8_t* __rest
     uint32_t b0 = read_off[r], L = read_off[r + 1] - b0;
     uint32_t ns = n_seeds_of(L, K, G);
     uint32_t lo = 0, hi = 0;
+    bool at_pos = false;  // lo is the seed's one text position (a tagged table entry)
     if (j < ns) {
         const uint8_t* read = bases + b0;
         uint32_t off = j * G;
@@ -179,6 +180,16 @@ __device__ inline void search_slot(const DevIndexView& ix, const uint8_t* __rest
                 lo = iv.x;
                 hi = iv.y;
                 i = (int)K - 1 - (int)ix.kmer_k;
+                if (kmer_tagged(iv)) {
+                    // one occurrence, at p: the m = i + 1 symbols in front must equal text[p-m, p)
+                    const uint32_t p = iv.x, m = (uint32_t)(i + 1);
+                    bool match = p >= m;
+                    for (uint32_t t = 0; match && t < m; t++) match = sym(t) == ix.text[p - m + t];
+                    at_pos = match;
+                    lo = match ? p - m : 0;
+                    hi = 0;
+                    i = -1;
+                }
             }
         }
         for (; i >= 0 && lo < hi; i--) {
@@ -196,10 +207,10 @@ __device__ inline void search_slot(const DevIndexView& ix, const uint8_t* __rest
             lo = nlo;
             hi = nhi;
         }
-        if (lo >= hi) lo = hi = 0;  // Partial / Absent: only Complete intervals count (index.rs:312-332)
+        if (!at_pos && lo >= hi) lo = hi = 0;  // Partial / Absent: only Complete intervals count (index.rs:312-332)
     }
     seed_lo[slot] = lo;
-    seed_cnt[slot] = hi - lo;
+    seed_cnt[slot] = at_pos ? kSeedAtPos : hi - lo;
 }
 
 __global__ __launch_bounds__(256) void k_search(DevIndexView ix, const uint8_t* __restrict__ bases,
@@ -223,8 +234,10 @@ __global__ __launch_bounds__(256) void k_search(DevIndexView ix, const uint8_t* 
 // atomic per wavefront was atomic-bound: ~9 ns per single-address atomic, 2.5 M wavefronts with such a seed on config2.)
 // KK = 17: the 16 packed symbols plus the one in front of them as bits 32-33 of the table index (a table of 2^34 entries).
 // one seed slot on the table path: stores its interval, or returns true when the slot needs the general code (an N in the
-// table part)
-template <int KK>
+// table part).  FRONT_TEXT: a tagged entry's m = K - KK front symbols may be more than the two the entry carries (they
+// are then compared with the text); without it the kernel never reads the text (m <= 2: the default seed of 18 on a
+// 17-mer table, and the 16-mer fallback), which keeps k_search_fast<17> at 8 waves per SIMD.
+template <int KK, bool FRONT_TEXT>
 __device__ inline bool fast_slot(const DevIndexView& ix, const uint8_t* __restrict__ bases, const uint32_t* __restrict__ read_off,
                                  uint32_t r0, uint32_t total, uint32_t max_ns, uint32_t K, uint32_t G, uint32_t slot,
                                  uint32_t* __restrict__ seed_lo, uint32_t* __restrict__ seed_cnt) {
@@ -234,7 +247,7 @@ __device__ inline bool fast_slot(const DevIndexView& ix, const uint8_t* __restri
     const uint32_t b0 = read_off[r], L = read_off[r + 1] - b0;
     const bool live = in_range && j < n_seeds_of(L, K, G);
     uint32_t lo = 0, hi = 0;
-    bool slow = false;
+    bool slow = false, at_pos = false;  // at_pos: lo is the seed's one text position (a tagged table entry)
     if (live) {
         const uint32_t off = j * G;
         const uint32_t s0 = b0 + (strand ? L - off - K : off);  // first byte of the seed's span in the read buffer
@@ -296,6 +309,35 @@ __device__ inline bool fast_slot(const DevIndexView& ix, const uint8_t* __restri
             const uint2 iv = ix.kmer_tab[slow ? 0 : tix];
             lo = iv.x;
             hi = iv.y;
+            if (kmer_tagged(iv)) {
+                // one occurrence, at p: the m = i + 1 symbols in front, front(m-1) first, must equal text[p-m, p).
+                // Two come with the entry; more (a table narrower than the seed minus two) are one text load.
+                const uint32_t p = iv.x;
+                const int m = i + 1;  // (wave-uniform, at most 8)
+                // front(t) at byte t: the span's first m bytes (forward), or its front bytes turned round and complemented
+                constexpr int F0 = KK > 16 ? 1 : 0;  // (the table's 17th symbol sits in front of the packed part too)
+                uint64_t fw = fm;
+                if (strand) {
+                    const int F = m + F0;  // front bytes in fm
+                    fw = F > 0 ? __builtin_bswap64(fm) >> (64 - 8 * F) : 0ull;
+                    const uint64_t c = (~fw >> 2) & 0x0101010101010101ull;  // codes below 4: x -> 3 - x = x ^ 3
+                    fw ^= c | (c << 1);
+                }
+                uint64_t tm;  // text[p-m, p) at byte t = text[p-m+t]
+                if (!FRONT_TEXT || m <= 2) {
+                    tm = m == 2 ? (kmer_tag_c2(iv) | kmer_tag_c1(iv) << 8) : kmer_tag_c1(iv);
+                } else {
+                    const uint32_t q = p >= (uint32_t)m ? p - m : 0u;
+                    const uint32_t* t32 = reinterpret_cast<const uint32_t*>(ix.text);
+                    const uint32_t qw = q >> 2, qsh = q & 3;
+                    const uint32_t t0 = t32[qw], t1 = t32[qw + 1], t2 = t32[qw + 2];  // (the text is padded past n)
+                    tm = ((uint64_t)__builtin_amdgcn_alignbyte(t2, t1, qsh) << 32) | __builtin_amdgcn_alignbyte(t1, t0, qsh);
+                }
+                const bool match = p >= (uint32_t)m && (m == 0 || ((tm ^ fw) << (64 - 8 * max(m, 1))) == 0);  // (bytes 0..m-1 only)
+                at_pos = match;
+                lo = match ? p - m : 0;
+                hi = 0;  // (the rank steps below skip the lane)
+            }
             for (; i >= 0; i--) {  // wave-uniform trip count
                 const uint32_t a = front(i);
                 if (lo < hi) {
@@ -313,19 +355,19 @@ __device__ inline bool fast_slot(const DevIndexView& ix, const uint8_t* __restri
                     hi = nhi;
                 }
             }
-            if (lo >= hi) lo = hi = 0;  // Partial / Absent: only Complete intervals count (index.rs:312-332)
+            if (!at_pos && lo >= hi) lo = hi = 0;  // Partial / Absent: only Complete intervals count (index.rs:312-332)
         }
     }
     if (in_range && !slow) {
         seed_lo[slot] = lo;
-        seed_cnt[slot] = hi - lo;
+        seed_cnt[slot] = at_pos ? kSeedAtPos : hi - lo;
     }
     return slow;
 }
 
 constexpr uint32_t kSlowCap = 128;  // slots a wavefront holds back in LDS before it appends 64 of them to the list
 
-template <int KK>
+template <int KK, bool FRONT_TEXT>
 __global__ __launch_bounds__(256) void k_search_fast(DevIndexView ix, const uint8_t* __restrict__ bases,
                                                      const uint32_t* __restrict__ read_off, uint32_t r0, uint32_t total,
                                                      uint32_t max_ns, uint32_t K, uint32_t G,
@@ -341,7 +383,7 @@ __global__ __launch_bounds__(256) void k_search_fast(DevIndexView ix, const uint
     const uint32_t n_tiles = (total + kWave - 1) / kWave;
     for (uint32_t tile = blockIdx.x * (256 / kWave) + wave; tile < n_tiles; tile += gridDim.x * (256 / kWave)) {
         const uint32_t slot = tile * kWave + lane;
-        const bool slow = fast_slot<KK>(ix, bases, read_off, r0, total, max_ns, K, G, slot, seed_lo, seed_cnt);
+        const bool slow = fast_slot<KK, FRONT_TEXT>(ix, bases, read_off, r0, total, max_ns, K, G, slot, seed_lo, seed_cnt);
         const unsigned long long sb = __ballot(slow);
         if (sb) {
             if (slow) slow_q[n_slow + __popcll(sb & ((1ull << lane) - 1))] = slot;
@@ -411,7 +453,8 @@ __global__ __launch_bounds__(256) void k_thin(const uint8_t* __restrict__ bases,
     uint32_t* pre = seed_pre + (uint64_t)rs * max_ns;
     for (uint32_t j = 0; j < ns; j++) {
         uint64_t offset = (uint64_t)j * G;
-        uint32_t c = cnt[j];
+        const uint32_t raw = cnt[j];
+        const uint32_t c = raw == kSeedAtPos ? 1u : raw;  // one hit whose position the search already knows
         if (offset < next_offset) {  // index.rs:300-302
             if (c) cnt[j] = 0;
             continue;
@@ -577,7 +620,9 @@ __global__ __launch_bounds__(256) void k_expand(DevIndexView ix, uint64_t n_slot
                                                 uint32_t* __restrict__ hit_row, uint32_t* __restrict__ hit_ref,
                                                 uint32_t* __restrict__ hit_q) {
     uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t c = slot < n_slots ? seed_cnt[slot] : 0;
+    const uint32_t raw = slot < n_slots ? seed_cnt[slot] : 0;
+    const bool at_pos = raw == kSeedAtPos;  // one hit, seed_lo is its text position (only with the full SA)
+    const uint32_t c = at_pos ? 1u : raw;
     uint32_t o = 0, l = 0, q = 0;
     if (c) {
         const uint32_t rs = (uint32_t)(slot / max_ns), j = (uint32_t)(slot % max_ns);
@@ -588,7 +633,10 @@ __global__ __launch_bounds__(256) void k_expand(DevIndexView ix, uint64_t n_slot
     // seeds with few hits: the lane writes them itself; repeats (up to max_hits per seed) are spread over the
     // wavefront, one seed after the other, so that no single lane walks thousands of entries
     constexpr uint32_t kOwn = 16;
-    if (c && c <= kOwn) {
+    if (at_pos) {
+        hit_ref[o] = l;
+        hit_q[o] = q;
+    } else if (c && c <= kOwn) {
         for (uint32_t i = 0; i < c; i++) {
             if (ix.sa_full) hit_ref[o + i] = ix.sa_full[l + i];
             else hit_row[o + i] = l + i;
@@ -714,8 +762,12 @@ void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, 
     // (two generations of resident workgroups: 0.81 ms per pass of 1 Mi reads, 0.84 with one, 0.82 with half of one)
     const dim3 grid(std::min<uint32_t>(cdiv(total, 256), 256 * 16));
 #define FAST_CASE(KKV)                                                                                                  \
-    hipLaunchKernelGGL((k_search_fast<KKV>), grid, dim3(256), 0, s, ix, bases, read_off, r0, (uint32_t)total, max_ns, K, G, seed_lo, \
-                       seed_cnt, slow_list, slow_count)
+    if (K - KKV > 2)                                                                                                    \
+        hipLaunchKernelGGL((k_search_fast<KKV, true>), grid, dim3(256), 0, s, ix, bases, read_off, r0, (uint32_t)total, max_ns, K, G, \
+                           seed_lo, seed_cnt, slow_list, slow_count);                                                   \
+    else                                                                                                                \
+        hipLaunchKernelGGL((k_search_fast<KKV, false>), grid, dim3(256), 0, s, ix, bases, read_off, r0, (uint32_t)total, max_ns, K, G, \
+                           seed_lo, seed_cnt, slow_list, slow_count)
     switch (ix.kmer_k) {
     case 12: FAST_CASE(12); break;
     case 13: FAST_CASE(13); break;
