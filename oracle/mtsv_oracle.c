@@ -402,6 +402,30 @@ uint32_t orc_min_edit_distance(const uint8_t *p, uint64_t m, const uint8_t *t, u
     return best;
 }
 
+/* The same recurrence and the same minimum over the last row, two rows at a time: O(n) memory, so a
+ * read of tens of kilobases against its window stays within reach of the batch driver below */
+uint32_t orc_min_edit_distance_rows(const uint8_t *p, uint64_t m, const uint8_t *t, uint64_t n) {
+    uint32_t *prev = calloc(n + 1, sizeof(uint32_t)), *cur = calloc(n + 1, sizeof(uint32_t));
+    for (uint64_t row = 1; row <= m; row++) {
+        cur[0] = (uint32_t)row;
+        for (uint64_t col = 1; col <= n; col++) {
+            uint32_t delta = p[row - 1] != t[col - 1];
+            uint32_t diag = prev[col - 1] + delta;
+            uint32_t up = prev[col] + 1;
+            uint32_t left = cur[col - 1] + 1;
+            uint32_t v = up < left ? up : left;
+            cur[col] = diag < v ? diag : v;
+        }
+        uint32_t *sw = prev; prev = cur; cur = sw;
+    }
+    uint32_t best = prev[0]; /* row m (row 0 when m == 0) */
+    for (uint64_t col = 1; col <= n; col++)
+        if (prev[col] < best) best = prev[col];
+    free(prev);
+    free(cur);
+    return best;
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* SW prefilter                                                                                */
 /* ------------------------------------------------------------------------------------------ */
@@ -760,7 +784,7 @@ int64_t orc_matching_tax_ids(const orc_index *ix, const uint8_t *seq, uint64_t l
         uint64_t score = wl ? orc_ssw_score(seq, len, w, wl) : 0; /* index.rs:401-402 */
         if (score >= thr) {                                       /* index.rs:406 */
             c->n_edit++;
-            uint32_t edits = orc_min_edit_distance(seq_no_n, len, w, wl); /* index.rs:409 */
+            uint32_t edits = orc_min_edit_distance_rows(seq_no_n, len, w, wl); /* index.rs:409 */
             if (edits <= edit_distance) {
                 matched[nm++] = bin->tax_id;
                 if (nout >= cap) { ret = -1; break; }
@@ -822,7 +846,7 @@ int orc_bin_batch(const orc_index *ix, const uint8_t *bases, const uint64_t *rea
         orc_hit *buf = malloc(2 * cap * sizeof *buf);
         uint8_t *fwd = NULL, *rev = NULL;
         uint64_t bcap = 0;
-#pragma omp for schedule(dynamic, 256)
+#pragma omp for schedule(dynamic, 1) /* a read at a time: a batch of a few long reads spreads over the threads */
         for (int64_t r = 0; r < (int64_t)n_reads; r++) {
             uint64_t len = read_off[r + 1] - read_off[r];
             if (len > bcap) {

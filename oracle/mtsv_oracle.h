@@ -13,7 +13,8 @@
  * (index.rs:305, :347, :560-574; io.rs:121,131).
  *
  * Pinning status:
- *   - min_edit_distance: pinned by the 9 known-answer tests of src/align.rs:100-170.
+ *   - min_edit_distance: pinned by the 9 known-answer tests of src/align.rs:100-170; the two-row
+ *     form the batch driver uses equals the full-matrix restatement (tests/test_oracle.py).
  *   - window arithmetic / merge rules: pinned by src/index.rs:721-857.
  *   - result line format: pinned by src/binner.rs:440-472.
  *   - SW prefilter score: pinned against the reference's own ssw/src/ssw.c compiled into
@@ -122,6 +123,8 @@ uint64_t orc_sa_get(const orc_index *ix, uint64_t row, orc_counters *c);
 
 /* ---- verification kernels ---- */
 uint32_t orc_min_edit_distance(const uint8_t *p, uint64_t m, const uint8_t *t, uint64_t n);
+/* the same value from two rows of the matrix (O(n) memory); orc_bin_batch uses this one */
+uint32_t orc_min_edit_distance_rows(const uint8_t *p, uint64_t m, const uint8_t *t, uint64_t n);
 /* exact local alignment score, scores +1/-1 (N==N matches), gap open go / extend ge in ssw's
  * convention (first gap base costs go, each further one ge) */
 uint32_t orc_sw_exact(const uint8_t *read, uint64_t m, const uint8_t *ref, uint64_t n, int go,

@@ -71,6 +71,8 @@ def lib():
         L.orc_sa_get.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
         L.orc_min_edit_distance.restype = C.c_uint32
         L.orc_min_edit_distance.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
+        L.orc_min_edit_distance_rows.restype = C.c_uint32
+        L.orc_min_edit_distance_rows.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
         for fn in (L.orc_ssw_score, L.orc_ssw_byte, L.orc_ssw_word):
             fn.restype = C.c_uint32
             fn.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]
@@ -191,6 +193,11 @@ class Index:
 
 def min_edit_distance(p, t):
     return lib().orc_min_edit_distance(p, len(p), t, len(t))
+
+
+def min_edit_distance_rows(p, t):
+    """the same value from two rows of the matrix (what orc_bin_batch uses)"""
+    return lib().orc_min_edit_distance_rows(p, len(p), t, len(t))
 
 
 def ssw_score(read, ref):

@@ -143,3 +143,98 @@ def assert_same_hits(got, want):
     for f in FIELDS:
         bad = np.nonzero(got[f] != want[f])[0]
         assert len(bad) == 0, (f, bad[:5], got[bad[:5]], want[bad[:5]])
+
+
+def substitute(rng, s, k, lo=0, hi=None, alpha=b"ACGT"):
+    """k substitutions at distinct positions of s[lo:hi], each to a different base"""
+    s = bytearray(s)
+    hi = len(s) if hi is None else hi
+    for i in rng.sample(range(lo, hi), min(k, max(0, hi - lo))):
+        s[i] = rng.choice([c for c in alpha if c != s[i]] or alpha)
+    return bytes(s)
+
+
+def damage_at_end(rng, src, length, n_edits, span):
+    """a read of `length` bases from src (which holds at least length + n_edits bases) with n_edits substitutions
+    and indels, all in its last `span` bases: a candidate that fails does so in the last columns of its sweep"""
+    r = bytearray(src[:length + n_edits])
+    lo = max(0, length - span)
+    for _ in range(n_edits):
+        i = rng.randrange(lo, length)
+        op = rng.randrange(3)
+        if op == 0:
+            r[i] = rng.choice([c for c in b"ACGT" if c != r[i]])
+        elif op == 1:
+            del r[i]
+        else:
+            r.insert(i, rng.choice(b"ACGT"))
+    return bytes(r[:length])
+
+
+def ladder_reads(rng, texts, L, edit_rate=0.13, n=240):
+    """n reads whose longest is exactly L bases, the others spread over L/3..L, on both strands: exact copies,
+    substitutions only, indels, ED-1 / ED / ED+1 edits (ED = ceil(len * edit_rate)), damage in the last bases,
+    exactly ED and ED+1 N, reads cut at the start or end of a database sequence (clipped windows) and, from 254
+    bases on, indels at the stripe rows k * ceil(L / 8) of the word kernel.  texts: database sequences, upper case."""
+    import math
+    long_texts = [t for t in texts if len(t) >= L + 40]
+    reads = []
+    for i in range(n):
+        Lr = L if i % 4 == 0 else rng.randrange(max(1, L // 3), L + 1)
+        ed = math.ceil(Lr * edit_rate)
+        t = rng.choice(long_texts)
+        st = rng.randrange(0, len(t) - Lr - 20)
+        seg = t[st:st + Lr + 20]
+        kind = i % 9
+        if kind == 0:
+            r = seg[:Lr]
+        elif kind == 1:
+            r = substitute(rng, seg[:Lr], rng.randrange(0, ed + 3))
+        elif kind == 2:
+            r = bytearray(seg)
+            for _ in range(rng.randrange(1, min(8, ed + 1) + 1)):
+                j = rng.randrange(Lr)
+                if rng.random() < 0.5:
+                    r[j:j] = rnd_seq(rng, rng.randrange(1, 3))
+                else:
+                    del r[j:j + rng.randrange(1, 3)]
+            r = bytes(r[:Lr])
+        elif kind == 3:
+            r = substitute(rng, seg[:Lr], max(0, ed + (i // 9) % 3 - 1))
+        elif kind == 4:
+            r = damage_at_end(rng, seg, Lr, ed + (i // 9) % 2, ed + 4)
+        elif kind == 5:
+            r = bytes(c if c in b"ACGT" else 65 for c in seg[:Lr])   # no N but the planted ones
+            r = substitute(rng, r, ed + (i // 9) % 2, alpha=b"N")
+        elif kind == 6:
+            t = rng.choice(long_texts)
+            r = t[:Lr] if (i // 9) % 2 else t[len(t) - Lr:]
+            r = substitute(rng, r, rng.randrange(0, ed + 1))
+        elif kind == 7 and L >= 254:
+            seg8 = (L + 7) // 8
+            r = bytearray(seg)
+            for _ in range(rng.randrange(1, 4)):
+                b = rng.randrange(1, 8) * seg8 + rng.randrange(-2, 3)
+                k = rng.randrange(1, 5)
+                if rng.random() < 0.6:
+                    r[b:b] = rnd_seq(rng, k)
+                else:
+                    del r[b:b + k]
+            r = bytes(r[:Lr])
+        else:
+            r = mutate(rng, seg[:Lr], rng.randrange(0, ed + 2), b"ACGT")[:Lr]
+        reads.append(r if rng.random() < 0.5 else revcomp(r))
+    assert max(map(len, reads)) == L
+    return reads
+
+
+def planted_db(rng, background, plants):
+    """A database of random sequences with segments planted a known number of times.
+    background: [(tax_id, gi, length)] random sequences; plants: [(segment, [(tax_id, gi), ...])] -- one exact copy of
+    the segment in a sequence of its own (random flanks of 60..200 bases) for every listed (tax_id, gi).
+    Returns the entries (tax_id, gi, sequence) in that order."""
+    entries = [(tax, gi, rnd_seq(rng, n)) for tax, gi, n in background]
+    for seg, owners in plants:
+        for tax, gi in owners:
+            entries.append((tax, gi, rnd_seq(rng, rng.randrange(60, 200)) + seg + rnd_seq(rng, rng.randrange(60, 200))))
+    return entries

@@ -30,6 +30,30 @@ def test_min_edit_distance_reference_kats(needle, haystack, expected):
     assert O.min_edit_distance(needle, haystack) == expected
 
 
+def test_two_row_edit_distance_equals_the_full_matrix():
+    """orc_bin_batch takes the edit distance from two rows of the matrix (reads of tens of kilobases); it is the
+    full-matrix restatement of align.rs:28-85 on the known answers and on random pairs with N, empty ones included"""
+    kats = [(b"TACGTCAGC", b"AACCCTATGTCATGCCTTGGA", 2), (HAY, HAY, 0), (b"AAAAAT", HAY, 0), (b"", HAY, 0),
+            (b"*********", HAY, 9), (b"ACGT", b"ACGA", 1), (b"ANNGTTCNGNT", HAY, 5), (b"***GTTATAA", HAY, 3),
+            (b"GTTATAA***", HAY, 3)]
+    for needle, hay, want in kats:
+        assert O.min_edit_distance_rows(needle, hay) == O.min_edit_distance(needle, hay) == want
+    rng = random.Random(17)
+    for _ in range(3000):
+        n = rng.choice([0, 0, 1, 2, rng.randrange(0, 40), rng.randrange(0, 601)])
+        m = rng.choice([0, 1, rng.randrange(0, 40), rng.randrange(0, 601), n])
+        t = helpers.rnd_seq(rng, n, b"ACGTN" if rng.random() < 0.5 else b"ACGT")
+        if m <= n and rng.random() < 0.6:   # a damaged copy of part of the window: small distances too
+            st = rng.randrange(0, n - m + 1)
+            p = helpers.mutate(rng, t[st:st + m], rng.randrange(0, max(1, m // 5)))
+        else:
+            p = helpers.rnd_seq(rng, m, b"ACGTN")
+        p = p.replace(b"N", b".") if rng.random() < 0.5 else p
+        assert O.min_edit_distance_rows(p, t) == O.min_edit_distance(p, t), (p, t)
+    assert O.min_edit_distance_rows(b"", b"") == O.min_edit_distance(b"", b"") == 0
+    assert O.min_edit_distance_rows(b"ACGT", b"") == O.min_edit_distance(b"ACGT", b"") == 4
+
+
 def test_candidate_indices_reference_cases():
     # src/index.rs:795-857: bin [100,200), read_len 50, edits 3
     s, e = O.candidate_indices(110, 1, 100, 200, 50, 3)
