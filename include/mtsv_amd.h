@@ -110,7 +110,8 @@ typedef struct {
                              * distances the reference computes (:407-409).  Counted where the prefilter is a
                              * kernel of its own (reference order, reads up to 253 bases); 0 otherwise */
     float sw_diag_ms;       /* k_sw_diag: the lower bounds on the seed diagonal */
-    float sw_bound_ms;      /* k_edit_myers in bound mode: the two-sided bound by the unit-cost edit distance */
+    float sw_bound_ms;      /* k_edit_myers in fused mode (bound + edit distance of round 0; sw_diag_ms is 0 then), or in bound mode
+                               (MTSV_SW_FUSED=0): the two-sided bound by the unit-cost edit distance */
     float edit_ms;          /* k_edit_myers on the candidates that passed the prefilter (first round of every pass) */
     uint64_t myers_columns; /* window columns the bit-vector recurrences of k_edit_myers advanced (bound + edit distance) */
     uint64_t n_sw_bound_refuted; /* candidates the edit-distance bound refuted without a sweep */

@@ -144,6 +144,7 @@ Batch::Batch(mtsv_index* ix_, DeviceIndex* di_, uint64_t max_reads_, uint64_t ma
     if (const char* e = getenv("MTSV_SW_PREPASS")) sw_prepass = atoi(e) != 0;
     if (const char* e = getenv("MTSV_SW_TOP")) sw_top = atoi(e) != 0;
     if (const char* e = getenv("MTSV_SW_BOUND")) sw_bound = atoi(e) != 0;
+    if (const char* e = getenv("MTSV_SW_FUSED")) sw_fused = atoi(e) != 0;
     verify_mode = g_default_verify_mode;
     if (const char* e = getenv("MTSV_VERIFY")) verify_mode = !strcmp(e, "edit_first") ? 1 : 0;
     for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
@@ -288,6 +289,7 @@ void Batch::begin_run(const mtsv_params& p) {
         l->sw_prepass = sw_prepass;
         l->sw_top = sw_top;
         l->sw_bound = sw_bound;
+        l->sw_fused = sw_fused;
         l->reset_lane();
     }
 }
@@ -581,8 +583,12 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                 // A candidate that passes the first and fails the second sends its TaxId's next
                 // candidate to another round (rare); rounds end when nothing is left.
                 // counters: [8] SW cursor, [9] pass count, [10] Myers cursor, [11]/[12] next-round counts, [16] sweep list
-                // Round 0 starts with k_sw_diag: the lower bounds on the seed diagonal, a lane per work item; what
-                // they decide goes straight to pass_list, the rest to sweep_list for k_sw_pairs.
+                // Round 0 is one pass of k_edit_myers in fused mode over the whole worklist: the unit-cost distance under the SW
+                // matrix's matches decides the prefilter from both sides and, wherever read or window holds no N, is the edit
+                // distance itself.  k_sw_pairs sweeps what lies between its thresholds, list mode finishes what the sweep passed.
+                // MTSV_SW_FUSED=0 (and MTSV_SW_BOUND=0) start with k_sw_diag instead: the lower bounds on the seed diagonal, a
+                // lane per work item; what they decide goes straight to pass_list, the rest to sweep_list for k_sw_pairs.
+                const bool fused = sw_bound && sw_fused;
                 uint32_t* pass_list = (uint32_t*)d_hit_key;                       // coalesce scratch is free now
                 uint32_t* sweep_list = (uint32_t*)d_hit_key + hit_cap;            // (8 bytes per seed hit)
                 uint32_t* next_lists[2] = {(uint32_t*)d_cand_tmp, (uint32_t*)d_cand_tmp + hit_cap};
@@ -608,7 +614,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                     sw.strip = d_strip;
 #endif
                     if (round == 0) HIP_CHECK(hipEventRecord(ev[10], stream));
-                    if (round == 0 && sw_diag && sw_prepass) {
+                    if (round == 0 && sw_diag && sw_prepass && !fused) {
                         HIP_CHECK(hipMemsetAsync(d_counters + 16, 0, sizeof(uint64_t), stream));
                         launch_sw_diag(stream, v, sw, items, pass_max_len, sweep_list, 16);
                         HIP_CHECK(hipEventRecord(ev[12], stream));
@@ -628,7 +634,8 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                         bd.und_list = (uint32_t*)d_hit_row;
                         bd.und_slot = 17;
                         bd.myers_ctr = (unsigned long long*)(d_counters + 19);
-                        launch_edit_myers(stream, v, bd, items, pass_max_len, 2);
+                        // (fused: from the worklist's end, and accepted candidates go straight to `out`)
+                        launch_edit_myers(stream, v, bd, items, pass_max_len, fused ? 3 : 2);
                         HIP_CHECK(hipEventRecord(ev[13], stream));
                         sw.worklist = bd.und_list;
                         sw.wl_count_slot = 17;
@@ -678,7 +685,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                         HIP_CHECK(hipEventElapsedTime(&ms, ev[10], ev[11]));
                         sw_ms_acc += ms;
                         int from = 10;  // the sweeps start after whichever bound kernels ran
-                        if (sw_diag && sw_prepass) {
+                        if (sw_diag && sw_prepass && !fused) {
                             HIP_CHECK(hipEventElapsedTime(&ms, ev[10], ev[12]));
                             diag_ms_acc += ms;
                             from = 12;

@@ -1334,7 +1334,15 @@ __device__ inline uint4 fetch_cols(const DevIndexView& ix, uint32_t start, uint3
 // bounded by the same lane, index.rs:393), and the few in between go to und_list for the sweep.  A chance candidate
 // sits near D = 0.4*L, far above 2*ED = 0.26*L.  A lane leaves the columns early once D <= ED is reached, or once the
 // last row can no longer come down to 2*ED in the columns that are left (neighbouring cells differ by at most 1).
-enum : int { MY_CHAIN = 0, MY_LIST = 1, MY_BOUND = 2 };
+//
+// MY_FUSED: both predicates of the unfiltered round-0 worklist in one pass.  The two recurrences differ in one relation only:
+// under the SW matrix a read N matches a window N, under the edit distance it matches nothing.  A read without N, or a
+// window without N, has no such pair, and then D is cell for cell the edit distance of align.rs:28-85.  So every candidate
+// starts where list mode starts a successor (ph = 1, SW matches): D > 2*ED refutes it, D <= ED passes index.rs:406 and -- unless
+// the read holds an N and the columns that streamed by held one too -- is accepted with edit = D; otherwise the lane runs the
+// edit distance's own pass (ph = 2).  What lies between the thresholds goes to und_list for the sweep of the same round.
+// The minimum over all columns is the reported distance, so only the refuting exit leaves the columns early.
+enum : int { MY_CHAIN = 0, MY_LIST = 1, MY_BOUND = 2, MY_FUSED = 3 };
 template <int W, int MODE>  // W 32-bit words per column: reads of up to 32*W bases
 __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a) {
     // match masks of the lane's read, one row per window symbol (A C G T, other), word-major so that a
@@ -1343,7 +1351,8 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
     // start at 0: they stay 0 in every column, i.e. they reproduce the all-zero first row of
     // align.rs:28-85 right under the read's first base, and the running score is simply the carry out
     // of the last word.
-    constexpr bool LIST = MODE == MY_LIST, BOUND = MODE == MY_BOUND;
+    // (LIST holds for the fused mode too: it is list mode whose items start at the prefilter, ph = 1)
+    constexpr bool FUSED = MODE == MY_FUSED, LIST = MODE == MY_LIST || FUSED, BOUND = MODE == MY_BOUND;
     // rows 0-3: the bases; 4: matches nothing; 5 (bound and list mode): the read's N positions, which a window N matches in
     // the SW matrix
     constexpr int NROW = (BOUND || LIST) ? 6 : 5;
@@ -1353,8 +1362,8 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
     const uint32_t maxc = a.maxc;  // max_candidates as a rank bound, clamped on the host
     const uint32_t lane = lane_id();
     const uint32_t* bases32 = reinterpret_cast<const uint32_t*>(a.bases);
-    unsigned long long verified = 0, wbytes = 0;
-    uint32_t cols = 0, refuted = 0;  // columns this lane's recurrences advanced; bound mode: candidates it refuted
+    uint32_t verified = 0, wbytes = 0;  // per lane: far below 2^32 in one launch, like cols
+    uint32_t cols = 0, refuted = 0;  // columns this lane's recurrences advanced; bound and fused mode: candidates it refuted
     // wave-uniform slice of the worklist, claimed 256 items at a time; a lane whose candidate passed
     // (or whose TaxId chain ended) takes the next item, a lane whose candidate failed keeps its read
     // and moves to the next candidate of the same TaxId (index.rs:393)
@@ -1367,8 +1376,10 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
     // list mode: what the lane is doing with candidate g.  0: the listed candidate's edit distance.  A candidate that fails it
     // hands on to its TaxId's next candidate (index.rs:393), which the same lane then decides: 1: that candidate's prefilter
     // by the edit-distance bound (as in bound mode), 2: its edit distance once the bound has passed it (reads with N only:
-    // without N the two distances are the same number).  Only a successor the bound leaves undecided goes to another round.
-    uint32_t ph = 0, read_n = 0, extra_passed = 0;
+    // without N, or without N in the window, the two distances are the same number).  Only a successor the bound leaves undecided
+    // goes to another round.  Fused mode: every item starts at 1, and what the bound leaves undecided is swept in the same round.
+    uint32_t ph = 0, extra_passed = 0;
+    bool read_n = false;  // the read holds an N
     for (;;) {
         unsigned long long need = __ballot(!active);
         if (need) {
@@ -1386,7 +1397,8 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
             }
             const uint32_t take = bnext + __popcll(need & ((1ull << lane) - 1));
             if (!active && take < bend) {
-                g = a.worklist[take];
+                // (fused mode, round 0: from the worklist's end, where the coalescing kernels put the strands with the most hits)
+                g = a.worklist[FUSED && a.wl_reverse ? n_work - 1 - take : take];
                 if (BOUND) {
                     counted = (g & kSweepFlag) != 0;
                     g &= ~kSweepFlag;
@@ -1454,8 +1466,8 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                 }
                 // edits >= number of read positions that match nothing (N): see k_evaluate
                 hopeless = thr_wrapped || (!BOUND && L - matchable > ED);
-                read_n = L - matchable;
-                ph = 0;
+                read_n = L != matchable;
+                ph = FUSED ? 1 : 0;
                 active = true;
             }
             bnext = min(bnext + (uint32_t)__popcll(need), bend);
@@ -1464,8 +1476,8 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
             if (exhausted) break;
             continue;
         }
-        uint32_t verdict = 0, vg = 0;  // bound mode: 1 = passes the prefilter, 2 = undecided (candidate vg)
-        if (!LIST && active && hopeless) {  // no sweep needed: every candidate of this strand fails
+        uint32_t verdict = 0, vg = 0;  // bound mode: 1 = passes the prefilter, 2 = undecided (candidate vg; fused mode: candidate g)
+        if ((FUSED ? thr_wrapped : !LIST && hopeless) && active) {  // no sweep needed: every candidate of this strand fails
             const uint4 c = a.cand[g];
             if (!BOUND || !counted) {
                 verified++;
@@ -1492,12 +1504,16 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
             uint4 nxt4 = Wn ? fetch_cols(ix, c.x, c.y, strand, 0, swm) : make_uint4(0, 0, 0, 0);
             const uint32_t* lane_tab = &eq_tab[0][0][tid];
             uint32_t j0 = 0;
+            // list mode: bit 2 of the clamped codes that streamed by, i.e. "the window may hold an N" (the don't-care columns
+            // past the window in the last 16 may set it too: that errs to the second pass)
+            uint32_t win_n = 0;
             for (; j0 < Wn; j0 += 16) {
                 if (swm) {  // decided already: passes, or the last row cannot come down to 2*ED any more
                     if (BOUND && best <= (int)ED) break;  // (list mode goes on: its minimum is the edit distance of a read without N)
                     if (best > 2 * (int)ED && score - (int)(Wn - j0) > 2 * (int)ED) break;
                 }
                 const uint4 cur = nxt4;
+                if (LIST) win_n |= cur.x | cur.y | cur.z | cur.w;
                 if (j0 + 16 < Wn) nxt4 = fetch_cols(ix, c.x, c.y, strand, j0 + 16, swm);  // prefetch the next 16 columns
                 const uint32_t lim = min(16u, Wn - j0);
 #pragma unroll
@@ -1554,18 +1570,23 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                     if (nxt == 0xffffffffu || nxt >= maxc) active = false;
                     else g = o + nxt;
                 }
-            } else if (LIST && ph == 1) {  // a successor's prefilter, decided by the bound
+            } else if (LIST && ph == 1) {  // a successor's prefilter (fused mode: every candidate's), decided by the bound
                 if (ed > 2 * ED) {  // refuted (index.rs:406)
+                    if (FUSED) refuted++;
                     a.cand_status[g] = 1;
                     const uint32_t nxt = a.cand_next[g];
                     if (nxt == 0xffffffffu || nxt >= maxc) active = false;
                     else g = o + nxt;
                 } else if (ed > ED) {  // neither bound decides: the sweep of the next round does (counted here: flagged)
-                    a.next_list[atomicAdd(a.next_count, 1u)] = g | kSweepFlag;
+                    if (FUSED) {  // ... of this round: k_sw_pairs runs on und_list after this kernel
+                        verdict = 2;
+                    } else {
+                        a.next_list[atomicAdd(a.next_count, 1u)] = g | kSweepFlag;
+                    }
                     active = false;
-                } else {  // passes the prefilter; without N in the read this number is its edit distance too
+                } else {  // passes the prefilter; with no N in the read, or none in the window, this number is its edit distance too
                     extra_passed++;
-                    if (read_n == 0) {
+                    if (!read_n || !(win_n & 0x04040404u)) {
                         const DevBin bin = ix.bins[c.z];
                         a.out[g] = make_uint4(bin.tax_id, bin.gi, c.x >= bin.start ? c.x - bin.start : 0, ed);
                         a.cand_status[g] = 2;
@@ -1592,8 +1613,8 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
             }
             }
         }
-        if (BOUND) {  // the wavefront's decisions of this trip: one atomic per list
-            const unsigned long long pm = __ballot(verdict == 1), um = __ballot(verdict == 2);
+        if (BOUND || FUSED) {  // the wavefront's decisions of this trip: one atomic per list
+            const unsigned long long pm = BOUND ? __ballot(verdict == 1) : 0ull, um = __ballot(verdict == 2);
             const unsigned long long lower = (1ull << lane) - 1ull;
             if (pm) {
                 uint32_t base = 0;
@@ -1605,17 +1626,19 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                 uint32_t base = 0;
                 if (lane == 0) base = atomicAdd(reinterpret_cast<uint32_t*>(a.counters + a.und_slot), (uint32_t)__popcll(um));
                 base = __builtin_amdgcn_readfirstlane(base);
-                if (verdict == 2) a.und_list[base + (uint32_t)__popcll(um & lower)] = vg | kSweepFlag;  // counted, bounds tried
+                // (fused mode: the lane went idle with the candidate, g still names it)
+                if (verdict == 2) a.und_list[base + (uint32_t)__popcll(um & lower)] = (FUSED ? g : vg) | kSweepFlag;  // counted, bounds tried
             }
         }
     }
+    unsigned long long v64 = verified, w64 = wbytes;
     for (int d = 32; d > 0; d >>= 1) {
-        verified += __shfl_down(verified, d);
-        wbytes += __shfl_down(wbytes, d);
+        v64 += __shfl_down(v64, d);
+        w64 += __shfl_down(w64, d);
     }
-    if (lane == 0 && verified) {
-        atomicAdd(a.n_verified, verified);
-        atomicAdd(a.window_bytes, wbytes);
+    if (lane == 0 && v64) {
+        atomicAdd(a.n_verified, v64);
+        atomicAdd(a.window_bytes, w64);
     }
     if (a.myers_ctr) {  // [0] columns (of W words each) advanced, [1] candidates refuted by the bound
         unsigned long long c64 = cols, r64 = refuted;
@@ -1627,7 +1650,7 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
         for (int d = 32; d > 0; d >>= 1) e64 += __shfl_down(e64, d);
         if (lane == 0) {
             atomicAdd(a.myers_ctr, c64);
-            if (BOUND && r64) atomicAdd(a.myers_ctr + 1, r64);
+            if ((BOUND || FUSED) && r64) atomicAdd(a.myers_ctr + 1, r64);
             if (LIST && e64) atomicAdd(a.myers_ctr + 2, e64);
         }
     }
@@ -1816,6 +1839,7 @@ void launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a_
 #define MYERS_CASE(WW)                                                                                   \
     do {                                                                                                 \
         if (mode == MY_LIST) hipLaunchKernelGGL((k_edit_myers<WW, MY_LIST>), dim3(blocks), dim3(256), 0, s, ix, a);        \
+        else if (mode == MY_FUSED) hipLaunchKernelGGL((k_edit_myers<WW, MY_FUSED>), dim3(blocks), dim3(256), 0, s, ix, a); \
         else if (mode == MY_BOUND) hipLaunchKernelGGL((k_edit_myers<WW, MY_BOUND>), dim3(blocks), dim3(256), 0, s, ix, a); \
         else hipLaunchKernelGGL((k_edit_myers<WW, MY_CHAIN>), dim3(blocks), dim3(256), 0, s, ix, a);                      \
     } while (0)

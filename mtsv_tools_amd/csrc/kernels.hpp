@@ -53,7 +53,7 @@ struct EvalArgs {
     const uint32_t* worklist;     // candidate indices of this round
     const uint32_t* wl_count;
     uint32_t* wl_cursor;         // dynamic scheduling: next unclaimed worklist position
-    uint32_t wl_reverse = 0;     // k_sw_pairs: consume the worklist from its end
+    uint32_t wl_reverse = 0;     // k_sw_pairs, k_edit_myers in fused mode: consume the worklist from its end
     // k_sw_pairs: the lane's counter block (kCtr* slots below) and the slot whose low word holds its worklist length
     uint64_t* counters = nullptr;
     uint32_t wl_count_slot = 0;
@@ -125,6 +125,9 @@ void launch_max_window(hipStream_t s, uint32_t n_strands, const uint32_t* strand
 // (reference order); 2: the recurrence as a two-sided bound on the prefilter's predicate itself -- what it proves to
 // pass goes to a.pass_list, what it refutes is marked failed (and the TaxId's next candidate bounded), the rest goes
 // to a.und_list (count in the low word of counter slot a.und_slot), flagged, for launch_sw_pairs; a.counters set
+// 3: fused -- bound and edit distance of the unfiltered worklist (read from its end when a.wl_reverse) in one pass: refutes
+// as mode 2 does, accepts into a.out what the bound passes when read or window holds no N (a second pass under the edit
+// distance's matches otherwise), and leaves the rest on a.und_list like mode 2; a.pass_list is not written
 void launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a, uint64_t max_items, uint32_t max_len,
                        int mode = 0);
 // reference order for reads <= 253 bases: SW prefilter alone, two candidates per 16-lane group
