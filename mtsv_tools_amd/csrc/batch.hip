@@ -166,6 +166,7 @@ Batch::~Batch() {
         (void)hipFree(p);
     (void)hipFree(d_codes);
     (void)hipFree(d_strip);
+    (void)hipFree(d_planes);
     if (h_hits_stage) pinned_hits_release(h_hits_stage);
     if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
     if (copy_stream) {
@@ -475,6 +476,18 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
             dev_alloc(&d_seed_pre, want, &dummy);
             seed_cap = want;
         }
+        // the reads' bit planes (EvalArgs::planes) for the passes k_edit_myers verifies: k_thin writes them, sized like
+        // the seed slot arrays for a full workspace of reads like these
+        const bool myers_pass = !tiled && pass_max_len <= 253 && (verify_mode == 1 || (sw_pairs && hit_cap < 0x80000000ull));
+        const uint32_t plane_words = myers_pass ? myers_words(pass_max_len) : 0;
+        if ((uint64_t)nr * 3 * plane_words > plane_cap) {
+            (void)hipFree(d_planes);
+            d_planes = nullptr;
+            const uint64_t want = std::max<uint64_t>(nr, ws_reads) * 3 * plane_words;
+            uint64_t dummy = 0;
+            dev_alloc(&d_planes, want, &dummy);
+            plane_cap = want;
+        }
         // ---- seeds ----
         HIP_CHECK(hipEventRecord(ev[0], stream));
         // (d_seed_pre is k_thin's output: until then it holds the list of the slots that take the general code -- an N in
@@ -485,7 +498,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
         HIP_CHECK(hipEventRecord(ev[1], stream));
         if (max_ns)
             launch_thin(stream, sb, so, (uint32_t)r0, nr, p.edit_rate, p.min_seed, max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,
-                        d_seed_pre, d_strand_hits, d_strand_nseeds);
+                        d_seed_pre, d_strand_hits, d_strand_nseeds, myers_pass ? d_planes : nullptr, plane_words);
         else {
             HIP_CHECK(hipMemsetAsync(d_strand_hits, 0, (uint64_t)nstr * 4, stream));
             HIP_CHECK(hipMemsetAsync(d_strand_nseeds, 0, (uint64_t)nstr * 4, stream));
@@ -548,6 +561,8 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
             a.cand = d_cand;
             a.cand_next = d_cand_next;
             a.cand_status = d_cand_status;
+            a.planes = myers_pass ? d_planes : nullptr;
+            a.plane_words = plane_words;
             a.out = d_out;
             a.n_verified = (unsigned long long*)(d_counters + 4);
             a.window_bytes = (unsigned long long*)(d_counters + 5);

@@ -71,6 +71,8 @@ struct Batch {
     DevHit* d_hits = nullptr;
     uint2* d_strip = nullptr;  // tiled long-read kernel: band hand-over strips, allocated when a pass first needs them
     uint64_t strip_cap = 0;
+    uint32_t* d_planes = nullptr;  // bit planes of a pass's reads (EvalArgs::planes): k_thin writes them, k_edit_myers sets up from them
+    uint64_t plane_cap = 0;        // ... in words; allocated when a pass first needs them, for a full workspace of such reads
     uint64_t* h_counters = nullptr;  // pinned
     hipEvent_t ev[15];  // [0..7] stage boundaries of a pass, [8..9] the lane's run, [10..11] around the prefilter kernels, [12] after k_sw_diag,
                         // [13] after the edit-distance bound, [14] after the first round's edit distances

@@ -440,7 +440,8 @@ __global__ __launch_bounds__(256) void k_thin(const uint8_t* __restrict__ bases,
                                               uint32_t max_ns, uint32_t K, uint32_t G, uint64_t max_hits,
                                               uint64_t tune_max_hits, uint32_t* __restrict__ seed_cnt,
                                               uint32_t* __restrict__ seed_pre, uint32_t* __restrict__ strand_hits,
-                                              uint32_t* __restrict__ strand_nseeds) {
+                                              uint32_t* __restrict__ strand_nseeds, uint32_t* __restrict__ planes,
+                                              uint32_t plane_words) {
     uint32_t rs = blockIdx.x * blockDim.x + threadIdx.x;
     if (rs >= n_reads * 2) return;
     uint32_t r = r0 + (rs >> 1);
@@ -473,42 +474,78 @@ __global__ __launch_bounds__(256) void k_thin(const uint8_t* __restrict__ bases,
         nseeds++;
     }
     {
-        // the two strands of a read sit in neighbouring lanes (rs even / odd): the pair counts the read's N once, half of
-        // the read each, and only when one of the strands has seed hits (only such strands can have candidates)
+        // the two strands of a read sit in neighbouring lanes (rs even / odd): the pair loads the read's bytes once, every
+        // other 16-byte group each, and only when one of the strands has seed hits (only such strands can have candidates)
         const bool need = total != 0;
         const int other_need = __shfl_xor((int)need, 1);  // (unconditionally: both lanes of the pair take part in the exchange)
         const bool pair_need = need || other_need != 0;
         const uint32_t ED = (uint32_t)ceil((double)L * edit_rate);  // index.rs:281-282
         bool hopeless = 2ull * ED > (uint64_t)L;
         uint32_t nn = 0;
-        if (pair_need && !hopeless) {
-            // codes are 0..4, N = 4: bit 2 of every byte; aligned 16-byte groups of the code buffer (padded past its end).
-            // The two lanes of the pair share the read's groups (even lane: even groups), and only the first and the last
-            // group hold bytes of the neighbouring reads.
+        // The read's bit planes (kernels.hpp: EvalArgs::planes), from which k_edit_myers sets up its match masks, and the
+        // read's N count as the population count of the N plane.  Strands under the wrapped threshold (2*ED > L) get
+        // their read's image like every other: k_edit_myers sets up an item's masks before it looks at the threshold.
+        if (pair_need) {
+            // codes are 0..4 (k_normalise), N = 4; aligned 16-byte groups of the code buffer (padded past its end).  Group
+            // q0 + 2i + half is this lane's share of chunk i: 32 buffer bytes from the group the read starts in.
             const uint4* b128 = reinterpret_cast<const uint4*>(bases);
             const uint32_t q0 = b0 >> 4, q1 = (b0 + L + 15) >> 4;  // groups [q0, q1)
-            auto masked = [&](uint32_t qi) {
-                const uint4 v = b128[qi];
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                uint32_t cnt = 0;
+            const uint32_t half = rs & 1, sh = b0 & 15u, nw = (L + 31) >> 5;
+            uint32_t* img = planes ? planes + ((uint64_t)(rs >> 1) * plane_words) * 3 : nullptr;
+            uint32_t a0 = 0, a1 = 0, an = 0;  // the chunk before: plane word w is bits [sh, sh + 32) of chunks w, w + 1
+            // groups loaded together, so that the loads of a batch are in flight side by side (k_thin per pass of 10 M reads
+            // of 150 bases: 1.73 ms one group at a time, 1.48 in batches of 3, 1.46 of 5, 1.53 of 6)
+            constexpr uint32_t kAhead = 3;
+            for (uint32_t i0 = 0; i0 <= nw; i0 += kAhead) {
+              uint4 vb[kAhead];
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t byte0 = qi * 16 + 4 * k;  // buffer position of this dword's first byte
-                    uint32_t m = (w[k] >> 2) & 0x01010101u;
-                    const int lo = (int)b0 - (int)byte0, hi = (int)(b0 + L) - (int)byte0;  // valid bytes [lo, hi) of this dword
-                    if (lo > 0) m = lo >= 4 ? 0u : (m & (0xffffffffu << (8 * lo)));
-                    if (hi < 4) m = hi <= 0 ? 0u : (m & ((1u << (8 * hi)) - 1u));
-                    cnt += __popc(m);
+              for (uint32_t u = 0; u < kAhead; u++) {
+                  const uint32_t q = q0 + 2 * (i0 + u) + half;
+                  vb[u] = make_uint4(0, 0, 0, 0);
+                  if (i0 + u <= nw && q < q1) vb[u] = b128[q];
+              }
+#pragma unroll
+              for (uint32_t u = 0; u < kAhead; u++) {
+                const uint32_t i = i0 + u;
+                if (i > nw) break;
+                const uint4 v = vb[u];
+                uint32_t h01 = 0, hn = 0;  // this lane's 16 bytes: plane 0 | plane 1 << 16, N plane
+                {
+                    // eight codes as the nibbles of a dword (byte k: bytes k and 4 + k), then bit b of each:
+                    // x | x >> 7, then | >> 14, brings the bits of four bytes together
+                    const uint32_t c0 = (v.x & 0x07070707u) | ((v.y & 0x07070707u) << 4);
+                    const uint32_t c1 = (v.z & 0x07070707u) | ((v.w & 0x07070707u) << 4);
+                    auto gather = [](uint32_t y) {
+                        y &= 0x11111111u;
+                        y |= y >> 7;
+                        y |= y >> 14;
+                        return y & 0xffu;
+                    };
+                    h01 = gather(c0) | (gather(c1) << 8) | (gather(c0 >> 1) << 16) | (gather(c1 >> 1) << 24);
+                    hn = gather(c0 >> 2) | (gather(c1 >> 2) << 8);
                 }
-                return cnt;
-            };
-            const uint32_t half = rs & 1, ng = q1 - q0;  // group g of the read goes to the lane with (g & 1) == half
-            if (ng >= 1 && half == 0) nn += masked(q0);
-            if (ng >= 2 && half == ((ng - 1) & 1)) nn += masked(q1 - 1);
-            for (uint32_t g = half ? 1 : 2; g + 1 < ng; g += 2) {  // the groups between the two: all bytes are the read's
-                const uint4 v = b128[q0 + g];
-                nn += __popc((v.x >> 2) & 0x01010101u) + __popc((v.y >> 2) & 0x01010101u) + __popc((v.z >> 2) & 0x01010101u) +
-                      __popc((v.w >> 2) & 0x01010101u);
+                // the neighbour's half of the chunk (quad_perm [1,0,3,2]; both lanes of a pair run the same trips)
+                const uint32_t o01 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h01, 0xB1, 0xf, 0xf, false);
+                const uint32_t on = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hn, 0xB1, 0xf, 0xf, false);
+                const uint32_t lo01 = half ? o01 : h01, hi01 = half ? h01 : o01;
+                const uint32_t c0 = (lo01 & 0xffffu) | (hi01 << 16), c1 = (lo01 >> 16) | (hi01 & 0xffff0000u);
+                const uint32_t cn = half ? (on | (hn << 16)) : (hn | (on << 16));
+                if (i && ((i - 1) & 1) == half) {  // word i - 1 is complete; the pair's lanes take the words in turn
+                    const uint32_t w = i - 1, left = L - 32 * w;  // bits past the read (the next read's bytes) are cleared
+                    const uint32_t m = left >= 32 ? 0xffffffffu : (1u << left) - 1u;
+                    const uint32_t w0 = __builtin_amdgcn_alignbit(c0, a0, sh) & m, w1 = __builtin_amdgcn_alignbit(c1, a1, sh) & m,
+                                   wn = __builtin_amdgcn_alignbit(cn, an, sh) & m;
+                    nn += __popc(wn);
+                    if (img) {
+                        img[3 * w] = w0;
+                        img[3 * w + 1] = w1;
+                        img[3 * w + 2] = wn;
+                    }
+                }
+                a0 = c0;
+                a1 = c1;
+                an = cn;
+              }
             }
         }
         nn += (uint32_t)__shfl_xor((int)nn, 1);  // the pair's two halves (every lane takes part in the exchange)
@@ -784,9 +821,9 @@ void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, 
 
 void launch_thin(hipStream_t s, const uint8_t* bases, const uint32_t* read_off, uint32_t r0, uint32_t n_reads, double edit_rate,
                  double min_seed, uint32_t max_ns, uint32_t K, uint32_t G, uint64_t max_hits, uint64_t tune, uint32_t* seed_cnt, uint32_t* seed_pre,
-                 uint32_t* strand_hits, uint32_t* strand_nseeds) {
+                 uint32_t* strand_hits, uint32_t* strand_nseeds, uint32_t* planes, uint32_t plane_words) {
     hipLaunchKernelGGL(k_thin, dim3(cdiv((uint64_t)n_reads * 2, 256)), dim3(256), 0, s, bases, read_off, r0, n_reads, edit_rate,
-                       min_seed, max_ns, K, G, max_hits, tune, seed_cnt, seed_pre, strand_hits, strand_nseeds);
+                       min_seed, max_ns, K, G, max_hits, tune, seed_cnt, seed_pre, strand_hits, strand_nseeds, planes, plane_words);
 }
 
 void launch_scan(hipStream_t s, const uint32_t* in, uint32_t n, uint64_t* tile_sums, uint64_t* total, uint32_t* out) {

@@ -1361,7 +1361,6 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
     const uint32_t n_work = *a.wl_count;
     const uint32_t maxc = a.maxc;  // max_candidates as a rank bound, clamped on the host
     const uint32_t lane = lane_id();
-    const uint32_t* bases32 = reinterpret_cast<const uint32_t*>(a.bases);
     uint32_t verified = 0, wbytes = 0;  // per lane: far below 2^32 in one launch, like cols
     uint32_t cols = 0, refuted = 0;  // columns this lane's recurrences advanced; bound and fused mode: candidates it refuted
     // wave-uniform slice of the worklist, claimed 256 items at a time; a lane whose candidate passed
@@ -1413,60 +1412,48 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                 thr_wrapped = 2ull * ED > (uint64_t)L;
                 // masks of the FORWARD read; the reverse strand walks the window backwards with
                 // complemented symbols instead (edit distance is invariant under reversing both strings)
+                // From the read's bit planes (k_thin; EvalArgs::planes): plane word j holds read positions 32j .. 32j+31, and
+                // rows 32k .. 32k+31 hold read positions 32k - pad .. (negative: wildcard rows), so a row word is two
+                // neighbouring plane words funnel-shifted up by pad.  Words outside the read's own are not loaded: they
+                // read as 0, which makes every wildcard row a row of base code 0 without N.
                 const int pad = 32 * W - (int)L;
-                uint32_t matchable = 0;
+                const uint32_t nw = (L + 31) >> 5, pw = (uint32_t)(pad + 31) >> 5, sh = (uint32_t)(-pad) & 31u;
+                const uint32_t* img = a.planes + ((uint64_t)(rs >> 1) * a.plane_words) * 3;
+                uint32_t P0[W + 1], P1[W + 1], PN[W + 1];  // plane words j - pw
+#pragma unroll
+                for (int j = 0; j <= W; j++) {
+                    const uint32_t idx = (uint32_t)j - pw;
+                    P0[j] = P1[j] = PN[j] = 0;
+                    if (idx < nw) {
+                        P0[j] = img[3 * idx];
+                        P1[j] = img[3 * idx + 1];
+                        PN[j] = img[3 * idx + 2];
+                    }
+                }
+                uint32_t read_ns = 0;
 #pragma unroll
                 for (int k = 0; k < W; k++) {
-                    // rows 32k .. 32k+31 hold read positions q0 .. q0+31 (negative: wildcard rows)
-                    const int q0 = 32 * k - pad;
-                    uint32_t mA = 0, mC = 0, mG = 0, mT = 0, wild = 0;
-                    if (q0 + 31 >= 0) {
-                        const long long byte0 = (long long)b0 + q0;  // may point before this read (or the buffer)
-                        const uint32_t sh = (uint32_t)(byte0 & 3), dsel = (uint32_t)(byte0 >> 2) & 3u;
-                        // the word's 33..36 bytes as three aligned 16-byte loads and a select (see load16): nine dword loads
-                        // per word made the set-up two thirds of the kernel's load instructions
-                        const long long q16 = byte0 >> 4;
-                        const uint4* bases128 = reinterpret_cast<const uint4*>(bases32);
-                        const uint4 zero4 = make_uint4(0, 0, 0, 0);
-                        const uint4 l0 = q16 >= 0 ? bases128[q16] : zero4, l1 = q16 + 1 >= 0 ? bases128[q16 + 1] : zero4,
-                                    l2 = q16 + 2 >= 0 ? bases128[q16 + 2] : zero4;
-                        const uint32_t dd[12] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w, l2.x, l2.y, l2.z, l2.w};
-                        uint32_t d[9];
-#pragma unroll
-                        for (int j = 0; j < 9; j++) d[j] = dsel == 0 ? dd[j] : dsel == 1 ? dd[j + 1] : dsel == 2 ? dd[j + 2] : dd[j + 3];
-#pragma unroll
-                        for (int j = 0; j < 8; j++) {
-                            const uint32_t four = __builtin_amdgcn_alignbyte(d[j + 1], d[j], sh);
-#pragma unroll
-                            for (int q = 0; q < 4; q++) {
-                                const int bit_i = 4 * j + q;
-                                const uint32_t code = (four >> (8 * q)) & 0xffu;  // already a code (k_normalise)
-                                const uint32_t bit = 1u << bit_i;
-                                const bool real = q0 + bit_i >= 0;
-                                mA |= (real && code == 0) ? bit : 0u;
-                                mC |= (real && code == 1) ? bit : 0u;
-                                mG |= (real && code == 2) ? bit : 0u;
-                                mT |= (real && code == 3) ? bit : 0u;
-                                wild |= real ? 0u : bit;
-                            }
-                        }
-                    } else {
-                        wild = 0xffffffffu;
-                    }
-                    matchable += __popc(mA | mC | mG | mT);
+                    const uint32_t p0 = __builtin_amdgcn_alignbit(P0[k + 1], P0[k], sh), p1 = __builtin_amdgcn_alignbit(P1[k + 1], P1[k], sh),
+                                   pn = __builtin_amdgcn_alignbit(PN[k + 1], PN[k], sh);
+                    const int below = pad - 32 * k;  // wildcard rows of this word
+                    const uint32_t wild = below >= 32 ? 0xffffffffu : below <= 0 ? 0u : (1u << below) - 1u;
+                    // (a wildcard row has p0 = p1 = pn = 0: it is in mA already)
+                    const uint32_t mA = ~(p0 | p1 | pn), mC = (p0 & ~p1 & ~pn) | wild, mG = (p1 & ~p0 & ~pn) | wild,
+                                   mT = (p0 & p1 & ~pn) | wild;
+                    read_ns += __popc(pn);
                     // reverse strand: the window is walked backwards and row c answers for the complement of c
-                    eq_tab[0][k][tid] = (strand ? mT : mA) | wild;
-                    eq_tab[1][k][tid] = (strand ? mG : mC) | wild;
-                    eq_tab[2][k][tid] = (strand ? mC : mG) | wild;
-                    eq_tab[3][k][tid] = (strand ? mA : mT) | wild;
+                    eq_tab[0][k][tid] = strand ? mT : mA;
+                    eq_tab[1][k][tid] = strand ? mG : mC;
+                    eq_tab[2][k][tid] = strand ? mC : mG;
+                    eq_tab[3][k][tid] = strand ? mA : mT;
                     eq_tab[4][k][tid] = wild;
                     // every read position that is no base is an N (k_normalise): it matches a window N in the SW matrix only
-                    if (NROW == 6) eq_tab[5][k][tid] = ~(mA | mC | mG | mT);
+                    if (NROW == 6) eq_tab[5][k][tid] = pn | wild;
                     pv0[k] = ~wild;
                 }
                 // edits >= number of read positions that match nothing (N): see k_evaluate
-                hopeless = thr_wrapped || (!BOUND && L - matchable > ED);
-                read_n = L != matchable;
+                hopeless = thr_wrapped || (!BOUND && read_ns > ED);
+                read_n = read_ns != 0;
                 ph = FUSED ? 1 : 0;
                 active = true;
             }
@@ -1830,12 +1817,13 @@ void launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a_
                        int mode) {
     EvalArgs a = a_;
     a.maxc = rank_bound(a.max_candidates);
+    if (!a.planes || a.plane_words != myers_words(max_len)) throw std::runtime_error("internal: k_edit_myers needs the pass's read planes");
     // max_items bounds the work list from far above (seed hits, not candidates); a grid of one resident generation at
     // most, and smaller when the list is short: workgroups cost ~0.1 us each to dispatch, with work or without, and
     // the lists are claimed 64 candidates at a time whatever the grid
     // (4096, 1024 or 512 hits per workgroup: the same within the noise on passes of 84 k to 1 M reads)
     uint32_t blocks = std::max<uint32_t>(16, std::min<uint32_t>(cdiv(max_items, 4096), 256 * 5));
-    uint32_t W = (max_len + 31) / 32;
+    const uint32_t W = myers_words(max_len);
 #define MYERS_CASE(WW)                                                                                   \
     do {                                                                                                 \
         if (mode == MY_LIST) hipLaunchKernelGGL((k_edit_myers<WW, MY_LIST>), dim3(blocks), dim3(256), 0, s, ix, a);        \
@@ -1843,12 +1831,12 @@ void launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a_
         else if (mode == MY_BOUND) hipLaunchKernelGGL((k_edit_myers<WW, MY_BOUND>), dim3(blocks), dim3(256), 0, s, ix, a); \
         else hipLaunchKernelGGL((k_edit_myers<WW, MY_CHAIN>), dim3(blocks), dim3(256), 0, s, ix, a);                      \
     } while (0)
-    if (W <= 2) MYERS_CASE(2);
-    else if (W <= 3) MYERS_CASE(3);
-    else if (W <= 4) MYERS_CASE(4);
-    else if (W <= 5) MYERS_CASE(5);
-    else if (W <= 6) MYERS_CASE(6);
-    else if (W <= 7) MYERS_CASE(7);
+    if (W == 2) MYERS_CASE(2);
+    else if (W == 3) MYERS_CASE(3);
+    else if (W == 4) MYERS_CASE(4);
+    else if (W == 5) MYERS_CASE(5);
+    else if (W == 6) MYERS_CASE(6);
+    else if (W == 7) MYERS_CASE(7);
     else MYERS_CASE(8);
 #undef MYERS_CASE
 }

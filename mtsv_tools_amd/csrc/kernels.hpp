@@ -6,6 +6,7 @@
 //
 //   k_search    lane per (read, strand, seed): FMIndex::backward_search           index.rs:305
 //   k_thin      lane per strand: adaptive seed thinning / max_hits filter         index.rs:293-344,354
+//               (and, a lane pair per read: the read's bit planes for k_edit_myers, its N count)
 //   scan        exclusive scan of per-strand seed-hit counts
 //   k_expand    lane per kept seed: its SA rows / text positions (Interval::occ)  index.rs:347-352
 //   k_locate    lane per seed hit with wavefront refill: SampledSuffixArray::get  index.rs:347
@@ -75,10 +76,20 @@ struct EvalArgs {
     // tiled long-read kernel: one strip of strip_len window columns per 16-lane group (bottom row of a band)
     uint2* strip = nullptr;
     uint32_t strip_len = 0;
+    // k_edit_myers: the bit planes of the pass's reads, written by k_thin for every read with a seed hit on either strand
+    // (only those have work items; the others' entries are never written nor read).  Read i of the pass (i = strand index
+    // >> 1) owns 3 * plane_words words at planes[3 * plane_words * i]: word j of its planes at [3j] (bit 0 of the code),
+    // [3j + 1] (bit 1) and [3j + 2] (is N, code >= 4), base q of the forward read being bit q & 31 of word q >> 5.  Bits past
+    // the read's end are 0; words past its last are not written.  plane_words = myers_words(longest read of the pass).
+    const uint32_t* planes = nullptr;
+    uint32_t plane_words = 0;
     // filled in by the launchers
     uint32_t maxc = 0xffffffffu;  // max_candidates as a bound on candidate ranks
     uint32_t claim_shift = 0;     // k_sw_pairs: work items per claim = clamp(n_work >> claim_shift, 4, 32)
 };
+
+// 32-bit words per column k_edit_myers<W> runs a pass whose longest read has max_len bases with (reads up to 253 bases)
+inline uint32_t myers_words(uint32_t max_len) { return std::min(std::max((max_len + 31) / 32, 2u), 8u); }
 
 constexpr uint32_t kMaxRegisterReadLen = 256;  // 16 lanes x 16 read rows per lane: k_evaluate with the whole matrix band in registers
 constexpr uint32_t kMaxReadLen = 32767;        // the tiled kernel's packed 16-bit cells (edit distance <= read length)
@@ -96,10 +107,11 @@ void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, 
 // (the caller compares *slow_count with it afterwards)
 // strand_nseeds receives one word per strand for the coalescing kernels: min_seeds (index.rs:358) | edit tolerance << 16 |
 // a flag for the strands no candidate of which can be accepted (more N in the read than the edit tolerance, or the usize
-// wrap of index.rs:406)
+// wrap of index.rs:406).  planes (may be null: a pass k_edit_myers does not verify): the bit planes of EvalArgs::planes,
+// plane_words words per plane and read
 void launch_thin(hipStream_t s, const uint8_t* bases, const uint32_t* read_off, uint32_t r0, uint32_t n_reads, double edit_rate,
                  double min_seed, uint32_t max_ns, uint32_t K, uint32_t G, uint64_t max_hits, uint64_t tune, uint32_t* seed_cnt, uint32_t* seed_pre,
-                 uint32_t* strand_hits, uint32_t* strand_nseeds);
+                 uint32_t* strand_hits, uint32_t* strand_nseeds, uint32_t* planes, uint32_t plane_words);
 // out has n+1 entries (out[n] = total); tile_sums needs scan_tiles(n) entries
 void launch_scan(hipStream_t s, const uint32_t* in, uint32_t n, uint64_t* tile_sums, uint64_t* total, uint32_t* out);
 uint32_t scan_tiles(uint32_t n);
