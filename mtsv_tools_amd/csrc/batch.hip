@@ -258,6 +258,8 @@ void Batch::finish_lane() {
     HIP_CHECK(hipEventElapsedTime(&stage_acc[7], ev[8], ev[9]));
     if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] last pass: %llu strands of 13..64 seed hits (or more than 4 candidates) to k_coalesce_mid, %llu heavier ones\n",
                                       (unsigned long long)(h_counters[15] & 0xffffffffull), (unsigned long long)(h_counters[1] >> 32));
+    if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] k_coalesce_heavy: %llu strands walked by runs, %llu by the wavefront walk (a run too long)\n",
+                                      (unsigned long long)(h_counters[kCtrHeavyWalk] & 0xffffffffull), (unsigned long long)(h_counters[kCtrHeavyWalk] >> 32));
     stats.sw_cell_pairs = h_counters[14];
     stats.sw_prefilter_ms = sw_ms_acc;
     stats.sw_sweep_ms = sweep_ms_acc;
@@ -494,7 +496,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
         //  the seed's table part; counter slot 22.  The second kernel's grid covers the share of such slots the passes before
         //  had, half as much again: the count is checked at the pass's first round trip below.)
         const uint32_t listed_cap = (uint32_t)std::min<uint64_t>(slots, std::max<uint64_t>(4096, (uint64_t)((double)slots * listed_share)));
-        launch_search(stream, v, sb, so, (uint32_t)r0, nr, max_ns, K, G, d_seed_lo, d_seed_cnt, d_seed_pre, (uint32_t*)(d_counters + 22), listed_cap);
+        launch_search(stream, v, sb, so, (uint32_t)r0, nr, max_ns, K, G, d_seed_lo, d_seed_cnt, d_seed_pre, (uint32_t*)(d_counters + 22), listed_cap, di->d_kmer_levels);
         HIP_CHECK(hipEventRecord(ev[1], stream));
         if (max_ns)
             launch_thin(stream, sb, so, (uint32_t)r0, nr, p.edit_rate, p.min_seed, max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,

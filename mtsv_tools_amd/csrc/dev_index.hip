@@ -34,6 +34,7 @@ DeviceIndex::~DeviceIndex() {
     (void)hipFree(d_bins);
     (void)hipFree(d_bin_lut);
     (void)hipFree(d_kmer);
+    (void)hipFree(d_kmer_levels);
 }
 
 namespace {
@@ -341,15 +342,34 @@ std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint3
             HIP_CHECK(hipMalloc((void**)&ta, entries * 8));
             HIP_CHECK(hipMalloc((void**)&tb, std::max<uint64_t>(entries / 4, 4) * 8));
         }
+        // the first levels are kept (dev_layout.hpp: kmer_level_start): a seed with an N in its table part starts from the
+        // entry of the symbols behind its last N.  Each is copied as it is finished, before its buffer is written again
+        // and before the table's singleton entries are tagged.
+        const char* kl = getenv("MTSV_KMER_LEVELS");
+        // (MTSV_KMER_LEVELS=0 builds none, for an A/B in one build; the sampled-SA mode, which is there to save memory, has none)
+        const uint32_t n_levels = ((kl && atoi(kl) == 0) || !v.sa_full) ? 0 : std::min(k, kKmerLevelsMax);
+        uint64_t level_bytes = 0;
+        if (n_levels) {
+            level_bytes = (uint64_t)kmer_level_start(n_levels + 1) * sizeof(uint2);
+            HIP_CHECK(hipMalloc((void**)&di->d_kmer_levels, level_bytes));
+            di->bytes += level_bytes;
+        }
+        auto keep_level = [&](uint32_t lvl, const uint2* src) {
+            if (lvl <= n_levels)
+                HIP_CHECK(hipMemcpyAsync(di->d_kmer_levels + kmer_level_start(lvl), src, (sizeof(uint2)) << (2 * lvl),
+                                         hipMemcpyDeviceToDevice, 0));
+        };
         // ping-pong so the last level lands in `ta`
         uint2* cur = (k % 2 == 1) ? ta : tb;
         uint2* oth = (k % 2 == 1) ? tb : ta;
         hipLaunchKernelGGL(k_kmer_level1, dim3(1), dim3(64), 0, 0, v, cur);
+        keep_level(1, cur);
         for (uint32_t lvl = 2; lvl <= k; lvl++) {
             const uint64_t total = 1ull << (2 * lvl);
             hipLaunchKernelGGL(k_kmer_level, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 1u << 22)), dim3(256), 0, 0, v, cur, oth,
                                2 * (lvl - 1));
             std::swap(cur, oth);
+            keep_level(lvl, cur);
         }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
@@ -358,6 +378,8 @@ std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint3
         di->bytes += entries * 8;
         v.kmer_tab = di->d_kmer;
         v.kmer_k = k;
+        if (getenv("MTSV_TRACE"))
+            fprintf(stderr, "[upload] kmer levels 1..%u kept: %llu bytes\n", n_levels, (unsigned long long)level_bytes);
         // singleton k-mers carry their text position (full SA only: the sampled-SA mode keeps its LF-walk locate)
         const char* kp = getenv("MTSV_KMER_POS");
         if (v.sa_full && !(kp && atoi(kp) == 0)) {

@@ -27,6 +27,7 @@ struct DeviceIndex {
     DevBin* d_bins = nullptr;
     uint32_t* d_bin_lut = nullptr;
     uint2* d_kmer = nullptr;
+    uint2* d_kmer_levels = nullptr;  // levels 1..min(kmer_k, kKmerLevelsMax) of the table's construction (dev_layout.hpp), or null
     DevIndexView view{};
     uint64_t bytes = 0;
     uint32_t flags = 0;

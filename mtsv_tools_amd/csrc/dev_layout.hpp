@@ -71,6 +71,12 @@ __host__ __device__ inline uint2 kmer_tag_entry(uint32_t p, uint32_t c1, uint32_
     return make_uint2(p, kKmerTag | c1 | (c2 << 3));
 }
 
+// The levels of the k-mer table's construction that are kept next to it (DeviceIndex::d_kmer_levels): level j, 1 <= j <=
+// min(kmer_k, kKmerLevelsMax), holds the plain SA interval (lo, hi) of every ACGT j-mer -- never a tagged entry -- indexed
+// like the table, first symbol highest, and starts at entry kmer_level_start(j).  Levels 1..12 are 179 MB.
+constexpr uint32_t kKmerLevelsMax = 12;
+__host__ __device__ inline uint32_t kmer_level_start(uint32_t j) { return ((1u << (2 * j)) - 4u) / 3u; }
+
 // seed_cnt value of a seed slot that resolved to one hit whose text position is known (seed_lo holds it).  No
 // interval count reaches it (n < 0xFFFFFF00).
 constexpr uint32_t kSeedAtPos = 0xFFFFFFFFu;

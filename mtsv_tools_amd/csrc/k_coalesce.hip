@@ -1,5 +1,7 @@
 // k_coalesce.hip -- coalesce_seed_sites, min_seeds, stable rank, same-TaxId chains (index.rs:358-369,435-487)
 // (one of the three kernel files of the hot path; the stage map is in kernels.hpp / DESIGN.md section 3)
+#include <cstring>
+
 #include "kernels_common.hpp"
 
 namespace mtsv {
@@ -23,7 +25,9 @@ __device__ inline uint64_t wave_bitonic_sort(uint64_t key) {
 
 // first bin whose end > site (the forward-only cursor of index.rs:455-458 on sorted hits): a coarse
 // table gives the first bin that can hold the site's bucket, then a short forward scan
-__device__ inline uint32_t find_bin(const DevIndexView& ix, uint32_t site) {
+// (V: the index view, or the BinView cut of it)
+template <class V>
+__device__ inline uint32_t find_bin(const V& ix, uint32_t site) {
     const uint32_t k = site >> ix.bin_lut_shift;
     uint32_t lo = ix.bin_lut[k], hi = ix.bin_lut[k + 1];  // the answer lies in [lo, hi]; usually lo == hi
     while (lo < hi) {
@@ -155,12 +159,134 @@ struct HeavyArgs {
     uint32_t* strand_ncand;
     uint32_t* worklist;
     uint32_t* wl_count;
-    unsigned long long* n_cand_total;
+    unsigned long long* n_cand_total;  // slot 3 of the lane's counter block (heavy_counter)
+};
+// slot `slot` of the counter block (no pointer of its own in the argument block: the kernel sits at the scalar register file's limit)
+__device__ inline uint32_t* heavy_counter(const HeavyArgs& a, uint32_t slot) {
+    return reinterpret_cast<uint32_t*>(a.n_cand_total + slot - 3);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The walk of index.rs:445-485 by runs.  The walk is serial only inside a run of hits that are all `ok` and lie in one
+// bin: merging needs `have && ok && b == w.b`, and w.b is always the bin of the hit before (a merged hit has the
+// segment's bin, any other hit starts a segment with its own).  So at a hit that is not ok, that follows one that is
+// not ok, or whose bin differs from that of the hit before, the serial walk flushes what it has and starts from this hit
+// alone -- exactly what a walk that starts there with empty state does.  A thread walks each run; a kept segment
+// is recorded at its last hit (cand_tmp entry of that hit, one bit of `kept`), and a scan over the bits moves the
+// records to the front in hit order, which is the serial walk's order.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kRunMax = 256;  // hits of one run a single thread walks; a strand with a longer run (a tandem repeat inside
+                                   // one sequence) takes the wavefront walk
+struct RunMem {  // LDS next to the keys
+    uint32_t bin[kHeavyKeysSmall];        // bin of the hit | ok << 31
+    uint32_t kept[kHeavyKeysSmall / 32];  // bit i: a candidate's segment ends at hit i
+    uint32_t too_long;
+    uint32_t wave_sum[256 / kWave];
+};
+static_assert(kHeavyKeysSmall == 256 * 8, "walk_by_runs: eight hits per thread in the compaction");
+struct BinView {  // what find_bin and the windows need of the index view
+    const uint32_t* bin_end;
+    const DevBin* bins;
+    uint32_t n_bins;
+    const uint32_t* bin_lut;
+    uint32_t bin_lut_shift;
 };
 
-// BLK: called by every thread of the workgroup (contains barriers); !BLK: by one wavefront
+// every thread of the workgroup; keys[0, nh) sorted (reference, query) keys on entry, (ws | we << 32) of each hit on return.
+// Returns kRunTooLong when a run was too long (rm.bin and keys then serve the wavefront walk), else the candidate count.
+// Not inlined on purpose: the caller's argument block and index view would otherwise all be live across this body (SGPR spills).
+constexpr uint32_t kRunTooLong = 0xffffffffu;
+__device__ __attribute__((noinline)) uint32_t walk_by_runs(BinView ix, StrandGeom g, uint64_t* keys, RunMem& rm, uint32_t nh, uint64_t* ct) {
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < nh; i += 256) {
+        const uint64_t key = keys[i];
+        const uint32_t site = (uint32_t)(key >> 32), q = (uint32_t)key;
+        const uint32_t b = min(find_bin(ix, site), ix.n_bins - 1);
+        const DevBin bin = ix.bins[b];
+        uint32_t ws, we;
+        const bool ok = candidate_window(site, q, bin, g.L, g.ED, &ws, &we);
+        keys[i] = ((uint64_t)we << 32) | ws;  // (only this thread reads or writes entry i up to the barrier)
+        rm.bin[i] = b | (ok ? 0x80000000u : 0u);
+    }
+    if (tid < kHeavyKeysSmall / 32) rm.kept[tid] = 0;
+    if (tid == 0) rm.too_long = 0;
+    __syncthreads();
+    for (uint32_t h = tid; h < nh; h += 256) {
+        const uint32_t v = rm.bin[h];
+        if (!(v >> 31)) continue;                  // not ok: a run of its own, and no candidate
+        if (h && rm.bin[h - 1] == v) continue;     // not a run's first hit
+        const uint32_t b = v & 0x7fffffffu;
+        const uint64_t se = keys[h];
+        uint32_t s = (uint32_t)se, e = (uint32_t)(se >> 32), n = 1;
+        auto keep = [&](uint32_t last) {  // index.rs:467-469, 481-485
+            if (n >= g.min_seeds) {
+                gstore(ct + 2ull * last, ((uint64_t)e << 32) | s);
+                gstore(ct + 2ull * last + 1, ((uint64_t)n << 32) | b);
+                atomicOr(&rm.kept[last >> 5], 1u << (last & 31));
+            }
+        };
+        uint32_t j = h + 1;
+        for (; j < nh && rm.bin[j] == v; j++) {
+            if (j - h >= kRunMax) {
+                rm.too_long = 1;
+                break;
+            }
+            const uint64_t x = keys[j];
+            const uint32_t wsj = (uint32_t)x, wej = (uint32_t)(x >> 32);
+            if ((s <= wsj && wsj < e) || (s < wej && wej <= e)) {  // add_seed_hit, index.rs:216-229
+                s = min(s, wsj);
+                e = max(e, wej);
+                n++;
+            } else {
+                keep(j - 1);
+                s = wsj; e = wej; n = 1;
+            }
+        }
+        keep(j - 1);
+    }
+    wave_mem_sync();
+    __syncthreads();
+    if (rm.too_long) return kRunTooLong;
+    // thread t owns hits [8t, 8t + 8): its records into registers, a scan over the counts, then to the front
+    const uint32_t bits = (rm.kept[tid >> 2] >> (8 * (tid & 3))) & 0xffu;
+    const uint32_t cnt = __popc(bits);
+    uint32_t incl = cnt;
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+        if (lane_id() >= (uint32_t)d) incl += up;
+    }
+    if (lane_id() == kWave - 1) rm.wave_sum[tid / kWave] = incl;
+    uint64_t r0[8], r1[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        r0[k] = r1[k] = 0;
+        if (bits >> k & 1) {
+            r0[k] = gload(ct + 2ull * (8 * tid + k));
+            r1[k] = gload(ct + 2ull * (8 * tid + k) + 1);
+        }
+    }
+    __syncthreads();  // every record is in registers before its place may be written
+    uint32_t pos = incl - cnt, total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 256 / kWave; w++) {
+        if (w < tid / kWave) pos += rm.wave_sum[w];
+        total += rm.wave_sum[w];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (bits >> k & 1) {
+            gstore(ct + 2ull * pos, r0[k]);
+            gstore(ct + 2ull * pos + 1, r1[k]);
+            pos++;
+        }
+    return total;
+}
+
+// BLK: called by every thread of the workgroup (contains barriers); !BLK: by one wavefront.  rm: the walk by runs
+// (BLK only), or null for the wavefront walk.  Returns whether the strand was walked by runs (the same in every thread).
 template <bool BLK>
-__device__ void coalesce_big(const DevIndexView& ix, const HeavyArgs& a, uint32_t rs, KeyMem<BLK> km, uint32_t* sh_nc) {
+__device__ bool coalesce_big(const DevIndexView& ix, const HeavyArgs& a, uint32_t rs, KeyMem<BLK> km, uint32_t* sh_nc,
+                             RunMem* rm = nullptr) {
     const uint32_t lane = lane_id();
     const uint32_t tid = km.tid(), nt = km.nthreads();
     const bool walker = !BLK || threadIdx.x < kWave;  // the sequential walk runs on one wavefront
@@ -174,7 +300,15 @@ __device__ void coalesce_big(const DevIndexView& ix, const HeavyArgs& a, uint32_
     big_sort(km, nh);  // seed_hits.sort(), index.rs:443
     uint32_t nc = 0;
     uint64_t* ct = a.cand_tmp + 2ull * o;
-    if (walker) {
+    bool by_runs = false, pre = false;  // pre: the hits' windows and bins are in LDS already (a run was too long)
+    if (BLK && rm) {
+        nc = walk_by_runs(BinView{ix.bin_end, ix.bins, ix.n_bins, ix.bin_lut, ix.bin_lut_shift}, g, km.p, *rm, nh, ct);
+        by_runs = nc != kRunTooLong;
+        pre = !by_runs;
+        if (!by_runs) nc = 0;
+        else if (threadIdx.x == 0) *sh_nc = nc;
+    }
+    if (walker && !by_runs) {
         Walk w{false, 0, 0, 0, 0};
         for (uint32_t base = 0; base < nh; base += kWave) {
             uint32_t cntv = min((uint32_t)kWave, nh - base);
@@ -182,10 +316,17 @@ __device__ void coalesce_big(const DevIndexView& ix, const HeavyArgs& a, uint32_
             bool ok = false;
             if (lane < cntv) {
                 uint64_t key = km.ld(base + lane);
-                uint32_t site = (uint32_t)(key >> 32), q = (uint32_t)key;
-                b = min(find_bin(ix, site), ix.n_bins - 1);
-                DevBin bin = ix.bins[b];
-                ok = candidate_window(site, q, bin, g.L, g.ED, &ws, &we);
+                if (pre) {
+                    ws = (uint32_t)key;
+                    we = (uint32_t)(key >> 32);
+                    b = rm->bin[base + lane] & 0x7fffffffu;
+                    ok = (rm->bin[base + lane] >> 31) != 0;
+                } else {
+                    uint32_t site = (uint32_t)(key >> 32), q = (uint32_t)key;
+                    b = min(find_bin(ix, site), ix.n_bins - 1);
+                    DevBin bin = ix.bins[b];
+                    ok = candidate_window(site, q, bin, g.L, g.ED, &ws, &we);
+                }
             }
             for (uint32_t i = 0; i < cntv; i++) {
                 uint32_t wsi = __builtin_amdgcn_readlane(ws, i), wei = __builtin_amdgcn_readlane(we, i);
@@ -238,7 +379,7 @@ __device__ void coalesce_big(const DevIndexView& ix, const HeavyArgs& a, uint32_
             }
         }
         km.sync();  // the key array is free for the next strand
-        return;
+        return by_runs;
     }
     // rank: sort (num_seeds descending, walk order ascending) -- the stable sort of index.rs:369
     for (uint32_t i = tid; i < nc; i += nt) {
@@ -291,26 +432,56 @@ __device__ void coalesce_big(const DevIndexView& ix, const HeavyArgs& a, uint32_
         if (nc) atomicAdd(a.n_cand_total, (unsigned long long)nc);
     }
     km.sync();  // the key array is free for the next strand
+    return by_runs;
 }
 
 // The heavy strands sit at the END of the strand list (entry list_len - 1 - h), the 17..64-hit ones at its front.
 // KEYS = kHeavyKeysSmall takes the strands of up to that many hits, KEYS = kHeavyKeys all longer ones.
-template <uint32_t KEYS>
+// RUNS (with KEYS = kHeavyKeysSmall only): the walk by runs, and the workgroups claim their strands from a ticket (counter
+// slot kCtrHeavyTicket, zero at launch) instead of striding over the list: a strand takes from a few to a few hundred
+// microseconds, and the kernel ended with its unluckiest workgroup.
+template <uint32_t KEYS, bool RUNS>
 __global__ __launch_bounds__(256) void k_coalesce_heavy(DevIndexView ix, HeavyArgs a, const uint32_t* __restrict__ heavy_list,
                                                         uint32_t list_len, const uint32_t* __restrict__ heavy_count) {
+    static_assert(!RUNS || KEYS == kHeavyKeysSmall, "the walk by runs is sized for the small key array");
     __shared__ uint64_t lk[KEYS];
     __shared__ uint32_t sh_nc;
+    __shared__ RunMem rm;  // (referenced, and so allocated, with RUNS only)
+    __shared__ uint32_t sh_ticket;
     const uint32_t n_heavy = *heavy_count;
-    for (uint32_t h = blockIdx.x; h < n_heavy; h += gridDim.x) {
+    uint32_t n_walked = 0;  // strands walked by runs (low half) / by the wavefront (high half); a vector register on purpose
+    uint32_t h = blockIdx.x;
+    for (;;) {
+        if (RUNS) {
+            if (threadIdx.x == 0) sh_ticket = atomicAdd(heavy_counter(a, kCtrHeavyTicket), 1u);
+            __syncthreads();
+            h = sh_ticket;
+        }
+        if (h >= n_heavy) break;
         const uint32_t rs = heavy_list[list_len - 1 - h];
         const uint32_t nh = a.strand_off[rs + 1] - a.strand_off[rs];
-        if (KEYS == kHeavyKeysSmall ? nh > kHeavyKeysSmall : nh <= kHeavyKeysSmall) continue;  // the other instantiation's
-        if (nh <= KEYS) {
-            coalesce_big<true>(ix, a, rs, KeyMem<true>{lk}, &sh_nc);
-        } else {
-            if (threadIdx.x < kWave) coalesce_big<false>(ix, a, rs, KeyMem<false>{a.hit_key + a.strand_off[rs]}, nullptr);
-            __syncthreads();
+        const bool other = KEYS == kHeavyKeysSmall ? nh > kHeavyKeysSmall : nh <= kHeavyKeysSmall;  // the other instantiation's
+        if (!other) {
+            if (nh <= KEYS) {
+                if (RUNS) {
+                    const bool by_runs = coalesce_big<true>(ix, a, rs, KeyMem<true>{lk}, &sh_nc, &rm);
+                    asm volatile("" : "+v"(n_walked));
+                    n_walked += by_runs ? 1u : 0x10000u;
+                } else {
+                    coalesce_big<true>(ix, a, rs, KeyMem<true>{lk}, &sh_nc);
+                }
+            } else {
+                if (threadIdx.x < kWave) coalesce_big<false>(ix, a, rs, KeyMem<false>{a.hit_key + a.strand_off[rs]}, nullptr);
+                __syncthreads();
+            }
         }
+        if (RUNS) __syncthreads();  // every thread has read sh_ticket before the next claim overwrites it
+        else h += gridDim.x;
+    }
+    if (RUNS && threadIdx.x == 0) {
+        uint32_t* c = heavy_counter(a, kCtrHeavyWalk);
+        if (n_walked & 0xffffu) atomicAdd(c, n_walked & 0xffffu);
+        if (n_walked >> 16) atomicAdd(c + 1, n_walked >> 16);
     }
 }
 
@@ -813,8 +984,17 @@ void launch_coalesce(hipStream_t s, const DevIndexView& ix, const uint32_t* read
     a.n_cand_total = n_cand_total;
     // persistent workgroups over the (device-side) list of heavy strands; usually a few thousand at most
     const dim3 hgrid(std::min<uint32_t>(std::max<uint32_t>(n_strands / 64, 1), 2048));
-    hipLaunchKernelGGL(k_coalesce_heavy<kHeavyKeysSmall>, hgrid, dim3(256), 0, s, ix, a, heavy_list, n_strands, heavy_count);
-    hipLaunchKernelGGL(k_coalesce_heavy<kHeavyKeys>, dim3(std::min<uint32_t>(hgrid.x, 512)), dim3(256), 0, s, ix, a, heavy_list, n_strands, heavy_count);
+    // MTSV_HEAVY_WALK=serial: the wavefront walk for every strand, for an A/B in one build (the bin | ok << 31 word of the
+    // walk by runs needs n_bins < 2^31)
+    const char* hw = getenv("MTSV_HEAVY_WALK");
+    const bool serial_walk = hw && !strcmp(hw, "serial");
+    if (serial_walk || ix.n_bins >= 0x80000000u) {
+        hipLaunchKernelGGL((k_coalesce_heavy<kHeavyKeysSmall, false>), hgrid, dim3(256), 0, s, ix, a, heavy_list, n_strands, heavy_count);
+    } else {
+        (void)hipMemsetAsync(counters + kCtrHeavyTicket, 0, sizeof(uint64_t), s);
+        hipLaunchKernelGGL((k_coalesce_heavy<kHeavyKeysSmall, true>), hgrid, dim3(256), 0, s, ix, a, heavy_list, n_strands, heavy_count);
+    }
+    hipLaunchKernelGGL((k_coalesce_heavy<kHeavyKeys, false>), dim3(std::min<uint32_t>(hgrid.x, 512)), dim3(256), 0, s, ix, a, heavy_list, n_strands, heavy_count);
 }
 
 // longest candidate window of a pass (the tiled kernel's strips are sized from it)

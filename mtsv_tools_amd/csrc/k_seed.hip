@@ -76,7 +76,8 @@ constexpr uint32_t kMaxPackedSeed = 32;
 // seeds whose table part holds an N, which k_search_fast hands over)
 __device__ inline void search_slot(const DevIndexView& ix, const uint8_t* __restrict__ bases, const uint32_t* __restrict__ read_off,
                                    uint32_t r0, uint32_t max_ns, uint32_t K, uint32_t G, uint64_t slot,
-                                   uint32_t* __restrict__ seed_lo, uint32_t* __restrict__ seed_cnt) {
+                                   uint32_t* __restrict__ seed_lo, uint32_t* __restrict__ seed_cnt,
+                                   const uint2* __restrict__ levels) {
 
     uint32_t j = (uint32_t)(slot % max_ns);
     uint64_t rs = slot / max_ns;
@@ -190,6 +191,24 @@ __device__ inline void search_slot(const DevIndexView& ix, const uint8_t* __rest
                     hi = 0;
                     i = -1;
                 }
+            } else if (levels) {
+                // An N in the table part.  The m symbols behind the seed's last N are all of A C G T, and the interval the
+                // walk below reaches after min(m, kKmerLevelsMax, kmer_k) of them is an entry of the kept level of that many
+                // symbols (dev_index.hip): one gather in a table small enough to stay in cache instead of that many
+                // dependent rank steps.  The walk goes on from the symbol in front of them.
+                const uint32_t Lk = min(ix.kmer_k, kKmerLevelsMax);
+                uint32_t m = 0, lidx = 0;  // symbol K-1-t at bits [2t, 2t+2): the table's order, first symbol highest
+                for (; m < Lk; m++) {
+                    const uint32_t a = sym(K - 1 - m);
+                    if (a > 3) break;
+                    lidx |= a << (2 * m);
+                }
+                if (m) {
+                    const uint2 iv = levels[kmer_level_start(m) + lidx];
+                    lo = iv.x;
+                    hi = iv.y;
+                    i = (int)K - 1 - (int)m;
+                }
             }
         }
         for (; i >= 0 && lo < hi; i--) {
@@ -216,11 +235,12 @@ __device__ inline void search_slot(const DevIndexView& ix, const uint8_t* __rest
 __global__ __launch_bounds__(256) void k_search(DevIndexView ix, const uint8_t* __restrict__ bases,
                                                 const uint32_t* __restrict__ read_off, uint32_t r0, uint32_t n_reads,
                                                 uint32_t max_ns, uint32_t K, uint32_t G,
-                                                uint32_t* __restrict__ seed_lo, uint32_t* __restrict__ seed_cnt) {
+                                                uint32_t* __restrict__ seed_lo, uint32_t* __restrict__ seed_cnt,
+                                                const uint2* __restrict__ levels) {
     uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t total = (uint64_t)n_reads * 2 * max_ns;
     if (slot >= total) return;
-    search_slot(ix, bases, read_off, r0, max_ns, K, G, slot, seed_lo, seed_cnt);
+    search_slot(ix, bases, read_off, r0, max_ns, K, G, slot, seed_lo, seed_cnt, levels);
 }
 
 // The common case -- k-mer table of KK symbols resident, 16 <= K <= 24, at most 8 symbols left for the FM
@@ -425,10 +445,10 @@ __global__ __launch_bounds__(256) void k_search_listed(DevIndexView ix, const ui
                                                        const uint32_t* __restrict__ read_off, uint32_t r0, uint32_t max_ns, uint32_t K,
                                                        uint32_t G, const uint32_t* __restrict__ slow_list,
                                                        const uint32_t* __restrict__ slow_count, uint32_t* __restrict__ seed_lo,
-                                                       uint32_t* __restrict__ seed_cnt) {
+                                                       uint32_t* __restrict__ seed_cnt, const uint2* __restrict__ levels) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *slow_count) return;
-    search_slot(ix, bases, read_off, r0, max_ns, K, G, slow_list[i], seed_lo, seed_cnt);
+    search_slot(ix, bases, read_off, r0, max_ns, K, G, slow_list[i], seed_lo, seed_cnt, levels);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -784,7 +804,7 @@ void launch_unpack(hipStream_t s, const uint8_t* packed, uint8_t* dst, uint64_t 
 
 void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, const uint32_t* read_off, uint32_t r0,
                    uint32_t n_reads, uint32_t max_ns, uint32_t K, uint32_t G, uint32_t* seed_lo, uint32_t* seed_cnt,
-                   uint32_t* slow_list, uint32_t* slow_count, uint32_t listed_cap) {
+                   uint32_t* slow_list, uint32_t* slow_count, uint32_t listed_cap, const uint2* kmer_levels) {
     (void)hipMemsetAsync(slow_count, 0, sizeof(uint32_t), s);  // (whichever path is taken: the caller reads it after every pass)
     uint64_t total = (uint64_t)n_reads * 2 * max_ns;
     if (!total) return;
@@ -792,7 +812,7 @@ void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, 
                       K >= ix.kmer_k && K - std::min<uint32_t>(ix.kmer_k, 16) <= 8 && !getenv("MTSV_SEARCH_GENERIC");
     if (!fast) {
         hipLaunchKernelGGL(k_search, dim3(cdiv(total, 256)), dim3(256), 0, s, ix, bases, read_off, r0, n_reads, max_ns, K, G,
-                           seed_lo, seed_cnt);
+                           seed_lo, seed_cnt, kmer_levels);
         return;
     }
     // resident wavefronts that stride over the slots (a wavefront fills a batch of 64 held-back slots every ~1900)
@@ -816,7 +836,7 @@ void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, 
 #undef FAST_CASE
     // (about one slot in thirty with the synthetic reads' 0.2 % of N)
     hipLaunchKernelGGL(k_search_listed, dim3(cdiv(std::max<uint32_t>(listed_cap, 1), 256)), dim3(256), 0, s, ix, bases, read_off, r0, max_ns, K, G,
-                       slow_list, slow_count, seed_lo, seed_cnt);
+                       slow_list, slow_count, seed_lo, seed_cnt, kmer_levels);
 }
 
 void launch_thin(hipStream_t s, const uint8_t* bases, const uint32_t* read_off, uint32_t r0, uint32_t n_reads, double edit_rate,

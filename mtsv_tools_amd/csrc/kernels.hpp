@@ -40,6 +40,9 @@ static_assert(sizeof(DevHit) == 32, "DevHit must match mtsv_hit");
 
 // slots of a lane's counter block (batch.hip: d_counters) that kernels address by number
 constexpr uint32_t kCtrVerified = 4, kCtrWindowBytes = 5, kCtrSwCursor = 8, kCtrPassCount = 9, kCtrSwCellPairs = 14;
+// k_coalesce_heavy: [kCtrHeavyWalk] lo = strands of the lane's passes walked by runs, hi = by the wavefront walk because a run
+// was too long; [kCtrHeavyTicket] lo = the next strand of the list to claim (zeroed by launch_coalesce)
+constexpr uint32_t kCtrHeavyWalk = 23, kCtrHeavyTicket = 24;
 
 struct EvalArgs {
     const uint8_t* bases;
@@ -102,9 +105,10 @@ void launch_normalise(hipStream_t s, const uint8_t* src, uint8_t* dst, uint64_t 
 void launch_unpack(hipStream_t s, const uint8_t* packed, uint8_t* dst, uint64_t lo, uint64_t hi);
 void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, const uint32_t* read_off, uint32_t r0,
                    uint32_t n_reads, uint32_t max_ns, uint32_t K, uint32_t G, uint32_t* seed_lo, uint32_t* seed_cnt,
-                   uint32_t* slow_list, uint32_t* slow_count, uint32_t listed_cap);
+                   uint32_t* slow_list, uint32_t* slow_count, uint32_t listed_cap, const uint2* kmer_levels);
 // slow_list: room for every seed slot; *slow_count: a counter of the lane; listed_cap: list entries the second kernel's grid covers
-// (the caller compares *slow_count with it afterwards)
+// (the caller compares *slow_count with it afterwards); kmer_levels: DeviceIndex::d_kmer_levels, or null (a kernel argument of
+// its own: the index view is at k_search_fast's scalar-register budget as it is)
 // strand_nseeds receives one word per strand for the coalescing kernels: min_seeds (index.rs:358) | edit tolerance << 16 |
 // a flag for the strands no candidate of which can be accepted (more N in the read than the edit tolerance, or the usize
 // wrap of index.rs:406).  planes (may be null: a pass k_edit_myers does not verify): the bit planes of EvalArgs::planes,
