@@ -229,6 +229,42 @@ int mtsv_batch_run_host(mtsv_batch *b, const uint8_t *bases, const uint64_t *rea
 int mtsv_batch_run_host_parts(mtsv_batch *b, int n_parts, const uint8_t *const *bases, const uint64_t *const *read_off,
                               const uint64_t *n_reads, const mtsv_params *params);
 int mtsv_batch_stats_get(const mtsv_batch *b, mtsv_batch_stats *st);
+
+/* ---- taxa report: per-TaxID read counts (mtsv-collapse --report, src/collapse.rs:43-62,120-146) ---------------
+ * Per read with at least one hit (the hits mtsv_batch_download returns for it): summary = {tax_id -> smallest edit over
+ * the read's hits, both strands}.  With m the smallest edit of the summary, every TaxID of it counts the read once:
+ *   only_hit   the summary has one entry
+ *   only_best  its edit is m and no other entry's is
+ *   tied_best  its edit is m and another entry's is too
+ *   not_best   its edit is above m
+ * total_reads counts the reads with a hit.  The counts are summed on the device, pass by pass, from the hits while they
+ * are in HBM (k_report.hip); they do not depend on how a batch was cut into passes, lanes or calls.  mtsv-collapse keys
+ * reads by their text ID and so merges records that carry the same ID; here every read counts by itself. */
+typedef struct {
+    uint32_t tax_id;
+    uint32_t _pad;
+    uint64_t only_hit, only_best, tied_best, not_best;
+} mtsv_taxon_stats;
+/* on != 0: every run of this workspace from now on (mtsv_batch_run, _run_host, _run_host_parts) adds its reads to the
+ * workspace's report.  Off by default, and off costs nothing: no allocation, no launch.  What the report needs on the
+ * device (the index's distinct TaxIDs, four counters each) is created when it is first switched on; the environment
+ * variable MTSV_REPORT_DENSE_MAX, read then, moves the number of taxa up to which the workgroups count in one LDS
+ * counter per (TaxID, category) instead of an LDS hash table (tests; at most 4095); MTSV_REPORT_HASH_SLOTS shrinks that table (tests). */
+int mtsv_batch_set_taxa_report(mtsv_batch *b, int on);
+/* Rows for every TaxID with a non-zero counter, ascending tax_id; the caller frees *rows with mtsv_free.  device_ms
+ * (may be NULL): device time of the report's kernels since the last reset.  reset != 0 zeroes the accumulation after
+ * reading it.  MTSV_E_ARG when the report is not on. */
+int mtsv_batch_taxa_report(mtsv_batch *b, mtsv_taxon_stats **rows, uint64_t *n_rows, uint64_t *total_reads,
+                           float *device_ms, int reset);
+/* Sum of two reports (several workspaces that shared one input): rows of the same TaxID add up.  Both inputs ascending
+ * by tax_id; *out is malloc'd (mtsv_free) and ascending.  Host only. */
+int mtsv_merge_taxa_reports(const mtsv_taxon_stats *a, uint64_t n_a, const mtsv_taxon_stats *b, uint64_t n_b,
+                            mtsv_taxon_stats **out, uint64_t *n_out);
+/* write_taxa_report (src/collapse.rs:716-750): the header line and one line per row, every count followed by its
+ * percentage of max(total_reads, 1) with two decimals, then the row's sum and its percentage.  *out is malloc'd
+ * (mtsv_free).  Host only, needs no device. */
+int mtsv_format_taxa_report(const mtsv_taxon_stats *rows, uint64_t n_rows, uint64_t total_reads, char **out,
+                            uint64_t *out_len);
 int mtsv_batch_download(mtsv_batch *b, mtsv_hit **hits, uint64_t *n_hits);
 void mtsv_batch_free(mtsv_batch *b);
 

@@ -8,6 +8,7 @@ when the library or a device is missing.
 """
 from ._lib import (  # noqa: F401
     HIT_DTYPE,
+    TAXON_STATS_DTYPE,
     HostBuffer,
     host_register,
     host_unregister,
@@ -21,6 +22,8 @@ from ._lib import (  # noqa: F401
     default_params,
     device_count,
     format_results,
+    format_taxa_report,
+    merge_taxa_reports,
     lib,
     lib_path,
     pack_bases,

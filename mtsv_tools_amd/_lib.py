@@ -57,6 +57,11 @@ HIT_DTYPE = np.dtype({"names": ["read", "tax_id", "gi", "edit", "strand", "offse
                       "formats": ["<u8", "<u4", "<u4", "<u4", "u1", "<u8"],
                       "offsets": [0, 8, 12, 16, 20, 24], "itemsize": 32})
 
+# mtsv_taxon_stats: 4 + 4 pad + 4 * 8 = 40 bytes
+TAXON_STATS_DTYPE = np.dtype({"names": ["tax_id", "only_hit", "only_best", "tied_best", "not_best"],
+                              "formats": ["<u4", "<u8", "<u8", "<u8", "<u8"],
+                              "offsets": [0, 8, 16, 24, 32], "itemsize": 40})
+
 EXPORTS = [
     "mtsv_last_error", "mtsv_version", "mtsv_params_default", "mtsv_device_count",
     "mtsv_index_load", "mtsv_index_build", "mtsv_index_build_fasta", "mtsv_index_write",
@@ -67,6 +72,7 @@ EXPORTS = [
     "mtsv_bin_batch_multi", "mtsv_bin_batch_chunks", "mtsv_set_default_verify_mode",
     "mtsv_host_alloc", "mtsv_host_free", "mtsv_host_register", "mtsv_host_unregister",
     "mtsv_batch_create_lanes", "mtsv_batch_reserve_host", "mtsv_pack_bases", "mtsv_host_pack_threads",
+    "mtsv_batch_set_taxa_report", "mtsv_batch_taxa_report", "mtsv_merge_taxa_reports", "mtsv_format_taxa_report",
 ]
 
 _lib = None
@@ -127,6 +133,10 @@ def lib():
         L.mtsv_host_free.restype = None
         L.mtsv_host_register.argtypes = [vp, C.c_size_t]
         L.mtsv_host_unregister.argtypes = [vp]
+        L.mtsv_batch_set_taxa_report.argtypes = [vp, i32]
+        L.mtsv_batch_taxa_report.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float), i32]
+        L.mtsv_merge_taxa_reports.argtypes = [vp, u64, vp, u64, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_format_taxa_report.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -363,6 +373,16 @@ class Batch:
         _check(lib().mtsv_batch_download(self.h, C.byref(out), C.byref(n)))
         return _hits_from(out, n.value)
 
+    def set_taxa_report(self, on):
+        """mtsv_batch_set_taxa_report: every run from now on adds its reads to the workspace's per-TaxID counts"""
+        _check(lib().mtsv_batch_set_taxa_report(self.h, int(bool(on))))
+
+    def taxa_report(self, reset=False):
+        """(rows as a TAXON_STATS_DTYPE array ascending by tax_id, total_reads, device_ms)"""
+        out, n, total, ms = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_batch_taxa_report(self.h, C.byref(out), C.byref(n), C.byref(total), C.byref(ms), int(bool(reset))))
+        return _taxon_rows_from(out, n.value), total.value, ms.value
+
     def close(self):
         if self.h is not None and _lib is not None:
             _lib.mtsv_batch_free(self.h)
@@ -386,6 +406,43 @@ def format_results(hits, read_ids, long_format=False):
                                      len(read_ids), int(long_format), C.byref(out), C.byref(n)))
     try:
         return C.string_at(out.value, n.value).decode()
+    finally:
+        lib().mtsv_free(out)
+
+
+def _taxon_rows_from(ptr, n):
+    try:
+        if n == 0:
+            return np.zeros(0, dtype=TAXON_STATS_DTYPE)
+        raw = (C.c_ubyte * (n * TAXON_STATS_DTYPE.itemsize)).from_address(ptr.value)
+        return np.frombuffer(raw, dtype=TAXON_STATS_DTYPE).copy()
+    finally:
+        lib().mtsv_free(ptr)
+
+
+def _taxon_rows(rows):
+    # (field by field: an array of another layout, or a zeroed one, must not carry its padding over)
+    out = np.zeros(len(rows), dtype=TAXON_STATS_DTYPE)
+    for f in TAXON_STATS_DTYPE.names:
+        out[f] = rows[f]
+    return out
+
+
+def merge_taxa_reports(a, b):
+    """mtsv_merge_taxa_reports: the rows of two workspaces that shared one input, summed per TaxID"""
+    a, b = _taxon_rows(a), _taxon_rows(b)
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_merge_taxa_reports(a.ctypes.data, len(a), b.ctypes.data, len(b), C.byref(out), C.byref(n)))
+    return _taxon_rows_from(out, n.value)
+
+
+def format_taxa_report(rows, total_reads):
+    """write_taxa_report: the TSV of mtsv-collapse --report, as bytes"""
+    rows = _taxon_rows(rows)
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_taxa_report(rows.ctypes.data, len(rows), int(total_reads), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value)
     finally:
         lib().mtsv_free(out)
 

@@ -167,6 +167,10 @@ Batch::~Batch() {
     (void)hipFree(d_codes);
     (void)hipFree(d_strip);
     (void)hipFree(d_planes);
+    (void)hipFree(report.d_taxa);
+    (void)hipFree(report.d_counts);
+    for (auto& e : report_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h_hits_stage) pinned_hits_release(h_hits_stage);
     if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
     if (copy_stream) {
@@ -333,6 +337,64 @@ void Batch::end_run() {
     total_hits = 0;
     for (auto& sg : segments) total_hits += sg.count;
     stats.n_hits = total_hits;
+}
+
+// The report's device side: the sorted list of the index's distinct TaxIDs (indexes from the builders are in TaxID
+// order; a loaded file is not checked for it, so the host copy of the bins is sorted here) and the counters.
+void Batch::set_taxa_report(bool on) {
+    if (parent) throw std::runtime_error("internal: the taxa report belongs to the workspace's owner");
+    if (on && !report.d_counts) {
+        std::vector<uint32_t>& t = report.h_taxa;
+        t.clear();
+        for (const Bin& b : ix->host.bins) t.push_back(b.tax_id);
+        std::sort(t.begin(), t.end());
+        t.erase(std::unique(t.begin(), t.end()), t.end());
+        if (t.size() >= (1ull << 30)) throw std::runtime_error("limit: taxa report of 2^30 TaxIDs or more");
+        report.n_taxa = (uint32_t)t.size();
+        uint32_t dense_max = kReportDenseTaxa;
+        if (const char* e = getenv("MTSV_REPORT_DENSE_MAX")) dense_max = (uint32_t)std::min<uint64_t>(strtoull(e, nullptr, 10), kReportDenseTaxa);  // (tests)
+        report.dense = report.n_taxa <= dense_max;
+        if (const char* e = getenv("MTSV_REPORT_HASH_SLOTS")) {  // (tests: a table small enough to overflow)
+            const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 16), kReportHashSlots);
+            report.hash_slots = 16;
+            while (report.hash_slots * 2 <= want) report.hash_slots *= 2;
+        }
+        report.trace = getenv("MTSV_TRACE") != nullptr;
+        if (report.trace)
+            fprintf(stderr, "[report] %u taxa: %s tier (dense up to %u taxa, hash table of %u slots)\n", report.n_taxa,
+                    report.dense ? "dense" : "hashed", dense_max, report.hash_slots);
+        HIP_CHECK(hipSetDevice(di->device));
+        uint64_t b = 0;
+        dev_alloc(&report.d_taxa, report.n_taxa, &b);
+        dev_alloc(&report.d_counts, 4ull * report.n_taxa + 2, &b);
+        if (report.n_taxa) HIP_CHECK(hipMemcpyAsync(report.d_taxa, t.data(), t.size() * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemsetAsync(report.d_counts, 0, (4ull * report.n_taxa + 2) * 8, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    report.on = on;
+}
+
+void Batch::taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_reads, float* device_ms, bool reset) {
+    if (!report.on) throw std::runtime_error("arg: the taxa report of this workspace is not switched on (mtsv_batch_set_taxa_report)");
+    HIP_CHECK(hipSetDevice(di->device));
+    const uint64_t n = 4ull * report.n_taxa + 2;
+    std::vector<uint64_t> c(n);
+    // (every run is synchronous: no lane has a pass in flight)
+    HIP_CHECK(hipMemcpyAsync(c.data(), report.d_counts, n * 8, hipMemcpyDeviceToHost, stream));
+    if (reset) HIP_CHECK(hipMemsetAsync(report.d_counts, 0, n * 8, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    rows.clear();
+    for (uint32_t k = 0; k < report.n_taxa; k++) {
+        const uint64_t* q = &c[4ull * k];
+        if (q[0] | q[1] | q[2] | q[3]) rows.push_back(mtsv_taxon_stats{report.h_taxa[k], 0, q[0], q[1], q[2], q[3]});
+    }
+    *total_reads = c[n - 2];
+    std::lock_guard<std::mutex> lk(report.mu);
+    *device_ms = report.ms;
+    if (report.trace)
+        fprintf(stderr, "[report] %llu kernel launches, %.3f ms, %llu atomic adds on the global counters\n", (unsigned long long)report.launches,
+                report.ms, (unsigned long long)c[n - 1]);
+    if (reset) report.ms = 0, report.launches = 0;
 }
 
 void Batch::run(const mtsv_params& p) {
@@ -756,8 +818,25 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
         }
         launch_gather(stream, nstr, read_base + r0, d_strand_off, d_strand_nout, d_out_off, d_out, d_hits, n_hits_total);
         HIP_CHECK(hipEventRecord(ev[7], stream));
+        // the pass is committed from here on (a pass that is run again has not come this far): its reads join the taxa report
+        TaxaReport& rep = (parent ? parent : this)->report;
+        if (rep.on) {
+            if (!report_ev[0])
+                for (auto& e : report_ev) HIP_CHECK(hipEventCreate(&e));
+            HIP_CHECK(hipEventRecord(report_ev[0], stream));
+            launch_report(stream, nr, d_strand_nout, d_out_off, d_hits + n_hits_total, rep.d_taxa, rep.n_taxa, rep.dense, rep.hash_slots, rep.d_counts,
+                          rep.d_counts + 4ull * rep.n_taxa, rep.trace ? rep.d_counts + 4ull * rep.n_taxa + 1 : nullptr);
+            HIP_CHECK(hipEventRecord(report_ev[1], stream));
+        }
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipGetLastError());
+        if (rep.on) {
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, report_ev[0], report_ev[1]));
+            std::lock_guard<std::mutex> lk(rep.mu);
+            rep.ms += ms;
+            rep.launches++;
+        }
         n_hits_total += total_out;
         for (int s = 0; s < 7; s++) {
             float ms = 0;

@@ -120,6 +120,28 @@ struct Batch {
     void download_into(mtsv_hit* dst, uint64_t n);
     bool keep_on_device = false;  // run_host: leave the hits in the lanes' result arrays (no copy to the host while it runs)
 
+    // Taxa report (k_report.hip): per-TaxID read counts, added to by every committed pass of every lane while it is on.
+    // Everything belongs to the owner and is created when the report is first switched on.
+    struct TaxaReport {
+        bool on = false;
+        bool dense = true;
+        uint32_t hash_slots = kReportHashSlots;  // of the hashed tier's LDS table (MTSV_REPORT_HASH_SLOTS: fewer, tests)
+        uint32_t n_taxa = 0;
+        uint32_t* d_taxa = nullptr;    // the index's distinct TaxIDs, ascending
+        uint64_t* d_counts = nullptr;  // 4 per taxon (only_hit, only_best, tied_best, not_best), then the reads with a hit,
+                                       // then (trace) the atomic adds the kernels made on all of these
+        bool trace = false;            // MTSV_TRACE was set when the report was switched on
+        uint64_t launches = 0;         // (under mu) report kernels since the last reset
+        std::vector<uint32_t> h_taxa;
+        std::mutex mu;                 // ms (the lanes' threads add to it)
+        float ms = 0;                  // device time of the report kernels since the last reset
+    };
+    TaxaReport report;
+    hipEvent_t report_ev[2] = {nullptr, nullptr};  // around a lane's report kernel; created with the lane's first one
+    void set_taxa_report(bool on);
+    // rows: every TaxID with a non-zero counter, ascending
+    void taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_reads, float* device_ms, bool reset);
+
    private:
     void begin_run(const mtsv_params& p);
     void reset_lane();

@@ -228,7 +228,7 @@ int resume_offset(const std::string& results, const std::string& input, bool fas
 }
 
 struct Args {
-    std::string fasta, fastq, index, results, output_format = "default";
+    std::string fasta, fastq, index, results, report, output_format = "default";
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
     bool verbose = false, force = false, parse_only = false;
@@ -330,13 +330,16 @@ int main(int argc, char** argv) {
                 usage_error("Invalid value for '--batch-reads <N>': a number of reads between 1 and 2147483647 is expected");
             a.batch_reads = n;
         }
+        else if (key == "--report") a.report = val();
         else if (key == "--parse-only") a.parse_only = true;
         else if (key == "-h" || key == "--help") {
             printf("mtsv-binner (MI355X) -- flags as the reference: --fasta|--fastq, -i/--index, -m/--results, -t/--threads,\n"
                    "-e/--edit-rate, --seed-size, --seed-interval, --min-seed, --max-hits, --tune-max-hits, --max-assignments,\n"
                    "--max-candidates, --read-offset, --output-format default|long, --force-overwrite, -v;\n"
                    "extras: --devices 0,1,.. (index replicated, reads shared out), --index a,b,.. (database chunks, one per GPU, hits merged),\n"
-                   "--batch-reads N, --parse-only\n");
+                   "--batch-reads N, --parse-only,\n"
+                   "--report TSV (per-TaxID read counts of the reads processed by this run, as mtsv-collapse --report writes them: with\n"
+                   "--read-offset or a resumed run, the reads binned now; counted on the GPU; not with a list of index chunks)\n");
             return 0;
         } else if (key == "-V" || key == "--version") {
             printf("mtsv 2.1.0 (%s)\n", mtsv_version());
@@ -348,6 +351,11 @@ int main(int argc, char** argv) {
         usage_error(a.fasta.empty() ? "The following required arguments were not provided: --fasta <FASTA> | --fastq <FASTQ>"
                                     : "The argument '--fasta <FASTA>' cannot be used with '--fastq <FASTQ>'");
     if (a.index.empty() && !a.parse_only) usage_error("The following required arguments were not provided: --index <INDEX>");
+    if (!a.report.empty() && a.index.find(',') != std::string::npos) {
+        // a read's taxa come from several chunks there and per-chunk counters do not add up
+        fprintf(stderr, "error: '--report <TSV>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-collapse --report on the results file instead\n");
+        return 1;
+    }
     if (a.output_format != "default" && a.output_format != "long")
         usage_error("'" + a.output_format + "' isn't a valid value for '--output-format <OUTPUT_FORMAT>'");
     g_verbose = a.verbose;
@@ -726,6 +734,7 @@ int main(int argc, char** argv) {
                                             : mtsv_batch_create(idx[0], dev, mtsv_bin_batch_workspace_reads(call_reads), 1 << 22, 0, &ws_ready[wk]);
             if (rc == MTSV_OK && !small_input && !getenv("MTSV_CLI_COLD"))
                 rc = mtsv_batch_reserve_host(ws_ready[wk], call_reads, call_reads * (uint64_t)(warm_len + warm_len / 8), warm_len);
+            if (rc == MTSV_OK && !a.report.empty()) rc = mtsv_batch_set_taxa_report(ws_ready[wk], 1);  // (after the warm-up reads)
             ws_rc[wk] = rc;
             if (rc != MTSV_OK) ws_msg[wk] = mtsv_last_error();  // (thread-local)
         };
@@ -1137,6 +1146,39 @@ int main(int argc, char** argv) {
         return 11;
     }
     mark("results file closed");
+    if (!a.report.empty()) {
+        // the workers' counts add up: every read went through exactly one of their workspaces
+        mtsv_taxon_stats* sum = nullptr;
+        uint64_t n_sum = 0, total_reads = 0;
+        bool ok = true;
+        for (auto* ws : ws_ready) {
+            mtsv_taxon_stats *rows = nullptr, *merged = nullptr;
+            uint64_t n_rows = 0, n_merged = 0, reads = 0;
+            ok = ok && mtsv_batch_taxa_report(ws, &rows, &n_rows, &reads, nullptr, 0) == MTSV_OK &&
+                 mtsv_merge_taxa_reports(sum, n_sum, rows, n_rows, &merged, &n_merged) == MTSV_OK;
+            mtsv_free(rows);
+            if (!ok) break;
+            mtsv_free(sum);
+            sum = merged;
+            n_sum = n_merged;
+            total_reads += reads;
+        }
+        char* text = nullptr;
+        uint64_t text_len = 0;
+        if (!ok || mtsv_format_taxa_report(sum, n_sum, total_reads, &text, &text_len) != MTSV_OK) {
+            logmsg("ERROR", std::string("Error running query: ") + mtsv_last_error());
+            return 2;
+        }
+        FILE* rf = fopen(a.report.c_str(), "wb");
+        const bool written = rf && fwrite(text, 1, text_len, rf) == text_len;
+        if ((rf && fclose(rf) != 0) || !written) {
+            logmsg("ERROR", "Error writing to taxa report file");
+            return 11;
+        }
+        mtsv_free(text);
+        mtsv_free(sum);
+        mark("taxa report written");
+    }
     struct timespec w1;
     clock_gettime(CLOCK_MONOTONIC, &w1);
     char msg[160];

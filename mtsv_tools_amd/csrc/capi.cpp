@@ -248,6 +248,13 @@ int mtsv_batch_reserve_host(mtsv_batch* b, uint64_t n_reads, uint64_t n_bases, u
     if (!b) return fail_arg("null argument");
     GUARD({
         b->impl.reserve_host(n_reads, n_bases);
+        // (the warm-up reads are not the caller's: they stay out of a taxa report that is already on)
+        struct ReportOff {
+            bool& on;
+            const bool was;
+            explicit ReportOff(bool& o) : on(o), was(o) { on = false; }
+            ~ReportOff() { on = was; }
+        } report_off(b->impl.report.on);
         const std::vector<uint8_t>& text = b->impl.ix->host.text;
         if (warm_read_len && text.size() >= (uint64_t)warm_read_len * 2 + 16) {
             // reads sampled from the index through every kernel once: the first launch of a kernel loads its code object,
@@ -301,6 +308,79 @@ int mtsv_batch_stats_get(const mtsv_batch* b, mtsv_batch_stats* st) {
     if (!b || !st) return fail_arg("null argument");
     *st = b->impl.stats;
     return MTSV_OK;
+}
+
+int mtsv_batch_set_taxa_report(mtsv_batch* b, int on) {
+    if (!b) return fail_arg("null argument");
+    GUARD(b->impl.set_taxa_report(on != 0))
+}
+
+int mtsv_batch_taxa_report(mtsv_batch* b, mtsv_taxon_stats** rows, uint64_t* n_rows, uint64_t* total_reads, float* device_ms, int reset) {
+    if (!b || !rows || !n_rows || !total_reads) return fail_arg("null argument");
+    GUARD({
+        std::vector<mtsv_taxon_stats> r;
+        float ms = 0;
+        b->impl.taxa_report(r, total_reads, &ms, reset != 0);
+        auto* out = (mtsv_taxon_stats*)malloc(std::max<size_t>(r.size(), 1) * sizeof(mtsv_taxon_stats));
+        if (!out) throw std::bad_alloc();
+        if (!r.empty()) memcpy(out, r.data(), r.size() * sizeof(mtsv_taxon_stats));
+        *rows = out;
+        *n_rows = r.size();
+        if (device_ms) *device_ms = ms;
+    })
+}
+
+int mtsv_merge_taxa_reports(const mtsv_taxon_stats* a, uint64_t n_a, const mtsv_taxon_stats* b, uint64_t n_b, mtsv_taxon_stats** out,
+                            uint64_t* n_out) {
+    if ((!a && n_a) || (!b && n_b) || !out || !n_out) return fail_arg("null argument");
+    for (uint64_t i = 1; i < n_a; i++)
+        if (a[i].tax_id <= a[i - 1].tax_id) return fail_arg("report rows are not ascending by tax_id");
+    for (uint64_t i = 1; i < n_b; i++)
+        if (b[i].tax_id <= b[i - 1].tax_id) return fail_arg("report rows are not ascending by tax_id");
+    GUARD({
+        auto* o = (mtsv_taxon_stats*)malloc(std::max<uint64_t>(n_a + n_b, 1) * sizeof(mtsv_taxon_stats));
+        if (!o) throw std::bad_alloc();
+        uint64_t i = 0, j = 0, n = 0;
+        while (i < n_a || j < n_b) {
+            if (j == n_b || (i < n_a && a[i].tax_id < b[j].tax_id)) o[n++] = a[i++];
+            else if (i == n_a || b[j].tax_id < a[i].tax_id) o[n++] = b[j++];
+            else {
+                mtsv_taxon_stats r = a[i++];
+                const mtsv_taxon_stats& q = b[j++];
+                r.only_hit += q.only_hit;
+                r.only_best += q.only_best;
+                r.tied_best += q.tied_best;
+                r.not_best += q.not_best;
+                o[n++] = r;
+            }
+        }
+        *out = o;
+        *n_out = n;
+    })
+}
+
+// write_taxa_report (collapse.rs:716-750)
+int mtsv_format_taxa_report(const mtsv_taxon_stats* rows, uint64_t n_rows, uint64_t total_reads, char** out, uint64_t* out_len) {
+    if ((!rows && n_rows) || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        std::string text = "taxid\tonly_hit\tonly_hit_pct\tonly_best\tonly_best_pct\ttied_best\ttied_best_pct\tnot_best\tnot_best_pct\ttotal_reads\ttotal_pct\n";
+        const double denom = (double)std::max<uint64_t>(total_reads, 1);
+        char line[512];
+        for (uint64_t i = 0; i < n_rows; i++) {
+            const mtsv_taxon_stats& s = rows[i];
+            const uint64_t tot = s.only_hit + s.only_best + s.tied_best + s.not_best;
+            snprintf(line, sizeof line, "%u\t%llu\t%.2f\t%llu\t%.2f\t%llu\t%.2f\t%llu\t%.2f\t%llu\t%.2f\n", s.tax_id,
+                     (unsigned long long)s.only_hit, s.only_hit / denom * 100.0, (unsigned long long)s.only_best, s.only_best / denom * 100.0,
+                     (unsigned long long)s.tied_best, s.tied_best / denom * 100.0, (unsigned long long)s.not_best, s.not_best / denom * 100.0,
+                     (unsigned long long)tot, tot / denom * 100.0);
+            text += line;
+        }
+        char* p = (char*)malloc(text.size() + 1);
+        if (!p) throw std::bad_alloc();
+        memcpy(p, text.c_str(), text.size() + 1);
+        *out = p;
+        *out_len = text.size();
+    })
 }
 
 int mtsv_batch_download(mtsv_batch* b, mtsv_hit** hits, uint64_t* n_hits) {

@@ -1,6 +1,6 @@
 // kernels.hpp -- launch interface of the hot-path kernels.
 //
-// The mtsv-binner hot path as gfx950 kernels (k_seed.hip, k_coalesce.hip, k_verify.hip).
+// The mtsv-binner hot path as gfx950 kernels (k_seed.hip, k_coalesce.hip, k_verify.hip; k_report.hip for the taxa report).
 //
 // One batch of reads flows through staged kernels with worklists in HBM:
 //
@@ -17,6 +17,7 @@
 //   k_evaluate  longer reads (tiled beyond 256 bases): both in one sweep + sw_sse2_word  ssw.c:354-530
 //   k_resolve   lane per strand: cut-offs and rank order of the selection loop    index.rs:384-428
 //   scan + k_gather  compact per-strand hits into (read, strand, rank) order      binner.rs:128
+//   k_report    (taxa report on) lane per read: per-TaxID read counts of the pass   collapse.rs:120-146
 //
 // All arithmetic is integer; positions are u32 (n < 2^32).  No MFMA: the path is rank queries and
 // small dynamic programs.
@@ -162,5 +163,16 @@ void launch_resolve(hipStream_t s, uint32_t n_strands, int64_t max_candidates, i
                     uint32_t* strand_nout);
 void launch_gather(hipStream_t s, uint32_t n_strands, uint64_t r0, const uint32_t* strand_off, const uint32_t* strand_nout,
                    const uint32_t* out_off, const uint4* out, DevHit* hits, uint64_t hits_base);
+// k_report.hip: the per-TaxID read counts of a pass (collapse.rs:120-146) from its gathered hits.  hits: the pass's first
+// hit (read r of the pass owns strand_nout[2r] + strand_nout[2r + 1] entries from out_off[2r] on); taxa: the index's n_taxa
+// distinct TaxIDs, ascending; counts: 4 u64 per taxon (only_hit, only_best, tied_best, not_best); *total_reads: reads with
+// a hit.  dense: the workgroups count in 4 * n_taxa LDS counters (n_taxa <= kReportDenseTaxa), else in an LDS hash table of
+// hash_slots entries (a power of two, 16 .. kReportHashSlots).  n_global (may be null; MTSV_TRACE): += the atomic adds the
+// launch made on counts and total_reads
+constexpr uint32_t kReportDenseTaxa = 4095;  // 4 * 4095 u32 and the read counter: 64 KiB, two workgroups per CU
+constexpr uint32_t kReportHashSlots = 4096;
+void launch_report(hipStream_t s, uint32_t n_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits,
+                   const uint32_t* taxa, uint32_t n_taxa, bool dense, uint32_t hash_slots, uint64_t* counts, uint64_t* total_reads,
+                   uint64_t* n_global);
 
 }  // namespace mtsv

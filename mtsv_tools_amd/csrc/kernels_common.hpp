@@ -1,5 +1,5 @@
 // kernels_common.hpp -- device helpers shared by the kernel files of the hot path (k_seed.hip: normalise, search,
-// thin, expand, locate; k_coalesce.hip; k_verify.hip: SW prefilter, edit distance, selection, gather).
+// thin, expand, locate; k_coalesce.hip; k_verify.hip: SW prefilter, edit distance, selection, gather; k_report.hip).
 #pragma once
 #include <cstdlib>
 #include <stdexcept>
