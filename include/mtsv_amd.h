@@ -21,6 +21,9 @@
  *   mtsv_format_results    write_assignments                              src/binner.rs:310-379
  *   mtsv_index_build*, mtsv_index_write
  *                          MGIndex::new + io::write_to_file               src/index.rs:491-582, src/io.rs:125-133
+ *   mtsv_batch_set_match_flags, mtsv_batch_match_flags
+ *                          the set of read IDs mtsv-partition collects from      src/bin/mtsv-partition.rs:34-54
+ *                          the results text, as one bit per read of a run
  *   mtsv_batch_*           the same path as mtsv_bin_batch, split so a host can keep read
  *                          batches resident in HBM and overlap upload / run / download
  *                          (replaces the bounded queue of vendor/cue/src/lib.rs:45-105)
@@ -265,6 +268,33 @@ int mtsv_merge_taxa_reports(const mtsv_taxon_stats *a, uint64_t n_a, const mtsv_
  * (mtsv_free).  Host only, needs no device. */
 int mtsv_format_taxa_report(const mtsv_taxon_stats *rows, uint64_t n_rows, uint64_t total_reads, char **out,
                             uint64_t *out_len);
+
+/* ---- match flags: did a read get a hit (mtsv-partition, src/bin/mtsv-partition.rs:34-54) ------------------------
+ * mtsv-partition splits a read file by whether a read's ID occurs in a results file: it parses the results text back
+ * into a hash set of IDs (:34-54) and reads the FASTX input a second time.  The binner decides the same question on the
+ * device: a read is MATCHED when the run returns at least one hit for it, on either strand, under the caller's
+ * mtsv_params.  With the flags on, every committed pass of a run sets one bit per matched read in a bitmap over the
+ * run's reads (k_match.hip), and counts them.  The flags describe ONE run -- the last mtsv_batch_run, _run_host or
+ * _run_host_parts of the workspace; they do not add up over runs as the taxa report does.  Every read counts by itself
+ * here; mtsv-partition keys reads by their text ID, so there two records that carry the same ID share a fate.
+ *   MTSV_MATCH_OFF        the default: no allocation, no launch, nothing changes
+ *   MTSV_MATCH_WITH_HITS  the hits as always, plus the flags
+ *   MTSV_MATCH_ONLY       the flags only (read depletion): the passes skip the scan and gather of their hits, no result
+ *                         array is kept or copied, mtsv_batch_download returns zero hits and n_hits of the stats is 0
+ *                         (the other counters keep their meaning for the work that was done).  The selection loop stops
+ *                         at a strand's first accepted candidate: whether there is one does not depend on
+ *                         max_assignments (src/index.rs:384-428 pushes a hit before it looks at the limit).
+ * MTSV_MATCH_ONLY and the taxa report (which reads gathered hits) exclude each other: whichever is asked for second
+ * fails with MTSV_E_ARG. */
+#define MTSV_MATCH_OFF 0
+#define MTSV_MATCH_WITH_HITS 1
+#define MTSV_MATCH_ONLY 2
+int mtsv_batch_set_match_flags(mtsv_batch *b, int mode);
+/* The flags of the last run: bit (r & 63) of (*words)[r >> 6] is read r in that call's numbering (through the parts of
+ * mtsv_batch_run_host_parts in order); bits at and above *n_reads are 0; *words holds (*n_reads + 63) / 64 words (at
+ * least one) and is malloc'd (mtsv_free); *n_matched is the number of set bits, counted on the device.  No run since the
+ * flags were switched on: *n_reads is 0.  MTSV_E_ARG when the mode is MTSV_MATCH_OFF. */
+int mtsv_batch_match_flags(mtsv_batch *b, uint64_t **words, uint64_t *n_reads, uint64_t *n_matched);
 int mtsv_batch_download(mtsv_batch *b, mtsv_hit **hits, uint64_t *n_hits);
 void mtsv_batch_free(mtsv_batch *b);
 

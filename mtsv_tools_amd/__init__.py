@@ -8,6 +8,9 @@ when the library or a device is missing.
 """
 from ._lib import (  # noqa: F401
     HIT_DTYPE,
+    MATCH_OFF,
+    MATCH_ONLY,
+    MATCH_WITH_HITS,
     TAXON_STATS_DTYPE,
     HostBuffer,
     host_register,

@@ -19,6 +19,7 @@ class MtsvError(RuntimeError):
 
 
 E_ARG, E_IO, E_FORMAT, E_DEVICE, E_LIMIT, E_NOMEM = -1, -2, -3, -4, -5, -6
+MATCH_OFF, MATCH_WITH_HITS, MATCH_ONLY = 0, 1, 2  # MTSV_MATCH_*
 
 
 class Params(C.Structure):  # mtsv_params
@@ -73,6 +74,7 @@ EXPORTS = [
     "mtsv_host_alloc", "mtsv_host_free", "mtsv_host_register", "mtsv_host_unregister",
     "mtsv_batch_create_lanes", "mtsv_batch_reserve_host", "mtsv_pack_bases", "mtsv_host_pack_threads",
     "mtsv_batch_set_taxa_report", "mtsv_batch_taxa_report", "mtsv_merge_taxa_reports", "mtsv_format_taxa_report",
+    "mtsv_batch_set_match_flags", "mtsv_batch_match_flags",
 ]
 
 _lib = None
@@ -137,6 +139,8 @@ def lib():
         L.mtsv_batch_taxa_report.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float), i32]
         L.mtsv_merge_taxa_reports.argtypes = [vp, u64, vp, u64, C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_format_taxa_report.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_batch_set_match_flags.argtypes = [vp, i32]
+        L.mtsv_batch_match_flags.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -382,6 +386,24 @@ class Batch:
         out, n, total, ms = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_float()
         _check(lib().mtsv_batch_taxa_report(self.h, C.byref(out), C.byref(n), C.byref(total), C.byref(ms), int(bool(reset))))
         return _taxon_rows_from(out, n.value), total.value, ms.value
+
+    def set_match_flags(self, mode):
+        """mtsv_batch_set_match_flags: MATCH_OFF, MATCH_WITH_HITS (hits and flags) or MATCH_ONLY (flags, no hits)"""
+        _check(lib().mtsv_batch_set_match_flags(self.h, int(mode)))
+
+    def match_flags(self):
+        """(bool array with one entry per read of the last run: the run returned a hit for it, n_matched)"""
+        out, n, m = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(lib().mtsv_batch_match_flags(self.h, C.byref(out), C.byref(n), C.byref(m)))
+        try:
+            nw = max((n.value + 63) // 64, 1)
+            words = np.frombuffer((C.c_ubyte * (nw * 8)).from_address(out.value), dtype="<u8").copy()
+        finally:
+            lib().mtsv_free(out)
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little").astype(bool)
+        if bits[n.value:].any():
+            raise MtsvError(E_DEVICE, "match flags set beyond the run's reads")
+        return bits[:n.value], m.value
 
     def close(self):
         if self.h is not None and _lib is not None:

@@ -171,6 +171,9 @@ Batch::~Batch() {
     (void)hipFree(report.d_counts);
     for (auto& e : report_ev)
         if (e) (void)hipEventDestroy(e);
+    (void)hipFree(match.d_words);
+    for (auto& e : match_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h_hits_stage) pinned_hits_release(h_hits_stage);
     if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
     if (copy_stream) {
@@ -279,7 +282,7 @@ void Batch::finish_lane() {
     stats.window_bytes = h_counters[5];
 }
 
-void Batch::begin_run(const mtsv_params& p) {
+void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
     if (!(p.edit_rate >= 0.0 && p.edit_rate <= 1.0)) throw std::runtime_error("arg: edit_rate must be within [0, 1]");
     if (!(p.min_seed >= 0.0) || !std::isfinite(p.min_seed)) throw std::runtime_error("arg: min_seed must be finite and >= 0");
     if (p.seed_size == 0 || p.seed_interval == 0) throw std::runtime_error("arg: seed_size and seed_interval must be > 0");
@@ -298,6 +301,25 @@ void Batch::begin_run(const mtsv_params& p) {
         l->sw_bound = sw_bound;
         l->sw_fused = sw_fused;
         l->reset_lane();
+    }
+    if (match.mode != MTSV_MATCH_OFF) {
+        // this run's flags: all zero before any lane's first pass (the lanes' streams do not wait for this one by themselves)
+        const uint64_t need = (n_reads + 63) / 64;
+        if (need > match.cap_words || !match.d_words) {
+            (void)hipFree(match.d_words);
+            match.d_words = nullptr;
+            match.cap_words = 0;
+            uint64_t b = 0;
+            dev_alloc(&match.d_words, need + need / 16 + 1, &b);
+            match.cap_words = need + need / 16;
+        }
+        match.n_reads = n_reads;
+        match.call_base = read_base;
+        match.ms = 0;
+        match.launches = 0;
+        // (the counter sits behind the last word the allocation holds, wherever this run's flags end)
+        HIP_CHECK(hipMemsetAsync(match.d_words, 0, (match.cap_words + 1) * sizeof(uint64_t), stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
     }
 }
 
@@ -343,6 +365,8 @@ void Batch::end_run() {
 // order; a loaded file is not checked for it, so the host copy of the bins is sorted here) and the counters.
 void Batch::set_taxa_report(bool on) {
     if (parent) throw std::runtime_error("internal: the taxa report belongs to the workspace's owner");
+    if (on && match.mode == MTSV_MATCH_ONLY)
+        throw std::runtime_error("arg: the taxa report reads gathered hits and MTSV_MATCH_ONLY gathers none (mtsv_batch_set_match_flags)");
     if (on && !report.d_counts) {
         std::vector<uint32_t>& t = report.h_taxa;
         t.clear();
@@ -395,6 +419,35 @@ void Batch::taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_rea
         fprintf(stderr, "[report] %llu kernel launches, %.3f ms, %llu atomic adds on the global counters\n", (unsigned long long)report.launches,
                 report.ms, (unsigned long long)c[n - 1]);
     if (reset) report.ms = 0, report.launches = 0;
+}
+
+void Batch::set_match_flags(int mode) {
+    if (parent) throw std::runtime_error("internal: the match flags belong to the workspace's owner");
+    if (mode != MTSV_MATCH_OFF && mode != MTSV_MATCH_WITH_HITS && mode != MTSV_MATCH_ONLY) throw std::runtime_error("arg: bad match-flags mode");
+    if (mode == MTSV_MATCH_ONLY && report.on)
+        throw std::runtime_error("arg: MTSV_MATCH_ONLY gathers no hits and the taxa report of this workspace, which reads them, is on");
+    if (mode != MTSV_MATCH_OFF && match.mode == MTSV_MATCH_OFF) match.n_reads = 0;  // no run to speak of yet
+    match.trace = getenv("MTSV_TRACE") != nullptr;
+    match.mode = mode;
+}
+
+void Batch::match_flags(std::vector<uint64_t>& words, uint64_t* n_reads_out, uint64_t* n_matched) {
+    if (match.mode == MTSV_MATCH_OFF) throw std::runtime_error("arg: the match flags of this workspace are not switched on (mtsv_batch_set_match_flags)");
+    const uint64_t nw = (match.n_reads + 63) / 64;
+    words.assign(std::max<uint64_t>(nw, 1), 0);
+    *n_reads_out = match.n_reads;
+    *n_matched = 0;
+    if (!match.n_reads) return;
+    HIP_CHECK(hipSetDevice(di->device));
+    // (every run is synchronous: no lane has a pass in flight)
+    HIP_CHECK(hipMemcpyAsync(words.data(), match.d_words, nw * 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(n_matched, match.d_words + match.cap_words, 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    std::lock_guard<std::mutex> lk(match.mu);
+    if (match.trace)
+        fprintf(stderr, "[match] %llu kernel launches, %.3f ms, %llu of %llu reads matched, %llu bytes of flags to the host\n",
+                (unsigned long long)match.launches, match.ms, (unsigned long long)*n_matched, (unsigned long long)match.n_reads,
+                (unsigned long long)(nw * 8 + 8));
 }
 
 void Batch::run(const mtsv_params& p) {
@@ -495,6 +548,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                                  std::to_string(kMaxReadLen));
     const DevIndexView& v = di->view;
     const uint32_t K = p.seed_size, G = p.seed_interval;
+    const bool only_flags = flags_only();
     float* stage_ms = stage_acc;
     // Long reads (beyond the register-resident kernels) run in passes of their own, through the tiled kernel:
     // a pass is a contiguous range of reads, so cutting the slice at them keeps the hits in read order, and
@@ -789,15 +843,21 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
             } else {
                 launch_evaluate(stream, v, a, total_hits, pass_max_len);
             }
-            launch_resolve(stream, nstr, p.max_candidates, p.max_assignments, d_strand_off, d_strand_ncand, d_cand_status,
+            // (flags only: whether a strand has a hit does not depend on max_assignments -- the loop of index.rs:384-428
+            //  pushes its first accepted candidate before it looks at the limit -- so the selection stops at the first)
+            launch_resolve(stream, nstr, p.max_candidates, only_flags ? 1 : p.max_assignments, d_strand_off, d_strand_ncand, d_cand_status,
                            d_out, d_strand_nout);
         }
         HIP_CHECK(hipEventRecord(ev[6], stream));
         // ---- gather ----
-        launch_scan(stream, d_strand_nout, nstr, d_tile_sums, d_counters + 6, d_out_off);
-        launch_publish(stream, d_counters, h_counters, 8);
-        HIP_CHECK(hipStreamSynchronize(stream));
-        const uint64_t total_out = h_counters[6];
+        // (flags only: no scan of the hit counts, no result array, no gather -- the pass ends with k_match below)
+        uint64_t total_out = 0;
+        if (!only_flags) {
+            launch_scan(stream, d_strand_nout, nstr, d_tile_sums, d_counters + 6, d_out_off);
+            launch_publish(stream, d_counters, h_counters, 8);
+            HIP_CHECK(hipStreamSynchronize(stream));
+            total_out = h_counters[6];
+        }
         if (n_hits_total + total_out > hits_cap) {
             // grow the result array, keeping what earlier passes produced
             uint64_t ncap = std::max(hits_cap * 2, n_hits_total + total_out);
@@ -816,7 +876,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
             d_hits = nh;
             hits_cap = ncap;
         }
-        launch_gather(stream, nstr, read_base + r0, d_strand_off, d_strand_nout, d_out_off, d_out, d_hits, n_hits_total);
+        if (!only_flags) launch_gather(stream, nstr, read_base + r0, d_strand_off, d_strand_nout, d_out_off, d_out, d_hits, n_hits_total);
         HIP_CHECK(hipEventRecord(ev[7], stream));
         // the pass is committed from here on (a pass that is run again has not come this far): its reads join the taxa report
         TaxaReport& rep = (parent ? parent : this)->report;
@@ -828,8 +888,26 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                           rep.d_counts + 4ull * rep.n_taxa, rep.trace ? rep.d_counts + 4ull * rep.n_taxa + 1 : nullptr);
             HIP_CHECK(hipEventRecord(report_ev[1], stream));
         }
+        // ... and they get their match flags
+        MatchFlags& mf = (parent ? parent : this)->match;
+        if (mf.mode != MTSV_MATCH_OFF) {
+            const uint64_t first_bit = read_base + r0 - mf.call_base;
+            if (first_bit + nr > mf.n_reads) throw std::runtime_error("internal: match flags of a pass beyond the run's reads");
+            if (!match_ev[0])
+                for (auto& e : match_ev) HIP_CHECK(hipEventCreate(&e));
+            HIP_CHECK(hipEventRecord(match_ev[0], stream));
+            launch_match(stream, nr, d_strand_nout, first_bit, mf.d_words, mf.d_words + mf.cap_words);
+            HIP_CHECK(hipEventRecord(match_ev[1], stream));
+        }
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipGetLastError());
+        if (mf.mode != MTSV_MATCH_OFF) {
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, match_ev[0], match_ev[1]));
+            std::lock_guard<std::mutex> lk(mf.mu);
+            mf.ms += ms;
+            mf.launches++;
+        }
         if (rep.on) {
             float ms = 0;
             HIP_CHECK(hipEventElapsedTime(&ms, report_ev[0], report_ev[1]));
@@ -1103,9 +1181,9 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
     n_reads = n;
     max_len = 0;
     if (trace) fprintf(stderr, "[run_host] entered; begin_run at %.2f ms\n", (now_s() - t_entry) * 1e3);
-    begin_run(p);
+    begin_run(p, read_base);
     staged_hits = 0;
-    if (!h_hits_stage && !keep_on_device) {
+    if (!h_hits_stage && !keep_on_device && !flags_only()) {
         // expect about as many hits as the last run produced (first run: one per read)
         // (a fresh page-locked array costs ~60 us per MB to create and is slow on its first copy: ask for little more than
         //  the last batch needed, so that the array that batch returned to the pool fits again)
@@ -1436,7 +1514,7 @@ void Batch::stage_reserve(uint64_t n_hits_needed) {
 void Batch::download(mtsv_hit** hits, uint64_t* n) {
     HIP_CHECK(hipSetDevice(di->device));
     last_total_hits = total_hits;
-    if (staged_valid) {  // run_host already brought them over
+    if (staged_valid && h_hits_stage) {  // run_host already brought them over
         *hits = h_hits_stage;
         *n = total_hits;
         h_hits_stage = nullptr;

@@ -139,11 +139,30 @@ struct Batch {
     TaxaReport report;
     hipEvent_t report_ev[2] = {nullptr, nullptr};  // around a lane's report kernel; created with the lane's first one
     void set_taxa_report(bool on);
+    // Match flags (k_match.hip): one bit per read of the last run, "the run returned a hit for it".  Like the report they
+    // belong to the owner; unlike it they describe one run: zeroed when a run begins, sized with it.
+    struct MatchFlags {
+        int mode = MTSV_MATCH_OFF;
+        uint64_t* d_words = nullptr;  // cap_words words of flags, then the matched-reads counter
+        uint64_t cap_words = 0;
+        uint64_t n_reads = 0;         // of the last run with the flags on
+        uint64_t call_base = 0;       // read_base of that run: bit 0 is its first read
+        bool trace = false;
+        std::mutex mu;                // ms, launches (the lanes' threads add to them)
+        float ms = 0;                 // device time of the run's k_match launches
+        uint64_t launches = 0;
+    };
+    MatchFlags match;
+    hipEvent_t match_ev[2] = {nullptr, nullptr};  // around a lane's k_match; created with the lane's first one
+    bool flags_only() const { return (parent ? parent : this)->match.mode == MTSV_MATCH_ONLY; }
+    void set_match_flags(int mode);
+    // the flags of the last run as ceil(n_reads / 64) words (at least one), bits at and above n_reads zero
+    void match_flags(std::vector<uint64_t>& words, uint64_t* n_reads, uint64_t* n_matched);
     // rows: every TaxID with a non-zero counter, ascending
     void taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_reads, float* device_ms, bool reset);
 
    private:
-    void begin_run(const mtsv_params& p);
+    void begin_run(const mtsv_params& p, uint64_t read_base = 0);
     void reset_lane();
     void stage_reserve(uint64_t n_hits_needed);
     void host_room(uint64_t n, uint64_t total_bases, bool trace);

@@ -3,7 +3,11 @@
 // (0 ok, 2 query error, 3 no results path, 4 resume error, 11 write error, 12 read error;
 // invalid numbers abort like the reference's panics, exit 101), same results grammar
 // (src/binner.rs:310-379), same resume rule (:347-411).  Extras: --device / --devices, --batch-reads,
-// --parse-only (ingest check: prints record / base counts and checksums, needs no index or GPU).
+// --parse-only (ingest check: prints record / base counts and checksums, needs no index or GPU), --report, and
+// --matched / --unmatched: the reads of the run split by "the read got a hit", what the reference's mtsv-partition
+// (src/bin/mtsv-partition.rs) makes of the results file and a second pass over the reads -- here from one flag bit per
+// read that the device sets (k_match.hip), with no results file at all when --results is left out (read depletion).
+// A read counts by itself there: mtsv-partition keys reads by their ID text, so two records with one ID share a fate.
 // The reads of a batch are processed on the GPU; result lines are written in input order (the
 // reference's order is unspecified: vendor/cue/src/lib.rs:67-74).
 //
@@ -54,127 +58,8 @@ void logmsg(const char* level, const std::string& msg) {
     exit(101);
 }
 
-// open_maybe_gz (binner.rs:21-33): gzip magic sniff; zlib reads both transparently
-struct Input {
-    gzFile f = nullptr;
-    std::vector<char> buf;
-    size_t pos = 0, len = 0;
-    bool eof = false;
-    bool open(const std::string& path) {
-        f = gzopen(path.c_str(), "rb");
-        if (!f) return false;
-        gzbuffer(f, 1 << 20);
-        buf.resize(1 << 20);
-        return true;
-    }
-    ~Input() {
-        if (f) gzclose(f);
-    }
-    // returns false at EOF with no data; sets *err on a read error
-    bool getline(std::string& out, bool* err) {
-        out.clear();
-        for (;;) {
-            if (pos == len) {
-                if (eof) return !out.empty();
-                int n = gzread(f, buf.data(), (unsigned)buf.size());
-                if (n < 0) {
-                    *err = true;
-                    return false;
-                }
-                if (n == 0) {
-                    eof = true;
-                    return !out.empty();
-                }
-                pos = 0;
-                len = (size_t)n;
-            }
-            char* nl = (char*)memchr(buf.data() + pos, '\n', len - pos);
-            if (nl) {
-                out.append(buf.data() + pos, nl - (buf.data() + pos));
-                pos = nl - buf.data() + 1;
-                if (!out.empty() && out.back() == '\r') out.pop_back();
-                return true;
-            }
-            out.append(buf.data() + pos, len - pos);
-            pos = len;
-        }
-    }
-};
-
-struct Record {
-    std::string id, seq;
-};
-
-// bio::io::{fasta,fastq} readers as used at binner.rs:169-199; id = first token of the header
-struct FastxReader {
-    Input in;
-    bool fastq;
-    std::string pending;  // a header line already consumed (FASTA)
-    bool have_pending = false;
-    bool error = false;
-    std::string err_msg;
-
-    static std::string first_token(const std::string& h) {
-        size_t e = h.find_first_of(" \t", 1);
-        return h.substr(1, e == std::string::npos ? std::string::npos : e - 1);
-    }
-    bool next(Record& r) {
-        std::string line;
-        bool ioerr = false;
-        if (fastq) {
-            do {
-                if (!in.getline(line, &ioerr)) {
-                    if (ioerr) fail("read error");
-                    return false;
-                }
-            } while (line.empty());
-            if (line[0] != '@') return fail("Expected @ at record start.");
-            r.id = first_token(line);
-            r.seq.clear();
-            for (;;) {
-                if (!in.getline(line, &ioerr)) return fail("Incomplete record.");
-                if (!line.empty() && line[0] == '+') break;
-                r.seq += line;
-            }
-            size_t q = 0;
-            while (q < r.seq.size()) {
-                if (!in.getline(line, &ioerr)) return fail("Incomplete record.");
-                q += line.size();
-            }
-            if (r.seq.empty()) in.getline(line, &ioerr);  // empty quality line of an empty read
-            if (q != r.seq.size() && !r.seq.empty()) return fail("Unequal length of sequence an qualities.");
-            return true;
-        }
-        if (!have_pending) {
-            do {
-                if (!in.getline(line, &ioerr)) {
-                    if (ioerr) fail("read error");
-                    return false;
-                }
-            } while (line.empty());
-            pending = line;
-        }
-        have_pending = false;
-        if (pending.empty() || pending[0] != '>') return fail("Expected > at record start.");
-        r.id = first_token(pending);
-        r.seq.clear();
-        while (in.getline(line, &ioerr)) {
-            if (!line.empty() && line[0] == '>') {
-                pending = line;
-                have_pending = true;
-                break;
-            }
-            r.seq += line;
-        }
-        if (ioerr) return fail("read error");
-        return true;
-    }
-    bool fail(const char* m) {
-        error = true;
-        err_msg = m;
-        return false;
-    }
-};
+using mtsv_ingest::FastxReader;  // the serial reader (fastx_ingest.hpp)
+using mtsv_ingest::Record;
 
 // resume_offset_from_results (mtsv-binner.rs:366-396): index of the last input record whose id
 // appears in the results file, plus one
@@ -228,7 +113,7 @@ int resume_offset(const std::string& results, const std::string& input, bool fas
 }
 
 struct Args {
-    std::string fasta, fastq, index, results, report, output_format = "default";
+    std::string fasta, fastq, index, results, report, matched, unmatched, output_format = "default";
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
     bool verbose = false, force = false, parse_only = false;
@@ -331,6 +216,8 @@ int main(int argc, char** argv) {
             a.batch_reads = n;
         }
         else if (key == "--report") a.report = val();
+        else if (key == "--matched") a.matched = val();
+        else if (key == "--unmatched") a.unmatched = val();
         else if (key == "--parse-only") a.parse_only = true;
         else if (key == "-h" || key == "--help") {
             printf("mtsv-binner (MI355X) -- flags as the reference: --fasta|--fastq, -i/--index, -m/--results, -t/--threads,\n"
@@ -339,7 +226,13 @@ int main(int argc, char** argv) {
                    "extras: --devices 0,1,.. (index replicated, reads shared out), --index a,b,.. (database chunks, one per GPU, hits merged),\n"
                    "--batch-reads N, --parse-only,\n"
                    "--report TSV (per-TaxID read counts of the reads processed by this run, as mtsv-collapse --report writes them: with\n"
-                   "--read-offset or a resumed run, the reads binned now; counted on the GPU; not with a list of index chunks)\n");
+                   "--read-offset or a resumed run, the reads binned now; counted on the GPU; not with a list of index chunks),\n"
+                   "--matched PATH, --unmatched PATH (either or both: every read processed by this run is written, in input order, to\n"
+                   "--matched when it got a hit and to --unmatched when it did not, as mtsv-partition would from the results file; the\n"
+                   "decision is one bit per read set on the GPU.  Without -m/--results no results file is written and the hits are not\n"
+                   "even gathered: read depletion.  Reads skipped by --read-offset go to neither file; a run that would resume an\n"
+                   "existing results file is refused; not with a list of index chunks.  Every read counts by itself: mtsv-partition\n"
+                   "keys reads by their ID, so there records that share an ID share a fate)\n");
             return 0;
         } else if (key == "-V" || key == "--version") {
             printf("mtsv 2.1.0 (%s)\n", mtsv_version());
@@ -356,6 +249,15 @@ int main(int argc, char** argv) {
         fprintf(stderr, "error: '--report <TSV>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-collapse --report on the results file instead\n");
         return 1;
     }
+    const bool partition = !a.matched.empty() || !a.unmatched.empty();
+    if (partition && a.parse_only) usage_error("The argument '--parse-only' cannot be used with '--matched <PATH>' / '--unmatched <PATH>'");
+    if (partition && a.index.find(',') != std::string::npos) {
+        // (the flags of the chunks would have to be OR-ed per read)
+        fprintf(stderr, "error: '--matched <PATH>' / '--unmatched <PATH>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-partition on the results file instead\n");
+        return 1;
+    }
+    if (partition && !a.report.empty() && a.results.empty())
+        usage_error("The argument '--report <TSV>' requires '-m/--results <RESULTS>': the report is counted from gathered hits, and '--matched' / '--unmatched' without a results file gather none");
     if (a.output_format != "default" && a.output_format != "long")
         usage_error("'" + a.output_format + "' isn't a valid value for '--output-format <OUTPUT_FORMAT>'");
     g_verbose = a.verbose;
@@ -390,17 +292,22 @@ int main(int argc, char** argv) {
     p.seed_interval = (uint32_t)seed_gap;
     const bool long_fmt = a.output_format == "long";
 
-    if (a.results.empty() && !a.parse_only) {
+    const bool have_results = !a.results.empty();
+    if (a.results.empty() && !a.parse_only && !partition) {
         logmsg("ERROR", "No results path provided!");
         return 3;
     }
-    FILE* probe = fopen(a.results.c_str(), "rb");
+    FILE* probe = have_results ? fopen(a.results.c_str(), "rb") : nullptr;
     const bool exists = probe != nullptr;
     if (probe) fclose(probe);
     const bool append = !a.force && exists;
     uint64_t resume = 0;
     if (a.force) {
         logmsg("INFO", "Forcing overwrite of " + a.results);
+    } else if (exists && partition) {
+        // a resumed run sees only the reads after the last one in the results file: the partition files would be incomplete
+        fprintf(stderr, "error: results file %s exists and the run would resume it; '--matched' / '--unmatched' need the whole input: give --force-overwrite or another results path\n", a.results.c_str());
+        return 1;
     } else if (exists && !a.parse_only) {
         logmsg("INFO", "Existing results detected at " + a.results + "; resuming previous run.");
         if (resume_offset(a.results, input, fastq, &resume) != 0) {
@@ -415,6 +322,7 @@ int main(int argc, char** argv) {
     // Producer: block-parallel ingest for plain files (fastx_ingest.hpp), the serial reader for gzip
     // input and from the first irregular block on.  `emit` gets records in input order.
     using mtsv_ingest::ReadBlock;
+    mtsv_ingest::keep_records() = partition;  // descriptions and qualities: only when records are written out again
     FastxReader rd;
     rd.fastq = fastq;
     if (!rd.in.open(input)) {
@@ -542,20 +450,8 @@ int main(int argc, char** argv) {
                 while (from < blk.n()) {
                     const uint64_t room = batch_reads > w->n() ? batch_reads - w->n() : 0;
                     const uint64_t take = std::min<uint64_t>(room, blk.n() - from);
-                    if (take == blk.n() - from) {
-                        w->append(blk, from);
-                        from = blk.n();
-                    } else {
-                        ReadBlock part;  // records [from, from + take)
-                        part.bases.assign(blk.bases.begin() + (ptrdiff_t)blk.off[from], blk.bases.begin() + (ptrdiff_t)blk.off[from + take]);
-                        part.ids.assign(blk.ids, blk.id_off[from], blk.id_off[from + take] - blk.id_off[from]);
-                        for (uint64_t r = from + 1; r <= from + take; r++) {
-                            part.off.push_back(blk.off[r] - blk.off[from]);
-                            part.id_off.push_back(blk.id_off[r] - blk.id_off[from]);
-                        }
-                        w->append(part);
-                        from += take;
-                    }
+                    w->append(blk, from, from + take);  // records [from, from + take)
+                    from += take;
                     if (full()) {
                         if (!emit(std::move(w))) return true;
                         w = pool.get();
@@ -578,11 +474,7 @@ int main(int argc, char** argv) {
                 skipped++;
                 continue;
             }
-            w->bases.insert(w->bases.end(), (const uint8_t*)r.seq.data(), (const uint8_t*)r.seq.data() + r.seq.size());
-            w->off.push_back(w->bases.size());
-            w->ids += r.id;
-            w->ids.push_back('\0');
-            w->id_off.push_back(w->ids.size());
+            mtsv_ingest::push_record(*w, r);
             if (full()) {
                 if (!emit(std::move(w))) return true;
                 w = pool.get();
@@ -624,12 +516,25 @@ int main(int argc, char** argv) {
     }
 
     // positional writes from several threads: the result file is written at page-cache speed per thread
-    const int out_fd = ::open(a.results.c_str(), O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
+    const int out_fd = have_results ? ::open(a.results.c_str(), O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644) : -1;
     off_t out_pos = out_fd >= 0 ? lseek(out_fd, 0, SEEK_END) : 0;
-    if (out_fd < 0) {
+    if (have_results && out_fd < 0) {
         logmsg("ERROR", "Error running query: cannot open results file " + a.results);
         return 2;
     }
+    // the partition files: [0] matched, [1] unmatched (-1: not asked for)
+    int part_fd[2] = {-1, -1};
+    off_t part_pos[2] = {0, 0};
+    for (int k = 0; k < 2; k++) {
+        const std::string& path = k ? a.unmatched : a.matched;
+        if (path.empty()) continue;
+        part_fd[k] = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (part_fd[k] < 0) {
+            logmsg("ERROR", "Error running query: cannot open " + path);
+            return 2;
+        }
+    }
+    const int match_mode = !partition ? MTSV_MATCH_OFF : have_results ? MTSV_MATCH_WITH_HITS : MTSV_MATCH_ONLY;
     logmsg("INFO", "Deserializing candidate filter ...");
     std::vector<std::string> index_paths;
     for (size_t at = 0; at <= a.index.size();) {
@@ -735,6 +640,7 @@ int main(int argc, char** argv) {
             if (rc == MTSV_OK && !small_input && !getenv("MTSV_CLI_COLD"))
                 rc = mtsv_batch_reserve_host(ws_ready[wk], call_reads, call_reads * (uint64_t)(warm_len + warm_len / 8), warm_len);
             if (rc == MTSV_OK && !a.report.empty()) rc = mtsv_batch_set_taxa_report(ws_ready[wk], 1);  // (after the warm-up reads)
+            if (rc == MTSV_OK && partition) rc = mtsv_batch_set_match_flags(ws_ready[wk], match_mode);
             ws_rc[wk] = rc;
             if (rc != MTSV_OK) ws_msg[wk] = mtsv_last_error();  // (thread-local)
         };
@@ -784,6 +690,7 @@ int main(int argc, char** argv) {
         uint64_t n_hits = 0;
         uint64_t read_first = 0;  // the batch's first read in the numbering of its call (the formatter subtracts it)
         std::shared_ptr<void> hits_owner;  // the result array of the library call the batch was part of
+        std::shared_ptr<uint64_t> flags;   // --matched / --unmatched: the match flags of that call; read i of the batch is bit read_first + i
     };
     struct Queue {
         std::mutex mu;
@@ -852,6 +759,7 @@ int main(int argc, char** argv) {
     parsed.n_takers = n_workers;
     done.cap = n_workers * group_max + 1;
     std::atomic<int> calls_in_flight{0};
+    std::atomic<uint64_t> reads_matched{0}, reads_partitioned{0};
     std::mutex err_mu;
     int exit_code = 0;
     auto set_code = [&](int c) {
@@ -983,11 +891,63 @@ int main(int argc, char** argv) {
                 while (c > cut[k - 1] && c < w->n_hits && w->hits[c].read == w->hits[c - 1].read) c++;
                 cut[k] = c;
             }
+            // --matched / --unmatched: the batch's records, each to its side, serialised over ranges of reads in parallel and
+            // written at offsets fixed in batch order, like the result lines
+            if (partition && w->flags && !failed() && !write_failed.load()) {
+                const unsigned pp = n_reads >= (1u << 14) ? host_threads : 1;
+                std::vector<std::string> side[2];
+                side[0].resize(pp);
+                side[1].resize(pp);
+                const ReadBlock& blk = *w->rb;
+                const uint64_t* fw = w->flags.get();
+                const uint64_t first = w->read_first;
+                const bool want[2] = {part_fd[0] >= 0, part_fd[1] >= 0};
+                auto ser = [&](unsigned k) {
+                    const uint64_t r0 = n_reads * k / pp, r1 = n_reads * (k + 1) / pp;
+                    for (int sd = 0; sd < 2; sd++)
+                        if (want[sd]) side[sd][k].reserve((size_t)((blk.off[r1] - blk.off[r0]) * (fastq ? 2 : 1) + (r1 - r0) * 48));
+                    for (uint64_t i = r0; i < r1; i++) {
+                        const uint64_t bit = first + i;
+                        const int sd = (fw[bit >> 6] >> (bit & 63)) & 1 ? 0 : 1;
+                        if (want[sd]) mtsv_ingest::write_block_record(side[sd][k], fastq, blk, i);
+                    }
+                };
+                if (pp > 1) {
+                    for (unsigned k = 1; k < pp; k++) fmt_pool.submit([&ser, k] { ser(k); });
+                    ser(0);
+                    fmt_pool.wait_all();
+                } else {
+                    ser(0);
+                }
+                for (int sd = 0; sd < 2; sd++)
+                    for (unsigned k = 0; k < pp && want[sd]; k++) {
+                        if (side[sd][k].empty()) continue;
+                        auto tx = std::make_shared<std::string>(std::move(side[sd][k]));
+                        const off_t at = part_pos[sd];
+                        part_pos[sd] += (off_t)tx->size();
+                        const int fd = part_fd[sd];
+                        write_pool.submit([tx, at, fd, &write_failed, &set_code] {
+                            uint64_t done = 0;
+                            while (done < tx->size()) {
+                                ssize_t r = pwrite(fd, tx->data() + done, tx->size() - done, at + (off_t)done);
+                                if (r <= 0) {
+                                    write_failed.store(true);
+                                    set_code(11);
+                                    break;
+                                }
+                                done += (uint64_t)r;
+                            }
+                        });
+                    }
+                reads_partitioned += n_reads;
+            }
+            w->flags.reset();
             std::vector<char*> text(parts, nullptr);
             std::vector<uint64_t> len(parts, 0);
             std::vector<int> rc(parts, MTSV_OK);
             std::vector<std::string> msg(parts);
             auto fmt = [&](unsigned k) {
+                if (out_fd < 0) return;  // (no results file: --matched / --unmatched alone)
                 if (w->read_first)
                     for (uint64_t i = cut[k]; i < cut[k + 1]; i++) w->hits[i].read -= w->read_first;
                 rc[k] = mtsv_format_results(w->hits + cut[k], cut[k + 1] - cut[k], w->rb->ids.data(), w->rb->id_off.data(), n_reads,
@@ -1010,7 +970,7 @@ int main(int argc, char** argv) {
                     set_code(2);
                     ok = false;
                 }
-            if (ok && !failed() && !write_failed.load()) {
+            if (ok && !failed() && !write_failed.load() && out_fd >= 0) {
                 for (unsigned k = 0; k < parts; k++) {
                     const off_t at = out_pos;
                     out_pos += (off_t)len[k];
@@ -1092,7 +1052,21 @@ int main(int argc, char** argv) {
                     pn.push_back(w->rb->n());
                 }
                 rc = mtsv_batch_run_host_parts(ws, (int)group.size(), pb.data(), po.data(), pn.data(), &p);
-                if (rc == MTSV_OK) rc = mtsv_batch_download(ws, &hits, &n_hits);
+                if (rc == MTSV_OK && match_mode != MTSV_MATCH_ONLY) rc = mtsv_batch_download(ws, &hits, &n_hits);  // (flags only: there are none)
+            }
+            std::shared_ptr<uint64_t> flags;
+            if (rc == MTSV_OK && partition) {
+                uint64_t *words = nullptr, n_flagged = 0, n_match = 0;
+                rc = mtsv_batch_match_flags(ws, &words, &n_flagged, &n_match);
+                if (rc == MTSV_OK) {
+                    flags = std::shared_ptr<uint64_t>(words, [](uint64_t* q) { mtsv_free(q); });
+                    reads_matched += n_match;
+                    if (n_flagged != group_reads) {
+                        logmsg("ERROR", "Error running query: match flags for " + std::to_string(n_flagged) + " reads, the call held " + std::to_string(group_reads));
+                        set_code(2);
+                        continue;
+                    }
+                }
             }
             if (rc != MTSV_OK) {
                 logmsg("ERROR", std::string("Error running query: ") + mtsv_last_error());
@@ -1118,6 +1092,7 @@ int main(int argc, char** argv) {
                 w->n_hits = end - at;
                 w->read_first = first;
                 w->hits_owner = owner;
+                w->flags = flags;
                 at = end;
                 first += nr;
             }
@@ -1141,11 +1116,19 @@ int main(int argc, char** argv) {
         ~ReaderJoin() { t.join(); }
     } reader_join{reader};
     if (exit_code) return exit_code;
-    if (::close(out_fd) != 0) {
+    if (out_fd >= 0 && ::close(out_fd) != 0) {
         logmsg("ERROR", "Error writing to result file");
         return 11;
     }
     mark("results file closed");
+    for (int k = 0; k < 2; k++)
+        if (part_fd[k] >= 0 && ::close(part_fd[k]) != 0) {
+            logmsg("ERROR", std::string("Error writing to ") + (k ? a.unmatched : a.matched));
+            return 11;
+        }
+    if (partition)
+        logmsg("INFO", "Partitioned " + std::to_string(reads_partitioned.load()) + " reads: " + std::to_string(reads_matched.load()) + " matched, " +
+                           std::to_string(reads_partitioned.load() - reads_matched.load()) + " unmatched.");
     if (!a.report.empty()) {
         // the workers' counts add up: every read went through exactly one of their workspaces
         mtsv_taxon_stats* sum = nullptr;

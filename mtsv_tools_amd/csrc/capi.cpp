@@ -255,6 +255,13 @@ int mtsv_batch_reserve_host(mtsv_batch* b, uint64_t n_reads, uint64_t n_bases, u
             explicit ReportOff(bool& o) : on(o), was(o) { on = false; }
             ~ReportOff() { on = was; }
         } report_off(b->impl.report.on);
+        // (nor are they a run whose match flags anybody asked for; and they go through the gather kernels whatever the mode)
+        struct MatchOff {
+            int& mode;
+            const int was;
+            explicit MatchOff(int& m) : mode(m), was(m) { mode = MTSV_MATCH_OFF; }
+            ~MatchOff() { mode = was; }
+        } match_off(b->impl.match.mode);
         const std::vector<uint8_t>& text = b->impl.ix->host.text;
         if (warm_read_len && text.size() >= (uint64_t)warm_read_len * 2 + 16) {
             // reads sampled from the index through every kernel once: the first launch of a kernel loads its code object,
@@ -327,6 +334,23 @@ int mtsv_batch_taxa_report(mtsv_batch* b, mtsv_taxon_stats** rows, uint64_t* n_r
         *rows = out;
         *n_rows = r.size();
         if (device_ms) *device_ms = ms;
+    })
+}
+
+int mtsv_batch_set_match_flags(mtsv_batch* b, int mode) {
+    if (!b) return fail_arg("null argument");
+    GUARD(b->impl.set_match_flags(mode))
+}
+
+int mtsv_batch_match_flags(mtsv_batch* b, uint64_t** words, uint64_t* n_reads, uint64_t* n_matched) {
+    if (!b || !words || !n_reads || !n_matched) return fail_arg("null argument");
+    GUARD({
+        std::vector<uint64_t> w;
+        b->impl.match_flags(w, n_reads, n_matched);
+        auto* out = (uint64_t*)malloc(w.size() * sizeof(uint64_t));
+        if (!out) throw std::bad_alloc();
+        memcpy(out, w.data(), w.size() * sizeof(uint64_t));
+        *words = out;
     })
 }
 

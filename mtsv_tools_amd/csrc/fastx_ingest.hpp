@@ -116,31 +116,63 @@ class ByteBuf {
     bool pinned_ = false;
 };
 
+// Whether the readers keep what a record holds beside its ID and its bases: the rest of the header line and, for
+// FASTQ, the quality line (mtsv-binner --matched / --unmatched and mtsv-partition write records out again).  Off by
+// default: the parsers then do exactly what they do for binning alone.  Set before a reader is opened.
+inline bool& keep_records() {
+    static bool on = false;
+    return on;
+}
+
 struct ReadBlock {
     ByteBuf bases;
     std::vector<uint64_t> off{0};     // n + 1 offsets into bases
     std::string ids;                  // NUL-terminated ids, back to back
     std::vector<uint64_t> id_off{0};  // n + 1 offsets into ids
+    // keep_records() only (else empty, desc_off = {0}):
+    std::string desc;                   // descriptions back to back: the header after the ID's separator, trailing whitespace removed
+    std::vector<uint64_t> desc_off{0};  // n + 1 offsets into desc
+    std::string qual;                   // FASTQ: the quality strings, addressed by `off` like the bases (equal lengths)
     uint64_t n() const { return off.size() - 1; }
+    bool has_records() const { return desc_off.size() == off.size(); }
     void clear() {
         bases.clear();
         off.assign(1, 0);
         ids.clear();
         id_off.assign(1, 0);
+        desc.clear();
+        desc_off.assign(1, 0);
+        qual.clear();
     }
-    // append records [from, b.n()) of b
-    void append(const ReadBlock& b, uint64_t from = 0) {
-        const uint64_t nb = b.n();
+    // the description of a header line h[0, len) (marker included, line end removed): what follows the first space or tab
+    void push_desc(const uint8_t* h, uint64_t len) {
+        uint64_t e = 1;
+        while (e < len && h[e] != ' ' && h[e] != '\t') e++;
+        uint64_t a = e < len ? e + 1 : len, z = len;
+        while (z > a && (h[z - 1] == ' ' || h[z - 1] == '\t' || h[z - 1] == '\r' || h[z - 1] == '\n' || h[z - 1] == '\v' || h[z - 1] == '\f')) z--;
+        if (z > a) desc.append((const char*)h + a, z - a);
+        desc_off.push_back(desc.size());
+    }
+    // append records [from, to) of b (to: b.n() at most)
+    void append(const ReadBlock& b, uint64_t from = 0, uint64_t to = UINT64_MAX) {
+        const uint64_t nb = std::min(b.n(), to);
         if (from >= nb) return;
-        const uint64_t b0 = b.off[from], i0 = b.id_off[from];
+        const uint64_t b0 = b.off[from], b1 = b.off[nb], i0 = b.id_off[from], i1 = b.id_off[nb];
         const uint64_t base_b = bases.size(), base_i = ids.size();
-        bases.insert(bases.end(), b.bases.begin() + (ptrdiff_t)b0, b.bases.end());
-        ids.append(b.ids, i0, std::string::npos);
+        const bool rec = b.has_records() && (has_records() || n() == 0);
+        bases.insert(bases.end(), b.bases.begin() + (ptrdiff_t)b0, b.bases.begin() + (ptrdiff_t)b1);
+        ids.append(b.ids, i0, i1 - i0);
         off.reserve(off.size() + (nb - from));
         id_off.reserve(id_off.size() + (nb - from));
         for (uint64_t r = from + 1; r <= nb; r++) {
             off.push_back(base_b + (b.off[r] - b0));
             id_off.push_back(base_i + (b.id_off[r] - i0));
+        }
+        if (rec) {
+            const uint64_t d0 = b.desc_off[from], base_d = desc.size();
+            desc.append(b.desc, d0, b.desc_off[nb] - d0);
+            for (uint64_t r = from + 1; r <= nb; r++) desc_off.push_back(base_d + (b.desc_off[r] - d0));
+            if (!b.qual.empty()) qual.append(b.qual, b0, b1 - b0);
         }
     }
 };
@@ -384,6 +416,7 @@ class ParallelFastx {
         if (len > 1) b.ids.append((const char*)h + 1, e - 1);
         b.ids.push_back('\0');
         b.id_off.push_back(b.ids.size());
+        if (keep_records()) b.push_desc(h, len);
     }
 
     static uint64_t eol(const uint8_t* d, uint64_t s, uint64_t limit) {
@@ -412,6 +445,7 @@ class ParallelFastx {
             push_id(b, d + p, h_len);
             b.bases.insert(b.bases.end(), d + p1, d + p1 + s_len);
             b.off.push_back(b.bases.size());
+            if (keep_records()) b.qual.append((const char*)d + p3, q_len);
             p = e3 + 1;
         }
         return p == e || p == e + 1;  // ended on the boundary (or on a final line without '\n')
@@ -695,5 +729,189 @@ class GzFastx {
     uint64_t n_tasks_ = 0, consumed_ = 0, failed_at_ = UINT64_MAX;
     bool produced_all_ = false, stop_ = false, corrupt_ = false;
 };
+
+// ---- the serial reader: gzip input that cannot be decoded in parallel, irregular input, mtsv-partition ----
+// open_maybe_gz (binner.rs:21-33): gzip magic sniff; zlib reads both transparently
+struct Input {
+    gzFile f = nullptr;
+    std::vector<char> buf;
+    size_t pos = 0, len = 0;
+    bool eof = false;
+    bool open(const std::string& path) {
+        f = gzopen(path.c_str(), "rb");
+        if (!f) return false;
+        gzbuffer(f, 1 << 20);
+        buf.resize(1 << 20);
+        return true;
+    }
+    ~Input() {
+        if (f) gzclose(f);
+    }
+    // returns false at EOF with no data; sets *err on a read error
+    bool getline(std::string& out, bool* err) {
+        out.clear();
+        for (;;) {
+            if (pos == len) {
+                if (eof) return !out.empty();
+                int n = gzread(f, buf.data(), (unsigned)buf.size());
+                if (n < 0) {
+                    *err = true;
+                    return false;
+                }
+                if (n == 0) {
+                    eof = true;
+                    return !out.empty();
+                }
+                pos = 0;
+                len = (size_t)n;
+            }
+            char* nl = (char*)memchr(buf.data() + pos, '\n', len - pos);
+            if (nl) {
+                out.append(buf.data() + pos, nl - (buf.data() + pos));
+                pos = nl - buf.data() + 1;
+                if (!out.empty() && out.back() == '\r') out.pop_back();
+                return true;
+            }
+            out.append(buf.data() + pos, len - pos);
+            pos = len;
+        }
+    }
+};
+
+struct Record {
+    std::string id, seq;
+    std::string desc, qual;  // keep_records() only
+};
+
+// bio::io::{fasta,fastq} readers as used at binner.rs:169-199; id = first token of the header
+struct FastxReader {
+    Input in;
+    bool fastq;
+    std::string pending;  // a header line already consumed (FASTA)
+    bool have_pending = false;
+    bool error = false;
+    std::string err_msg;
+
+    static std::string first_token(const std::string& h) {
+        size_t e = h.find_first_of(" \t", 1);
+        return h.substr(1, e == std::string::npos ? std::string::npos : e - 1);
+    }
+    // what follows the ID's separator, trailing whitespace removed (ReadBlock::push_desc)
+    static std::string description(const std::string& h) {
+        size_t e = h.find_first_of(" \t", 1);
+        if (e == std::string::npos) return std::string();
+        size_t z = h.find_last_not_of(" \t\r\n\v\f");
+        return z == std::string::npos || z <= e ? std::string() : h.substr(e + 1, z - e);
+    }
+    bool next(Record& r) {
+        std::string line;
+        bool ioerr = false;
+        if (fastq) {
+            do {
+                if (!in.getline(line, &ioerr)) {
+                    if (ioerr) fail("read error");
+                    return false;
+                }
+            } while (line.empty());
+            if (line[0] != '@') return fail("Expected @ at record start.");
+            r.id = first_token(line);
+            const bool keep = keep_records();
+            if (keep) r.desc = description(line);
+            r.qual.clear();
+            r.seq.clear();
+            for (;;) {
+                if (!in.getline(line, &ioerr)) return fail("Incomplete record.");
+                if (!line.empty() && line[0] == '+') break;
+                r.seq += line;
+            }
+            size_t q = 0;
+            while (q < r.seq.size()) {
+                if (!in.getline(line, &ioerr)) return fail("Incomplete record.");
+                q += line.size();
+                if (keep) r.qual += line;
+            }
+            if (r.seq.empty()) in.getline(line, &ioerr);  // empty quality line of an empty read
+            if (q != r.seq.size() && !r.seq.empty()) return fail("Unequal length of sequence an qualities.");
+            return true;
+        }
+        if (!have_pending) {
+            do {
+                if (!in.getline(line, &ioerr)) {
+                    if (ioerr) fail("read error");
+                    return false;
+                }
+            } while (line.empty());
+            pending = line;
+        }
+        have_pending = false;
+        if (pending.empty() || pending[0] != '>') return fail("Expected > at record start.");
+        r.id = first_token(pending);
+        if (keep_records()) r.desc = description(pending);
+        r.seq.clear();
+        while (in.getline(line, &ioerr)) {
+            if (!line.empty() && line[0] == '>') {
+                pending = line;
+                have_pending = true;
+                break;
+            }
+            r.seq += line;
+        }
+        if (ioerr) return fail("read error");
+        return true;
+    }
+    bool fail(const char* m) {
+        error = true;
+        err_msg = m;
+        return false;
+    }
+};
+
+// a record of the serial reader at the end of a block
+inline void push_record(ReadBlock& w, const Record& r) {
+    w.bases.insert(w.bases.end(), (const uint8_t*)r.seq.data(), (const uint8_t*)r.seq.data() + r.seq.size());
+    w.off.push_back(w.bases.size());
+    w.ids += r.id;
+    w.ids.push_back('\0');
+    w.id_off.push_back(w.ids.size());
+    if (keep_records()) {
+        w.desc += r.desc;
+        w.desc_off.push_back(w.desc.size());
+        if (!r.qual.empty()) {  // FASTQ (the reader has checked the lengths: `off` addresses both)
+            w.qual.resize(w.bases.size() - r.seq.size(), '!');
+            w.qual += r.qual;
+        }
+    }
+}
+
+// One record as the partitioning tools write it: FASTA ">ID[ DESC]\nSEQ\n", FASTQ "@ID[ DESC]\nSEQ\n+\nQUAL\n".
+// ID: the first token of the header (split at space or tab), as the binner uses it; DESC: the rest of the header after
+// that one separator, trailing whitespace removed, left out with its space when empty; SEQ: the bases as they stood in the
+// file, case kept, wrapped lines joined.  (What the reference's mtsv-partition writes through the bio crate's FASTA / FASTQ
+// writers: this format is this project's definition of it)
+inline void write_record(std::string& out, bool fastq, const char* id, size_t id_len, const char* desc, size_t desc_len, const char* seq,
+                         size_t seq_len, const char* qual) {
+    out.push_back(fastq ? '@' : '>');
+    out.append(id, id_len);
+    if (desc_len) {
+        out.push_back(' ');
+        out.append(desc, desc_len);
+    }
+    out.push_back('\n');
+    out.append(seq, seq_len);
+    out.push_back('\n');
+    if (fastq) {
+        out.append("+\n", 2);
+        out.append(qual, seq_len);
+        out.push_back('\n');
+    }
+}
+// record i of a block that was parsed with keep_records() on
+inline void write_block_record(std::string& out, bool fastq, const ReadBlock& b, uint64_t i) {
+    const char* id = b.ids.data() + b.id_off[i];
+    const size_t id_len = strnlen(id, b.id_off[i + 1] - b.id_off[i]);
+    write_record(out, fastq, id, id_len, b.desc.data() + b.desc_off[i], b.desc_off[i + 1] - b.desc_off[i], (const char*)b.bases.data() + b.off[i],
+                 b.off[i + 1] - b.off[i], fastq ? b.qual.data() + b.off[i] : nullptr);
+}
+
 
 }  // namespace mtsv_ingest

@@ -1,6 +1,7 @@
 // kernels.hpp -- launch interface of the hot-path kernels.
 //
-// The mtsv-binner hot path as gfx950 kernels (k_seed.hip, k_coalesce.hip, k_verify.hip; k_report.hip for the taxa report).
+// The mtsv-binner hot path as gfx950 kernels (k_seed.hip, k_coalesce.hip, k_verify.hip; k_report.hip for the taxa report, k_match.hip for
+// the per-read match flags).
 //
 // One batch of reads flows through staged kernels with worklists in HBM:
 //
@@ -18,6 +19,7 @@
 //   k_resolve   lane per strand: cut-offs and rank order of the selection loop    index.rs:384-428
 //   scan + k_gather  compact per-strand hits into (read, strand, rank) order      binner.rs:128
 //   k_report    (taxa report on) lane per read: per-TaxID read counts of the pass   collapse.rs:120-146
+//   k_match     (match flags on) lane per read: one bit, "the read has a hit"      mtsv-partition.rs:34-54
 //
 // All arithmetic is integer; positions are u32 (n < 2^32).  No MFMA: the path is rank queries and
 // small dynamic programs.
@@ -174,5 +176,9 @@ constexpr uint32_t kReportHashSlots = 4096;
 void launch_report(hipStream_t s, uint32_t n_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits,
                    const uint32_t* taxa, uint32_t n_taxa, bool dense, uint32_t hash_slots, uint64_t* counts, uint64_t* total_reads,
                    uint64_t* n_global);
+// k_match.hip: the match flags of a pass.  Read r of the pass (strand_nout[2r], [2r + 1]: its hits per strand) sets bit
+// (first_bit + r) & 63 of words[(first_bit + r) >> 6] when it has a hit -- atomically: other streams may be writing the same
+// words -- and *n_matched grows by the number of such reads.  The words must be zero where no read has been flagged yet.
+void launch_match(hipStream_t s, uint32_t n_reads, const uint32_t* strand_nout, uint64_t first_bit, uint64_t* words, uint64_t* n_matched);
 
 }  // namespace mtsv
