@@ -118,6 +118,9 @@ typedef struct {
     float edit_ms;          /* k_edit_myers on the candidates that passed the prefilter (first round of every pass) */
     uint64_t myers_columns; /* window columns the bit-vector recurrences of k_edit_myers advanced (bound + edit distance) */
     uint64_t n_sw_bound_refuted; /* candidates the edit-distance bound refuted without a sweep */
+    uint64_t verify_turns;     /* passes that took the workspace's verify turn (0: one lane, or MTSV_VERIFY_TURN=0) */
+    uint64_t verify_lanes_max; /* lanes that had the verify kernels of a pass in flight at once, at most (1 with the turn) */
+    uint64_t myers_grid_max;   /* largest k_edit_myers grid of the run, in workgroups (at most 256 x MTSV_MYERS_WGS_PER_CU) */
 } mtsv_batch_stats;
 
 const char *mtsv_last_error(void);

@@ -92,6 +92,7 @@ bool host_pinned_unregister(void* p) {
 
 int g_default_verify_mode = MTSV_VERIFY_REFERENCE;
 
+constexpr uint32_t kMyersWgsPerCuLanes = 3;  // k_edit_myers workgroups per CU on a workspace of several lanes (4: 0.44 ms per step slower, profiles/README.md r10)
 constexpr uint64_t kLaneMinReads = 32768;  // a lane below this many reads does not fill the device
 constexpr uint64_t kChunkMaxReads = 4ull << 20;  // lanes take a range in chunks of at most this many reads (smaller chunks measured slower: per-pass launches and host round trips)
 
@@ -147,6 +148,19 @@ Batch::Batch(mtsv_index* ix_, DeviceIndex* di_, uint64_t max_reads_, uint64_t ma
     if (const char* e = getenv("MTSV_SW_FUSED")) sw_fused = atoi(e) != 0;
     verify_mode = g_default_verify_mode;
     if (const char* e = getenv("MTSV_VERIFY")) verify_mode = !strcmp(e, "edit_first") ? 1 : 0;
+    if (!parent) {
+        // (measured on config2, profiles/README.md r10)
+        myers_wgs_per_cu = n_lanes > 1 ? kMyersWgsPerCuLanes : kMyersWgsPerCuMax;
+        if (const char* e = getenv("MTSV_MYERS_WGS_PER_CU")) myers_wgs_per_cu = (uint32_t)std::max(1, std::min((int)kMyersWgsPerCuMax, atoi(e)));
+        verify_turn.on = n_lanes > 1;
+        if (const char* e = getenv("MTSV_VERIFY_TURN")) verify_turn.on = verify_turn.on && atoi(e) != 0;
+        if (const char* e = getenv("MTSV_TAIL_FROM_LIST")) tail_from_list = atoi(e) != 0;
+        if (const char* e = getenv("MTSV_FUSED_CLEAR")) fused_clear = atoi(e) != 0;
+    } else {
+        myers_wgs_per_cu = parent->myers_wgs_per_cu;
+        tail_from_list = parent->tail_from_list;
+        fused_clear = parent->fused_clear;
+    }
     for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
     for (int k = 1; k < n_lanes; k++) {
         extra.emplace_back(new Batch(ix, di, ws_reads, 0, hit_cap_user, this));
@@ -221,6 +235,33 @@ void Batch::grow_hit_workspace(uint64_t need) {
     alloc_hit_workspace();
 }
 
+void Batch::VerifyTurn::enter(uint64_t first_read, const Batch* lane) {
+    std::unique_lock<std::mutex> lk(mu);
+    if (on) {
+        const std::pair<uint64_t, const Batch*> me{first_read, lane};
+        waiting.push_back(me);
+        cv.wait(lk, [&] { return !held && *std::min_element(waiting.begin(), waiting.end()) == me; });
+        waiting.erase(std::find(waiting.begin(), waiting.end(), me));
+        held = true;
+        taken++;
+    }
+    max_in_verify = std::max(max_in_verify, ++in_verify);
+}
+
+void Batch::VerifyTurn::leave() {
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        in_verify--;
+        held = false;
+    }
+    cv.notify_all();
+}
+
+void Batch::VerifyTurn::note_grid(uint32_t blocks) {
+    std::lock_guard<std::mutex> lk(mu);
+    myers_grid_max = std::max<uint64_t>(myers_grid_max, blocks);
+}
+
 void Batch::upload(const uint8_t* bases, const uint64_t* read_off, uint64_t n) {
     if (n > max_reads) throw std::runtime_error("arg: batch holds more reads than the workspace was created for");
     const uint64_t first = n ? read_off[0] : 0;
@@ -255,6 +296,7 @@ void Batch::reset_lane() {
     sw_passed_acc = 0;
     n_hits_total = 0;
     HIP_CHECK(hipMemsetAsync(d_counters, 0, kCounters * sizeof(uint64_t), stream));
+    ctr22_zero = true;
     HIP_CHECK(hipEventRecord(ev[8], stream));
 }
 
@@ -291,6 +333,10 @@ void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
     lanes_used = 1;
     staged_valid = false;
     run_t0 = now_s();
+    {
+        std::lock_guard<std::mutex> lk(verify_turn.mu);
+        verify_turn.taken = verify_turn.max_in_verify = verify_turn.myers_grid_max = 0;
+    }
     reset_lane();
     for (auto& l : extra) {
         l->verify_mode = verify_mode;
@@ -356,6 +402,9 @@ void Batch::end_run() {
     for (int s = 0; s < MTSV_N_STAGES; s++) stats.stage_ms[s] = stage_acc[s];
     stats.n_reads = n_reads;
     stats.n_lanes = lanes_used;
+    stats.verify_turns = verify_turn.taken;
+    stats.verify_lanes_max = verify_turn.max_in_verify;
+    stats.myers_grid_max = verify_turn.myers_grid_max;
     total_hits = 0;
     for (auto& sg : segments) total_hits += sg.count;
     stats.n_hits = total_hits;
@@ -596,7 +645,11 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
         }
         // the reads' bit planes (EvalArgs::planes) for the passes k_edit_myers verifies: k_thin writes them, sized like
         // the seed slot arrays for a full workspace of reads like these
-        const bool myers_pass = !tiled && pass_max_len <= 253 && (verify_mode == 1 || (sw_pairs && hit_cap < 0x80000000ull));
+        // the verify path of the pass, decided once: edit-first order, or the reference order in rounds (k_sw_pairs +
+        // k_edit_myers; bit 31 of a work item is a flag, so hit_cap < 2^31) -- both through k_edit_myers, reads up to 253 bases
+        const bool edit_first_path = !tiled && verify_mode == 1 && pass_max_len <= 253;
+        const bool rounds_path = !tiled && !edit_first_path && sw_pairs && pass_max_len <= 253 && hit_cap < 0x80000000ull;
+        const bool myers_pass = edit_first_path || rounds_path;
         const uint32_t plane_words = myers_pass ? myers_words(pass_max_len) : 0;
         if ((uint64_t)nr * 3 * plane_words > plane_cap) {
             (void)hipFree(d_planes);
@@ -612,7 +665,9 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
         //  the seed's table part; counter slot 22.  The second kernel's grid covers the share of such slots the passes before
         //  had, half as much again: the count is checked at the pass's first round trip below.)
         const uint32_t listed_cap = (uint32_t)std::min<uint64_t>(slots, std::max<uint64_t>(4096, (uint64_t)((double)slots * listed_share)));
-        launch_search(stream, v, sb, so, (uint32_t)r0, nr, max_ns, K, G, d_seed_lo, d_seed_cnt, d_seed_pre, (uint32_t*)(d_counters + 22), listed_cap, di->d_kmer_levels);
+        launch_search(stream, v, sb, so, (uint32_t)r0, nr, max_ns, K, G, d_seed_lo, d_seed_cnt, d_seed_pre, (uint32_t*)(d_counters + 22), listed_cap, di->d_kmer_levels,
+                      fused_clear && ctr22_zero);
+        ctr22_zero = false;
         HIP_CHECK(hipEventRecord(ev[1], stream));
         if (max_ns)
             launch_thin(stream, sb, so, (uint32_t)r0, nr, p.edit_rate, p.min_seed, max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,
@@ -660,14 +715,32 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
         HIP_CHECK(hipEventRecord(ev[4], stream));
         // ---- candidates ----
         // counters: [1] lo = round-0 worklist count, [7] lo/hi = ping-pong counts of later rounds
-        HIP_CHECK(hipMemsetAsync(d_counters + 1, 0, 8, stream));
-        HIP_CHECK(hipMemsetAsync(d_counters + 7, 0, 8, stream));
-        HIP_CHECK(hipMemsetAsync(d_counters + 15, 0, 8, stream));  // [15] lo = strands for k_coalesce_mid, hi = strands of 13..16 seed hits
+        // [15] lo = strands for k_coalesce_mid, hi = strands of 13..16 seed hits
+        // One launch zeroes these, k_coalesce_heavy's ticket, the counters round 0 of the verify rounds starts from ([8..11],
+        // [17..18]; no coalescing kernel touches them) and k_search's list count of the next pass ([22]: the host has read it).
+        if (fused_clear) {
+            uint64_t mask = 1ull << 1 | 1ull << 7 | 1ull << 15 | 1ull << kCtrHeavyTicket | 1ull << 22;
+            if (rounds_path) mask |= 1ull << 8 | 1ull << 9 | 1ull << 10 | 1ull << 11 | 1ull << 17 | 1ull << 18;
+            launch_clear_counters(stream, d_counters, mask);
+            ctr22_zero = true;
+        } else {
+            HIP_CHECK(hipMemsetAsync(d_counters + 1, 0, 8, stream));
+            HIP_CHECK(hipMemsetAsync(d_counters + 7, 0, 8, stream));
+            HIP_CHECK(hipMemsetAsync(d_counters + 15, 0, 8, stream));
+        }
         launch_coalesce(stream, v, so, (uint32_t)r0, nstr, p.max_candidates, d_strand_off,
                         d_strand_nseeds, d_hit_ref, d_hit_q, d_hit_key, d_cand_tmp, d_cand, d_cand_next,
-                        d_cand_status, d_strand_ncand, d_worklist, d_heavy_list, d_counters);
+                        d_cand_status, d_strand_ncand, d_worklist, d_heavy_list, d_counters, fused_clear);
         HIP_CHECK(hipEventRecord(ev[5], stream));
         // ---- verify: rounds over the same-TaxId chains ----
+        // One lane of the workspace at a time (the turn): this lane's coalescing kernels are enqueued and run while it waits,
+        // beside the verify kernels of the lane that has it.  It goes back after the pass's last verify round trip, or with
+        // whatever leaves this pass early.  (A pass without seed hits does not take it; its kernels are still launched, at
+        // their smallest grids, and find nothing.)
+        Batch* const root = parent ? parent : this;
+        VerifyTurn::Guard turn;
+        if (total_hits) turn.take(root->verify_turn, read_base + r0, this);
+        const uint32_t R = root->myers_wgs_per_cu;
         {
             EvalArgs a;
             a.bases = sb;
@@ -708,9 +781,9 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                 a.strip = d_strip;
                 a.strip_len = strip_len;
                 launch_evaluate_tiled(stream, v, a, total_hits);
-            } else if (verify_mode == 1 && pass_max_len <= 253) {
-                launch_edit_myers(stream, v, a, total_hits, pass_max_len);
-            } else if (sw_pairs && pass_max_len <= 253 && hit_cap < 0x80000000ull) {  // (bit 31 of a work item is a flag)
+            } else if (edit_first_path) {
+                root->verify_turn.note_grid(launch_edit_myers(stream, v, a, total_hits, pass_max_len, 0, R));
+            } else if (rounds_path) {
                 // Reference order, split by predicate: k_sw_pairs runs the prefilter of index.rs:406 two
                 // candidates per group, k_edit_myers the edit distance of :407-410 on those that passed.
                 // A candidate that passes the first and fails the second sends its TaxId's next
@@ -730,8 +803,17 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                 uint64_t items = total_hits;
                 for (uint32_t round = 0;; round++) {
                     uint64_t* next_slot = d_counters + 11 + (round & 1);
-                    HIP_CHECK(hipMemsetAsync(d_counters + 8, 0, 3 * sizeof(uint64_t), stream));
-                    HIP_CHECK(hipMemsetAsync(next_slot, 0, sizeof(uint64_t), stream));
+                    if (!fused_clear) {
+                        HIP_CHECK(hipMemsetAsync(d_counters + 8, 0, 3 * sizeof(uint64_t), stream));
+                        HIP_CHECK(hipMemsetAsync(next_slot, 0, sizeof(uint64_t), stream));
+                    } else if (round) {  // (round 0: zeroed with the coalescing kernels' counters)
+                        launch_clear_counters(stream, d_counters, 1ull << 8 | 1ull << 9 | 1ull << 10 | 1ull << (11 + (round & 1)));
+                    }
+                    // The tail of a round -- k_sw_pairs and list-mode k_edit_myers -- is sized from its own list: later rounds
+                    // have its length on the host (n_next); round 0 asks for what the fused pass left undecided, one more round
+                    // trip in place of two persistent grids sized from the pass's seed hits.  An empty list launches nothing.
+                    uint64_t tail_items = items;
+                    bool tail_listed = tail_from_list && round > 0;
                     EvalArgs sw = a;
                     sw.worklist = wl;
                     sw.wl_count = wl_count;
@@ -760,7 +842,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                         // matrix's matches bounds the score from both sides (k_edit_myers in bound mode) at a third of a
                         // sweep's instructions: it refutes those, passes most of the rest, and only what lies between its
                         // two thresholds ([17] counts it; the seed-hit rows of k_expand are free by now) is swept below.
-                        HIP_CHECK(hipMemsetAsync(d_counters + 17, 0, 2 * sizeof(uint64_t), stream));  // [18]: its claim cursor
+                        if (!fused_clear) HIP_CHECK(hipMemsetAsync(d_counters + 17, 0, 2 * sizeof(uint64_t), stream));  // [18]: its claim cursor
                         EvalArgs bd = sw;
                         bd.wl_count = (const uint32_t*)(d_counters + sw.wl_count_slot);
                         bd.wl_cursor = (uint32_t*)(d_counters + 18);
@@ -768,11 +850,17 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                         bd.und_slot = 17;
                         bd.myers_ctr = (unsigned long long*)(d_counters + 19);
                         // (fused: from the worklist's end, and accepted candidates go straight to `out`)
-                        launch_edit_myers(stream, v, bd, items, pass_max_len, fused ? 3 : 2);
+                        root->verify_turn.note_grid(launch_edit_myers(stream, v, bd, items, pass_max_len, fused ? 3 : 2, R));
                         HIP_CHECK(hipEventRecord(ev[13], stream));
                         sw.worklist = bd.und_list;
                         sw.wl_count_slot = 17;
                         sw.wl_reverse = 0;
+                        if (fused && tail_from_list) {  // (fused: the pass list holds only what k_sw_pairs passes of these)
+                            launch_publish(stream, d_counters + 17, h_counters + 17, 1);
+                            HIP_CHECK(hipStreamSynchronize(stream));
+                            tail_items = h_counters[17] & 0xffffffffull;
+                            tail_listed = true;
+                        }
                     } else if (round == 0 && sw_diag && sw_prepass && sw_top) {
                         // (MTSV_SW_BOUND=0) most of these are refuted on the top half of the read rows; the full-height launch
                         // below takes what is left ([17] counts it)
@@ -784,7 +872,8 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                         sw.worklist = sw.und_list;
                         sw.wl_count_slot = 17;
                     }
-                    launch_sw_pairs(stream, v, sw, items, pass_max_len, sw_diag, false, round == 0 && sw_bound);
+                    const bool tail_empty = tail_listed && tail_items == 0;
+                    if (!tail_empty) launch_sw_pairs(stream, v, sw, tail_items, pass_max_len, sw_diag, false, round == 0 && sw_bound && !tail_listed);
 #ifdef MTSV_SW_HIST
                     {
                         static uint32_t hh[768];
@@ -807,11 +896,16 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                     my.next_list = next_lists[round & 1];
                     my.next_count = (uint32_t*)next_slot;
                     my.myers_ctr = (unsigned long long*)(d_counters + 19);
-                    launch_edit_myers(stream, v, my, items, pass_max_len, 1);
+                    if (!tail_empty) root->verify_turn.note_grid(launch_edit_myers(stream, v, my, tail_items, pass_max_len, 1, R, tail_listed));
                     if (round == 0) HIP_CHECK(hipEventRecord(ev[14], stream));
-                    launch_publish(stream, next_slot, h_counters + 11, 1);
-                    launch_publish(stream, d_counters + 9, h_counters + 9, 1);
-                    HIP_CHECK(hipStreamSynchronize(stream));
+                    if (tail_empty) {
+                        h_counters[9] = h_counters[11] = 0;  // nothing passed, nothing for another round
+                        if (round == 0) HIP_CHECK(hipEventSynchronize(ev[14]));
+                    } else {
+                        launch_publish(stream, next_slot, h_counters + 11, 1);
+                        launch_publish(stream, d_counters + 9, h_counters + 9, 1);
+                        HIP_CHECK(hipStreamSynchronize(stream));
+                    }
                     sw_passed_acc += h_counters[9] & 0xffffffffull;
                     if (round == 0) {
                         float ms = 0;
@@ -840,6 +934,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                     wl_count = (const uint32_t*)next_slot;
                     items = n_next;
                 }
+                turn.release();
             } else {
                 launch_evaluate(stream, v, a, total_hits, pass_max_len);
             }
@@ -857,6 +952,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
             launch_publish(stream, d_counters, h_counters, 8);
             HIP_CHECK(hipStreamSynchronize(stream));
             total_out = h_counters[6];
+            turn.release();  // (the paths without rounds: their verify kernels are through)
         }
         if (n_hits_total + total_out > hits_cap) {
             // grow the result array, keeping what earlier passes produced
@@ -901,6 +997,7 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
         }
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipGetLastError());
+        turn.release();
         if (mf.mode != MTSV_MATCH_OFF) {
             float ms = 0;
             HIP_CHECK(hipEventElapsedTime(&ms, match_ev[0], match_ev[1]));

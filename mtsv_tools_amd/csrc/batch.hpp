@@ -1,5 +1,6 @@
 // batch.hpp -- device workspace of one read batch (see batch.hip).
 #pragma once
+#include <condition_variable>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -89,6 +90,48 @@ struct Batch {
     bool sw_fused = true;    // ... and that pass decides the edit distance too, on the whole worklist, with no k_sw_diag before it (MTSV_SW_FUSED=0: off)
     bool sw_prepass = true;  // the first round's bounds run as a kernel of their own, k_sw_diag (MTSV_SW_PREPASS=0: inside k_sw_pairs)
     bool sw_pairs = true;  // reference order for reads <= 253 bases: k_sw_pairs + k_edit_myers (MTSV_SW=packed: k_evaluate)
+    // Lane policies, read from the environment when the owner is created and handed to its lanes ("Lanes"):
+    uint32_t myers_wgs_per_cu = kMyersWgsPerCuMax;  // k_edit_myers' grid is 256 x this many workgroups at most: five fill a CU's LDS, a workspace
+                                                    // of several lanes leaves room for the other lanes' kernels (MTSV_MYERS_WGS_PER_CU)
+    bool tail_from_list = true;  // round 0's k_sw_pairs and list-mode k_edit_myers are sized from the undecided count the fused pass
+                                 // publishes, and not launched when it is zero (MTSV_TAIL_FROM_LIST=0: sized from the seed hits)
+    bool fused_clear = true;     // the counters of a stage are zeroed by one launch_clear_counters (MTSV_FUSED_CLEAR=0: a memset each)
+    bool ctr22_zero = false;     // ... slot 22 (k_search's list count) is known to be zero on the stream
+    // The verify turn: one lane of a workspace at a time has the verify kernels of a pass in flight (two VALU-bound launches beside
+    // each other gain nothing, and the second takes the LDS the first frees from the memory-bound kernels that could use it).  The
+    // owner holds it; lanes waiting for it are served in the order of their passes' first reads (MTSV_VERIFY_TURN=0: off; never
+    // used by a workspace of one lane).
+    struct VerifyTurn {
+        bool on = false;
+        std::mutex mu;
+        std::condition_variable cv;
+        bool held = false;
+        std::vector<std::pair<uint64_t, const Batch*>> waiting;
+        // of the last run (mtsv_batch_stats): passes that took the turn; lanes inside the verify section of a pass at once, at
+        // most (counted with the turn on or off: 1 shows that it serialises); the largest k_edit_myers grid launched
+        uint64_t taken = 0, in_verify = 0, max_in_verify = 0, myers_grid_max = 0;
+        void enter(uint64_t first_read, const Batch* lane);  // waits for the turn when it is on
+        void leave();
+        void note_grid(uint32_t blocks);
+        // holds the turn from take() until release() or the end of the scope, whichever comes first
+        struct Guard {
+            VerifyTurn* t = nullptr;
+            Guard() = default;
+            Guard(const Guard&) = delete;
+            Guard& operator=(const Guard&) = delete;
+            ~Guard() { release(); }
+            void take(VerifyTurn& turn, uint64_t first_read, const Batch* lane) {
+                if (t) return;
+                turn.enter(first_read, lane);
+                t = &turn;
+            }
+            void release() {
+                if (t) t->leave();
+                t = nullptr;
+            }
+        };
+    };
+    VerifyTurn verify_turn;
     int verify_mode = 0;  // 0 = reference order (SW + edit per candidate), 1 = edit first (MTSV_VERIFY_EDIT_FIRST)
     uint64_t n_reads = 0;
     uint64_t n_hits_total = 0;

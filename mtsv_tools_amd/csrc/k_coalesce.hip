@@ -935,7 +935,8 @@ void launch_coalesce(hipStream_t s, const DevIndexView& ix, const uint32_t* read
                      int64_t max_candidates, const uint32_t* strand_off,
                      const uint32_t* strand_nseeds, const uint32_t* hit_ref, const uint32_t* hit_q, uint64_t* hit_key,
                      uint64_t* cand_tmp, uint4* cand, uint32_t* cand_next, uint32_t* cand_status,
-                     uint32_t* strand_ncand, uint32_t* worklist, uint32_t* heavy_list, uint64_t* counters) {
+                     uint32_t* strand_ncand, uint32_t* worklist, uint32_t* heavy_list, uint64_t* counters,
+                     bool ticket_is_zero) {
     uint32_t* wl_count = reinterpret_cast<uint32_t*>(counters + 1);
     uint32_t* heavy_count = wl_count + 1;
     unsigned long long* n_cand_total = reinterpret_cast<unsigned long long*>(counters + 3);
@@ -991,7 +992,7 @@ void launch_coalesce(hipStream_t s, const DevIndexView& ix, const uint32_t* read
     if (serial_walk || ix.n_bins >= 0x80000000u) {
         hipLaunchKernelGGL((k_coalesce_heavy<kHeavyKeysSmall, false>), hgrid, dim3(256), 0, s, ix, a, heavy_list, n_strands, heavy_count);
     } else {
-        (void)hipMemsetAsync(counters + kCtrHeavyTicket, 0, sizeof(uint64_t), s);
+        if (!ticket_is_zero) (void)hipMemsetAsync(counters + kCtrHeavyTicket, 0, sizeof(uint64_t), s);
         hipLaunchKernelGGL((k_coalesce_heavy<kHeavyKeysSmall, true>), hgrid, dim3(256), 0, s, ix, a, heavy_list, n_strands, heavy_count);
     }
     hipLaunchKernelGGL((k_coalesce_heavy<kHeavyKeys, false>), dim3(std::min<uint32_t>(hgrid.x, 512)), dim3(256), 0, s, ix, a, heavy_list, n_strands, heavy_count);

@@ -785,10 +785,17 @@ namespace {
 __global__ void k_publish(const uint64_t* __restrict__ src, uint64_t* dst, uint32_t n) {
     if (threadIdx.x < n) __hip_atomic_store(dst + threadIdx.x, src[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+__global__ void k_clear_counters(uint64_t* counters, uint64_t mask) {
+    if ((mask >> threadIdx.x) & 1) counters[threadIdx.x] = 0;
+}
 }  // namespace
 
 void launch_publish(hipStream_t s, const uint64_t* src, uint64_t* dst_host, uint32_t n) {
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, s, src, dst_host, n);
+}
+
+void launch_clear_counters(hipStream_t s, uint64_t* counters, uint64_t mask) {
+    if (mask) hipLaunchKernelGGL(k_clear_counters, dim3(1), dim3(64), 0, s, counters, mask);
 }
 
 void launch_normalise(hipStream_t s, const uint8_t* src, uint8_t* dst, uint64_t begin, uint64_t end) {
@@ -804,8 +811,10 @@ void launch_unpack(hipStream_t s, const uint8_t* packed, uint8_t* dst, uint64_t 
 
 void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, const uint32_t* read_off, uint32_t r0,
                    uint32_t n_reads, uint32_t max_ns, uint32_t K, uint32_t G, uint32_t* seed_lo, uint32_t* seed_cnt,
-                   uint32_t* slow_list, uint32_t* slow_count, uint32_t listed_cap, const uint2* kmer_levels) {
-    (void)hipMemsetAsync(slow_count, 0, sizeof(uint32_t), s);  // (whichever path is taken: the caller reads it after every pass)
+                   uint32_t* slow_list, uint32_t* slow_count, uint32_t listed_cap, const uint2* kmer_levels,
+                   bool count_is_zero) {
+    // (whichever path is taken: the caller reads the count after every pass)
+    if (!count_is_zero) (void)hipMemsetAsync(slow_count, 0, sizeof(uint32_t), s);
     uint64_t total = (uint64_t)n_reads * 2 * max_ns;
     if (!total) return;
     const bool fast = ix.kmer_tab && total < 0xffffffffull && K >= 16 && K <= 24 && ix.kmer_k >= 12 && ix.kmer_k <= 17 &&

@@ -1813,8 +1813,8 @@ void launch_sw_diag(hipStream_t s, const DevIndexView& ix, const EvalArgs& a, ui
     else hipLaunchKernelGGL(k_sw_diag<4>, dim3(grid), dim3(256), 0, s, ix, a, sweep_list, sweep_slot);
 }
 
-void launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a_, uint64_t max_items, uint32_t max_len,
-                       int mode) {
+uint32_t launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a_, uint64_t max_items, uint32_t max_len,
+                           int mode, uint32_t wgs_per_cu, bool listed) {
     EvalArgs a = a_;
     a.maxc = rank_bound(a.max_candidates);
     if (!a.planes || a.plane_words != myers_words(max_len)) throw std::runtime_error("internal: k_edit_myers needs the pass's read planes");
@@ -1822,7 +1822,11 @@ void launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a_
     // most, and smaller when the list is short: workgroups cost ~0.1 us each to dispatch, with work or without, and
     // the lists are claimed 64 candidates at a time whatever the grid
     // (4096, 1024 or 512 hits per workgroup: the same within the noise on passes of 84 k to 1 M reads)
-    uint32_t blocks = std::max<uint32_t>(16, std::min<uint32_t>(cdiv(max_items, 4096), 256 * 5));
+    // wgs_per_cu < 5 (a workspace of several lanes): the persistent workgroups hold their 30 KiB of LDS until the launch
+    // ends, and five per CU leave another lane's coalescing kernels no room beside them
+    // listed: max_items is the length of the list itself, a lane per entry
+    const uint32_t resident = 256 * std::max<uint32_t>(1, std::min<uint32_t>(wgs_per_cu, kMyersWgsPerCuMax));
+    uint32_t blocks = std::max<uint32_t>(16, std::min<uint32_t>(cdiv(max_items, listed ? 256 : 4096), resident));
     const uint32_t W = myers_words(max_len);
 #define MYERS_CASE(WW)                                                                                   \
     do {                                                                                                 \
@@ -1839,6 +1843,7 @@ void launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a_
     else if (W == 7) MYERS_CASE(7);
     else MYERS_CASE(8);
 #undef MYERS_CASE
+    return blocks;
 }
 
 void launch_resolve(hipStream_t s, uint32_t n_strands, int64_t max_candidates, int64_t max_assignments,

@@ -102,13 +102,17 @@ constexpr uint32_t kMaxReadLen = 32767;        // the tiled kernel's packed 16-b
 
 // n <= 64 counters from HBM into mapped page-locked host memory, by a kernel on stream s (no copy engine involved)
 void launch_publish(hipStream_t s, const uint64_t* src, uint64_t* dst_host, uint32_t n);
+// zeroes counters[i] for every bit i < 64 set in mask: the counters a stage starts from, in one launch
+void launch_clear_counters(hipStream_t s, uint64_t* counters, uint64_t mask);
 // base normalisation of bytes [begin, end) of a read buffer, src -> dst (may be equal): every other kernel expects codes
 void launch_normalise(hipStream_t s, const uint8_t* src, uint8_t* dst, uint64_t begin, uint64_t end);
 // run_host's transfer format (4-bit codes, host_pack.hpp) into byte codes: bytes [lo, hi) of dst from packed[lo / 2 ...]
 void launch_unpack(hipStream_t s, const uint8_t* packed, uint8_t* dst, uint64_t lo, uint64_t hi);
 void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, const uint32_t* read_off, uint32_t r0,
                    uint32_t n_reads, uint32_t max_ns, uint32_t K, uint32_t G, uint32_t* seed_lo, uint32_t* seed_cnt,
-                   uint32_t* slow_list, uint32_t* slow_count, uint32_t listed_cap, const uint2* kmer_levels);
+                   uint32_t* slow_list, uint32_t* slow_count, uint32_t listed_cap, const uint2* kmer_levels,
+                   bool count_is_zero = false);
+// count_is_zero: the caller has zeroed *slow_count on this stream already (launch_clear_counters)
 // slow_list: room for every seed slot; *slow_count: a counter of the lane; listed_cap: list entries the second kernel's grid covers
 // (the caller compares *slow_count with it afterwards); kmer_levels: DeviceIndex::d_kmer_levels, or null (a kernel argument of
 // its own: the index view is at k_search_fast's scalar-register budget as it is)
@@ -131,7 +135,9 @@ void launch_coalesce(hipStream_t s, const DevIndexView& ix, const uint32_t* read
                      int64_t max_candidates, const uint32_t* strand_off,
                      const uint32_t* strand_nseeds, const uint32_t* hit_ref, const uint32_t* hit_q, uint64_t* hit_key,
                      uint64_t* cand_tmp, uint4* cand, uint32_t* cand_next, uint32_t* cand_status,
-                     uint32_t* strand_ncand, uint32_t* worklist, uint32_t* heavy_list, uint64_t* counters);
+                     uint32_t* strand_ncand, uint32_t* worklist, uint32_t* heavy_list, uint64_t* counters,
+                     bool ticket_is_zero = false);
+// ticket_is_zero: the caller has zeroed counters[kCtrHeavyTicket] on this stream already (launch_clear_counters)
 void launch_evaluate(hipStream_t s, const DevIndexView& ix, const EvalArgs& a, uint64_t max_items, uint32_t max_len);
 // reads of kMaxRegisterReadLen + 1 .. kMaxReadLen bases: the same sweep in bands of 256 rows (a.strip / a.strip_len set:
 // tiled_groups(max_items, strip_len) strips of strip_len uint2 each, strip_len >= the pass's longest window)
@@ -147,8 +153,13 @@ void launch_max_window(hipStream_t s, uint32_t n_strands, const uint32_t* strand
 // 3: fused -- bound and edit distance of the unfiltered worklist (read from its end when a.wl_reverse) in one pass: refutes
 // as mode 2 does, accepts into a.out what the bound passes when read or window holds no N (a second pass under the edit
 // distance's matches otherwise), and leaves the rest on a.und_list like mode 2; a.pass_list is not written
-void launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a, uint64_t max_items, uint32_t max_len,
-                       int mode = 0);
+// wgs_per_cu: the grid is capped at 256 * wgs_per_cu persistent workgroups of 30 KiB of LDS each (1..5; five fill a CU's
+// LDS, fewer leave room for other streams' kernels beside them).  listed: max_items counts the entries of the work list
+// itself (known on the host), not the pass's seed hits: a lane per entry
+constexpr uint32_t kMyersWgsPerCuMax = 5;
+// returns the grid it launched, in workgroups
+uint32_t launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a, uint64_t max_items, uint32_t max_len,
+                           int mode = 0, uint32_t wgs_per_cu = kMyersWgsPerCuMax, bool listed = false);
 // reference order for reads <= 253 bases: SW prefilter alone, two candidates per 16-lane group
 // diag = false: without the lower bounds on the seed diagonal (every candidate that is not hopeless is swept)
 // top = true: the sweep on the top half of the read rows (k_sw_pairs<R/2, false, TOP>): refutes or passes what those rows
