@@ -238,3 +238,230 @@ def planted_db(rng, background, plants):
         for tax, gi in owners:
             entries.append((tax, gi, rnd_seq(rng, rng.randrange(60, 200)) + seg + rnd_seq(rng, rng.randrange(60, 200))))
     return entries
+
+
+# ---- the index geometry ladder (test_index_geometry_cpu.py, test_index_geometry.py) ----------------------------------
+# One rung = one database whose text (the concatenation of its sequences plus '$') has exactly n symbols, with its own
+# sampling intervals.  The kinds and sizes sit where the device index and the GPU builder branch on n, on the row of
+# the sentinel, on the suffix sampling interval or on the composition of the text.
+
+RANDOM_N = (1, 2, 3, 17, 18, 19, 25, 127, 128, 129, 255, 256, 257, 4095, 4096, 4097, 8191, 8192, 8193, 32767, 32768, 32769,
+            65535, 65536, 65537, 131071, 131072, 131073, 524159, 524160, 524161)
+# (n = 1, the text "$" of one empty sequence, leads the tiny rungs: 2 and 3 hold one and two bases; 17, 18, 19 end one
+# short of, at, and one past the first text that holds a default seed of 18 symbols; 25 holds one probe of 24)
+SENTINEL_N = 4096
+SENTINEL_TARGETS = ("res0", "res1", "res63", "res64", "res127", "first_block", "last_block")
+SENTINEL_TRIES = 4096
+SAMPLING_N = (4097, 257)
+REPEAT_KINDS = ("A", "AC", "tandem97")
+
+
+def sampling_intervals(n):
+    return [(k, s) for s in (1, 2, 3, 7, 31, 32, n - 1, n, n + 1, 1 << 20) for k in (1, 64, n + 5)]
+
+
+def _fast_seq(rng, n, alpha=b"ACGT"):
+    return bytes(rng.choices(alpha, k=n)) if n else b""
+
+
+def _cut_into_bins(rng, body, n_cuts=4):
+    """body in a handful of sequences of uneven length with one empty sequence among them; TaxIDs ascend with the order
+    (so the order of the entries is the order of the text), two of them twice"""
+    L = len(body)
+    cuts = sorted(rng.randrange(0, L + 1) for _ in range(n_cuts if L else 0))
+    edges = [0] + cuts + [L]
+    seqs = [body[a:b] for a, b in zip(edges, edges[1:])]
+    seqs.insert(min(2, len(seqs)), b"")
+    taxa = (2, 2, 5, 9, 9, 4000000000, 4000000001)
+    return [(taxa[i], 100 + 7 * i, s) for i, s in enumerate(seqs)]
+
+
+def geometry_db(kind, n, rng):
+    """entries (tax_id, gi, sequence), already in the order of the text, whose sequences hold n - 1 symbols in all"""
+    L = n - 1
+    if kind == "random":
+        entries = _cut_into_bins(rng, _fast_seq(rng, L))
+    elif kind == "sentinel":  # random text with a few N runs of 1..30 symbols
+        body = bytearray(_fast_seq(rng, L))
+        for _ in range(rng.randrange(3, 7)):
+            k = rng.randrange(1, 31)
+            at = rng.randrange(0, L - k)
+            body[at:at + k] = b"N" * k
+        entries = _cut_into_bins(rng, bytes(body))
+    elif kind == "A":
+        entries = _cut_into_bins(rng, b"A" * L)
+    elif kind == "AC":
+        entries = _cut_into_bins(rng, (b"AC" * (L // 2 + 1))[:L])
+    elif kind == "tandem97":
+        unit = _fast_seq(rng, 97)
+        entries = _cut_into_bins(rng, (unit * (L // 97 + 1))[:L])
+    elif kind == "nrun":  # one run of 5000 N in random text
+        body = bytearray(_fast_seq(rng, L))
+        at = rng.randrange(100, L - 5100)
+        body[at:at + 5000] = b"N" * 5000
+        entries = _cut_into_bins(rng, bytes(body))
+    elif kind == "ACG":
+        entries = _cut_into_bins(rng, _fast_seq(rng, L, b"ACG"))
+    elif kind == "CGT":
+        entries = _cut_into_bins(rng, _fast_seq(rng, L, b"CGT"))
+    elif kind == "tinybins":  # 6000 sequences of 0..39 symbols over 2000 taxa
+        lens = [rng.randrange(0, 40) for _ in range(6000)]
+        while sum(lens) != L:
+            i = rng.randrange(6000)
+            d = 1 if sum(lens) < L else -1
+            if 0 <= lens[i] + d < 40:
+                lens[i] += d
+        taxa = sorted(rng.randrange(1, 2001) for _ in range(6000))
+        entries = [(taxa[i], 10 + i, _fast_seq(rng, k)) for i, k in enumerate(lens)]
+    else:
+        raise ValueError(kind)
+    assert sum(len(e[2]) for e in entries) + 1 == n, (kind, n)
+    return entries
+
+
+def geometry_text(entries):
+    return b"".join(e[2] for e in entries)
+
+
+_sentinel_seeds = None
+
+
+def sentinel_seeds():
+    """{target: (seed, row)} of the sentinel-row rungs: the first seeds whose database puts the row of the whole text (the
+    row whose BWT symbol is '$') at each residue modulo 128, and into the first and the last rank block.  The row comes
+    from the oracle: lo of backward_search(text[:40]) when that interval has one row.  Residue 0 is where the derived
+    rank of N changes its meaning (the sentinel lies "before the block" from the next block on), and a block shows its
+    rank of N only where one of its rows holds an N in the BWT: that rung also wants the suffix behind one of its N runs
+    in the sentinel row's block, which a probe with one N in front of that suffix then finds."""
+    global _sentinel_seeds
+    if _sentinel_seeds is None:
+        import re
+        from oracle import oracle as O
+        n = SENTINEL_N
+        found = {}
+        for seed in range(SENTINEL_TRIES):
+            if len(found) == len(SENTINEL_TARGETS):
+                break
+            entries = geometry_db("sentinel", n, random.Random(0x5E17 * 4096 + seed))
+            text = geometry_text(entries)
+            ix = O.Index.build(entries, 64, 32)
+            ok, lo, hi = ix.backward_search(text[:40])
+            if not ok or hi - lo != 1:
+                continue
+            hit = ["res%d" % (lo % 128)]
+            if lo < 128:
+                hit.append("first_block")
+            if lo >= ((n - 1) >> 7) << 7:
+                hit.append("last_block")
+            if lo % 128 == 0:
+                behind = [ix.backward_search(text[m.end():m.end() + 40]) for m in re.finditer(rb"N+", text)]
+                if not any(ok2 and h2 - l2 == 1 and lo <= l2 < lo + 128 for ok2, l2, h2 in behind):
+                    hit.remove("res0")
+            for t in hit:
+                if t in SENTINEL_TARGETS:
+                    found.setdefault(t, (seed, lo))
+        assert len(found) == len(SENTINEL_TARGETS), sorted(set(SENTINEL_TARGETS) - set(found))
+        _sentinel_seeds = found
+    return _sentinel_seeds
+
+
+class Rung:
+    def __init__(self, name, kind, n, occ_k=64, sa_s=32, target=None):
+        self.name, self.kind, self.n, self.occ_k, self.sa_s, self.target = name, kind, n, occ_k, sa_s, target
+
+    def __repr__(self):
+        return self.name
+
+    def entries(self):
+        if self.kind == "sentinel":
+            seed = 0x5E17 * 4096 + sentinel_seeds()[self.target][0]
+        else:
+            seed = int.from_bytes(hashlib.sha256(("%s/%d" % (self.kind, self.n)).encode()).digest()[:6], "big")
+        return geometry_db(self.kind, self.n, random.Random(seed))
+
+    def sentinel_row(self):
+        return sentinel_seeds()[self.target][1]
+
+
+def _rungs():
+    out = [Rung("random-%d" % n, "random", n) for n in RANDOM_N]
+    out += [Rung("sentinel-%s" % t, "sentinel", SENTINEL_N, target=t) for t in SENTINEL_TARGETS]
+    out += [Rung("A-65536", "A", 65536), Rung("AC-65536", "AC", 65536), Rung("tandem97-20000", "tandem97", 20000),
+            Rung("A-3000", "A", 3000), Rung("AC-3000", "AC", 3000), Rung("tandem97-3000", "tandem97", 3000),
+            Rung("A-129", "A", 129, occ_k=3, sa_s=5),
+            Rung("nrun-20000", "nrun", 20000), Rung("ACG-65536", "ACG", 65536), Rung("CGT-32768", "CGT", 32768),
+            Rung("ACG-4096", "ACG", 4096, occ_k=128, sa_s=7),
+            Rung("tinybins-117001", "tinybins", 117001)]
+    for n in SAMPLING_N:
+        out += [Rung("sampling-%d-k%d-s%d" % (n, k, s), "random", n, occ_k=k, sa_s=s) for k, s in sampling_intervals(n)]
+    return out
+
+
+RUNGS = _rungs()
+RUNG_BY_NAME = {r.name: r for r in RUNGS}
+assert len(RUNG_BY_NAME) == len(RUNGS)
+
+
+def kmer_width_for(n):
+    """the k-mer table width the upload picks for a text of n symbols (dev_index.hip), where HBM is no limit"""
+    k = 1
+    while k < 16 and 4 ** (k + 1) <= 2 * n:
+        k += 1
+    return 17 if k == 16 and n >= 1 << 31 else k
+
+
+def position_probes(text, exhaustive_up_to=131073, width=24):
+    """[(text position, read)]: every substring of `width` symbols of the text (of the whole text, where it is shorter),
+    alternately as it stands and reverse-complemented; on texts of more than exhaustive_up_to symbols every 5th position
+    and the first and last 300"""
+    L = len(text)
+    w = min(width, L)
+    if w == 0:
+        return []
+    last = L - w
+    if L + 1 <= exhaustive_up_to:
+        pos = range(0, last + 1)
+    else:
+        pos = sorted(set(range(0, last + 1, 5)) | set(range(0, 300)) | set(range(last - 299, last + 1)))
+    return [(i, text[i:i + w] if k % 2 == 0 else revcomp(text[i:i + w])) for k, i in enumerate(pos)]
+
+
+def n_edge_probes(rng, text):
+    """reads of 30..60 symbols across both edges of every N run of the text, placed so that their first seed of 18
+    symbols holds 1..18 N, on both strands"""
+    L = len(text)
+    runs, i = [], 0
+    while i < L:
+        if text[i] == 78:
+            j = i
+            while j < L and text[j] == 78:
+                j += 1
+            runs.append((i, j))
+            i = j
+        else:
+            i += 1
+    reads = []
+    for a, b in runs:
+        for k in range(1, 19):
+            for start in (a - (18 - k), b - k):
+                start = max(0, min(start, L - 30))
+                r = text[start:start + rng.randrange(30, 61)]
+                reads.append(r if len(reads) % 2 == 0 else revcomp(r))
+    return reads
+
+
+def geometry_reads(rng, entries, n=300):
+    """n ordinary reads of 40..150 symbols: ladder_reads where a sequence is long enough for it, else damaged pieces of
+    the text (which then span the junctions of its short sequences)"""
+    import math
+    texts = [e[2] for e in entries]
+    if any(len(t) >= 190 for t in texts):
+        return ladder_reads(rng, texts, 150, n=n)
+    text = b"".join(texts)
+    reads = []
+    for _ in range(n):
+        Lr = rng.randrange(40, min(150, len(text)) + 1)
+        st = rng.randrange(0, len(text) - Lr + 1)
+        r = mutate(rng, text[st:st + Lr], rng.randrange(0, math.ceil(Lr * 0.13) + 3))
+        reads.append(r if rng.random() < 0.5 else revcomp(r))
+    return reads
