@@ -298,6 +298,35 @@ int mtsv_batch_set_match_flags(mtsv_batch *b, int mode);
  * least one) and is malloc'd (mtsv_free); *n_matched is the number of set bits, counted on the device.  No run since the
  * flags were switched on: *n_reads is 0.  MTSV_E_ARG when the mode is MTSV_MATCH_OFF. */
 int mtsv_batch_match_flags(mtsv_batch *b, uint64_t **words, uint64_t *n_reads, uint64_t *n_matched);
+
+/* ---- chaining workspaces: the unmatched (matched) reads of one run as the input of another, on the device ----------
+ * Read depletion followed by binning -- a filter index (a host genome), then the database -- goes through a file in the
+ * reference's workflow: mtsv-partition writes the unmatched reads (src/bin/mtsv-partition.rs:56-93), a second
+ * mtsv-binner run parses them again.  Here both indexes are resident on one device, a workspace each, and
+ * mtsv_batch_take_reads hands the reads over in HBM (k_compact.hip): dst's resident batch becomes the reads of src's
+ * last run whose match flag is clear (MTSV_KEEP_UNMATCHED) or set (MTSV_KEEP_MATCHED), in order, as if they had been
+ * given to mtsv_batch_upload -- no base crosses PCIe again, no flag goes to the host; the host reads 24 bytes of counts
+ * and four bytes per survivor (their offsets).  dst also receives a READ MAP, survivor -> read number in src's run, and
+ * mtsv_batch_run on dst writes the mapped number into the `read` field of every hit, so the hits are numbered like
+ * the caller's batch and stay ordered by it.  dst's own match flags and taxa report stay per resident read
+ * (mtsv_batch_read_map translates).  A workspace filled this way can be a source in turn, and the maps compose: the
+ * reads no chunk of a filter matches are a chain of MTSV_KEEP_UNMATCHED steps, each on fewer reads.
+ * src: match flags on, in either mode, and a completed run whose reads are still in HBM -- mtsv_batch_upload +
+ * mtsv_batch_run, or a host batch of mtsv_batch_run_host* that fitted one input segment (3 GiB of bases; a larger one
+ * took turns through two segments and has lost its first reads: MTSV_E_ARG).  Also MTSV_E_ARG: flags off, no such run,
+ * dst == src, workspaces of different devices, a bad `keep`, more survivors (or bases) than dst was created for -- dst
+ * is then as it was.  Synchronous.  device_ms (may be NULL): device time of the kernels.  mtsv_batch_upload and
+ * mtsv_batch_run_host* on dst drop the map.  (Both indexes share the device's HBM: mtsv_index_to_device of the second
+ * may settle for a narrower k-mer table, or fail for want of memory.) */
+#define MTSV_KEEP_UNMATCHED 0
+#define MTSV_KEEP_MATCHED 1
+int mtsv_batch_take_reads(mtsv_batch *dst, mtsv_batch *src, int keep, uint64_t *n_kept, uint64_t *bases_kept,
+                          float *device_ms);
+/* (*map)[j] = the caller's number of resident read j (the identity after mtsv_batch_upload); malloc'd, mtsv_free */
+int mtsv_batch_read_map(mtsv_batch *b, uint64_t **map, uint64_t *n_reads);
+/* For tests, like mtsv_pack_bases: the resident batch as the kernels see it -- byte codes 0..4 (src/binner.rs:88-100)
+ * and *n_reads + 1 offsets from 0; both malloc'd, mtsv_free.  MTSV_E_ARG when the workspace's last input was a host batch. */
+int mtsv_batch_download_reads(mtsv_batch *b, uint8_t **codes, uint64_t **read_off, uint64_t *n_reads);
 int mtsv_batch_download(mtsv_batch *b, mtsv_hit **hits, uint64_t *n_hits);
 void mtsv_batch_free(mtsv_batch *b);
 

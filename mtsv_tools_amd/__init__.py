@@ -8,6 +8,8 @@ when the library or a device is missing.
 """
 from ._lib import (  # noqa: F401
     HIT_DTYPE,
+    KEEP_MATCHED,
+    KEEP_UNMATCHED,
     MATCH_OFF,
     MATCH_ONLY,
     MATCH_WITH_HITS,

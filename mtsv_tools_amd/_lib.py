@@ -20,6 +20,7 @@ class MtsvError(RuntimeError):
 
 E_ARG, E_IO, E_FORMAT, E_DEVICE, E_LIMIT, E_NOMEM = -1, -2, -3, -4, -5, -6
 MATCH_OFF, MATCH_WITH_HITS, MATCH_ONLY = 0, 1, 2  # MTSV_MATCH_*
+KEEP_UNMATCHED, KEEP_MATCHED = 0, 1  # MTSV_KEEP_*
 
 
 class Params(C.Structure):  # mtsv_params
@@ -76,6 +77,7 @@ EXPORTS = [
     "mtsv_batch_create_lanes", "mtsv_batch_reserve_host", "mtsv_pack_bases", "mtsv_host_pack_threads",
     "mtsv_batch_set_taxa_report", "mtsv_batch_taxa_report", "mtsv_merge_taxa_reports", "mtsv_format_taxa_report",
     "mtsv_batch_set_match_flags", "mtsv_batch_match_flags",
+    "mtsv_batch_take_reads", "mtsv_batch_read_map", "mtsv_batch_download_reads",
 ]
 
 _lib = None
@@ -142,6 +144,9 @@ def lib():
         L.mtsv_format_taxa_report.argtypes = [vp, u64, u64, C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_batch_set_match_flags.argtypes = [vp, i32]
         L.mtsv_batch_match_flags.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+        L.mtsv_batch_take_reads.argtypes = [vp, vp, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_batch_read_map.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_batch_download_reads.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -405,6 +410,35 @@ class Batch:
         if bits[n.value:].any():
             raise MtsvError(E_DEVICE, "match flags set beyond the run's reads")
         return bits[:n.value], m.value
+
+    def take_reads(self, src, keep=KEEP_UNMATCHED):
+        """mtsv_batch_take_reads: this workspace's resident batch := the reads of src's last run whose match flag is clear
+        (KEEP_MATCHED: set), handed over on the device; returns (n_kept, bases_kept, device ms of the kernels)"""
+        n, nb, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_batch_take_reads(self.h, src.h, int(keep), C.byref(n), C.byref(nb), C.byref(ms)))
+        return n.value, nb.value, ms.value
+
+    def read_map(self):
+        """the caller's read number of every resident read (uint64 array; the identity after upload)"""
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(lib().mtsv_batch_read_map(self.h, C.byref(out), C.byref(n)))
+        try:
+            return np.frombuffer((C.c_ubyte * (max(n.value, 1) * 8)).from_address(out.value), dtype="<u8")[:n.value].copy()
+        finally:
+            lib().mtsv_free(out)
+
+    def download_reads(self):
+        """(codes uint8 0..4, read_off uint64 with n + 1 entries): the resident batch as the kernels see it (tests)"""
+        codes, off, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(lib().mtsv_batch_download_reads(self.h, C.byref(codes), C.byref(off), C.byref(n)))
+        try:
+            o = np.frombuffer((C.c_ubyte * ((n.value + 1) * 8)).from_address(off.value), dtype="<u8").copy()
+            nb = int(o[-1])
+            c = np.frombuffer((C.c_ubyte * max(nb, 1)).from_address(codes.value), dtype=np.uint8)[:nb].copy()
+        finally:
+            lib().mtsv_free(codes)
+            lib().mtsv_free(off)
+        return c, o
 
     def close(self):
         if self.h is not None and _lib is not None:

@@ -188,6 +188,10 @@ Batch::~Batch() {
     (void)hipFree(match.d_words);
     for (auto& e : match_ev)
         if (e) (void)hipEventDestroy(e);
+    (void)hipFree(d_read_map);
+    (void)hipFree(d_compact);
+    for (auto& e : compact_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h_hits_stage) pinned_hits_release(h_hits_stage);
     if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
     if (copy_stream) {
@@ -283,6 +287,9 @@ void Batch::upload(const uint8_t* bases, const uint64_t* read_off, uint64_t n) {
     n_hits_total = 0;
     total_hits = 0;
     segments.clear();
+    last_run = kRunNone;  // (the flags of the run before are not this batch's)
+    resident = true;
+    codes_resident = mapped = false;
 }
 
 // counters in d_counters: [0] scan total (u64), [1] wl_count (u32), [2] lf_steps, [3] n_cand,
@@ -332,6 +339,7 @@ void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
     total_hits = 0;
     lanes_used = 1;
     staged_valid = false;
+    last_run = kRunNone;  // until this one completes
     run_t0 = now_s();
     {
         std::lock_guard<std::mutex> lk(verify_turn.mu);
@@ -501,8 +509,115 @@ void Batch::match_flags(std::vector<uint64_t>& words, uint64_t* n_reads_out, uin
 
 void Batch::run(const mtsv_params& p) {
     begin_run(p);
-    run_range(p, d_bases, d_codes, d_read_off, h_read_off.data(), n_reads, max_len, 0);
+    // (a batch take_reads left is codes already: fast_code would turn every one of them into N)
+    run_range(p, codes_resident ? nullptr : d_bases, d_codes, d_read_off, h_read_off.data(), n_reads, max_len, 0);
     end_run();
+    last_run = kRunResident;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Chaining: the unmatched (matched) reads of src's last run become this workspace's resident batch.  The bases go from
+// HBM to HBM, the flags are read where k_match wrote them; the host sees the 24-byte result block (the capacity check
+// needs the counts before anything is written) and the survivors' offsets, which run_range cuts its chunks by.
+// ---------------------------------------------------------------------------------------------
+void Batch::take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_kept, float* device_ms) {
+    if (parent || src.parent) throw std::runtime_error("internal: take_reads on a lane");
+    if (&src == this) throw std::runtime_error("arg: take_reads from a workspace into itself");
+    if (keep != MTSV_KEEP_UNMATCHED && keep != MTSV_KEEP_MATCHED) throw std::runtime_error("arg: bad keep (MTSV_KEEP_UNMATCHED or MTSV_KEEP_MATCHED)");
+    if (src.di->device != di->device) throw std::runtime_error("arg: take_reads between workspaces of different devices");
+    if (src.match.mode == MTSV_MATCH_OFF) throw std::runtime_error("arg: the match flags of the source workspace are not switched on (mtsv_batch_set_match_flags)");
+    if (src.last_run == kRunHostSegments)
+        throw std::runtime_error("arg: the source's host batch took turns through the input segments: its first reads are no longer in HBM");
+    if (src.last_run == kRunNone) throw std::runtime_error("arg: the source workspace has no completed run whose reads are still in HBM");
+    // (flags switched on after the last run: they describe no run yet)
+    if (src.match.n_reads != src.n_reads) throw std::runtime_error("arg: the source workspace has no completed run since its match flags were switched on");
+    const bool trace = getenv("MTSV_TRACE") != nullptr;
+    const uint64_t n = src.n_reads;
+    const bool host_batch = src.last_run == kRunHostOneSegment;
+    const uint8_t* s_codes = host_batch ? src.arena[0].d_bases : src.d_codes;
+    const uint32_t* s_off = host_batch ? src.arena[0].d_off : src.d_read_off;
+    const uint32_t* s_map = src.mapped ? src.d_read_map : nullptr;
+    HIP_CHECK(hipSetDevice(di->device));
+    const uint64_t tiles = compact_tiles(n);
+    if (!d_compact || compact_cap < tiles) {
+        (void)hipFree(d_compact);
+        d_compact = nullptr;
+        compact_cap = 0;
+        uint64_t b = 0;
+        dev_alloc(&d_compact, 3 + 2 * (tiles + tiles / 16), &b);
+        compact_cap = tiles + tiles / 16;
+    }
+    if (!d_read_map) {
+        uint64_t b = 0;
+        dev_alloc(&d_read_map, max_reads, &b);
+    }
+    if (!compact_ev[0])
+        for (auto& e : compact_ev) HIP_CHECK(hipEventCreate(&e));
+    uint64_t* result = d_compact;
+    uint64_t *tile_cnt = d_compact + 3, *tile_bases = d_compact + 3 + compact_cap;
+    HIP_CHECK(hipMemsetAsync(result, 0, 3 * sizeof(uint64_t), stream));
+    HIP_CHECK(hipEventRecord(compact_ev[0], stream));
+    launch_compact_scan(stream, (uint32_t)n, src.match.d_words, s_off, keep, tile_cnt, tile_bases, result);
+    HIP_CHECK(hipEventRecord(compact_ev[1], stream));
+    uint64_t h_result[3] = {0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(h_result, result, sizeof h_result, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    const uint64_t m = h_result[0], nb = h_result[1];
+    if (m > max_reads || nb > max_bases)
+        throw std::runtime_error("arg: " + std::to_string(m) + " reads of " + std::to_string(nb) + " bases survive, the destination workspace was created for " +
+                                 std::to_string(max_reads) + " reads of " + std::to_string(max_bases) + " bases");
+    // from here on the destination's resident batch is being replaced
+    resident = false;
+    last_run = kRunNone;
+    HIP_CHECK(hipEventRecord(compact_ev[2], stream));
+    launch_compact_copy(stream, (uint32_t)n, src.match.d_words, s_off, s_codes, keep, s_map, tile_cnt, tile_bases, result, d_codes, d_read_off, d_read_map);
+    HIP_CHECK(hipEventRecord(compact_ev[3], stream));
+    h_read_off.resize(m + 1);
+    HIP_CHECK(hipMemcpyAsync(h_read_off.data(), d_read_off, (m + 1) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipGetLastError());
+    if (h_read_off[0] != 0 || h_read_off[m] != nb) throw std::runtime_error("internal: offsets of the compacted batch do not close on its bases");
+    float ms_scan = 0, ms_copy = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms_scan, compact_ev[0], compact_ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms_copy, compact_ev[2], compact_ev[3]));
+    n_reads = m;
+    max_len = (uint32_t)h_result[2];
+    n_hits_total = 0;
+    total_hits = 0;
+    segments.clear();
+    resident = codes_resident = mapped = true;
+    *n_kept = m;
+    *bases_kept = nb;
+    if (device_ms) *device_ms = ms_scan + ms_copy;
+    if (trace)
+        fprintf(stderr, "[compact] %llu of %llu reads kept (%s), %llu bases; scan %.3f ms, copy %.3f ms; %llu bytes to the host, 0 to the device\n",
+                (unsigned long long)m, (unsigned long long)n, keep == MTSV_KEEP_MATCHED ? "matched" : "unmatched", (unsigned long long)nb, ms_scan, ms_copy,
+                (unsigned long long)(sizeof h_result + (m + 1) * 4));
+}
+
+void Batch::read_map(std::vector<uint64_t>& map) {
+    map.resize(n_reads);
+    if (!mapped) {
+        for (uint64_t i = 0; i < n_reads; i++) map[i] = i;
+        return;
+    }
+    std::vector<uint32_t> m32(n_reads);
+    HIP_CHECK(hipSetDevice(di->device));
+    if (n_reads) HIP_CHECK(hipMemcpyAsync(m32.data(), d_read_map, n_reads * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (uint64_t i = 0; i < n_reads; i++) map[i] = m32[i];
+}
+
+void Batch::download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& read_off) {
+    if (!resident) throw std::runtime_error("arg: the workspace holds no resident batch (mtsv_batch_upload, mtsv_batch_take_reads)");
+    HIP_CHECK(hipSetDevice(di->device));
+    const uint64_t nb = h_read_off[n_reads];
+    // (an uploaded batch is normalised into d_codes as run() would do it)
+    if (!codes_resident && nb) launch_normalise(stream, d_bases, d_codes, 0, nb);
+    codes.resize(nb);
+    if (nb) HIP_CHECK(hipMemcpyAsync(codes.data(), d_codes, nb, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    read_off.assign(h_read_off.begin(), h_read_off.begin() + n_reads + 1);
 }
 
 // A resident range of reads, split over the lanes; the hits stay in the lanes, `segments` records them in
@@ -973,6 +1088,8 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
             hits_cap = ncap;
         }
         if (!only_flags) launch_gather(stream, nstr, read_base + r0, d_strand_off, d_strand_nout, d_out_off, d_out, d_hits, n_hits_total);
+        // (a compacted batch: the hits carry the caller's read numbers; the report and the flags below are per resident read)
+        if (!only_flags && root->mapped) launch_remap_reads(stream, d_hits + n_hits_total, total_out, root->d_read_map);
         HIP_CHECK(hipEventRecord(ev[7], stream));
         // the pass is committed from here on (a pass that is run again has not come this far): its reads join the taxa report
         TaxaReport& rep = (parent ? parent : this)->report;
@@ -1277,6 +1394,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
 
     n_reads = n;
     max_len = 0;
+    resident = codes_resident = mapped = false;  // (what upload() or take_reads() left is not this batch)
     if (trace) fprintf(stderr, "[run_host] entered; begin_run at %.2f ms\n", (now_s() - t_entry) * 1e3);
     begin_run(p, read_base);
     staged_hits = 0;
@@ -1590,6 +1708,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
     end_run();
     HIP_CHECK(hipStreamSynchronize(copy_stream2));
     staged_valid = !keep_on_device && staged_hits == total_hits;
+    last_run = seg_begin.size() == 1 ? kRunHostOneSegment : kRunHostSegments;
     if (trace) fprintf(stderr, "[run_host] hits on the host at %.1f ms (%llu ranges, %llu chunks); %.1f ms since the call began\n", (now_s() - run_t0) * 1e3, (unsigned long long)ranges.size(), (unsigned long long)chunks.size(), (now_s() - t_entry) * 1e3);
     if (!staged_valid && !keep_on_device) throw std::runtime_error("internal: run_host staged " + std::to_string(staged_hits) + " of " + std::to_string(total_hits) + " hits");
 }

@@ -201,6 +201,21 @@ struct Batch {
     void set_match_flags(int mode);
     // the flags of the last run as ceil(n_reads / 64) words (at least one), bits at and above n_reads zero
     void match_flags(std::vector<uint64_t>& words, uint64_t* n_reads, uint64_t* n_matched);
+    // Chaining (k_compact.hip): the reads of src's last run whose match flag is clear (keep = MTSV_KEEP_UNMATCHED) or set become
+    // this workspace's resident batch, as codes, with a map to the caller's read numbers.  All of it belongs to the owner
+    // and is created by the first take_reads.
+    enum LastRun { kRunNone = 0, kRunResident, kRunHostOneSegment, kRunHostSegments };
+    int last_run = kRunNone;       // what the last completed run left in HBM (a source of take_reads needs its reads)
+    bool resident = false;         // upload() or take_reads() filled the resident batch, no host batch has run since
+    bool codes_resident = false;   // ... take_reads did: d_codes holds it (d_bases does not), run() must not normalise
+    bool mapped = false;           // ... and d_read_map translates its read numbers in every gathered hit
+    uint32_t* d_read_map = nullptr;   // max_reads entries
+    uint64_t* d_compact = nullptr;    // the result block (3 words), then two arrays of tile sums
+    uint64_t compact_cap = 0;         // ... entries each
+    hipEvent_t compact_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the scan and around the copy
+    void take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_kept, float* device_ms);
+    void read_map(std::vector<uint64_t>& map);
+    void download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& read_off);
     // rows: every TaxID with a non-zero counter, ascending
     void taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_reads, float* device_ms, bool reset);
 

@@ -8,6 +8,9 @@
 // (src/bin/mtsv-partition.rs) makes of the results file and a second pass over the reads -- here from one flag bit per
 // read that the device sets (k_match.hip), with no results file at all when --results is left out (read depletion).
 // A read counts by itself there: mtsv-partition keys reads by their ID text, so two records with one ID share a fate.
+// --filter-index F1[,F2,..]: reads that get a hit in any of these indexes are dropped on the device and the rest are binned
+// against --index, in one process: the filters' workspaces run flags-only, and the unmatched reads of each stage are handed
+// to the next workspace in HBM (mtsv_batch_take_reads) -- what `--unmatched tmp.fq` and a second run do through a file.
 // The reads of a batch are processed on the GPU; result lines are written in input order (the
 // reference's order is unspecified: vendor/cue/src/lib.rs:67-74).
 //
@@ -113,7 +116,7 @@ int resume_offset(const std::string& results, const std::string& input, bool fas
 }
 
 struct Args {
-    std::string fasta, fastq, index, results, report, matched, unmatched, output_format = "default";
+    std::string fasta, fastq, index, results, report, matched, unmatched, filter_index, output_format = "default";
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
     bool verbose = false, force = false, parse_only = false;
@@ -218,6 +221,7 @@ int main(int argc, char** argv) {
         else if (key == "--report") a.report = val();
         else if (key == "--matched") a.matched = val();
         else if (key == "--unmatched") a.unmatched = val();
+        else if (key == "--filter-index") a.filter_index = val();
         else if (key == "--parse-only") a.parse_only = true;
         else if (key == "-h" || key == "--help") {
             printf("mtsv-binner (MI355X) -- flags as the reference: --fasta|--fastq, -i/--index, -m/--results, -t/--threads,\n"
@@ -232,7 +236,12 @@ int main(int argc, char** argv) {
                    "decision is one bit per read set on the GPU.  Without -m/--results no results file is written and the hits are not\n"
                    "even gathered: read depletion.  Reads skipped by --read-offset go to neither file; a run that would resume an\n"
                    "existing results file is refused; not with a list of index chunks.  Every read counts by itself: mtsv-partition\n"
-                   "keys reads by their ID, so there records that share an ID share a fate)\n");
+                   "keys reads by their ID, so there records that share an ID share a fate),\n"
+                   "--filter-index F1[,F2,..] (reads that get a hit in any of these indexes, under the run's own parameters, are dropped\n"
+                   "and the rest are binned against --index: every filter index is made resident on each device beside the database --\n"
+                   "they share its HBM, and the k-mer table of an index may come out narrower for it -- and the surviving reads go from\n"
+                   "stage to stage on the GPU, with no intermediate file.  Not with --matched / --unmatched, --parse-only or a list of\n"
+                   "index chunks)\n");
             return 0;
         } else if (key == "-V" || key == "--version") {
             printf("mtsv 2.1.0 (%s)\n", mtsv_version());
@@ -254,6 +263,14 @@ int main(int argc, char** argv) {
     if (partition && a.index.find(',') != std::string::npos) {
         // (the flags of the chunks would have to be OR-ed per read)
         fprintf(stderr, "error: '--matched <PATH>' / '--unmatched <PATH>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-partition on the results file instead\n");
+        return 1;
+    }
+    const bool filtered = !a.filter_index.empty();
+    if (filtered && partition) usage_error("The argument '--filter-index <INDEX>' cannot be used with '--matched <PATH>' / '--unmatched <PATH>'");
+    if (filtered && a.parse_only) usage_error("The argument '--parse-only' cannot be used with '--filter-index <INDEX>'");
+    if (filtered && a.index.find(',') != std::string::npos) {
+        // (every chunk would need the survivors, and its hits merged per read)
+        fprintf(stderr, "error: '--filter-index <INDEX>' cannot be used with a list of index chunks ('--index a,b,..'): filter first with '--unmatched <PATH>', then bin the chunks\n");
         return 1;
     }
     if (partition && !a.report.empty() && a.results.empty())
@@ -545,6 +562,15 @@ int main(int argc, char** argv) {
     }
     if (index_paths.empty()) usage_error("The following required arguments were not provided: --index <INDEX>");
     const bool chunked = index_paths.size() > 1;  // Mode B
+    std::vector<std::string> filter_paths;
+    for (size_t at = 0; filtered && at <= a.filter_index.size();) {
+        size_t c = a.filter_index.find(',', at);
+        if (c == std::string::npos) c = a.filter_index.size();
+        if (c > at) filter_paths.push_back(a.filter_index.substr(at, c - at));
+        at = c + 1;
+    }
+    if (filtered && filter_paths.empty()) usage_error("The argument '--filter-index <INDEX>' requires a value but none was supplied");
+    const size_t n_filters = filter_paths.size();
     // One library call takes every batch that is waiting, up to kGroupReads reads (mtsv_batch_run_host_parts): the device
     // is several times faster on passes of a million reads than on a quarter of that (a pass costs ~2.5 ms before it does
     // any work), while the parser is fastest on blocks of ~80 MB.
@@ -625,20 +651,54 @@ int main(int argc, char** argv) {
                 return 2;
             }
     }
+    // the filter indexes: every one resident on every listed device, beside the database
+    std::vector<mtsv_index*> fidx(n_filters, nullptr);
+    for (size_t c = 0; c < n_filters; c++) {
+        if (mtsv_index_load(filter_paths[c].c_str(), &fidx[c]) != MTSV_OK) {
+            logmsg("ERROR", std::string("Error running query: ") + mtsv_last_error());
+            return 2;
+        }
+        for (size_t d = 0; d < a.devices.size(); d++)
+            if (mtsv_index_to_device(fidx[c], a.devices[d], MTSV_DEV_DEFAULT) != MTSV_OK) {
+                logmsg("ERROR", std::string("Error running query: ") + mtsv_last_error());
+                return 2;
+            }
+    }
     setup_mark("index loaded and resident");
     // the workers' workspaces (one index): part of the device set-up, like making the index resident -- created, sized for
     // the calls to come and run once on reads sampled from the index (mtsv_batch_reserve_host)
     std::vector<mtsv_batch*> ws_ready(chunked ? 0 : n_workers, nullptr);
+    // --filter-index: a workspace per worker and filter stage.  The first takes the host batch; the later ones and the
+    // database's receive their reads in HBM (mtsv_batch_take_reads) and hold them as a resident batch, so they are created
+    // with room for the bases of a call: chain_bases (a call whose blocks hold more is cut into several).
+    std::vector<std::vector<mtsv_batch*>> fws(ws_ready.size(), std::vector<mtsv_batch*>(n_filters, nullptr));
+    const uint64_t chain_reads = kGroupReads + a.batch_reads + a.batch_reads / 2;
+    const uint64_t chain_bases = std::min<uint64_t>(3ull << 30, chain_reads * std::max<uint64_t>(512, 2 * (uint64_t)warm_len));
     {
         std::vector<int> ws_rc(ws_ready.size(), MTSV_OK);
         std::vector<std::string> ws_msg(ws_ready.size());
         auto make_ws = [&](size_t wk) {
             const uint64_t call_reads = kGroupReads + a.batch_reads + a.batch_reads / 2;
             const int dev = a.devices[wk % a.devices.size()];
-            int rc = workers_per_device > 1 ? mtsv_batch_create_lanes(idx[0], dev, call_reads, 1 << 22, 0, 1, &ws_ready[wk])
-                                            : mtsv_batch_create(idx[0], dev, mtsv_bin_batch_workspace_reads(call_reads), 1 << 22, 0, &ws_ready[wk]);
-            if (rc == MTSV_OK && !small_input && !getenv("MTSV_CLI_COLD"))
-                rc = mtsv_batch_reserve_host(ws_ready[wk], call_reads, call_reads * (uint64_t)(warm_len + warm_len / 8), warm_len);
+            // (a workspace that receives its reads from a filter stage runs them as one resident batch: room for all of them)
+            auto create = [&](mtsv_index* ix, bool resident, mtsv_batch** out) {
+                const uint64_t ws_bases = resident ? chain_bases : 1 << 22;
+                return workers_per_device > 1 ? mtsv_batch_create_lanes(ix, dev, call_reads, ws_bases, 0, 1, out)
+                                              : mtsv_batch_create(ix, dev, resident ? call_reads : mtsv_bin_batch_workspace_reads(call_reads), ws_bases, 0, out);
+            };
+            int rc = create(idx[0], filtered, &ws_ready[wk]);
+            const bool warm = !small_input && !getenv("MTSV_CLI_COLD");
+            // (only the workspace that takes the host batches needs their arenas; the others are warmed on a small batch)
+            if (rc == MTSV_OK && warm)
+                rc = filtered ? mtsv_batch_reserve_host(ws_ready[wk], 4096, 4096 * (uint64_t)(warm_len + warm_len / 8), warm_len)
+                              : mtsv_batch_reserve_host(ws_ready[wk], call_reads, call_reads * (uint64_t)(warm_len + warm_len / 8), warm_len);
+            for (size_t k = 0; k < n_filters && rc == MTSV_OK; k++) {
+                rc = create(fidx[k], k > 0, &fws[wk][k]);
+                if (rc == MTSV_OK && warm)
+                    rc = k ? mtsv_batch_reserve_host(fws[wk][k], 4096, 4096 * (uint64_t)(warm_len + warm_len / 8), warm_len)
+                           : mtsv_batch_reserve_host(fws[wk][k], call_reads, call_reads * (uint64_t)(warm_len + warm_len / 8), warm_len);
+                if (rc == MTSV_OK) rc = mtsv_batch_set_match_flags(fws[wk][k], MTSV_MATCH_ONLY);  // (after the warm-up reads)
+            }
             if (rc == MTSV_OK && !a.report.empty()) rc = mtsv_batch_set_taxa_report(ws_ready[wk], 1);  // (after the warm-up reads)
             if (rc == MTSV_OK && partition) rc = mtsv_batch_set_match_flags(ws_ready[wk], match_mode);
             ws_rc[wk] = rc;
@@ -707,7 +767,8 @@ int main(int argc, char** argv) {
         }
         // the next batches in order, up to max_reads reads / max_n batches: a full group, or -- when the input has ended or
         // `idle` says that the device has nothing else to do -- whatever is waiting
-        std::vector<std::unique_ptr<Work>> pop_group(uint64_t max_reads, size_t max_n, const std::function<bool()>& idle) {
+        // (max_bases: a group holds at most that many bases -- or one batch)
+        std::vector<std::unique_ptr<Work>> pop_group(uint64_t max_reads, size_t max_n, const std::function<bool()>& idle, uint64_t max_bases = ~0ull) {
             std::unique_lock<std::mutex> lk(mu);
             auto waiting = [&] {
                 uint64_t r = 0;
@@ -722,8 +783,10 @@ int main(int argc, char** argv) {
             // (the input has ended: what is left is shared out, so that the workers finish together)
             if (closed && n_takers > 1) max_n = std::min(max_n, (q.size() + n_takers - 1) / n_takers);
             std::vector<std::unique_ptr<Work>> g;
-            uint64_t r = 0;
+            uint64_t r = 0, nb = 0;
             while (!q.empty() && g.size() < max_n && r < max_reads) {
+                nb += q.front()->rb->bases.size();
+                if (!g.empty() && nb > max_bases) break;
                 r += q.front()->rb->n();
                 g.push_back(std::move(q.front()));
                 q.pop_front();
@@ -760,6 +823,8 @@ int main(int argc, char** argv) {
     done.cap = n_workers * group_max + 1;
     std::atomic<int> calls_in_flight{0};
     std::atomic<uint64_t> reads_matched{0}, reads_partitioned{0};
+    std::vector<std::atomic<uint64_t>> stage_in(n_filters), stage_removed(n_filters);  // --filter-index: reads into / dropped by each stage
+    for (size_t k = 0; k < n_filters; k++) stage_in[k] = 0, stage_removed[k] = 0;
     std::mutex err_mu;
     int exit_code = 0;
     auto set_code = [&](int c) {
@@ -1022,11 +1087,17 @@ int main(int argc, char** argv) {
                 if (!group[0]) break;
             } else {
                 // a full group, or what there is when no call is running on any device (the start of the input, a slow parser)
-                group = parsed.pop_group(kGroupReads, group_max, [&] { return calls_in_flight.load() == 0; });
+                // (--filter-index: a call's reads must fit the chain's workspaces as one resident batch)
+                group = parsed.pop_group(kGroupReads, group_max, [&] { return calls_in_flight.load() == 0; }, filtered ? chain_bases : ~0ull);
                 if (group.empty()) break;
             }
             acc(t_gpu_wait, now() - t_p);
             if (failed()) continue;  // drain
+            if (filtered && (group.size() == 1 && (group[0]->rb->bases.size() > chain_bases || group[0]->rb->n() > chain_reads))) {
+                logmsg("ERROR", "Error running query: a batch of reads holds more than " + std::to_string(chain_bases) + " bases, which the workspaces behind a filter index were sized for: give a smaller --batch-reads");
+                set_code(2);
+                continue;
+            }
             uint64_t group_reads = 0;
             for (auto& w : group) group_reads += w->rb->n();
             calls_in_flight++;
@@ -1051,7 +1122,23 @@ int main(int argc, char** argv) {
                     po.push_back(w->rb->off.data());
                     pn.push_back(w->rb->n());
                 }
-                rc = mtsv_batch_run_host_parts(ws, (int)group.size(), pb.data(), po.data(), pn.data(), &p);
+                rc = mtsv_batch_run_host_parts(filtered ? fws[wk][0] : ws, (int)group.size(), pb.data(), po.data(), pn.data(), &p);
+                // the chain: what no filter matched goes down the stages and into the database's workspace, in HBM
+                for (size_t k = 0; k < n_filters && rc == MTSV_OK; k++) {
+                    mtsv_batch* next = k + 1 < n_filters ? fws[wk][k + 1] : ws;
+                    uint64_t kept = 0, kept_bases = 0, n_in = k ? 0 : group_reads;
+                    if (k) {
+                        mtsv_batch_stats st;
+                        rc = mtsv_batch_stats_get(fws[wk][k], &st);
+                        n_in = st.n_reads;
+                    }
+                    if (rc == MTSV_OK) rc = mtsv_batch_take_reads(next, fws[wk][k], MTSV_KEEP_UNMATCHED, &kept, &kept_bases, nullptr);
+                    if (rc == MTSV_OK) {
+                        stage_in[k] += n_in;
+                        stage_removed[k] += n_in - kept;
+                        rc = mtsv_batch_run(next, &p);
+                    }
+                }
                 if (rc == MTSV_OK && match_mode != MTSV_MATCH_ONLY) rc = mtsv_batch_download(ws, &hits, &n_hits);  // (flags only: there are none)
             }
             std::shared_ptr<uint64_t> flags;
@@ -1129,6 +1216,9 @@ int main(int argc, char** argv) {
     if (partition)
         logmsg("INFO", "Partitioned " + std::to_string(reads_partitioned.load()) + " reads: " + std::to_string(reads_matched.load()) + " matched, " +
                            std::to_string(reads_partitioned.load() - reads_matched.load()) + " unmatched.");
+    for (size_t k = 0; k < n_filters; k++)
+        logmsg("INFO", "Filter stage " + std::to_string(k + 1) + " (" + filter_paths[k] + "): removed " + std::to_string(stage_removed[k].load()) + " of " +
+                           std::to_string(stage_in[k].load()) + " reads.");
     if (!a.report.empty()) {
         // the workers' counts add up: every read went through exactly one of their workspaces
         mtsv_taxon_stats* sum = nullptr;
@@ -1184,8 +1274,11 @@ int main(int argc, char** argv) {
         _exit(0);
     }
     for (auto* ws : ws_ready) mtsv_batch_free(ws);  // (30 ms per workspace: after the queries' clock, like the index)
+    for (auto& stage : fws)
+        for (auto* ws : stage) mtsv_batch_free(ws);
     setup_mark("workspaces freed");
     for (auto* ix : idx) mtsv_index_free(ix);
+    for (auto* ix : fidx) mtsv_index_free(ix);
     setup_mark("index freed");
     return 0;
 }

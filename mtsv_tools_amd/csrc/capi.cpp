@@ -354,6 +354,45 @@ int mtsv_batch_match_flags(mtsv_batch* b, uint64_t** words, uint64_t* n_reads, u
     })
 }
 
+int mtsv_batch_take_reads(mtsv_batch* dst, mtsv_batch* src, int keep, uint64_t* n_kept, uint64_t* bases_kept, float* device_ms) {
+    if (!dst || !src || !n_kept || !bases_kept) return fail_arg("null argument");
+    GUARD(dst->impl.take_reads(src->impl, keep, n_kept, bases_kept, device_ms))
+}
+
+int mtsv_batch_read_map(mtsv_batch* b, uint64_t** map, uint64_t* n_reads) {
+    if (!b || !map || !n_reads) return fail_arg("null argument");
+    GUARD({
+        std::vector<uint64_t> m;
+        b->impl.read_map(m);
+        auto* out = (uint64_t*)malloc(std::max<size_t>(m.size(), 1) * sizeof(uint64_t));
+        if (!out) throw std::bad_alloc();
+        if (!m.empty()) memcpy(out, m.data(), m.size() * sizeof(uint64_t));
+        *map = out;
+        *n_reads = m.size();
+    })
+}
+
+int mtsv_batch_download_reads(mtsv_batch* b, uint8_t** codes, uint64_t** read_off, uint64_t* n_reads) {
+    if (!b || !codes || !read_off || !n_reads) return fail_arg("null argument");
+    GUARD({
+        std::vector<uint8_t> c;
+        std::vector<uint64_t> o;
+        b->impl.download_reads(c, o);
+        auto* oc = (uint8_t*)malloc(std::max<size_t>(c.size(), 1));
+        auto* oo = (uint64_t*)malloc(o.size() * sizeof(uint64_t));
+        if (!oc || !oo) {
+            free(oc);
+            free(oo);
+            throw std::bad_alloc();
+        }
+        if (!c.empty()) memcpy(oc, c.data(), c.size());
+        memcpy(oo, o.data(), o.size() * sizeof(uint64_t));
+        *codes = oc;
+        *read_off = oo;
+        *n_reads = o.size() - 1;
+    })
+}
+
 int mtsv_merge_taxa_reports(const mtsv_taxon_stats* a, uint64_t n_a, const mtsv_taxon_stats* b, uint64_t n_b, mtsv_taxon_stats** out,
                             uint64_t* n_out) {
     if ((!a && n_a) || (!b && n_b) || !out || !n_out) return fail_arg("null argument");

@@ -1,7 +1,7 @@
 // kernels.hpp -- launch interface of the hot-path kernels.
 //
 // The mtsv-binner hot path as gfx950 kernels (k_seed.hip, k_coalesce.hip, k_verify.hip; k_report.hip for the taxa report, k_match.hip for
-// the per-read match flags).
+// the per-read match flags, k_compact.hip for the hand-over of a run's unmatched or matched reads to another workspace).
 //
 // One batch of reads flows through staged kernels with worklists in HBM:
 //
@@ -191,5 +191,20 @@ void launch_report(hipStream_t s, uint32_t n_reads, const uint32_t* strand_nout,
 // (first_bit + r) & 63 of words[(first_bit + r) >> 6] when it has a hit -- atomically: other streams may be writing the same
 // words -- and *n_matched grows by the number of such reads.  The words must be zero where no read has been flagged yet.
 void launch_match(hipStream_t s, uint32_t n_reads, const uint32_t* strand_nout, uint64_t first_bit, uint64_t* words, uint64_t* n_matched);
+// k_compact.hip: the reads of a resident batch (codes, read_off[n_reads + 1]) whose bit in `words` (bit r = read r) is clear
+// (keep_matched: set), in order, as the resident batch of another workspace.  The scan: tile_cnt / tile_bases
+// (compact_tiles(n_reads) entries each) become the exclusive prefixes of the survivors and of their bases per tile of reads,
+// result[0] = survivors m, [1] = their bases, [2] = the longest of them (the caller zeroes [2] first).  The copy, once the
+// host has checked m and the bases against the destination: dst_off[0 .. m] (from 0), dst_map[j] = src_map[i] (src_map
+// null: i) for survivor j = source read i, dst_codes = the survivors' codes.  codes must be readable four bytes past its
+// last base; nothing is written behind dst_codes' last.
+uint32_t compact_tiles(uint64_t n_reads);
+void launch_compact_scan(hipStream_t s, uint32_t n_reads, const uint64_t* words, const uint32_t* read_off, int keep_matched, uint64_t* tile_cnt,
+                         uint64_t* tile_bases, uint64_t* result);
+void launch_compact_copy(hipStream_t s, uint32_t n_reads, const uint64_t* words, const uint32_t* read_off, const uint8_t* codes, int keep_matched,
+                         const uint32_t* src_map, const uint64_t* tile_cnt, const uint64_t* tile_bases, const uint64_t* result, uint8_t* dst_codes,
+                         uint32_t* dst_off, uint32_t* dst_map);
+// hits[i].read = map[hits[i].read] for the n_hits hits a pass of a compacted workspace has just gathered
+void launch_remap_reads(hipStream_t s, DevHit* hits, uint64_t n_hits, const uint32_t* map);
 
 }  // namespace mtsv
