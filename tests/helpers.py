@@ -465,3 +465,197 @@ def geometry_reads(rng, entries, n=300):
         r = mutate(rng, text[st:st + Lr], rng.randrange(0, math.ceil(Lr * 0.13) + 3))
         reads.append(r if rng.random() < 0.5 else revcomp(r))
     return reads
+
+
+# ---- chains of refused candidates (test_verify_rounds_cpu.py, test_verify_rounds.py) ---------------------------------
+# One chain = one TaxID whose sequences (one GI each, in file order, between random flanks of 80..200 bases) are damaged
+# copies of one random segment.  All damage lies inside one region [lo, hi] of the segment, every copy changes lo and hi,
+# and every 18-mer that touches the region holds a change in every copy: a read cut across the region keeps the same
+# intact seeds on all of them, they tie in the rank order, and the stable sort leaves them in file order.  With
+# ED = ceil(0.13 * L) and thr = L - 2 * ED, D the unit-cost distance under the SW matrix's matches:
+#   A  every region base complemented                              D > 2*ED: the bound refutes it
+#   B  nB substitutions lo..hi, ED < nB <= 2*ED, L - 2*nB < thr     undecided by the bound, the sweep refutes it
+#   C  s substitutions + i bases inserted at hi - 4,               undecided, the score passes (i + 2*s <= 2*ED), the edit
+#      ED < s + i <= 2*ED                                          distance s + i refuses it
+#   G  nG <= ED substitutions lo..hi                               accepted
+# and for reads that hold N at 180..191 of the segment (region 180..239, L = 150):
+#   g  5 substitutions                                             accepted with 17 edits
+#   e  N under the read's N + 13 substitutions                     D = 13 <= ED < 25 edits: passes the bound, refused
+#   b  17 substitutions, bases under the read's N                  D = 29: undecided, the sweep refutes it
+#   c  N under the read's N + the 5 of g + 16 bases inserted       D = 21: undecided, the score passes, 33 edits refuse it
+CHAIN_LO = 180
+CHAIN_SHAPES = {  # L: region length, nG, nB, C's (s, i), read starts lo - (first .. last)
+    150: dict(region=90, nG=9, nB=26, s=9, i=14, back=(15, 35)),
+    96: dict(region=50, nG=5, nB=14, s=5, i=10, back=(19, 24)),
+    253: dict(region=160, nG=15, nB=34, s=15, i=20, back=(20, 50)),
+}
+CHAIN_N_SHAPE = dict(region=60, back=(15, 35))  # the N family: L = 150, read starts 145..165
+
+
+def _spread(lo, hi, n):
+    """n positions evenly spaced from lo to hi, both included"""
+    return sorted({lo + round(k * (hi - lo) / (n - 1)) for k in range(n)}) if n > 1 else [lo]
+
+
+def _complemented(seg, positions):
+    s = bytearray(seg)
+    for p in positions:
+        s[p] = COMP[s[p]]
+    return s
+
+
+def chain_copy(rng, seg, kind, L):
+    """the copy of `kind` of a segment whose region starts at CHAIN_LO"""
+    lo = CHAIN_LO
+    if kind in "ABCG":
+        sh = CHAIN_SHAPES[L]
+        hi = lo + sh["region"] - 1
+        if kind == "A":
+            return bytes(_complemented(seg, range(lo, hi + 1)))
+        if kind == "B":
+            return bytes(_complemented(seg, _spread(lo, hi, sh["nB"])))
+        if kind == "G":
+            return bytes(_complemented(seg, _spread(lo, hi, sh["nG"])))
+        s = _complemented(seg, _spread(lo, hi - 12, sh["s"] - 1) + [hi])
+        s[hi - 4:hi - 4] = rnd_seq(rng, sh["i"])
+        return bytes(s)
+    assert L == 150
+    if kind == "g":
+        return bytes(_complemented(seg, [192, 204, 216, 228, 239]))
+    if kind == "b":
+        return bytes(_complemented(seg, list(range(192, 240, 3)) + [239]))
+    if kind == "e":
+        s = _complemented(seg, list(range(192, 240, 4)) + [239])
+        s[180:192] = b"N" * 12
+        return bytes(s)
+    if kind == "c":
+        s = _complemented(seg, [192, 204, 216, 228, 239])
+        s[180:192] = b"N" * 12
+        s[235:235] = rnd_seq(rng, 16)
+        return bytes(s)
+    raise ValueError(kind)
+
+
+def chain_kinds(with_n=False):
+    """the chains of one database: every sequence over the three failing kinds of length 1..3, once ending in a good copy
+    and once without one; for the reads without N also CCCC, CCCCC and CCCCCC before a good copy (seven copies: a cut at
+    max_candidates = 6 falls inside a chain too)"""
+    import itertools
+    fail, good = ("ebc", "g") if with_n else ("ABC", "G")
+    out = []
+    for n in (1, 2, 3):
+        for t in itertools.product(fail, repeat=n):
+            out += ["".join(t) + good, "".join(t)]
+    if not with_n:
+        out += ["CCCCG", "CCCCCG", "CCCCCCG"]
+    return out
+
+
+class ChainDb:
+    """entries: (tax_id, gi, sequence) in file order; chains: [(tax_id, kinds, [gi per copy])]; segments: the segment of
+    every chain; copies: {gi: the copy between its flanks}; reads: the batch, with read_chain[k] the index into chains of
+    read k"""
+
+    def __init__(self, L, entries, chains, segments, copies, reads, read_chain):
+        self.L, self.entries, self.chains, self.segments, self.copies = L, entries, chains, segments, copies
+        self.reads, self.read_chain = reads, read_chain
+
+    def kinds_of(self, k):
+        return self.chains[self.read_chain[k]][1]
+
+    def good_gi(self, k):
+        tax, kinds, gis = self.chains[self.read_chain[k]]
+        return gis[-1] if kinds[-1] in "Gg" else None
+
+
+def chain_db(rng, L, with_n=False, reads_per_strand=3):
+    """the chain database for reads of L bases and its reads: reads_per_strand exact cuts of every chain's segment per
+    strand (with N at 180..191 for the N family), in the order of the chains"""
+    sh = CHAIN_N_SHAPE if with_n else CHAIN_SHAPES[L]
+    seg_len = CHAIN_LO + sh["region"] + 180
+    entries = [(10 + t, 500 + t, rnd_seq(rng, 3000)) for t in range(3)]
+    chains, segments, copies, reads, read_chain = [], [], {}, [], []
+    for ci, kinds in enumerate(chain_kinds(with_n)):
+        seg = rnd_seq(rng, seg_len)
+        tax = 1000 + ci
+        gis = []
+        for k, kind in enumerate(kinds):
+            gi = 100000 + 10 * ci + k
+            copies[gi] = chain_copy(rng, seg, kind, L)
+            entries.append((tax, gi, rnd_seq(rng, rng.randrange(80, 201)) + copies[gi] + rnd_seq(rng, rng.randrange(80, 201))))
+            gis.append(gi)
+        chains.append((tax, kinds, gis))
+        segments.append(seg)
+        src = bytearray(seg)
+        if with_n:
+            src[180:192] = b"N" * 12
+        for k in range(2 * reads_per_strand):
+            st = CHAIN_LO - rng.randrange(sh["back"][0], sh["back"][1] + 1)
+            r = bytes(src[st:st + L])
+            reads.append(r if k < reads_per_strand else revcomp(r))
+            read_chain.append(ci)
+    return ChainDb(L, entries, chains, segments, copies, reads, read_chain)
+
+
+def chain_prediction(kinds):
+    """(prefilter runs, edit distances, hits) of the reference for a read of a chain: every copy up to the good one is
+    prefiltered, the copies whose score passes (C, c, e and the good one) get an edit distance, the good one is the hit"""
+    g = 1 if kinds[-1] in "Gg" else 0
+    return len(kinds), sum(k in "Cce" for k in kinds) + g, g
+
+
+def expected_rounds(kinds):
+    """n_rounds of the default arrangement for a read of a chain (mtsv_amd.h, the mode comment of k_edit_myers).
+    A lane of k_edit_myers (fused in round 0, list mode behind every sweep) refutes A and walks on, passes e, refuses it
+    and walks on, accepts G/g; an undecided kind (B C b c) met in the fused lane goes to the sweep of the same round, met
+    in a list lane it starts a new round.  The sweep fails A B b and walks on; what it passes (C c e, G g) goes to a list
+    lane, which refuses C c e and walks on, and accepts G g.  n_rounds = 1 + the times a list lane met an undecided kind."""
+    rounds, where = 1, "fused"
+    for k in kinds:
+        if where == "sweep":
+            if k in "ABb":
+                continue
+            if k in "Gg":
+                break
+            where = "list"  # C c e: passed by the sweep, refused by the list lane, which walks on
+            continue
+        if k == "A" or k == "e":
+            continue
+        if k in "Gg":
+            break
+        if where == "list":
+            rounds += 1
+        if k in "Cc":  # the sweep of this round passes it, its list lane refuses it and walks on
+            where = "list"
+        else:  # B b: the sweep refutes it and walks on
+            where = "sweep"
+    return rounds
+
+
+CHAIN_CASES = ((96, False), (150, False), (253, False), (150, True))  # (L, the N family)
+CHAIN_SEED = 4100
+_chain_cases = {}
+
+
+def chain_case(L, with_n=False):
+    """the chain database of (L, family), built once per process, with the oracle's word on it: .orc the oracle's index
+    of the entries, .per_read [(hits, counters)] of every read binned alone at default parameters, .as_predicted [bool]
+    whether (n_sw, n_edit, hits) of read k is chain_prediction() of its chain"""
+    key = (L, bool(with_n))
+    if key not in _chain_cases:
+        from concurrent.futures import ThreadPoolExecutor
+        from oracle import oracle as O
+        db = chain_db(random.Random(CHAIN_SEED), L, with_n)
+        db.orc = O.Index.build(db.entries)
+        op = O.default_params()
+
+        def one(r):
+            b, o = reads_to_batch([r])
+            return db.orc.bin_batch(b, o, op, threads=1)
+
+        with ThreadPoolExecutor(8) as ex:
+            db.per_read = list(ex.map(one, db.reads))
+        db.as_predicted = [(c["n_sw"], c["n_edit"], len(h)) == chain_prediction(db.kinds_of(k))
+                           for k, (h, c) in enumerate(db.per_read)]
+        _chain_cases[key] = db
+    return _chain_cases[key]
