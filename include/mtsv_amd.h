@@ -121,6 +121,8 @@ typedef struct {
     uint64_t verify_turns;     /* passes that took the workspace's verify turn (0: one lane, or MTSV_VERIFY_TURN=0) */
     uint64_t verify_lanes_max; /* lanes that had the verify kernels of a pass in flight at once, at most (1 with the turn) */
     uint64_t myers_grid_max;   /* largest k_edit_myers grid of the run, in workgroups (at most 256 x MTSV_MYERS_WGS_PER_CU) */
+    uint64_t n_seed_tile_passes; /* of n_passes, those whose seed stage ran by tiles (k_thin_tiled, k_expand_tiled); the others
+                                  * (MTSV_SEED_STAGE=legacy, or a pass that does not fit the tile) ran k_thin and k_expand */
 } mtsv_batch_stats;
 
 const char *mtsv_last_error(void);

@@ -47,7 +47,8 @@ class BatchStats(C.Structure):  # mtsv_batch_stats
                 ("n_rounds", C.c_uint64), ("n_lanes", C.c_uint64), ("sw_cell_pairs", C.c_uint64), ("sw_prefilter_ms", C.c_float),
                 ("sw_sweep_ms", C.c_float), ("n_sw_passed", C.c_uint64), ("sw_diag_ms", C.c_float), ("sw_bound_ms", C.c_float),
                 ("edit_ms", C.c_float), ("myers_columns", C.c_uint64), ("n_sw_bound_refuted", C.c_uint64),
-                ("verify_turns", C.c_uint64), ("verify_lanes_max", C.c_uint64), ("myers_grid_max", C.c_uint64)]
+                ("verify_turns", C.c_uint64), ("verify_lanes_max", C.c_uint64), ("myers_grid_max", C.c_uint64),
+                ("n_seed_tile_passes", C.c_uint64)]
 
     def as_dict(self):
         d = {n: (float(getattr(self, n)) if t is C.c_float else int(getattr(self, n))) for n, t in self._fields_[1:]}

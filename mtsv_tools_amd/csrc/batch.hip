@@ -156,10 +156,12 @@ Batch::Batch(mtsv_index* ix_, DeviceIndex* di_, uint64_t max_reads_, uint64_t ma
         if (const char* e = getenv("MTSV_VERIFY_TURN")) verify_turn.on = verify_turn.on && atoi(e) != 0;
         if (const char* e = getenv("MTSV_TAIL_FROM_LIST")) tail_from_list = atoi(e) != 0;
         if (const char* e = getenv("MTSV_FUSED_CLEAR")) fused_clear = atoi(e) != 0;
+        if (const char* e = getenv("MTSV_SEED_STAGE")) seed_tiles = strcmp(e, "legacy") != 0;
     } else {
         myers_wgs_per_cu = parent->myers_wgs_per_cu;
         tail_from_list = parent->tail_from_list;
         fused_clear = parent->fused_clear;
+        seed_tiles = parent->seed_tiles;
     }
     for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
     for (int k = 1; k < n_lanes; k++) {
@@ -391,6 +393,7 @@ void Batch::end_run() {
         stats.n_seed_slots += l->stats.n_seed_slots;
         stats.n_seed_hits += l->stats.n_seed_hits;
         stats.n_passes += l->stats.n_passes;
+        stats.n_seed_tile_passes += l->stats.n_seed_tile_passes;
         stats.n_rounds = std::max(stats.n_rounds, l->stats.n_rounds);
         stats.lf_steps += l->stats.lf_steps;
         stats.n_candidates += l->stats.n_candidates;
@@ -784,7 +787,12 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
                       fused_clear && ctr22_zero);
         ctr22_zero = false;
         HIP_CHECK(hipEventRecord(ev[1], stream));
-        if (max_ns)
+        // the seed stage by tiles when the pass fits them (kernels.hpp); k_thin and k_expand with seed_pre between them otherwise
+        const bool tile_pass = seed_tiles && max_ns && seed_tile_fits(max_ns, pass_max_len, slots);
+        if (tile_pass)
+            launch_thin_tiled(stream, sb, so, (uint32_t)r0, nr, p.edit_rate, p.min_seed, max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,
+                              d_strand_hits, d_strand_nseeds, myers_pass ? d_planes : nullptr, plane_words);
+        else if (max_ns)
             launch_thin(stream, sb, so, (uint32_t)r0, nr, p.edit_rate, p.min_seed, max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,
                         d_seed_pre, d_strand_hits, d_strand_nseeds, myers_pass ? d_planes : nullptr, plane_words);
         else {
@@ -818,11 +826,16 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
             grow_hit_workspace(total_hits);
         }
         stats.n_passes++;
+        stats.n_seed_tile_passes += tile_pass;
+        if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] pass of %u reads, max_ns %u, longest read %u: seed stage %s\n", nr, max_ns, pass_max_len, tile_pass ? "by tiles" : "legacy");
         stats.n_seed_slots += slots;
         stats.n_seed_hits += total_hits;
         // ---- locate ----
-        launch_expand(stream, v, nstr, max_ns, G, d_seed_lo, d_seed_cnt, d_seed_pre, d_strand_off, d_hit_row, d_hit_ref,
-                      d_hit_q);
+        if (tile_pass)
+            launch_expand_tiled(stream, v, nstr, max_ns, G, d_seed_lo, d_seed_cnt, d_strand_off, d_hit_row, d_hit_ref, d_hit_q);
+        else
+            launch_expand(stream, v, nstr, max_ns, G, d_seed_lo, d_seed_cnt, d_seed_pre, d_strand_off, d_hit_row, d_hit_ref,
+                          d_hit_q);
         HIP_CHECK(hipEventRecord(ev[3], stream));
         if (!v.sa_full)
             launch_locate(stream, v, (uint32_t)total_hits, d_strand_off + nstr, d_hit_row, d_hit_ref,

@@ -96,6 +96,8 @@ struct Batch {
     bool tail_from_list = true;  // round 0's k_sw_pairs and list-mode k_edit_myers are sized from the undecided count the fused pass
                                  // publishes, and not launched when it is zero (MTSV_TAIL_FROM_LIST=0: sized from the seed hits)
     bool fused_clear = true;     // the counters of a stage are zeroed by one launch_clear_counters (MTSV_FUSED_CLEAR=0: a memset each)
+    bool seed_tiles = true;      // the seed stage by tiles, k_thin_tiled + k_expand_tiled, for the passes that fit them (MTSV_SEED_STAGE=legacy:
+                                 // k_thin writing seed_pre and k_expand reading it, for every pass)
     bool ctr22_zero = false;     // ... slot 22 (k_search's list count) is known to be zero on the stream
     // The verify turn: one lane of a workspace at a time has the verify kernels of a pass in flight (two VALU-bound launches beside
     // each other gain nothing, and the second takes the LDS the first frees from the memory-bound kernels that could use it).  The

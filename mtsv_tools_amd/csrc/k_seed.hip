@@ -580,6 +580,147 @@ __global__ __launch_bounds__(256) void k_thin(const uint8_t* __restrict__ bases,
     strand_nseeds[rs] = nseeds;
 }
 
+// The same by tiles of kThinTile consecutive reads of the pass, a workgroup per tile, so that the loads and stores of a
+// wavefront fall on consecutive addresses (k_thin: a lane per strand walks its own counts at a stride of max_ns words and a
+// lane pair its read's bytes at the read length's stride).  Passes of max_ns <= kTileMaxNs and reads up to
+// kMaxRegisterReadLen bases (seed_tile_fits); the others keep k_thin.  Nothing is written for k_expand_tiled: after the
+// policy a slot's count is non-zero exactly when its seed is kept, and the offset of a kept seed inside its strand is the
+// sum of the counts in front of it.
+//   1. the tile's read offsets, its 2 * tn * max_ns counts (rows padded to an odd pitch: the policy lanes below read a
+//      column each) and the bit streams of its byte span: a lane turns an aligned 16-byte group of codes into 16 bits of
+//      each plane, group g of the span being bits [16g, 16g + 16) of the stream
+//   2. a lane per strand runs the policy out of LDS; counts it drops are cleared in global memory (rare)
+//   3. a lane per (read, word) cuts the word's 32 bits out of the three streams at the read's bit offset, clears what lies
+//      past the read's end and stores them; the N plane's population counts are summed per read
+//   4. the lane of a strand stores its two words
+// The groups at the two ends of the span may hold bytes of other reads (a neighbouring range may be unpacking into them
+// on another stream): their bits lie outside every cut.
+constexpr uint32_t kThinTile = 128;
+constexpr uint32_t kTileMaxNs = 16;
+constexpr uint32_t kTilePitch = kTileMaxNs | 1;
+constexpr uint32_t kTileMaxWords = kMaxRegisterReadLen / 32;  // plane words of the longest read of such a pass
+// 32-bit words of one bit stream: the span, a group's worth of bytes in front and behind, and the word past the last cut
+constexpr uint32_t kThinStreamWords = (kThinTile * kMaxRegisterReadLen + 32) / 32 + 2;
+
+__global__ __launch_bounds__(256) void k_thin_tiled(const uint8_t* __restrict__ bases, const uint32_t* __restrict__ read_off,
+                                                    uint32_t r0, uint32_t n_reads, double edit_rate, double min_seed,
+                                                    uint32_t max_ns, uint32_t K, uint32_t G, uint64_t max_hits,
+                                                    uint64_t tune_max_hits, uint32_t* __restrict__ seed_cnt,
+                                                    uint32_t* __restrict__ strand_hits, uint32_t* __restrict__ strand_nseeds,
+                                                    uint32_t* __restrict__ planes, uint32_t plane_words) {
+    __shared__ uint32_t s_off[kThinTile + 1];
+    __shared__ uint32_t s_cnt[2 * kThinTile * kTilePitch];
+    __shared__ uint32_t s_bits[3][kThinStreamWords];
+    __shared__ uint32_t s_need[kThinTile];  // one of the read's strands has seed hits
+    __shared__ uint32_t s_nn[kThinTile];    // the read's N count (reads with seed hits)
+    const uint32_t tid = threadIdx.x;
+    const uint32_t t0 = blockIdx.x * kThinTile, tn = min(kThinTile, n_reads - t0);
+    for (uint32_t i = tid; i <= tn; i += 256) s_off[i] = read_off[r0 + t0 + i];
+    if (tid < kThinTile) s_nn[tid] = 0;
+    __syncthreads();
+    // ---- 1 ----
+    const uint32_t pitch = max_ns | 1;
+    {
+        const uint32_t n_cnt = 2 * tn * max_ns;
+        const uint32_t* gc = seed_cnt + (uint64_t)2 * t0 * max_ns;
+        for (uint32_t e = tid; e < n_cnt; e += 256) {
+            const uint32_t row = e / max_ns;
+            s_cnt[row * pitch + (e - row * max_ns)] = gc[e];
+        }
+    }
+    const uint32_t g0 = s_off[0] >> 4;
+    {
+        const uint4* b128 = reinterpret_cast<const uint4*>(bases);
+        const uint32_t ng = min(((s_off[tn] + 15) >> 4) - g0, 2 * (kThinStreamWords - 1));  // (never more: reads of this path have <= 256 bases)
+        uint16_t* h0 = reinterpret_cast<uint16_t*>(s_bits[0]);
+        uint16_t* h1 = reinterpret_cast<uint16_t*>(s_bits[1]);
+        uint16_t* hn = reinterpret_cast<uint16_t*>(s_bits[2]);
+        for (uint32_t g = tid; g < ng; g += 256) {
+            const uint4 v = b128[g0 + g];
+            // eight codes as the nibbles of a dword (byte k: bytes k and 4 + k), then bit b of each:
+            // x | x >> 7, then | >> 14, brings the bits of four bytes together
+            const uint32_t c0 = (v.x & 0x07070707u) | ((v.y & 0x07070707u) << 4);
+            const uint32_t c1 = (v.z & 0x07070707u) | ((v.w & 0x07070707u) << 4);
+            auto gather = [](uint32_t y) {
+                y &= 0x11111111u;
+                y |= y >> 7;
+                y |= y >> 14;
+                return y & 0xffu;
+            };
+            h0[g] = (uint16_t)(gather(c0) | (gather(c1) << 8));
+            h1[g] = (uint16_t)(gather(c0 >> 1) | (gather(c1 >> 1) << 8));
+            hn[g] = (uint16_t)(gather(c0 >> 2) | (gather(c1 >> 2) << 8));
+        }
+    }
+    __syncthreads();
+    // ---- 2 ----
+    const bool strand_lane = tid < 2 * tn;
+    uint32_t L = 0, total = 0, nseeds = 0;
+    if (strand_lane) {
+        L = s_off[(tid >> 1) + 1] - s_off[tid >> 1];
+        const uint32_t ns = n_seeds_of(L, K, G);
+        uint64_t next_offset = 0, seed_interval = G;
+        const uint32_t* cnt = s_cnt + tid * pitch;
+        uint32_t* gcnt = seed_cnt + ((uint64_t)2 * t0 + tid) * max_ns;
+        for (uint32_t j = 0; j < ns; j++) {
+            uint64_t offset = (uint64_t)j * G;
+            const uint32_t raw = cnt[j];
+            const uint32_t c = raw == kSeedAtPos ? 1u : raw;  // one hit whose position the search already knows
+            if (offset < next_offset) {  // index.rs:300-302
+                if (c) gcnt[j] = 0;
+                continue;
+            }
+            if (c == 0) continue;        // index.rs:330-332
+            if ((uint64_t)c > max_hits) {  // index.rs:335-337
+                gcnt[j] = 0;
+                continue;
+            }
+            if ((uint64_t)c > tune_max_hits) {  // index.rs:338-344
+                seed_interval *= 2;
+                next_offset = offset + seed_interval;
+            }
+            total += c;
+            nseeds++;
+        }
+    }
+    const bool need = total != 0;
+    {
+        const int other_need = __shfl_xor((int)need, 1);  // (the two strands of a read sit in neighbouring lanes; every lane takes part)
+        if (strand_lane && !(tid & 1)) s_need[tid >> 1] = need || other_need != 0;
+    }
+    __syncthreads();
+    // ---- 3 ----
+    for (uint32_t e = tid; e < tn * kTileMaxWords; e += 256) {
+        const uint32_t t = e / kTileMaxWords, w = e % kTileMaxWords;
+        const uint32_t b0 = s_off[t], Lt = s_off[t + 1] - b0;
+        if (!s_need[t] || w >= ((Lt + 31) >> 5)) continue;
+        const uint32_t bp = b0 - (g0 << 4) + 32 * w;  // the word's first bit in the streams
+        const uint32_t wi = min(bp >> 5, kThinStreamWords - 2), sh = bp & 31u;
+        const uint32_t left = Lt - 32 * w;  // bits past the read (the next read's bytes) are cleared
+        const uint32_t m = left >= 32 ? 0xffffffffu : (1u << left) - 1u;
+        const uint32_t w0 = __builtin_amdgcn_alignbit(s_bits[0][wi + 1], s_bits[0][wi], sh) & m;
+        const uint32_t w1 = __builtin_amdgcn_alignbit(s_bits[1][wi + 1], s_bits[1][wi], sh) & m;
+        const uint32_t wn = __builtin_amdgcn_alignbit(s_bits[2][wi + 1], s_bits[2][wi], sh) & m;
+        if (wn) atomicAdd(&s_nn[t], (uint32_t)__popc(wn));
+        if (planes) {
+            uint32_t* img = planes + ((uint64_t)(t0 + t) * plane_words + w) * 3;
+            img[0] = w0;
+            img[1] = w1;
+            img[2] = wn;
+        }
+    }
+    __syncthreads();
+    // ---- 4 ----
+    if (!strand_lane) return;
+    const uint32_t ED = (uint32_t)ceil((double)L * edit_rate);  // index.rs:281-282
+    const bool hopeless = 2ull * ED > (uint64_t)L || s_nn[tid >> 1] > ED;
+    // min_seeds = max(1, floor(n_seeds * pct)) (index.rs:358; saturated at 16 bits), the edit tolerance, the flag: as k_thin
+    const double ms = floor((double)nseeds * min_seed);
+    const uint32_t min_seeds = ms < 1.0 ? 1u : (ms > 65535.0 ? 65535u : (uint32_t)ms);
+    strand_hits[2 * t0 + tid] = total;
+    strand_nseeds[2 * t0 + tid] = min_seeds | (ED << 16) | ((need && hopeless) ? kHopeless : 0u);
+}
+
 // ---------------------------------------------------------------------------------------------
 // exclusive scan of u32 counts (block sums in u64 so the host can detect > 2^32 totals)
 // ---------------------------------------------------------------------------------------------
@@ -712,6 +853,110 @@ __global__ __launch_bounds__(256) void k_expand(DevIndexView ix, uint64_t n_slot
             else hit_row[os + i] = ls + i;
             hit_q[os + i] = qs;
         }
+    }
+}
+
+// The same after k_thin_tiled (max_ns <= kTileMaxNs, fewer than 2^32 slots), without seed_pre: a kept seed's offset inside
+// its strand is the sum of the counts of the strand's slots in front of it (kSeedAtPos counting 1; dropped seeds were
+// cleared).  The wavefronts stride over the slots, 64 at a time; each stages its counts in LDS behind those of the
+// kTileMaxNs slots in front of them (strands straddle the wavefronts' ranges) and a lane with a kept seed adds up its j
+// predecessors.  Hits are written exactly as k_expand writes them.
+__global__ __launch_bounds__(256) void k_expand_tiled(DevIndexView ix, uint32_t n_slots, uint32_t max_ns, uint32_t G,
+                                                      const uint32_t* __restrict__ seed_lo,
+                                                      const uint32_t* __restrict__ seed_cnt,
+                                                      const uint32_t* __restrict__ strand_off,
+                                                      uint32_t* __restrict__ hit_row, uint32_t* __restrict__ hit_ref,
+                                                      uint32_t* __restrict__ hit_q) {
+    __shared__ uint32_t stage[256 / kWave][kTileMaxNs + kWave];
+    __shared__ uint32_t flat[256 / kWave][4][kWave];  // per lane: inclusive count of the hits taken by flat index, o, l, q
+    const uint32_t lane = lane_id(), wave = threadIdx.x / kWave;
+    uint32_t* st = stage[wave];
+    uint32_t (*fl)[kWave] = flat[wave];
+    const uint32_t n_tiles = (n_slots + kWave - 1) / kWave;
+    const uint32_t stride = gridDim.x * (256 / kWave);
+    // what a trip reads at addresses its slots alone decide -- the counts, those of the halo in front of them, seed_lo and
+    // the strands' offsets -- is loaded one trip ahead, so that only the SA gathers stand between a trip and its stores
+    struct Ahead {
+        uint32_t raw, halo, lo, off;
+    };
+    auto load_ahead = [&](uint32_t tile) {
+        Ahead a{0, 0, 0, 0};
+        const uint32_t base = tile * kWave, slot = base + lane;
+        if (tile < n_tiles && slot < n_slots) {
+            a.raw = seed_cnt[slot];
+            a.lo = seed_lo[slot];
+            a.off = strand_off[slot / max_ns];
+        }
+        const uint32_t back = kTileMaxNs - lane;  // (lanes below kTileMaxNs) slot base - back, read by lanes whose j reaches it: back < max_ns
+        if (tile < n_tiles && lane < kTileMaxNs && back < max_ns && back <= base) a.halo = seed_cnt[base - back];
+        return a;
+    };
+    uint32_t tile = blockIdx.x * (256 / kWave) + wave;
+    Ahead next = load_ahead(tile);
+    for (; tile < n_tiles; tile += stride) {
+        const uint32_t slot = tile * kWave + lane;
+        const Ahead cur = next;
+        next = load_ahead(tile + stride);
+        const uint32_t raw = cur.raw, halo = cur.halo;
+        const bool at_pos = raw == kSeedAtPos;  // one hit, seed_lo is its text position (only with the full SA)
+        const uint32_t c = at_pos ? 1u : raw;
+        st[kTileMaxNs + lane] = c;
+        if (lane < kTileMaxNs) st[lane] = halo == kSeedAtPos ? 1u : halo;
+        // (wavefront scope: the LDS serves a wavefront's accesses in order, and nothing waits for the trip's stores)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        uint32_t o = 0, l = 0, q = 0;
+        if (c) {
+            const uint32_t rs = slot / max_ns, j = slot - rs * max_ns;
+            uint32_t pre = 0;
+            for (uint32_t i = 1; i <= j; i++) pre += st[kTileMaxNs + lane - i];
+            o = cur.off + pre;
+            l = cur.lo;
+            q = j * G;
+        }
+        constexpr uint32_t kOwn = 16;
+        if (at_pos) {
+            hit_ref[o] = l;
+            hit_q[o] = q;
+        }
+        // seeds of 1..kOwn hits: the wavefront takes their hits by flat index, 64 independent gathers and 64 stores a trip
+        // (a lane walking its own seed alone issued up to kOwn dependent gathers while the others waited)
+        const uint32_t cc = !at_pos && c <= kOwn ? c : 0;
+        const uint32_t inc = wave_incl_scan(cc);
+        const uint32_t sum = __builtin_amdgcn_readlane(inc, kWave - 1);
+        if (sum) {
+            fl[0][lane] = inc;
+            fl[1][lane] = o;
+            fl[2][lane] = l;
+            fl[3][lane] = q;
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (uint32_t f = lane; f < sum; f += kWave) {
+                uint32_t src = 0;  // the first lane whose inclusive count exceeds f
+#pragma unroll
+                for (uint32_t step = kWave / 2; step; step >>= 1)
+                    if (fl[0][src + step - 1] <= f) src += step;
+                const uint32_t i = f - (src ? fl[0][src - 1] : 0u);
+                const uint32_t os = fl[1][src], ls = fl[2][src];
+                if (ix.sa_full) hit_ref[os + i] = ix.sa_full[ls + i];
+                else hit_row[os + i] = ls + i;
+                hit_q[os + i] = fl[3][src];
+            }
+        }
+        unsigned long long big = __ballot(c > kOwn);
+        while (big) {
+            const int src = __ffsll((long long)big) - 1;
+            big &= big - 1;
+            const uint32_t cs = __builtin_amdgcn_readlane(c, src), os = __builtin_amdgcn_readlane(o, src);
+            const uint32_t ls = __builtin_amdgcn_readlane(l, src), qs = __builtin_amdgcn_readlane(q, src);
+            for (uint32_t i = lane; i < cs; i += kWave) {
+                if (ix.sa_full) hit_ref[os + i] = ix.sa_full[ls + i];
+                else hit_row[os + i] = ls + i;
+                hit_q[os + i] = qs;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // (the next trip overwrites the staged counts)
+        __builtin_amdgcn_wave_barrier();
     }
 }
 
@@ -853,6 +1098,30 @@ void launch_thin(hipStream_t s, const uint8_t* bases, const uint32_t* read_off, 
                  uint32_t* strand_hits, uint32_t* strand_nseeds, uint32_t* planes, uint32_t plane_words) {
     hipLaunchKernelGGL(k_thin, dim3(cdiv((uint64_t)n_reads * 2, 256)), dim3(256), 0, s, bases, read_off, r0, n_reads, edit_rate,
                        min_seed, max_ns, K, G, max_hits, tune, seed_cnt, seed_pre, strand_hits, strand_nseeds, planes, plane_words);
+}
+
+bool seed_tile_fits(uint32_t max_ns, uint32_t max_len, uint64_t n_slots) {
+    return max_ns <= kTileMaxNs && max_len <= kMaxRegisterReadLen && n_slots <= 0xffffff00ull;
+}
+uint32_t seed_tile_reads() { return kThinTile; }
+uint32_t seed_tile_max_ns() { return kTileMaxNs; }
+
+void launch_thin_tiled(hipStream_t s, const uint8_t* bases, const uint32_t* read_off, uint32_t r0, uint32_t n_reads, double edit_rate,
+                       double min_seed, uint32_t max_ns, uint32_t K, uint32_t G, uint64_t max_hits, uint64_t tune, uint32_t* seed_cnt,
+                       uint32_t* strand_hits, uint32_t* strand_nseeds, uint32_t* planes, uint32_t plane_words) {
+    if (!n_reads) return;
+    hipLaunchKernelGGL(k_thin_tiled, dim3(cdiv(n_reads, kThinTile)), dim3(256), 0, s, bases, read_off, r0, n_reads, edit_rate, min_seed,
+                       max_ns, K, G, max_hits, tune, seed_cnt, strand_hits, strand_nseeds, planes, plane_words);
+}
+
+void launch_expand_tiled(hipStream_t s, const DevIndexView& ix, uint32_t n_strands, uint32_t max_ns, uint32_t G, const uint32_t* seed_lo,
+                         const uint32_t* seed_cnt, const uint32_t* strand_off, uint32_t* hit_row, uint32_t* hit_ref, uint32_t* hit_q) {
+    const uint64_t n_slots = (uint64_t)n_strands * max_ns;
+    if (!n_slots) return;
+    // resident wavefronts that stride over the slots
+    const dim3 grid(std::min<uint32_t>(cdiv(n_slots, 256), 256 * 8));
+    hipLaunchKernelGGL(k_expand_tiled, grid, dim3(256), 0, s, ix, (uint32_t)n_slots, max_ns, G, seed_lo, seed_cnt, strand_off, hit_row,
+                       hit_ref, hit_q);
 }
 
 void launch_scan(hipStream_t s, const uint32_t* in, uint32_t n, uint64_t* tile_sums, uint64_t* total, uint32_t* out) {

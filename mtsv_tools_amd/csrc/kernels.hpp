@@ -8,8 +8,10 @@
 //   k_search    lane per (read, strand, seed): FMIndex::backward_search           index.rs:305
 //   k_thin      lane per strand: adaptive seed thinning / max_hits filter         index.rs:293-344,354
 //               (and, a lane pair per read: the read's bit planes for k_edit_myers, its N count)
+//               (k_thin_tiled: the same by tiles of 128 reads, out of LDS -- the passes seed_tile_fits() accepts)
 //   scan        exclusive scan of per-strand seed-hit counts
 //   k_expand    lane per kept seed: its SA rows / text positions (Interval::occ)  index.rs:347-352
+//               (k_expand_tiled, behind k_thin_tiled: offsets from the counts themselves, no seed_pre)
 //   k_locate    lane per seed hit with wavefront refill: SampledSuffixArray::get  index.rs:347
 //   k_coalesce  wavefront per strand: sort, coalesce_seed_sites, min_seeds, rank  index.rs:358-369,435-487
 //   k_sw_pairs  16-lane group per two candidates: the SW prefilter                index.rs:401-406, ssw.c:123-328
@@ -123,6 +125,17 @@ void launch_search(hipStream_t s, const DevIndexView& ix, const uint8_t* bases, 
 void launch_thin(hipStream_t s, const uint8_t* bases, const uint32_t* read_off, uint32_t r0, uint32_t n_reads, double edit_rate,
                  double min_seed, uint32_t max_ns, uint32_t K, uint32_t G, uint64_t max_hits, uint64_t tune, uint32_t* seed_cnt, uint32_t* seed_pre,
                  uint32_t* strand_hits, uint32_t* strand_nseeds, uint32_t* planes, uint32_t plane_words);
+// The seed stage by tiles (k_thin_tiled, k_expand_tiled): the same outputs without seed_pre -- k_expand_tiled forms a kept
+// seed's offset from the counts k_thin_tiled left.  For the passes seed_tile_fits() accepts (max_ns <= seed_tile_max_ns(),
+// reads up to kMaxRegisterReadLen bases, fewer than 2^32 slots); the two launches of a pass go together, tiled or not.
+bool seed_tile_fits(uint32_t max_ns, uint32_t max_len, uint64_t n_slots);
+uint32_t seed_tile_reads();   // reads per workgroup of k_thin_tiled
+uint32_t seed_tile_max_ns();
+void launch_thin_tiled(hipStream_t s, const uint8_t* bases, const uint32_t* read_off, uint32_t r0, uint32_t n_reads, double edit_rate,
+                       double min_seed, uint32_t max_ns, uint32_t K, uint32_t G, uint64_t max_hits, uint64_t tune, uint32_t* seed_cnt,
+                       uint32_t* strand_hits, uint32_t* strand_nseeds, uint32_t* planes, uint32_t plane_words);
+void launch_expand_tiled(hipStream_t s, const DevIndexView& ix, uint32_t n_strands, uint32_t max_ns, uint32_t G, const uint32_t* seed_lo,
+                         const uint32_t* seed_cnt, const uint32_t* strand_off, uint32_t* hit_row, uint32_t* hit_ref, uint32_t* hit_q);
 // out has n+1 entries (out[n] = total); tile_sums needs scan_tiles(n) entries
 void launch_scan(hipStream_t s, const uint32_t* in, uint32_t n, uint64_t* tile_sums, uint64_t* total, uint32_t* out);
 uint32_t scan_tiles(uint32_t n);
