@@ -324,6 +324,43 @@ int mtsv_batch_match_flags(mtsv_batch *b, uint64_t **words, uint64_t *n_reads, u
 #define MTSV_KEEP_MATCHED 1
 int mtsv_batch_take_reads(mtsv_batch *dst, mtsv_batch *src, int keep, uint64_t *n_kept, uint64_t *bases_kept,
                           float *device_ms);
+/* ---- chunked databases on one device: the same reads in several workspaces, their runs merged in HBM -----------------
+ * A database cut with mtsv-chunk is binned chunk by chunk and a read's hits come from several chunks; what is counted per
+ * read -- the taxa report, the match flags -- has to see them together (a TaxID's smallest edit may come from any chunk,
+ * and a read matched in two chunks is one matched read).  With every chunk resident on one device, a workspace each:
+ * the reads go up once (mtsv_batch_upload, or mtsv_batch_take_reads behind a filter), mtsv_batch_copy_reads gives them
+ * to the other chunks' workspaces, every workspace runs (mtsv_batch_run), and mtsv_batch_merge_runs puts the hits
+ * together per read in a further workspace, the collector (k_merge.hip).  K chunks take K + 1 workspaces of HBM.
+ *
+ * mtsv_batch_copy_reads: dst's resident batch becomes a copy of src's -- codes (or the bases as uploaded), offsets,
+ * longest read, read map -- as if the same reads had been handed to dst: mtsv_batch_run on it skips the normalisation
+ * when src held codes and writes mapped read numbers when src was mapped.  src holds a resident batch from
+ * mtsv_batch_upload, _take_reads, _copy_reads, or a host batch that fitted one input segment; it needs no match flags and
+ * no completed run.  Everything moves from HBM to HBM; the host copies its own offset table.  MTSV_E_ARG, with dst as it
+ * was: dst == src, different devices, nothing resident in src, more reads or bases than dst was created for.
+ * device_ms (may be NULL): device time of the copies. */
+int mtsv_batch_copy_reads(mtsv_batch *dst, mtsv_batch *src, float *device_ms);
+/* mtsv_batch_merge_runs: the last runs of srcs[0 .. n_srcs), which all hold the same reads, merged per read into dst.
+ * Afterwards mtsv_batch_download(dst) returns, per read in read order, the hits of srcs[0], then of srcs[1], and so on,
+ * every source in its own order: the list mtsv_bin_batch_chunks returns.  mtsv_batch_stats_get(dst) gives n_reads and
+ * n_hits of the merge, the rest 0.  With dst's match flags on (MTSV_MATCH_WITH_HITS) they describe the merge: bit j is
+ * set when resident read j has a hit in any source, and n_matched is counted on the device.  With dst's taxa report on,
+ * the merged reads are added to it once; the report's TaxID list becomes the union of dst's index and every source's
+ * (when a merge brings new TaxIDs the list and the counters so far are rebuilt, host work, and the dense / hashed tier is
+ * decided again for the new size).  Sources are meant to run with their own reports off: those would count per chunk.
+ * Sources: 1..64 workspaces of dst's device, each with a completed mtsv_batch_run on a resident batch whose hits are still
+ * in HBM (a host batch is refused), none in MTSV_MATCH_ONLY (that mode gathers no hits); equal n_reads and equal offset
+ * tables (the host copies are compared); all mapped or none (equal maps are the caller's business, mtsv_batch_copy_reads
+ * gives them; the hits then carry the caller's numbers, flags and report stay per resident read).  They are only read and
+ * keep their own results.  dst: any workspace of the device that is not among the sources and is not in
+ * MTSV_MATCH_ONLY; its resident reads, if any, are not touched.  mtsv_batch_take_reads from a merged dst is refused
+ * (MTSV_E_ARG): its flags describe reads it does not hold.  2^32 merged hits or more: MTSV_E_LIMIT (the scan's and the
+ * report's offsets are 32 bits, as in a pass).  Every refusal leaves dst as it was: its last result, its counters, its
+ * flags.  Only a refusal for want of device memory, with the report on, may come after the report's TaxID list has taken
+ * the sources' TaxIDs; the counts so far are kept, the new rows are 0.  The host receives 16 bytes of counts; the hits
+ * cross on mtsv_batch_download.  What the merge needs on the device is created by dst's first merge.
+ * device_ms (may be NULL): device time of the merge kernels (bounds, sum, scan, copy). */
+int mtsv_batch_merge_runs(mtsv_batch *dst, mtsv_batch *const *srcs, int n_srcs, float *device_ms);
 /* (*map)[j] = the caller's number of resident read j (the identity after mtsv_batch_upload); malloc'd, mtsv_free */
 int mtsv_batch_read_map(mtsv_batch *b, uint64_t **map, uint64_t *n_reads);
 /* For tests, like mtsv_pack_bases: the resident batch as the kernels see it -- byte codes 0..4 (src/binner.rs:88-100)

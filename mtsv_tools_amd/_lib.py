@@ -79,6 +79,7 @@ EXPORTS = [
     "mtsv_batch_set_taxa_report", "mtsv_batch_taxa_report", "mtsv_merge_taxa_reports", "mtsv_format_taxa_report",
     "mtsv_batch_set_match_flags", "mtsv_batch_match_flags",
     "mtsv_batch_take_reads", "mtsv_batch_read_map", "mtsv_batch_download_reads",
+    "mtsv_batch_copy_reads", "mtsv_batch_merge_runs",
 ]
 
 _lib = None
@@ -146,6 +147,8 @@ def lib():
         L.mtsv_batch_set_match_flags.argtypes = [vp, i32]
         L.mtsv_batch_match_flags.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.mtsv_batch_take_reads.argtypes = [vp, vp, i32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_batch_copy_reads.argtypes = [vp, vp, C.POINTER(C.c_float)]
+        L.mtsv_batch_merge_runs.argtypes = [vp, vp, i32, C.POINTER(C.c_float)]
         L.mtsv_batch_read_map.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_batch_download_reads.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
         _lib = L
@@ -418,6 +421,23 @@ class Batch:
         n, nb, ms = C.c_uint64(), C.c_uint64(), C.c_float()
         _check(lib().mtsv_batch_take_reads(self.h, src.h, int(keep), C.byref(n), C.byref(nb), C.byref(ms)))
         return n.value, nb.value, ms.value
+
+    def copy_reads(self, src):
+        """mtsv_batch_copy_reads: this workspace's resident batch := a copy of src's (codes, offsets, read map), device to
+        device; returns the device ms of the copies"""
+        ms = C.c_float()
+        _check(lib().mtsv_batch_copy_reads(self.h, src.h, C.byref(ms)))
+        return ms.value
+
+    def merge_runs(self, srcs):
+        """mtsv_batch_merge_runs: the last runs of srcs (the same reads in each) merged per read into this workspace, in
+        source order; download(), stats(), match_flags() and taxa_report() then speak of the merge.  Returns the device
+        ms of the merge kernels"""
+        srcs = list(srcs)
+        arr = (C.c_void_p * max(len(srcs), 1))(*[s.h for s in srcs])
+        ms = C.c_float()
+        _check(lib().mtsv_batch_merge_runs(self.h, arr, len(srcs), C.byref(ms)))
+        return ms.value
 
     def read_map(self):
         """the caller's read number of every resident read (uint64 array; the identity after upload)"""

@@ -194,6 +194,10 @@ Batch::~Batch() {
     (void)hipFree(d_compact);
     for (auto& e : compact_ev)
         if (e) (void)hipEventDestroy(e);
+    for (void* p : {(void*)merge.d_nout, (void*)merge.d_off, (void*)merge.d_tiles, (void*)merge.d_lo, (void*)merge.d_base, (void*)merge.d_parts})
+        (void)hipFree(p);
+    for (auto& e : merge.ev)
+        if (e) (void)hipEventDestroy(e);
     if (h_hits_stage) pinned_hits_release(h_hits_stage);
     if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
     if (copy_stream) {
@@ -358,25 +362,27 @@ void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
         l->sw_fused = sw_fused;
         l->reset_lane();
     }
-    if (match.mode != MTSV_MATCH_OFF) {
-        // this run's flags: all zero before any lane's first pass (the lanes' streams do not wait for this one by themselves)
-        const uint64_t need = (n_reads + 63) / 64;
-        if (need > match.cap_words || !match.d_words) {
-            (void)hipFree(match.d_words);
-            match.d_words = nullptr;
-            match.cap_words = 0;
-            uint64_t b = 0;
-            dev_alloc(&match.d_words, need + need / 16 + 1, &b);
-            match.cap_words = need + need / 16;
-        }
-        match.n_reads = n_reads;
-        match.call_base = read_base;
-        match.ms = 0;
-        match.launches = 0;
-        // (the counter sits behind the last word the allocation holds, wherever this run's flags end)
-        HIP_CHECK(hipMemsetAsync(match.d_words, 0, (match.cap_words + 1) * sizeof(uint64_t), stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
+    if (match.mode != MTSV_MATCH_OFF) match_begin(n_reads, read_base);
+}
+
+// this run's flags: all zero before any lane's first pass (the lanes' streams do not wait for this one by themselves)
+void Batch::match_begin(uint64_t n, uint64_t read_base) {
+    const uint64_t need = (n + 63) / 64;
+    if (need > match.cap_words || !match.d_words) {
+        (void)hipFree(match.d_words);
+        match.d_words = nullptr;
+        match.cap_words = 0;
+        uint64_t b = 0;
+        dev_alloc(&match.d_words, need + need / 16 + 1, &b);
+        match.cap_words = need + need / 16;
     }
+    match.n_reads = n;
+    match.call_base = read_base;
+    match.ms = 0;
+    match.launches = 0;
+    // (the counter sits behind the last word the allocation holds, wherever this run's flags end)
+    HIP_CHECK(hipMemsetAsync(match.d_words, 0, (match.cap_words + 1) * sizeof(uint64_t), stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
 }
 
 void Batch::end_run() {
@@ -531,6 +537,7 @@ void Batch::take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_k
     if (src.match.mode == MTSV_MATCH_OFF) throw std::runtime_error("arg: the match flags of the source workspace are not switched on (mtsv_batch_set_match_flags)");
     if (src.last_run == kRunHostSegments)
         throw std::runtime_error("arg: the source's host batch took turns through the input segments: its first reads are no longer in HBM");
+    if (src.last_run == kRunMerged) throw std::runtime_error("arg: the source workspace holds a merge of other workspaces' runs (mtsv_batch_merge_runs): its flags describe reads it does not hold");
     if (src.last_run == kRunNone) throw std::runtime_error("arg: the source workspace has no completed run whose reads are still in HBM");
     // (flags switched on after the last run: they describe no run yet)
     if (src.match.n_reads != src.n_reads) throw std::runtime_error("arg: the source workspace has no completed run since its match flags were switched on");
@@ -596,6 +603,272 @@ void Batch::take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_k
         fprintf(stderr, "[compact] %llu of %llu reads kept (%s), %llu bases; scan %.3f ms, copy %.3f ms; %llu bytes to the host, 0 to the device\n",
                 (unsigned long long)m, (unsigned long long)n, keep == MTSV_KEEP_MATCHED ? "matched" : "unmatched", (unsigned long long)nb, ms_scan, ms_copy,
                 (unsigned long long)(sizeof h_result + (m + 1) * 4));
+}
+
+// ---------------------------------------------------------------------------------------------
+// The resident batch of another workspace of the device, copied: what several chunks of a database need of the same reads
+// (one upload, or one take_reads behind a filter, and a copy per further chunk).  Plain device-to-device copies; the host
+// copies its offset table.
+// ---------------------------------------------------------------------------------------------
+void Batch::copy_reads(Batch& src, float* device_ms) {
+    if (parent || src.parent) throw std::runtime_error("internal: copy_reads on a lane");
+    if (&src == this) throw std::runtime_error("arg: copy_reads from a workspace into itself");
+    if (src.di->device != di->device) throw std::runtime_error("arg: copy_reads between workspaces of different devices");
+    const bool host_batch = !src.resident && src.last_run == kRunHostOneSegment;
+    if (!src.resident && !host_batch)
+        throw std::runtime_error("arg: the source workspace holds no resident batch (mtsv_batch_upload, mtsv_batch_take_reads, mtsv_batch_copy_reads, or a host batch of one input segment)");
+    const uint64_t n = src.n_reads;
+    const uint32_t* ho = host_batch ? src.h_off_all : src.h_read_off.data();
+    const uint64_t nb = n ? ho[n] : 0;
+    if (n > max_reads || nb > max_bases)
+        throw std::runtime_error("arg: the source holds " + std::to_string(n) + " reads of " + std::to_string(nb) + " bases, the destination workspace was created for " +
+                                 std::to_string(max_reads) + " reads of " + std::to_string(max_bases) + " bases");
+    const bool codes = host_batch || src.codes_resident;
+    const bool with_map = !host_batch && src.mapped;
+    const uint8_t* s_bytes = host_batch ? src.arena[0].d_bases : codes ? src.d_codes : src.d_bases;
+    const uint32_t* s_off = host_batch ? src.arena[0].d_off : src.d_read_off;
+    HIP_CHECK(hipSetDevice(di->device));
+    if (with_map && !d_read_map) {
+        uint64_t b = 0;
+        dev_alloc(&d_read_map, max_reads, &b);
+    }
+    if (!compact_ev[0])
+        for (auto& e : compact_ev) HIP_CHECK(hipEventCreate(&e));
+    // from here on the destination's resident batch is being replaced
+    resident = false;
+    last_run = kRunNone;
+    HIP_CHECK(hipEventRecord(compact_ev[0], stream));
+    if (nb) HIP_CHECK(hipMemcpyDtoDAsync(codes ? d_codes : d_bases, const_cast<uint8_t*>(s_bytes), nb, stream));
+    if (n) HIP_CHECK(hipMemcpyDtoDAsync(d_read_off, const_cast<uint32_t*>(s_off), (n + 1) * 4, stream));
+    else HIP_CHECK(hipMemsetAsync(d_read_off, 0, 4, stream));
+    if (with_map && n) HIP_CHECK(hipMemcpyDtoDAsync(d_read_map, src.d_read_map, n * 4, stream));
+    HIP_CHECK(hipEventRecord(compact_ev[1], stream));
+    if (n) h_read_off.assign(ho, ho + n + 1);
+    else h_read_off.assign(1, 0u);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, compact_ev[0], compact_ev[1]));
+    n_reads = n;
+    max_len = src.max_len;
+    n_hits_total = 0;
+    total_hits = 0;
+    segments.clear();
+    resident = true;
+    codes_resident = codes;
+    mapped = with_map;
+    if (device_ms) *device_ms = ms;
+    if (getenv("MTSV_TRACE"))
+        fprintf(stderr, "[copy_reads] %llu reads, %llu bases (%s%s), %.3f ms; 0 bytes to the host, 0 to the device\n", (unsigned long long)n, (unsigned long long)nb,
+                codes ? "codes" : "bases as uploaded", with_map ? ", mapped" : "", ms);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Merging the runs of several workspaces over the same reads (the chunks of one database): k_merge.hip puts the hits
+// together per read in this workspace's result array, laid out as one pass, so that the report and the flags take the
+// merged reads with the kernels a pass uses and download() returns the list.  Everything the merge needs to know of the
+// sources is on the host (counts, segments, offsets); the host reads back the scan's total and the copy's count of hits without a place, 16 bytes.
+// ---------------------------------------------------------------------------------------------
+void Batch::report_extend(Batch* const* srcs, int n_srcs) {
+    // (checked on every merge, from the sources' indexes as they are now: nothing is remembered about an index handle)
+    std::vector<uint32_t> u = report.h_taxa;
+    for (int k = 0; k < n_srcs; k++) {
+        if (srcs[k]->ix == ix) continue;  // (the list began as this index's)
+        std::vector<uint32_t> t;
+        for (const Bin& b : srcs[k]->ix->host.bins) t.push_back(b.tax_id);
+        std::sort(t.begin(), t.end());
+        t.erase(std::unique(t.begin(), t.end()), t.end());
+        u.insert(u.end(), t.begin(), t.end());
+    }
+    std::sort(u.begin(), u.end());
+    u.erase(std::unique(u.begin(), u.end()), u.end());
+    if (u.size() >= (1ull << 30)) throw std::runtime_error("limit: taxa report of 2^30 TaxIDs or more");
+    if (u.size() == report.h_taxa.size()) return;  // (a superset of the same size: nothing new)
+    // new TaxIDs: the list and the counters so far, rebuilt (host work; a database's chunks bring theirs once)
+    const uint64_t n_old = 4ull * report.n_taxa + 2, n_new = 4ull * u.size() + 2;
+    std::vector<uint64_t> c_old(n_old), c_new(n_new, 0);
+    HIP_CHECK(hipMemcpyAsync(c_old.data(), report.d_counts, n_old * 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (uint32_t k = 0; k < report.n_taxa; k++) {
+        const uint64_t at = (uint64_t)(std::lower_bound(u.begin(), u.end(), report.h_taxa[k]) - u.begin());
+        for (int q = 0; q < 4; q++) c_new[4 * at + q] = c_old[4ull * k + q];
+    }
+    c_new[n_new - 2] = c_old[n_old - 2];
+    c_new[n_new - 1] = c_old[n_old - 1];
+    uint32_t* nt = nullptr;
+    uint64_t* nc = nullptr;
+    uint64_t b = 0;
+    dev_alloc(&nt, u.size(), &b);
+    dev_alloc(&nc, n_new, &b);
+    HIP_CHECK(hipMemcpyAsync(nt, u.data(), u.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(nc, c_new.data(), n_new * 8, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    (void)hipFree(report.d_taxa);
+    (void)hipFree(report.d_counts);
+    report.d_taxa = nt;
+    report.d_counts = nc;
+    report.h_taxa.swap(u);
+    report.n_taxa = (uint32_t)report.h_taxa.size();
+    uint32_t dense_max = kReportDenseTaxa;
+    if (const char* e = getenv("MTSV_REPORT_DENSE_MAX")) dense_max = (uint32_t)std::min<uint64_t>(strtoull(e, nullptr, 10), kReportDenseTaxa);  // (tests)
+    report.dense = report.n_taxa <= dense_max;
+    if (report.trace)
+        fprintf(stderr, "[report] list rebuilt for a merge: %u taxa, %s tier\n", report.n_taxa, report.dense ? "dense" : "hashed");
+}
+
+void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
+    if (parent) throw std::runtime_error("internal: merge_runs on a lane");
+    if (n_srcs < 1 || n_srcs > 64) throw std::runtime_error("arg: merge_runs takes 1 to 64 sources");
+    if (match.mode == MTSV_MATCH_ONLY) throw std::runtime_error("arg: the destination workspace is in MTSV_MATCH_ONLY, which keeps no hits");
+    for (int k = 0; k < n_srcs; k++) {
+        const Batch* s = srcs[k];
+        if (!s) throw std::runtime_error("arg: null source workspace");
+        if (s->parent) throw std::runtime_error("internal: merge_runs from a lane");
+        if (s == this) throw std::runtime_error("arg: the destination workspace is among the sources");
+        if (s->di->device != di->device) throw std::runtime_error("arg: merge_runs between workspaces of different devices");
+        if (s->match.mode == MTSV_MATCH_ONLY) throw std::runtime_error("arg: a source workspace is in MTSV_MATCH_ONLY: its run gathered no hits");
+        if (s->last_run == kRunHostOneSegment || s->last_run == kRunHostSegments)
+            throw std::runtime_error("arg: a source's last run was a host batch (merge_runs takes runs on a resident batch: mtsv_batch_upload / _take_reads / _copy_reads + mtsv_batch_run)");
+        if (s->last_run != kRunResident) throw std::runtime_error("arg: a source workspace has no completed run on a resident batch whose hits are still in HBM");
+    }
+    const Batch& s0 = *srcs[0];
+    const uint64_t n = s0.n_reads;
+    uint64_t total = 0;
+    std::vector<MergePart> parts;
+    uint64_t max_part_reads = 0, max_part_hits = 0;
+    for (int k = 0; k < n_srcs; k++) {
+        const Batch& s = *srcs[k];
+        if (s.n_reads != n) throw std::runtime_error("arg: the sources hold different numbers of reads");
+        if (memcmp(s.h_read_off.data(), s0.h_read_off.data(), (n + 1) * sizeof(uint32_t)) != 0)
+            throw std::runtime_error("arg: the sources' reads have different offsets: not the same batch");
+        if (s.mapped != s0.mapped) throw std::runtime_error("arg: some sources carry a read map and some do not");
+        total += s.total_hits;
+        uint64_t next = 0;
+        for (const Segment& sg : s.segments) {
+            if (sg.first_read != next) throw std::runtime_error("internal: a source's segments do not follow each other in read order");
+            next += sg.n_reads;
+            if (sg.count >= (1ull << 32)) throw std::runtime_error("limit: 2^32 hits or more in one stretch of a source");
+            if (!sg.n_reads) continue;
+            parts.push_back(MergePart{sg.lane->d_hits + sg.offset, (uint32_t)sg.count, (uint32_t)sg.first_read, (uint32_t)sg.n_reads, (uint32_t)k, 0});
+            max_part_reads = std::max(max_part_reads, sg.n_reads);
+            max_part_hits = std::max(max_part_hits, sg.count);
+        }
+        if (next != n) throw std::runtime_error("internal: a source's segments do not cover its reads");
+    }
+    if (total >= (1ull << 32)) throw std::runtime_error("limit: the merge holds " + std::to_string(total) + " hits, 2^32 or more");
+    if (parts.size() > 65535) throw std::runtime_error("limit: more than 65535 stretches of hits in the sources of one merge");
+    const uint32_t* map = s0.mapped ? s0.d_read_map : nullptr;
+    HIP_CHECK(hipSetDevice(di->device));
+    // ---- room (created by the first merge; whatever fails here leaves the last result where it was) ----
+    MergeState& m = merge;
+    if (!m.ev[0])
+        for (auto& e : m.ev) HIP_CHECK(hipEventCreate(&e));
+    uint64_t dummy = 0;
+    if (n > m.cap_reads || !m.d_nout) {
+        for (void* p : {(void*)m.d_nout, (void*)m.d_off, (void*)m.d_tiles}) (void)hipFree(p);
+        m.d_nout = m.d_off = nullptr;
+        m.d_tiles = nullptr;
+        m.cap_reads = 0;
+        const uint64_t cap = std::min<uint64_t>(n + n / 16, 0x7fffffffull);  // (a workspace's limit)
+        dev_alloc(&m.d_nout, 2 * cap + 1, &dummy);
+        dev_alloc(&m.d_off, 2 * cap + 1, &dummy);
+        m.cap_tiles = (uint64_t)scan_tiles((uint32_t)(2 * cap)) + 1;
+        dev_alloc(&m.d_tiles, m.cap_tiles + 2, &dummy);
+        m.cap_reads = cap;
+    }
+    if ((uint64_t)n_srcs * n > m.cap_sn || !m.d_lo) {
+        (void)hipFree(m.d_lo);
+        (void)hipFree(m.d_base);
+        m.d_lo = m.d_base = nullptr;
+        m.cap_sn = 0;
+        const uint64_t cap = (uint64_t)n_srcs * (n + n / 16);
+        dev_alloc(&m.d_lo, cap, &dummy);
+        dev_alloc(&m.d_base, cap, &dummy);
+        m.cap_sn = cap;
+    }
+    if (parts.size() > m.cap_parts || !m.d_parts) {
+        (void)hipFree(m.d_parts);
+        m.d_parts = nullptr;
+        m.cap_parts = 0;
+        const uint64_t cap = std::max<uint64_t>(parts.size() * 2, 64);
+        dev_alloc(&m.d_parts, cap, &dummy);
+        m.cap_parts = cap;
+    }
+    // (before the result array grows, so that it cannot fail once the result is being replaced; if that allocation then
+    //  fails, the list has grown already, with the counts so far kept and the new rows 0: the header says so)
+    if (report.on) report_extend(srcs, n_srcs);
+    DevHit* grown = nullptr;  // (the last result stays in the old array until nothing can refuse the merge any more)
+    if (total > hits_cap) dev_alloc(&grown, total + total / 16, &dummy);
+    // ---- from here on the destination's result is being replaced ----
+    if (grown) {
+        (void)hipFree(d_hits);
+        d_hits = grown;
+        hits_cap = total + total / 16;
+    }
+    segments.clear();
+    total_hits = 0;
+    n_hits_total = 0;
+    staged_valid = false;
+    last_run = kRunNone;
+    memset(&stats, 0, sizeof stats);
+    if (match.mode != MTSV_MATCH_OFF) match_begin(n, 0);
+    uint64_t h_total[2] = {0, 0};  // the scan's total, the hits the copy could not place
+    float ms = 0, ms_report = 0, ms_match = 0;
+    if (n) {
+        HIP_CHECK(hipMemcpyAsync(m.d_parts, parts.data(), parts.size() * sizeof(MergePart), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemsetAsync(m.d_tiles + m.cap_tiles, 0, 2 * sizeof(uint64_t), stream));
+        HIP_CHECK(hipEventRecord(m.ev[0], stream));
+        launch_merge_bounds(stream, m.d_parts, (uint32_t)parts.size(), (uint32_t)max_part_reads, (uint32_t)n, map, m.d_lo, m.d_base);
+        launch_merge_sum(stream, (uint32_t)n, (uint32_t)n_srcs, m.d_lo, m.d_base, m.d_nout);
+        launch_scan(stream, m.d_nout, (uint32_t)(2 * n), m.d_tiles, m.d_tiles + m.cap_tiles, m.d_off);
+        launch_merge_copy(stream, m.d_parts, (uint32_t)parts.size(), (uint32_t)max_part_hits, (uint32_t)n, map, m.d_base, m.d_off, d_hits, (uint32_t)total, m.d_tiles + m.cap_tiles + 1);
+        HIP_CHECK(hipEventRecord(m.ev[1], stream));
+        HIP_CHECK(hipMemcpyAsync(h_total, m.d_tiles + m.cap_tiles, sizeof h_total, hipMemcpyDeviceToHost, stream));
+        if (report.on) {
+            if (!report_ev[0])
+                for (auto& e : report_ev) HIP_CHECK(hipEventCreate(&e));
+            HIP_CHECK(hipEventRecord(report_ev[0], stream));
+            launch_report(stream, (uint32_t)n, m.d_nout, m.d_off, d_hits, report.d_taxa, report.n_taxa, report.dense, report.hash_slots, report.d_counts,
+                          report.d_counts + 4ull * report.n_taxa, report.trace ? report.d_counts + 4ull * report.n_taxa + 1 : nullptr);
+            HIP_CHECK(hipEventRecord(report_ev[1], stream));
+        }
+        if (match.mode != MTSV_MATCH_OFF) {
+            if (!match_ev[0])
+                for (auto& e : match_ev) HIP_CHECK(hipEventCreate(&e));
+            HIP_CHECK(hipEventRecord(match_ev[0], stream));
+            launch_match(stream, (uint32_t)n, m.d_nout, 0, match.d_words, match.d_words + match.cap_words);
+            HIP_CHECK(hipEventRecord(match_ev[1], stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
+        HIP_CHECK(hipGetLastError());
+        if (h_total[0] != total)
+            throw std::runtime_error("internal: the merge counted " + std::to_string(h_total[0]) + " hits, the sources hold " + std::to_string(total));
+        if (h_total[1])
+            throw std::runtime_error("internal: " + std::to_string(h_total[1]) + " hits of the sources have no place in the merge: a source's hits are not ordered by read");
+        HIP_CHECK(hipEventElapsedTime(&ms, m.ev[0], m.ev[1]));
+        if (report.on) {
+            HIP_CHECK(hipEventElapsedTime(&ms_report, report_ev[0], report_ev[1]));
+            std::lock_guard<std::mutex> lk(report.mu);
+            report.ms += ms_report;
+            report.launches++;
+        }
+        if (match.mode != MTSV_MATCH_OFF) {
+            HIP_CHECK(hipEventElapsedTime(&ms_match, match_ev[0], match_ev[1]));
+            std::lock_guard<std::mutex> lk(match.mu);
+            match.ms += ms_match;
+            match.launches++;
+        }
+    }
+    n_hits_total = total;
+    total_hits = total;
+    segments.push_back(Segment{this, 0, total, 0, n});
+    stats.n_reads = n;
+    stats.n_hits = total;
+    last_run = kRunMerged;
+    if (device_ms) *device_ms = ms;
+    if (getenv("MTSV_TRACE"))
+        fprintf(stderr, "[merge] %d sources in %llu stretches, %llu reads, %llu hits: merge kernels %.3f ms, report %.3f ms, flags %.3f ms; %llu bytes to the host, %llu to the device\n",
+                n_srcs, (unsigned long long)parts.size(), (unsigned long long)n, (unsigned long long)total, ms, ms_report, ms_match, (unsigned long long)16,
+                (unsigned long long)(parts.size() * sizeof(MergePart)));
 }
 
 void Batch::read_map(std::vector<uint64_t>& map) {
@@ -673,7 +946,7 @@ void Batch::run_range(const mtsv_params& p, const uint8_t* raw, uint8_t* sb, con
             // base normalisation (binner.rs:88-100) of this chunk's bytes: raw -> codes, on the lane's stream
             if (raw) launch_normalise(lane->stream, raw, sb, h_off[a], h_off[b]);
             lane->run_slice(p, sb, so + a, h_off ? h_off + a : nullptr, b - a, range_max_len, read_base + a);
-            segs[c] = Segment{lane, before, lane->n_hits_total - before};
+            segs[c] = Segment{lane, before, lane->n_hits_total - before, a, b - a};
         }
     };
     if (k == 1) {

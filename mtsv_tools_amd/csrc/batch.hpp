@@ -50,6 +50,7 @@ struct Batch {
     struct Segment {
         Batch* lane;
         uint64_t offset, count;
+        uint64_t first_read = 0, n_reads = 0;  // (resident runs) the range of the batch's reads whose hits these are
     };
     std::vector<Segment> segments;  // where the hits of the last run sit, in read order
     uint64_t total_hits = 0;
@@ -206,7 +207,7 @@ struct Batch {
     // Chaining (k_compact.hip): the reads of src's last run whose match flag is clear (keep = MTSV_KEEP_UNMATCHED) or set become
     // this workspace's resident batch, as codes, with a map to the caller's read numbers.  All of it belongs to the owner
     // and is created by the first take_reads.
-    enum LastRun { kRunNone = 0, kRunResident, kRunHostOneSegment, kRunHostSegments };
+    enum LastRun { kRunNone = 0, kRunResident, kRunHostOneSegment, kRunHostSegments, kRunMerged };
     int last_run = kRunNone;       // what the last completed run left in HBM (a source of take_reads needs its reads)
     bool resident = false;         // upload() or take_reads() filled the resident batch, no host batch has run since
     bool codes_resident = false;   // ... take_reads did: d_codes holds it (d_bases does not), run() must not normalise
@@ -216,6 +217,23 @@ struct Batch {
     uint64_t compact_cap = 0;         // ... entries each
     hipEvent_t compact_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the scan and around the copy
     void take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_kept, float* device_ms);
+    // this workspace's resident batch := a copy of src's (codes or bases, offsets, longest read, read map), HBM to HBM
+    void copy_reads(Batch& src, float* device_ms);
+    // Merging (k_merge.hip): the last runs of srcs[0 .. n_srcs), which hold the same reads, merged per read into this
+    // workspace's result array, laid out as one pass; the report and the flags, where on, take the merged reads.  All of
+    // it belongs to the owner and is created by the first merge_runs.
+    struct MergeState {
+        uint32_t *d_nout = nullptr, *d_off = nullptr;  // 2 n + 1 entries each
+        uint64_t* d_tiles = nullptr;                   // the scan's tile sums, then its total, then the copy's dropped hits
+        uint64_t cap_reads = 0, cap_tiles = 0;
+        uint32_t *d_lo = nullptr, *d_base = nullptr;   // per (source, read)
+        uint64_t cap_sn = 0;
+        MergePart* d_parts = nullptr;
+        uint64_t cap_parts = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+    };
+    MergeState merge;
+    void merge_runs(Batch* const* srcs, int n_srcs, float* device_ms);
     void read_map(std::vector<uint64_t>& map);
     void download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& read_off);
     // rows: every TaxID with a non-zero counter, ascending
@@ -223,6 +241,8 @@ struct Batch {
 
    private:
     void begin_run(const mtsv_params& p, uint64_t read_base = 0);
+    void match_begin(uint64_t n, uint64_t read_base);  // flags on: room for n reads' flags, all zero
+    void report_extend(Batch* const* srcs, int n_srcs);  // the report's TaxID list := its union with the sources' indexes
     void reset_lane();
     void stage_reserve(uint64_t n_hits_needed);
     void host_room(uint64_t n, uint64_t total_bases, bool trace);

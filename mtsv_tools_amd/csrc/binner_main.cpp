@@ -22,6 +22,9 @@
 //                     robin): every chunk sees every batch and the hits are merged per read, so the one results
 //                     file equals what mtsv-collapse makes of the per-chunk files (README.md:189,
 //                     collapse.rs:597-625: smallest edit per read and TaxId)
+//   --merge-on-gpu    with --index a,b,.. and ONE device: every chunk resident there, and a call's hits merged per read in
+//                     HBM (mtsv_batch_copy_reads, mtsv_batch_merge_runs) -- the reads go up once per call, and --report,
+//                     --matched / --unmatched work on the merged hits as they do for one index
 #include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -119,7 +122,7 @@ struct Args {
     std::string fasta, fastq, index, results, report, matched, unmatched, filter_index, output_format = "default";
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
-    bool verbose = false, force = false, parse_only = false;
+    bool verbose = false, force = false, parse_only = false, merge_gpu = false;
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
 };
@@ -223,6 +226,7 @@ int main(int argc, char** argv) {
         else if (key == "--unmatched") a.unmatched = val();
         else if (key == "--filter-index") a.filter_index = val();
         else if (key == "--parse-only") a.parse_only = true;
+        else if (key == "--merge-on-gpu") a.merge_gpu = true;
         else if (key == "-h" || key == "--help") {
             printf("mtsv-binner (MI355X) -- flags as the reference: --fasta|--fastq, -i/--index, -m/--results, -t/--threads,\n"
                    "-e/--edit-rate, --seed-size, --seed-interval, --min-seed, --max-hits, --tune-max-hits, --max-assignments,\n"
@@ -241,7 +245,11 @@ int main(int argc, char** argv) {
                    "and the rest are binned against --index: every filter index is made resident on each device beside the database --\n"
                    "they share its HBM, and the k-mer table of an index may come out narrower for it -- and the surviving reads go from\n"
                    "stage to stage on the GPU, with no intermediate file.  Not with --matched / --unmatched, --parse-only or a list of\n"
-                   "index chunks)\n");
+                   "index chunks),\n"
+                   "--merge-on-gpu (with --index a,b,.. of two or more chunks and one --devices entry: every chunk is made resident on\n"
+                   "that device, a call's reads go up once and are copied from chunk to chunk on the GPU, and the chunks' hits are merged\n"
+                   "per read on the GPU; the results file is the same, and --report and --matched / --unmatched are accepted: they are\n"
+                   "counted from the merged hits.  Each worker holds a workspace per chunk and one more.  Not with --filter-index)\n");
             return 0;
         } else if (key == "-V" || key == "--version") {
             printf("mtsv 2.1.0 (%s)\n", mtsv_version());
@@ -253,16 +261,36 @@ int main(int argc, char** argv) {
         usage_error(a.fasta.empty() ? "The following required arguments were not provided: --fasta <FASTA> | --fastq <FASTQ>"
                                     : "The argument '--fasta <FASTA>' cannot be used with '--fastq <FASTQ>'");
     if (a.index.empty() && !a.parse_only) usage_error("The following required arguments were not provided: --index <INDEX>");
-    if (!a.report.empty() && a.index.find(',') != std::string::npos) {
+    if (a.merge_gpu) {
+        // (decided here, before any file or device is touched)
+        size_t n_chunks = 0;
+        for (size_t at = 0; at <= a.index.size();) {
+            size_t c = a.index.find(',', at);
+            if (c == std::string::npos) c = a.index.size();
+            n_chunks += c > at;
+            at = c + 1;
+        }
+        if (n_chunks < 2) {
+            fprintf(stderr, "error: '--merge-on-gpu' needs a list of two or more index chunks ('--index a,b,..')\n");
+            return 1;
+        }
+        if (a.devices.size() != 1) {
+            fprintf(stderr, "error: '--merge-on-gpu' needs exactly one '--devices' entry: every chunk is made resident on that device\n");
+            return 1;
+        }
+        if (a.parse_only) usage_error("The argument '--parse-only' cannot be used with '--merge-on-gpu'");
+    }
+    const bool merged = a.merge_gpu;
+    if (!merged && !a.report.empty() && a.index.find(',') != std::string::npos) {
         // a read's taxa come from several chunks there and per-chunk counters do not add up
-        fprintf(stderr, "error: '--report <TSV>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-collapse --report on the results file instead\n");
+        fprintf(stderr, "error: '--report <TSV>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-collapse --report on the results file instead, or give '--merge-on-gpu' (one device)\n");
         return 1;
     }
     const bool partition = !a.matched.empty() || !a.unmatched.empty();
     if (partition && a.parse_only) usage_error("The argument '--parse-only' cannot be used with '--matched <PATH>' / '--unmatched <PATH>'");
-    if (partition && a.index.find(',') != std::string::npos) {
+    if (!merged && partition && a.index.find(',') != std::string::npos) {
         // (the flags of the chunks would have to be OR-ed per read)
-        fprintf(stderr, "error: '--matched <PATH>' / '--unmatched <PATH>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-partition on the results file instead\n");
+        fprintf(stderr, "error: '--matched <PATH>' / '--unmatched <PATH>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-partition on the results file instead, or give '--merge-on-gpu' (one device)\n");
         return 1;
     }
     const bool filtered = !a.filter_index.empty();
@@ -273,7 +301,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "error: '--filter-index <INDEX>' cannot be used with a list of index chunks ('--index a,b,..'): filter first with '--unmatched <PATH>', then bin the chunks\n");
         return 1;
     }
-    if (partition && !a.report.empty() && a.results.empty())
+    if (!merged && partition && !a.report.empty() && a.results.empty())
         usage_error("The argument '--report <TSV>' requires '-m/--results <RESULTS>': the report is counted from gathered hits, and '--matched' / '--unmatched' without a results file gather none");
     if (a.output_format != "default" && a.output_format != "long")
         usage_error("'" + a.output_format + "' isn't a valid value for '--output-format <OUTPUT_FORMAT>'");
@@ -551,7 +579,8 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
-    const int match_mode = !partition ? MTSV_MATCH_OFF : have_results ? MTSV_MATCH_WITH_HITS : MTSV_MATCH_ONLY;
+    // (--merge-on-gpu: the flags come from the merged hits, so the hits are gathered with or without a results file)
+    const int match_mode = !partition ? MTSV_MATCH_OFF : (have_results || merged) ? MTSV_MATCH_WITH_HITS : MTSV_MATCH_ONLY;
     logmsg("INFO", "Deserializing candidate filter ...");
     std::vector<std::string> index_paths;
     for (size_t at = 0; at <= a.index.size();) {
@@ -592,7 +621,7 @@ int main(int argc, char** argv) {
     }
     const bool small_input = input_bytes < (256ull << 20) && !getenv("MTSV_CLI_WORKERS");
     if (small_input) workers_per_device = 1;
-    const size_t n_workers = chunked ? 2 : a.devices.size() * workers_per_device;
+    const size_t n_workers = chunked && !merged ? 2 : a.devices.size() * workers_per_device;
     // the length of the input's first read (plain text; 150 otherwise): the workspaces are warmed with reads like it
     uint32_t warm_len = 150;
     if (FILE* hf = fopen(input.c_str(), "rb")) {
@@ -667,7 +696,13 @@ int main(int argc, char** argv) {
     setup_mark("index loaded and resident");
     // the workers' workspaces (one index): part of the device set-up, like making the index resident -- created, sized for
     // the calls to come and run once on reads sampled from the index (mtsv_batch_reserve_host)
-    std::vector<mtsv_batch*> ws_ready(chunked ? 0 : n_workers, nullptr);
+    std::vector<mtsv_batch*> ws_ready(chunked && !merged ? 0 : n_workers, nullptr);
+    // --merge-on-gpu: a workspace per worker and chunk, which hold a call's reads as a resident batch (the first by upload, the
+    // others by mtsv_batch_copy_reads); ws_ready[wk] is the worker's collector, which mtsv_batch_merge_runs fills and the
+    // report and the flags are read from.  A call is one block of reads.
+    std::vector<std::vector<mtsv_batch*>> cws(merged ? n_workers : 0, std::vector<mtsv_batch*>(index_paths.size(), nullptr));
+    const uint64_t merge_reads = a.batch_reads + a.batch_reads / 2;
+    const uint64_t merge_bases = std::min<uint64_t>(3ull << 30, std::max<uint64_t>(merge_reads * std::max<uint64_t>(512, 2 * (uint64_t)warm_len), 1 << 22));
     // --filter-index: a workspace per worker and filter stage.  The first takes the host batch; the later ones and the
     // database's receive their reads in HBM (mtsv_batch_take_reads) and hold them as a resident batch, so they are created
     // with room for the bases of a call: chain_bases (a call whose blocks hold more is cut into several).
@@ -686,8 +721,20 @@ int main(int argc, char** argv) {
                 return workers_per_device > 1 ? mtsv_batch_create_lanes(ix, dev, call_reads, ws_bases, 0, 1, out)
                                               : mtsv_batch_create(ix, dev, resident ? call_reads : mtsv_bin_batch_workspace_reads(call_reads), ws_bases, 0, out);
             };
-            int rc = create(idx[0], filtered, &ws_ready[wk]);
             const bool warm = !small_input && !getenv("MTSV_CLI_COLD");
+            if (merged) {
+                int rc = mtsv_batch_create_lanes(idx[0], dev, 1024, 1 << 16, 0, 1, &ws_ready[wk]);
+                for (size_t c = 0; c < idx.size() && rc == MTSV_OK; c++) {
+                    rc = mtsv_batch_create_lanes(idx[c], dev, merge_reads, merge_bases, 0, 1, &cws[wk][c]);
+                    if (rc == MTSV_OK && warm) rc = mtsv_batch_reserve_host(cws[wk][c], 4096, 4096 * (uint64_t)(warm_len + warm_len / 8), warm_len);
+                }
+                if (rc == MTSV_OK && !a.report.empty()) rc = mtsv_batch_set_taxa_report(ws_ready[wk], 1);
+                if (rc == MTSV_OK && partition) rc = mtsv_batch_set_match_flags(ws_ready[wk], match_mode);
+                ws_rc[wk] = rc;
+                if (rc != MTSV_OK) ws_msg[wk] = mtsv_last_error();  // (thread-local)
+                return;
+            }
+            int rc = create(idx[0], filtered, &ws_ready[wk]);
             // (only the workspace that takes the host batches needs their arenas; the others are warmed on a small batch)
             if (rc == MTSV_OK && warm)
                 rc = filtered ? mtsv_batch_reserve_host(ws_ready[wk], 4096, 4096 * (uint64_t)(warm_len + warm_len / 8), warm_len)
@@ -1078,7 +1125,7 @@ int main(int argc, char** argv) {
     });
 
     auto gpu_worker = [&](size_t wk) {
-        mtsv_batch* ws = chunked ? nullptr : ws_ready[wk];  // one index: this worker's own workspace on its device
+        mtsv_batch* ws = chunked && !merged ? nullptr : ws_ready[wk];  // one index: this worker's own workspace on its device (--merge-on-gpu: its collector)
         for (;;) {
             const double t_p = now();
             std::vector<std::unique_ptr<Work>> group;
@@ -1109,7 +1156,22 @@ int main(int argc, char** argv) {
             int rc;
             mtsv_hit* hits = nullptr;
             uint64_t n_hits = 0;
-            if (chunked) {
+            if (merged) {
+                auto& w = group[0];
+                if (w->rb->n() > merge_reads || w->rb->bases.size() > merge_bases) {
+                    logmsg("ERROR", "Error running query: a batch of reads holds more than " + std::to_string(merge_reads) + " reads or " + std::to_string(merge_bases) +
+                                        " bases, which the chunks' workspaces were sized for: give a smaller --batch-reads");
+                    set_code(2);
+                    continue;
+                }
+                // the reads go up once; the other chunks receive them in HBM; every chunk runs; the collector merges
+                auto& cw = cws[wk];
+                rc = mtsv_batch_upload(cw[0], w->rb->bases.data(), w->rb->off.data(), w->rb->n());
+                for (size_t c = 1; c < cw.size() && rc == MTSV_OK; c++) rc = mtsv_batch_copy_reads(cw[c], cw[0], nullptr);
+                for (size_t c = 0; c < cw.size() && rc == MTSV_OK; c++) rc = mtsv_batch_run(cw[c], &p);
+                if (rc == MTSV_OK) rc = mtsv_batch_merge_runs(ws, cw.data(), (int)cw.size(), nullptr);
+                if (rc == MTSV_OK) rc = mtsv_batch_download(ws, &hits, &n_hits);
+            } else if (chunked) {
                 auto& w = group[0];
                 rc = mtsv_bin_batch_chunks(idx.data(), chunk_dev.data(), (int)idx.size(), w->rb->bases.data(), w->rb->off.data(), w->rb->n(), &p,
                                            &hits, &n_hits);
@@ -1276,6 +1338,8 @@ int main(int argc, char** argv) {
     for (auto* ws : ws_ready) mtsv_batch_free(ws);  // (30 ms per workspace: after the queries' clock, like the index)
     for (auto& stage : fws)
         for (auto* ws : stage) mtsv_batch_free(ws);
+    for (auto& chunk_ws : cws)
+        for (auto* ws : chunk_ws) mtsv_batch_free(ws);
     setup_mark("workspaces freed");
     for (auto* ix : idx) mtsv_index_free(ix);
     for (auto* ix : fidx) mtsv_index_free(ix);

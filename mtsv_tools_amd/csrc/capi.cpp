@@ -359,6 +359,23 @@ int mtsv_batch_take_reads(mtsv_batch* dst, mtsv_batch* src, int keep, uint64_t* 
     GUARD(dst->impl.take_reads(src->impl, keep, n_kept, bases_kept, device_ms))
 }
 
+int mtsv_batch_copy_reads(mtsv_batch* dst, mtsv_batch* src, float* device_ms) {
+    if (!dst || !src) return fail_arg("null argument");
+    GUARD(dst->impl.copy_reads(src->impl, device_ms))
+}
+
+int mtsv_batch_merge_runs(mtsv_batch* dst, mtsv_batch* const* srcs, int n_srcs, float* device_ms) {
+    if (!dst || (n_srcs > 0 && !srcs)) return fail_arg("null argument");
+    GUARD({
+        std::vector<mtsv::Batch*> s;
+        for (int k = 0; k < n_srcs; k++) {
+            if (!srcs[k]) throw std::runtime_error("arg: null source workspace");
+            s.push_back(&srcs[k]->impl);
+        }
+        dst->impl.merge_runs(s.data(), n_srcs, device_ms);
+    })
+}
+
 int mtsv_batch_read_map(mtsv_batch* b, uint64_t** map, uint64_t* n_reads) {
     if (!b || !map || !n_reads) return fail_arg("null argument");
     GUARD({

@@ -1,7 +1,8 @@
 // kernels.hpp -- launch interface of the hot-path kernels.
 //
 // The mtsv-binner hot path as gfx950 kernels (k_seed.hip, k_coalesce.hip, k_verify.hip; k_report.hip for the taxa report, k_match.hip for
-// the per-read match flags, k_compact.hip for the hand-over of a run's unmatched or matched reads to another workspace).
+// the per-read match flags, k_compact.hip for the hand-over of a run's unmatched or matched reads to another workspace,
+// k_merge.hip for the per-read merge of several runs' hits).
 //
 // One batch of reads flows through staged kernels with worklists in HBM:
 //
@@ -219,5 +220,29 @@ void launch_compact_copy(hipStream_t s, uint32_t n_reads, const uint64_t* words,
                          uint32_t* dst_off, uint32_t* dst_map);
 // hits[i].read = map[hits[i].read] for the n_hits hits a pass of a compacted workspace has just gathered
 void launch_remap_reads(hipStream_t s, DevHit* hits, uint64_t n_hits, const uint32_t* map);
+// k_merge.hip: the hits of several runs over the same n_reads resident reads, merged per read in source order.  A PART is a
+// stretch of one source's hits: `count` hits ordered by `read`, all the hits that source has for resident reads
+// [first_read, first_read + n_reads); the parts of a source cover every read once.  map (null: the identity): resident read
+// -> the number its hits carry, ascending.  Without a map the key of resident read j is j itself: that rests on a resident
+// mtsv_batch_run numbering its hits from 0.  A resident run with a read base of its own would need the base in the part;
+// as it stands every hit of such a run would count as dropped, which merge_runs reports as an internal error.
+// Arrays per (source, read) are indexed [src * n_reads + read].
+//   bounds: lo = the read's first hit in its part, cnt = how many it has there
+//   sum:    nout[2j] = read j's merged count, nout[2j + 1] = 0; cnt_base: counts in, the copy's offsets out
+//   (launch_scan over the 2 * n_reads entries of nout: out_off)
+//   copy:   every hit of every part to its place among dst[0 .. n_dst); *n_dropped (zeroed by the caller) += the hits
+//           that have no read in their part or no place in dst -- none, unless a part is not ordered as stated
+// max_part_reads / max_part_hits: the largest n_reads / count of any part (the grids' x extent; n_parts is their y: < 65536)
+struct MergePart {
+    const DevHit* hits;
+    uint32_t count, first_read, n_reads, src;
+    uint64_t pad;
+};
+static_assert(sizeof(MergePart) == 32, "MergePart is uploaded as it is");
+void launch_merge_bounds(hipStream_t s, const MergePart* parts, uint32_t n_parts, uint32_t max_part_reads, uint32_t n_reads,
+                         const uint32_t* map, uint32_t* lo, uint32_t* cnt);
+void launch_merge_sum(hipStream_t s, uint32_t n_reads, uint32_t n_srcs, const uint32_t* lo, uint32_t* cnt_base, uint32_t* nout);
+void launch_merge_copy(hipStream_t s, const MergePart* parts, uint32_t n_parts, uint32_t max_part_hits, uint32_t n_reads,
+                       const uint32_t* map, const uint32_t* base, const uint32_t* out_off, DevHit* dst, uint32_t n_dst, uint64_t* n_dropped);
 
 }  // namespace mtsv
