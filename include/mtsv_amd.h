@@ -19,6 +19,9 @@
  *   mtsv_params            matching_tax_ids' scalar arguments             src/index.rs:258-269
  *                          (defaults: src/bin/mtsv-binner.rs:63-94)
  *   mtsv_format_results    write_assignments                              src/binner.rs:310-379
+ *   mtsv_batch_set_assignments, mtsv_batch_download_assignments, mtsv_format_assignments
+ *                          its reduction, smallest edit per TaxID ascending,     src/binner.rs:355-378
+ *                          on the device, and the default-format lines from that
  *   mtsv_index_build*, mtsv_index_write
  *                          MGIndex::new + io::write_to_file               src/index.rs:491-582, src/io.rs:125-133
  *   mtsv_batch_set_match_flags, mtsv_batch_match_flags
@@ -367,6 +370,47 @@ int mtsv_batch_read_map(mtsv_batch *b, uint64_t **map, uint64_t *n_reads);
  * and *n_reads + 1 offsets from 0; both malloc'd, mtsv_free.  MTSV_E_ARG when the workspace's last input was a host batch. */
 int mtsv_batch_download_reads(mtsv_batch *b, uint8_t **codes, uint64_t **read_off, uint64_t *n_reads);
 int mtsv_batch_download(mtsv_batch *b, mtsv_hit **hits, uint64_t *n_hits);
+
+/* ---- assignments: one (TaxID, smallest edit) per read and TaxID (write_assignments, src/binner.rs:355-378) ----------
+ * The default results line of mtsv-binner is READ_ID:TAXID=EDIT,...: the smallest edit per TaxID of the read, over both
+ * strands, ascending by TaxID; mtsv-collapse --mode taxid builds the same across result files (src/collapse.rs:269-297).
+ * With the assignments on, every committed pass reduces its gathered hits to that on the device (k_collapse.hip): one
+ * 16-byte record per read and distinct TaxID.  Records are ordered like the hits -- by `read`, the caller's numbering,
+ * ascending -- and inside a read by tax_id ascending as unsigned.  `read` is copied from the hit: on a workspace filled by
+ * mtsv_batch_take_reads it is the caller's number.  In a collector (mtsv_batch_merge_runs into a workspace with the
+ * assignments on) the reduction runs over the merged hits, all chunks together: what mtsv-collapse would write from the
+ * per-chunk result files.  Assignments describe ONE run -- the last mtsv_batch_run, _run_host, _run_host_parts or
+ * mtsv_batch_merge_runs into the workspace -- like the match flags and unlike the taxa report; a refused merge leaves
+ * them as they were.
+ *   MTSV_ASSIGN_OFF        the default: no allocation, no launch, nothing changes
+ *   MTSV_ASSIGN_WITH_HITS  the hits as always, plus the assignments
+ *   MTSV_ASSIGN_ONLY       the hits are gathered on the device (the collapse reads them, and so do the taxa report and
+ *                          the match flags) but never copied to the host: mtsv_batch_download returns zero hits; the
+ *                          stats keep their meaning, n_hits included
+ * Limits: the short format only (TAXID-GI-OFFSET=EDIT needs the hits); one run's worth; not together with
+ * MTSV_MATCH_ONLY, which gathers no hits -- whichever of the two is asked for second fails with MTSV_E_ARG; a bad mode is
+ * MTSV_E_ARG; mtsv_bin_batch, _multi and _chunks do not produce assignments.  The taxa report and MTSV_MATCH_WITH_HITS
+ * work beside every mode.  MTSV_COLLAPSE_LANE_MAX (1..16), MTSV_COLLAPSE_WAVE_MAX (..64) and MTSV_COLLAPSE_LDS_MAX (a power
+ * of two, 2..4096) move the kernel's tier edges (tests); they are read when the assignments are switched on. */
+typedef struct {
+    uint64_t read;
+    uint32_t tax_id;
+    uint32_t edit;
+} mtsv_assignment; /* 16 bytes */
+#define MTSV_ASSIGN_OFF 0
+#define MTSV_ASSIGN_WITH_HITS 1
+#define MTSV_ASSIGN_ONLY 2
+int mtsv_batch_set_assignments(mtsv_batch *b, int mode);
+/* The assignments of the last run.  *a is page-locked memory from the library's pool of result arrays, also when *n is 0;
+ * the caller returns it with mtsv_free (which hands pool arrays back to the pool and frees everything else).  On
+ * mtsv_batch_run_host* a finished range's records leave for that array on the result copy stream, in read order, while
+ * later ranges still compute, as its hits do; this call then only hands the array out.  After a resident run or a merge,
+ * and on a second call after the same run, the records are copied here from HBM stretch by stretch.  device_ms (may be
+ * NULL): device time of the run's collapse kernels.  No run since the assignments were switched on: *n is 0.
+ * MTSV_E_ARG when the mode is MTSV_ASSIGN_OFF.
+ * A host batch run in MTSV_ASSIGN_ONLY keeps none of its hits: mtsv_batch_download after leaving that mode, without a new
+ * run, is MTSV_E_ARG. */
+int mtsv_batch_download_assignments(mtsv_batch *b, mtsv_assignment **a, uint64_t *n, float *device_ms);
 void mtsv_batch_free(mtsv_batch *b);
 
 /* ---- result lines (host) ---------------------------------------------------------------- */
@@ -376,6 +420,12 @@ void mtsv_batch_free(mtsv_batch *b);
 int mtsv_format_results(const mtsv_hit *hits, uint64_t n_hits, const char *ids,
                         const uint64_t *id_off, uint64_t n_reads, int long_format, char **out,
                         uint64_t *out_len);
+/* The same lines from assignments (mtsv_batch_download_assignments): one per read that has any, READ_ID:TAXID=EDIT,...
+ * in the order given -- nothing is de-duplicated or sorted here.  Byte-identical to mtsv_format_results(long_format = 0)
+ * on the hits of the same run.  MTSV_E_ARG: reads not in ascending order, a read >= n_reads.  Host only, needs no device. */
+int mtsv_format_assignments(const mtsv_assignment *a, uint64_t n, const char *ids, const uint64_t *id_off,
+                            uint64_t n_reads, char **out, uint64_t *out_len);
+/* frees what the library malloc'd, and returns arrays of its page-locked pool (mtsv_batch_download_assignments) to it */
 void mtsv_free(void *p);
 
 /* ---- the transfer format of mtsv_batch_run_host*, exposed for tests (not part of the drop-in) ---- */

@@ -7,6 +7,10 @@ holds no algorithm and has no CPU fallback: every call that needs the GPU raises
 when the library or a device is missing.
 """
 from ._lib import (  # noqa: F401
+    ASSIGN_DTYPE,
+    ASSIGN_OFF,
+    ASSIGN_ONLY,
+    ASSIGN_WITH_HITS,
     HIT_DTYPE,
     KEEP_MATCHED,
     KEEP_UNMATCHED,
@@ -26,6 +30,7 @@ from ._lib import (  # noqa: F401
     bin_batch_slice_reads,
     default_params,
     device_count,
+    format_assignments,
     format_results,
     format_taxa_report,
     merge_taxa_reports,

@@ -20,6 +20,7 @@ class MtsvError(RuntimeError):
 
 E_ARG, E_IO, E_FORMAT, E_DEVICE, E_LIMIT, E_NOMEM = -1, -2, -3, -4, -5, -6
 MATCH_OFF, MATCH_WITH_HITS, MATCH_ONLY = 0, 1, 2  # MTSV_MATCH_*
+ASSIGN_OFF, ASSIGN_WITH_HITS, ASSIGN_ONLY = 0, 1, 2  # MTSV_ASSIGN_*
 KEEP_UNMATCHED, KEEP_MATCHED = 0, 1  # MTSV_KEEP_*
 
 
@@ -66,6 +67,9 @@ TAXON_STATS_DTYPE = np.dtype({"names": ["tax_id", "only_hit", "only_best", "tied
                               "formats": ["<u4", "<u8", "<u8", "<u8", "<u8"],
                               "offsets": [0, 8, 16, 24, 32], "itemsize": 40})
 
+# mtsv_assignment: 8 + 4 + 4 = 16 bytes
+ASSIGN_DTYPE = np.dtype({"names": ["read", "tax_id", "edit"], "formats": ["<u8", "<u4", "<u4"], "offsets": [0, 8, 12], "itemsize": 16})
+
 EXPORTS = [
     "mtsv_last_error", "mtsv_version", "mtsv_params_default", "mtsv_device_count",
     "mtsv_index_load", "mtsv_index_build", "mtsv_index_build_fasta", "mtsv_index_write",
@@ -80,6 +84,7 @@ EXPORTS = [
     "mtsv_batch_set_match_flags", "mtsv_batch_match_flags",
     "mtsv_batch_take_reads", "mtsv_batch_read_map", "mtsv_batch_download_reads",
     "mtsv_batch_copy_reads", "mtsv_batch_merge_runs",
+    "mtsv_batch_set_assignments", "mtsv_batch_download_assignments", "mtsv_format_assignments",
 ]
 
 _lib = None
@@ -151,6 +156,9 @@ def lib():
         L.mtsv_batch_merge_runs.argtypes = [vp, vp, i32, C.POINTER(C.c_float)]
         L.mtsv_batch_read_map.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_batch_download_reads.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_batch_set_assignments.argtypes = [vp, i32]
+        L.mtsv_batch_download_assignments.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_format_assignments.argtypes = [vp, u64, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -415,6 +423,24 @@ class Batch:
             raise MtsvError(E_DEVICE, "match flags set beyond the run's reads")
         return bits[:n.value], m.value
 
+    def set_assignments(self, mode):
+        """mtsv_batch_set_assignments: ASSIGN_OFF, ASSIGN_WITH_HITS (hits and assignments) or ASSIGN_ONLY (the hits stay
+        on the device: download() returns none)"""
+        _check(lib().mtsv_batch_set_assignments(self.h, int(mode)))
+
+    def download_assignments(self):
+        """(the last run's assignments as an ASSIGN_DTYPE array -- per read one record per distinct TaxID with the smallest
+        edit, ascending by TaxID --, device ms of the collapse kernels)"""
+        out, n, ms = C.c_void_p(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_batch_download_assignments(self.h, C.byref(out), C.byref(n), C.byref(ms)))
+        try:
+            if n.value == 0:
+                return np.zeros(0, dtype=ASSIGN_DTYPE), ms.value
+            raw = (C.c_ubyte * (n.value * ASSIGN_DTYPE.itemsize)).from_address(out.value)
+            return np.frombuffer(raw, dtype=ASSIGN_DTYPE).copy(), ms.value
+        finally:
+            lib().mtsv_free(out)
+
     def take_reads(self, src, keep=KEEP_UNMATCHED):
         """mtsv_batch_take_reads: this workspace's resident batch := the reads of src's last run whose match flag is clear
         (KEEP_MATCHED: set), handed over on the device; returns (n_kept, bases_kept, device ms of the kernels)"""
@@ -482,6 +508,20 @@ def format_results(hits, read_ids, long_format=False):
     out, n = C.c_void_p(), C.c_uint64()
     _check(lib().mtsv_format_results(hits.ctypes.data, len(hits), blob, off.ctypes.data,
                                      len(read_ids), int(long_format), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value).decode()
+    finally:
+        lib().mtsv_free(out)
+
+
+def format_assignments(a, read_ids):
+    """mtsv_format_assignments: the short-format result lines from assignments, as one str"""
+    a = np.ascontiguousarray(a, dtype=ASSIGN_DTYPE)
+    blob = b"".join(i.encode() + b"\0" for i in read_ids)
+    off = np.zeros(len(read_ids) + 1, dtype=np.uint64)
+    np.cumsum([len(i.encode()) + 1 for i in read_ids], out=off[1:])
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_assignments(a.ctypes.data, len(a), blob, off.ctypes.data, len(read_ids), C.byref(out), C.byref(n)))
     try:
         return C.string_at(out.value, n.value).decode()
     finally:

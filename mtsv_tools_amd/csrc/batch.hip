@@ -198,7 +198,14 @@ Batch::~Batch() {
         (void)hipFree(p);
     for (auto& e : merge.ev)
         if (e) (void)hipEventDestroy(e);
+    for (void* p : {(void*)d_assign, (void*)collapse.keys, (void*)collapse.flags, (void*)collapse.place, (void*)collapse.tiles, (void*)collapse.list,
+                    (void*)collapse.d_ctr})
+        (void)hipFree(p);
+    if (collapse.h_ctr) (void)hipHostFree(collapse.h_ctr);
+    for (auto& e : collapse.ev)
+        if (e) (void)hipEventDestroy(e);
     if (h_hits_stage) pinned_hits_release(h_hits_stage);
+    if (h_assign_stage) pinned_hits_release(h_assign_stage);
     if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
     if (copy_stream) {
         (void)hipStreamSynchronize(copy_stream);
@@ -308,6 +315,7 @@ void Batch::reset_lane() {
     sweep_ms_acc = diag_ms_acc = bound_ms_acc = edit_ms_acc = 0;
     sw_passed_acc = 0;
     n_hits_total = 0;
+    n_assign_total = 0;
     HIP_CHECK(hipMemsetAsync(d_counters, 0, kCounters * sizeof(uint64_t), stream));
     ctr22_zero = true;
     HIP_CHECK(hipEventRecord(ev[8], stream));
@@ -345,6 +353,9 @@ void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
     total_hits = 0;
     lanes_used = 1;
     staged_valid = false;
+    assign_staged_valid = false;
+    staged_assign = 0;
+    host_hits_dropped = false;
     last_run = kRunNone;  // until this one completes
     run_t0 = now_s();
     {
@@ -363,6 +374,7 @@ void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
         l->reset_lane();
     }
     if (match.mode != MTSV_MATCH_OFF) match_begin(n_reads, read_base);
+    if (assign.mode != MTSV_ASSIGN_OFF) collapse_begin();
 }
 
 // this run's flags: all zero before any lane's first pass (the lanes' streams do not wait for this one by themselves)
@@ -425,6 +437,7 @@ void Batch::end_run() {
     total_hits = 0;
     for (auto& sg : segments) total_hits += sg.count;
     stats.n_hits = total_hits;
+    if (assign.mode != MTSV_ASSIGN_OFF && assign.trace) collapse_trace("run");
 }
 
 // The report's device side: the sorted list of the index's distinct TaxIDs (indexes from the builders are in TaxID
@@ -492,6 +505,8 @@ void Batch::set_match_flags(int mode) {
     if (mode != MTSV_MATCH_OFF && mode != MTSV_MATCH_WITH_HITS && mode != MTSV_MATCH_ONLY) throw std::runtime_error("arg: bad match-flags mode");
     if (mode == MTSV_MATCH_ONLY && report.on)
         throw std::runtime_error("arg: MTSV_MATCH_ONLY gathers no hits and the taxa report of this workspace, which reads them, is on");
+    if (mode == MTSV_MATCH_ONLY && assign.mode != MTSV_ASSIGN_OFF)
+        throw std::runtime_error("arg: MTSV_MATCH_ONLY gathers no hits and the assignments of this workspace, which are reduced from them, are on");
     if (mode != MTSV_MATCH_OFF && match.mode == MTSV_MATCH_OFF) match.n_reads = 0;  // no run to speak of yet
     match.trace = getenv("MTSV_TRACE") != nullptr;
     match.mode = mode;
@@ -514,6 +529,163 @@ void Batch::match_flags(std::vector<uint64_t>& words, uint64_t* n_reads_out, uin
         fprintf(stderr, "[match] %llu kernel launches, %.3f ms, %llu of %llu reads matched, %llu bytes of flags to the host\n",
                 (unsigned long long)match.launches, match.ms, (unsigned long long)*n_matched, (unsigned long long)match.n_reads,
                 (unsigned long long)(nw * 8 + 8));
+}
+
+// ---- assignments (k_collapse.hip) ----
+void Batch::set_assignments(int mode) {
+    if (parent) throw std::runtime_error("internal: the assignments belong to the workspace's owner");
+    if (mode != MTSV_ASSIGN_OFF && mode != MTSV_ASSIGN_WITH_HITS && mode != MTSV_ASSIGN_ONLY) throw std::runtime_error("arg: bad assignments mode");
+    if (mode != MTSV_ASSIGN_OFF && match.mode == MTSV_MATCH_ONLY)
+        throw std::runtime_error("arg: assignments are reduced from gathered hits and MTSV_MATCH_ONLY gathers none (mtsv_batch_set_match_flags)");
+    if (mode != MTSV_ASSIGN_OFF && assign.mode == MTSV_ASSIGN_OFF) {
+        for (auto& sg : segments) sg.a_offset = sg.a_count = 0;  // no run to speak of yet
+        // the tier edges (tests move them to reach every tier with small databases)
+        auto env_u = [](const char* name, uint32_t dflt, uint32_t lo, uint32_t hi) {
+            const char* e = getenv(name);
+            if (!e) return dflt;
+            const long long v = atoll(e);
+            return (uint32_t)std::max<long long>(lo, std::min<long long>(hi, v));
+        };
+        assign.lane_max = env_u("MTSV_COLLAPSE_LANE_MAX", kCollapseLaneMax, 1, kCollapseLaneMax);
+        assign.wave_max = env_u("MTSV_COLLAPSE_WAVE_MAX", 64, 1, 64);
+        uint32_t lds = env_u("MTSV_COLLAPSE_LDS_MAX", kCollapseLdsKeys, 2, kCollapseLdsKeys);
+        while (lds & (lds - 1)) lds &= lds - 1;  // (a power of two: the largest one not above what was asked for)
+        assign.lds_max = lds;
+        assign.trace = getenv("MTSV_TRACE") != nullptr;
+        assign.ms = 0;
+        assign.launches = 0;
+        for (auto& t : assign.tiers) t = 0;
+    }
+    assign.mode = mode;
+}
+
+void Batch::collapse_begin() {
+    std::lock_guard<std::mutex> lk(assign.mu);
+    assign.ms = 0;
+    assign.launches = 0;
+    for (auto& t : assign.tiers) t = 0;
+}
+
+void Batch::collapse_trace(const char* what) {
+    uint64_t n_a = 0, n_h = 0;
+    for (auto& sg : segments) n_a += sg.a_count, n_h += sg.count;
+    std::lock_guard<std::mutex> lk(assign.mu);
+    fprintf(stderr, "[collapse] %s: %llu launches, %.3f ms, %llu hits -> %llu assignments; reads by tier: lane %llu, wavefront %llu, lds %llu, global %llu "
+                    "(tiers end at %u / %u / %u hits)\n",
+            what, (unsigned long long)assign.launches, assign.ms, (unsigned long long)n_h, (unsigned long long)n_a, (unsigned long long)assign.tiers[0],
+            (unsigned long long)assign.tiers[1], (unsigned long long)assign.tiers[3], (unsigned long long)assign.tiers[4], assign.lane_max, assign.wave_max,
+            assign.lds_max);
+}
+
+void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
+    CollapseScratch& c = collapse;
+    uint64_t dummy = 0;
+    if (n_hits >= (1ull << 32)) throw std::runtime_error("limit: 2^32 hits or more in one pass of the collapse");
+    if (!c.d_ctr) dev_alloc(&c.d_ctr, kCollapseCounters, &dummy);
+    if (!c.h_ctr) HIP_CHECK(hipHostMalloc((void**)&c.h_ctr, kCollapseCounters * sizeof(uint64_t), hipHostMallocMapped));
+    for (auto& e : c.ev)
+        if (!e) HIP_CHECK(hipEventCreate(&e));
+    if (n_hits > c.cap_hits || !c.keys) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        for (void* p : {(void*)c.keys, (void*)c.flags, (void*)c.place, (void*)c.tiles}) (void)hipFree(p);
+        c.keys = c.tiles = nullptr;
+        c.flags = c.place = nullptr;
+        c.cap_hits = 0;
+        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(n_hits + n_hits / 8, 1ull << 16), 0xffffffffull);
+        dev_alloc(&c.keys, cap, &dummy);
+        dev_alloc(&c.flags, cap + 1, &dummy);
+        dev_alloc(&c.place, cap + 1, &dummy);
+        dev_alloc(&c.tiles, (uint64_t)scan_tiles((uint32_t)cap) + 1, &dummy);
+        c.cap_hits = cap;
+    }
+    if (n_pass_reads > c.cap_reads || !c.list) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        (void)hipFree(c.list);
+        c.list = nullptr;
+        c.cap_reads = 0;
+        const uint64_t cap = std::max<uint64_t>(n_pass_reads + n_pass_reads / 16, 1024);
+        dev_alloc(&c.list, cap, &dummy);
+        c.cap_reads = cap;
+    }
+    if (n_assign_total + n_hits > assign_cap || !d_assign) {
+        // grow the result array, keeping what earlier passes produced
+        const uint64_t ncap = std::max<uint64_t>(std::max(assign_cap * 2, n_assign_total + n_hits), 1ull << 16);
+        uint4* na = nullptr;
+        dev_alloc(&na, ncap, &dummy);
+        if (n_assign_total) HIP_CHECK(hipMemcpyAsync(na, d_assign, n_assign_total * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        // run_host may be copying an earlier range's assignments out of the old array on the owner's copy stream (and another
+        // lane's thread may be issuing such a copy right now: the commit mutex covers the pointer swap), as with d_hits
+        Batch* root = parent ? parent : this;
+        std::unique_lock<std::mutex> commit_lk;
+        if (root->commit_mu) commit_lk = std::unique_lock<std::mutex>(*root->commit_mu);
+        if (root->commit_mu && root->copy_stream2) HIP_CHECK(hipStreamSynchronize(root->copy_stream2));
+        (void)hipFree(d_assign);
+        d_assign = na;
+        assign_cap = ncap;
+    }
+}
+
+void Batch::collapse_enqueue(uint32_t n_pass_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits, uint64_t n_hits) {
+    const Assignments& as = (parent ? parent : this)->assign;
+    collapse_room(n_pass_reads, n_hits);
+    CollapseScratch& c = collapse;
+    c.pending_hits = n_hits;
+    HIP_CHECK(hipEventRecord(c.ev[0], stream));
+    launch_collapse(stream, n_pass_reads, strand_nout, out_off, hits, (uint32_t)n_hits, as.lane_max, as.wave_max, as.lds_max, c.keys, c.flags, c.place,
+                    c.tiles, c.list, c.d_ctr, d_assign + n_assign_total);
+    HIP_CHECK(hipEventRecord(c.ev[1], stream));
+    // the pass's record count reaches the host with the synchronise the pass ends with anyway
+    launch_publish(stream, c.d_ctr, c.h_ctr, kCollapseCounters);
+}
+
+uint64_t Batch::collapse_commit() {
+    Assignments& as = (parent ? parent : this)->assign;
+    CollapseScratch& c = collapse;
+    const uint64_t cnt = c.h_ctr[kCollapseCtrTotal];
+    if (cnt > c.pending_hits) throw std::runtime_error("internal: the collapse wrote " + std::to_string(cnt) + " assignments from " + std::to_string(c.pending_hits) + " hits");
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    n_assign_total += cnt;
+    std::lock_guard<std::mutex> lk(as.mu);
+    as.ms += ms;
+    as.launches++;
+    for (int t = 0; t < 5; t++) as.tiers[t] += c.h_ctr[kCollapseCtrLane + t];
+    return cnt;
+}
+
+void Batch::download_assignments(mtsv_assignment** a, uint64_t* n, float* device_ms) {
+    if (parent) throw std::runtime_error("internal: the assignments belong to the workspace's owner");
+    if (assign.mode == MTSV_ASSIGN_OFF) throw std::runtime_error("arg: the assignments of this workspace are not switched on (mtsv_batch_set_assignments)");
+    HIP_CHECK(hipSetDevice(di->device));
+    uint64_t total = 0;
+    for (auto& sg : segments) total += sg.a_count;
+    last_total_assign = total;
+    mtsv_assignment* out = nullptr;
+    if (assign_staged_valid && h_assign_stage && staged_assign == total) {  // run_host already brought them over
+        out = h_assign_stage;
+        h_assign_stage = nullptr;
+        h_assign_cap = 0;
+        assign_staged_valid = false;
+    } else {
+        uint64_t cap = 0;
+        out = (mtsv_assignment*)pinned_hits_alloc((total + 1) / 2, &cap);  // (the pool counts in 32-byte hits)
+        uint64_t at = 0;
+        // (every run is synchronous: no lane has a pass in flight)
+        for (auto& sg : segments) {
+            if (!sg.a_count) continue;
+            const hipError_t e = hipMemcpy(out + at, sg.lane->d_assign + sg.a_offset, sg.a_count * sizeof(mtsv_assignment), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                pinned_hits_release(out);
+                throw_hip(e, "hipMemcpy(assignments)", __FILE__, __LINE__);
+            }
+            at += sg.a_count;
+        }
+    }
+    *a = out;
+    *n = total;
+    std::lock_guard<std::mutex> lk(assign.mu);
+    if (device_ms) *device_ms = assign.ms;
 }
 
 void Batch::run(const mtsv_params& p) {
@@ -796,6 +968,8 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
     // (before the result array grows, so that it cannot fail once the result is being replaced; if that allocation then
     //  fails, the list has grown already, with the counts so far kept and the new rows 0: the header says so)
     if (report.on) report_extend(srcs, n_srcs);
+    // (the collapse's scratch and the room behind the assignments so far: the last ones stay readable until then)
+    if (assign.mode != MTSV_ASSIGN_OFF && n) collapse_room(n, total);
     DevHit* grown = nullptr;  // (the last result stays in the old array until nothing can refuse the merge any more)
     if (total > hits_cap) dev_alloc(&grown, total + total / 16, &dummy);
     // ---- from here on the destination's result is being replaced ----
@@ -808,9 +982,15 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
     total_hits = 0;
     n_hits_total = 0;
     staged_valid = false;
+    assign_staged_valid = false;
+    host_hits_dropped = false;
     last_run = kRunNone;
     memset(&stats, 0, sizeof stats);
     if (match.mode != MTSV_MATCH_OFF) match_begin(n, 0);
+    const bool collapse_on = assign.mode != MTSV_ASSIGN_OFF;
+    n_assign_total = 0;
+    if (collapse_on) collapse_begin();
+    uint64_t n_assign = 0;
     uint64_t h_total[2] = {0, 0};  // the scan's total, the hits the copy could not place
     float ms = 0, ms_report = 0, ms_match = 0;
     if (n) {
@@ -838,8 +1018,11 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
             launch_match(stream, (uint32_t)n, m.d_nout, 0, match.d_words, match.d_words + match.cap_words);
             HIP_CHECK(hipEventRecord(match_ev[1], stream));
         }
+        // the collector is laid out as one pass: its assignments are those of the merged reads, all sources together
+        if (collapse_on) collapse_enqueue((uint32_t)n, m.d_nout, m.d_off, d_hits, total);
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipGetLastError());
+        if (collapse_on) n_assign = collapse_commit();
         if (h_total[0] != total)
             throw std::runtime_error("internal: the merge counted " + std::to_string(h_total[0]) + " hits, the sources hold " + std::to_string(total));
         if (h_total[1])
@@ -860,7 +1043,7 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
     }
     n_hits_total = total;
     total_hits = total;
-    segments.push_back(Segment{this, 0, total, 0, n});
+    segments.push_back(Segment{this, 0, total, 0, n, 0, n_assign});
     stats.n_reads = n;
     stats.n_hits = total;
     last_run = kRunMerged;
@@ -869,6 +1052,7 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
         fprintf(stderr, "[merge] %d sources in %llu stretches, %llu reads, %llu hits: merge kernels %.3f ms, report %.3f ms, flags %.3f ms; %llu bytes to the host, %llu to the device\n",
                 n_srcs, (unsigned long long)parts.size(), (unsigned long long)n, (unsigned long long)total, ms, ms_report, ms_match, (unsigned long long)16,
                 (unsigned long long)(parts.size() * sizeof(MergePart)));
+    if (collapse_on && assign.trace) collapse_trace("merge");
 }
 
 void Batch::read_map(std::vector<uint64_t>& map) {
@@ -942,11 +1126,11 @@ void Batch::run_range(const mtsv_params& p, const uint8_t* raw, uint8_t* sb, con
             const uint64_t c = next.fetch_add(1);
             if (c >= n_chunks) return;
             const uint64_t a = bound[c], b = bound[c + 1];
-            const uint64_t before = lane->n_hits_total;
+            const uint64_t before = lane->n_hits_total, a_before = lane->n_assign_total;
             // base normalisation (binner.rs:88-100) of this chunk's bytes: raw -> codes, on the lane's stream
             if (raw) launch_normalise(lane->stream, raw, sb, h_off[a], h_off[b]);
             lane->run_slice(p, sb, so + a, h_off ? h_off + a : nullptr, b - a, range_max_len, read_base + a);
-            segs[c] = Segment{lane, before, lane->n_hits_total - before, a, b - a};
+            segs[c] = Segment{lane, before, lane->n_hits_total - before, a, b - a, a_before, lane->n_assign_total - a_before};
         }
     };
     if (k == 1) {
@@ -1398,9 +1582,13 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
             launch_match(stream, nr, d_strand_nout, first_bit, mf.d_words, mf.d_words + mf.cap_words);
             HIP_CHECK(hipEventRecord(match_ev[1], stream));
         }
+        // ... and their hits are reduced to assignments
+        const bool collapse_on = !only_flags && root->assign.mode != MTSV_ASSIGN_OFF;
+        if (collapse_on) collapse_enqueue(nr, d_strand_nout, d_out_off, d_hits + n_hits_total, total_out);
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipGetLastError());
         turn.release();
+        if (collapse_on) collapse_commit();
         if (mf.mode != MTSV_MATCH_OFF) {
             float ms = 0;
             HIP_CHECK(hipEventElapsedTime(&ms, match_ev[0], match_ev[1]));
@@ -1649,6 +1837,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
         bool done = false;
         Batch* lane = nullptr;
         uint64_t hit_off = 0, hit_cnt = 0;
+        uint64_t a_off = 0, a_cnt = 0;  // its assignments: they stay in the lane until mtsv_batch_download_assignments
     };
     std::mutex mu;  // chunks, ranges, cursors, commit state
     std::condition_variable cv;
@@ -1684,11 +1873,24 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
     if (trace) fprintf(stderr, "[run_host] entered; begin_run at %.2f ms\n", (now_s() - t_entry) * 1e3);
     begin_run(p, read_base);
     staged_hits = 0;
-    if (!h_hits_stage && !keep_on_device && !flags_only()) {
+    // (MTSV_ASSIGN_ONLY: the hits stay on the device, no hit byte crosses to the host)
+    const bool stage_hits = !keep_on_device && !assign_only();
+    if (assign_only() && h_hits_stage) {  // no hit will be staged: a pinned array left from an earlier run goes back to the pool
+        pinned_hits_release(h_hits_stage);
+        h_hits_stage = nullptr;
+        h_hits_cap = 0;
+    }
+    if (!h_hits_stage && stage_hits && !flags_only()) {
         // expect about as many hits as the last run produced (first run: one per read)
         // (a fresh page-locked array costs ~60 us per MB to create and is slow on its first copy: ask for little more than
         //  the last batch needed, so that the array that batch returned to the pool fits again)
         h_hits_stage = pinned_hits_alloc(last_total_hits ? last_total_hits + last_total_hits / 64 : n + n / 8, &h_hits_cap);
+    }
+    const bool stage_assign = assign.mode != MTSV_ASSIGN_OFF;
+    if (stage_assign && !h_assign_stage) {
+        uint64_t cap = 0;  // (in 32-byte hits: two records each)
+        h_assign_stage = (mtsv_assignment*)pinned_hits_alloc(((last_total_assign ? last_total_assign + last_total_assign / 64 : n + n / 8) + 1) / 2, &cap);
+        h_assign_cap = 2 * cap;
     }
     if (trace) fprintf(stderr, "[run_host] result array of %llu hits ready at %.2f ms\n", (unsigned long long)h_hits_cap, (now_s() - t_entry) * 1e3);
     const uint64_t n_lanes_used = n >= ls.size() * kLaneMinReads ? ls.size() : 1;
@@ -1874,13 +2076,19 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
     auto commit_ready = [&]() {  // mu held: hits of finished ranges leave for the host in read order
         while (next_commit < ranges.size() && ranges[next_commit].done) {
             Range& rg = ranges[next_commit];
-            if (rg.hit_cnt && !keep_on_device) {
+            if (rg.hit_cnt && stage_hits) {
                 stage_reserve(staged_hits + rg.hit_cnt);
                 HIP_CHECK(hipMemcpyAsync(h_hits_stage + staged_hits, rg.lane->d_hits + rg.hit_off, rg.hit_cnt * sizeof(mtsv_hit),
                                          hipMemcpyDeviceToHost, copy_stream2));
                 staged_hits += rg.hit_cnt;
             }
-            segments.push_back(Segment{rg.lane, rg.hit_off, rg.hit_cnt});
+            if (rg.a_cnt && stage_assign) {
+                assign_stage_reserve(staged_assign + rg.a_cnt);
+                HIP_CHECK(hipMemcpyAsync(h_assign_stage + staged_assign, rg.lane->d_assign + rg.a_off, rg.a_cnt * sizeof(mtsv_assignment),
+                                         hipMemcpyDeviceToHost, copy_stream2));
+                staged_assign += rg.a_cnt;
+            }
+            segments.push_back(Segment{rg.lane, rg.hit_off, rg.hit_cnt, 0, 0, rg.a_off, rg.a_cnt});
             done_prefix = rg.end;
             next_commit++;
         }
@@ -1951,7 +2159,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                 const Arena& ar = arena[seg & 1];
                 const uint32_t* ho = h_off_all + rb + seg;  // offsets of reads rb .. re inside segment seg
                 const uint32_t* dso = ar.d_off + (rb - seg_first);
-                const uint64_t before = lane->n_hits_total;
+                const uint64_t before = lane->n_hits_total, a_before = lane->n_assign_total;
                 const double t0 = now_s();
                 // base normalisation (binner.rs:88-100) in place, on the lane's own stream: a kernel on the copy
                 // stream would queue behind the persistent verification kernels of the other lanes
@@ -1964,6 +2172,8 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                     ranges[k].lane = lane;
                     ranges[k].hit_off = before;
                     ranges[k].hit_cnt = lane->n_hits_total - before;
+                    ranges[k].a_off = a_before;
+                    ranges[k].a_cnt = lane->n_assign_total - a_before;
                     ranges[k].done = true;
                     last_done = k;
                     max_len = std::max(max_len, ml);
@@ -1993,10 +2203,17 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
     }
     end_run();
     HIP_CHECK(hipStreamSynchronize(copy_stream2));
-    staged_valid = !keep_on_device && staged_hits == total_hits;
+    staged_valid = stage_hits && staged_hits == total_hits;
+    host_hits_dropped = !stage_hits && !keep_on_device;
+    if (stage_assign) {
+        uint64_t total_a = 0;
+        for (auto& sg : segments) total_a += sg.a_count;
+        assign_staged_valid = staged_assign == total_a;
+        if (!assign_staged_valid) throw std::runtime_error("internal: run_host staged " + std::to_string(staged_assign) + " of " + std::to_string(total_a) + " assignments");
+    }
     last_run = seg_begin.size() == 1 ? kRunHostOneSegment : kRunHostSegments;
     if (trace) fprintf(stderr, "[run_host] hits on the host at %.1f ms (%llu ranges, %llu chunks); %.1f ms since the call began\n", (now_s() - run_t0) * 1e3, (unsigned long long)ranges.size(), (unsigned long long)chunks.size(), (now_s() - t_entry) * 1e3);
-    if (!staged_valid && !keep_on_device) throw std::runtime_error("internal: run_host staged " + std::to_string(staged_hits) + " of " + std::to_string(total_hits) + " hits");
+    if (!staged_valid && stage_hits) throw std::runtime_error("internal: run_host staged " + std::to_string(staged_hits) + " of " + std::to_string(total_hits) + " hits");
 }
 
 // pinned result array of run_host: grown geometrically through the pool (mu of run_host held)
@@ -2012,10 +2229,31 @@ void Batch::stage_reserve(uint64_t n_hits_needed) {
     h_hits_cap = ncap;
 }
 
+// the same for the assignments' pinned array (two 16-byte records per pool unit of 32 bytes)
+void Batch::assign_stage_reserve(uint64_t n_needed) {
+    if (n_needed <= h_assign_cap) return;
+    if (getenv("MTSV_TRACE")) fprintf(stderr, "[run_host] assignment array grows %llu -> %llu records\n", (unsigned long long)h_assign_cap, (unsigned long long)n_needed);
+    HIP_CHECK(hipStreamSynchronize(copy_stream2));
+    uint64_t ncap = 0;
+    auto* na = (mtsv_assignment*)pinned_hits_alloc((std::max<uint64_t>(2 * h_assign_cap, n_needed) + 1) / 2, &ncap);
+    if (staged_assign) memcpy(na, h_assign_stage, staged_assign * sizeof(mtsv_assignment));
+    if (h_assign_stage) pinned_hits_release(h_assign_stage);
+    h_assign_stage = na;
+    h_assign_cap = 2 * ncap;
+}
+
 // The result array is pinned host memory from the pool; the caller owns it until mtsv_hits_free.
 void Batch::download(mtsv_hit** hits, uint64_t* n) {
     HIP_CHECK(hipSetDevice(di->device));
     last_total_hits = total_hits;
+    if (assign.mode != MTSV_ASSIGN_ONLY && host_hits_dropped)
+        throw std::runtime_error("arg: the last run was a host batch in MTSV_ASSIGN_ONLY, which kept none of its hits: run again in the new mode");
+    if (assign.mode == MTSV_ASSIGN_ONLY) {  // the hits stay where they are
+        uint64_t cap = 0;
+        *hits = pinned_hits_alloc(0, &cap);
+        *n = 0;
+        return;
+    }
     if (staged_valid && h_hits_stage) {  // run_host already brought them over
         *hits = h_hits_stage;
         *n = total_hits;

@@ -51,6 +51,7 @@ struct Batch {
         Batch* lane;
         uint64_t offset, count;
         uint64_t first_read = 0, n_reads = 0;  // (resident runs) the range of the batch's reads whose hits these are
+        uint64_t a_offset = 0, a_count = 0;    // (assignments on) the same stretch's assignments in the lane's d_assign
     };
     std::vector<Segment> segments;  // where the hits of the last run sit, in read order
     uint64_t total_hits = 0;
@@ -233,6 +234,47 @@ struct Batch {
         hipEvent_t ev[2] = {nullptr, nullptr};
     };
     MergeState merge;
+    // Assignments (k_collapse.hip): per read of the last run one (read, tax_id, smallest edit) record per distinct TaxID,
+    // ascending by TaxID -- the default results line of mtsv-binner, reduced on the device.  The mode, the thresholds and the
+    // times belong to the owner; every lane has a result array and a scratch of its own, created by its first pass with the
+    // assignments on.  Like the flags they describe one run.
+    struct Assignments {
+        int mode = MTSV_ASSIGN_OFF;
+        // a read of up to lane_max hits is reduced by one lane, up to wave_max by its wavefront, up to lds_max by a workgroup
+        // in LDS, a larger one by a workgroup in global memory (MTSV_COLLAPSE_LANE_MAX, _WAVE_MAX, _LDS_MAX: tests)
+        uint32_t lane_max = kCollapseLaneMax, wave_max = 64, lds_max = kCollapseLdsKeys;
+        bool trace = false;
+        std::mutex mu;          // ms, launches, tiers (the lanes' threads add to them)
+        float ms = 0;           // device time of the run's collapse kernels
+        uint64_t launches = 0;
+        uint64_t tiers[5] = {0, 0, 0, 0, 0};  // reads of the run by tier: lane, wavefront, listed = LDS + global
+    };
+    Assignments assign;
+    // run_host: a finished range's assignments leave for this pinned array (pool) on the result copy stream, in read order,
+    // like its hits; mtsv_batch_download_assignments hands the array out.  (owner only)
+    mtsv_assignment* h_assign_stage = nullptr;
+    uint64_t h_assign_cap = 0, staged_assign = 0, last_total_assign = 0;
+    bool assign_staged_valid = false;
+    bool host_hits_dropped = false;  // the last run was a host batch in MTSV_ASSIGN_ONLY: its hits were never staged and the lanes' arrays were recycled
+    void assign_stage_reserve(uint64_t n_needed);
+    uint4* d_assign = nullptr;  // the lane's assignments (mtsv_assignment), those of a pass behind those of the passes before
+    uint64_t assign_cap = 0, n_assign_total = 0;
+    struct CollapseScratch {
+        uint64_t* keys = nullptr;   // cap_hits sort keys, mirroring a pass's hits
+        uint32_t *flags = nullptr, *place = nullptr;  // cap_hits + 1 each
+        uint64_t* tiles = nullptr;  // the scan's tile sums
+        uint32_t* list = nullptr;   // cap_reads: the reads left to k_collapse_heavy
+        uint64_t cap_hits = 0, cap_reads = 0;
+        uint64_t pending_hits = 0;  // the hits of the pass whose collapse is on the stream
+        uint64_t* d_ctr = nullptr;  // kCollapseCounters
+        uint64_t* h_ctr = nullptr;  // pinned, mapped: the pass's counters (launch_publish)
+        hipEvent_t ev[2] = {nullptr, nullptr};
+    };
+    CollapseScratch collapse;
+    bool assign_only() const { return (parent ? parent : this)->assign.mode == MTSV_ASSIGN_ONLY; }
+    void set_assignments(int mode);
+    // the assignments of the last run, in read order, in a pinned array of the pool (*n may be 0: *a is still to be freed)
+    void download_assignments(mtsv_assignment** a, uint64_t* n, float* device_ms);
     void merge_runs(Batch* const* srcs, int n_srcs, float* device_ms);
     void read_map(std::vector<uint64_t>& map);
     void download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& read_off);
@@ -243,6 +285,14 @@ struct Batch {
     void begin_run(const mtsv_params& p, uint64_t read_base = 0);
     void match_begin(uint64_t n, uint64_t read_base);  // flags on: room for n reads' flags, all zero
     void report_extend(Batch* const* srcs, int n_srcs);  // the report's TaxID list := its union with the sources' indexes
+    // room for a pass of n_reads reads and n_hits hits in the lane's collapse scratch and behind its assignments so far
+    void collapse_room(uint64_t n_reads, uint64_t n_hits);
+    // (assignments on) the collapse of a committed pass on the lane's stream, its counters published; collapse_commit, after
+    // the stream has been synchronised, takes them: returns the pass's assignments, now part of d_assign
+    void collapse_enqueue(uint32_t n_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits, uint64_t n_hits);
+    uint64_t collapse_commit();
+    void collapse_begin();  // a run begins: no assignments, counts and times zero
+    void collapse_trace(const char* what);
     void reset_lane();
     void stage_reserve(uint64_t n_hits_needed);
     void host_room(uint64_t n, uint64_t total_bases, bool trace);

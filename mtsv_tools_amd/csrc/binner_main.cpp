@@ -591,6 +591,14 @@ int main(int argc, char** argv) {
     }
     if (index_paths.empty()) usage_error("The following required arguments were not provided: --index <INDEX>");
     const bool chunked = index_paths.size() > 1;  // Mode B
+    // MTSV_CLI_ASSIGN=1: the default results format is written from assignments -- the smallest edit per read and TaxID,
+    // reduced on the device (mtsv_batch_set_assignments, MTSV_ASSIGN_ONLY: no hit crosses to the host) -- where one workspace
+    // per worker holds a call's hits: a single index (behind --filter-index: the database's workspace) or the collector of
+    // --merge-on-gpu.  The file is the same byte for byte.  --output-format long needs the hits and stays on them.
+    // The default is 0 (profiles/README.md r14: the measurement and what it decided).
+    bool cli_assign = false;
+    if (const char* e = getenv("MTSV_CLI_ASSIGN")) cli_assign = atoi(e) != 0;
+    cli_assign = cli_assign && have_results && !long_fmt && (!chunked || merged) && match_mode != MTSV_MATCH_ONLY;
     std::vector<std::string> filter_paths;
     for (size_t at = 0; filtered && at <= a.filter_index.size();) {
         size_t c = a.filter_index.find(',', at);
@@ -730,6 +738,7 @@ int main(int argc, char** argv) {
                 }
                 if (rc == MTSV_OK && !a.report.empty()) rc = mtsv_batch_set_taxa_report(ws_ready[wk], 1);
                 if (rc == MTSV_OK && partition) rc = mtsv_batch_set_match_flags(ws_ready[wk], match_mode);
+                if (rc == MTSV_OK && cli_assign) rc = mtsv_batch_set_assignments(ws_ready[wk], MTSV_ASSIGN_ONLY);
                 ws_rc[wk] = rc;
                 if (rc != MTSV_OK) ws_msg[wk] = mtsv_last_error();  // (thread-local)
                 return;
@@ -748,6 +757,7 @@ int main(int argc, char** argv) {
             }
             if (rc == MTSV_OK && !a.report.empty()) rc = mtsv_batch_set_taxa_report(ws_ready[wk], 1);  // (after the warm-up reads)
             if (rc == MTSV_OK && partition) rc = mtsv_batch_set_match_flags(ws_ready[wk], match_mode);
+            if (rc == MTSV_OK && cli_assign) rc = mtsv_batch_set_assignments(ws_ready[wk], MTSV_ASSIGN_ONLY);  // (after the warm-up reads)
             ws_rc[wk] = rc;
             if (rc != MTSV_OK) ws_msg[wk] = mtsv_last_error();  // (thread-local)
         };
@@ -797,6 +807,10 @@ int main(int argc, char** argv) {
         uint64_t n_hits = 0;
         uint64_t read_first = 0;  // the batch's first read in the numbering of its call (the formatter subtracts it)
         std::shared_ptr<void> hits_owner;  // the result array of the library call the batch was part of
+        // MTSV_CLI_ASSIGN=1: the batch's assignments instead (the same slicing and numbering), and their array
+        mtsv_assignment* assigns = nullptr;
+        uint64_t n_assigns = 0;
+        std::shared_ptr<void> assigns_owner;
         std::shared_ptr<uint64_t> flags;   // --matched / --unmatched: the match flags of that call; read i of the batch is bit read_first + i
     };
     struct Queue {
@@ -995,12 +1009,14 @@ int main(int argc, char** argv) {
             const double t_f0 = now();
             // write_assignments over slices of the batch's hits (cut between reads), one thread each
             const uint64_t n_reads = w->rb->n();
-            const unsigned parts = w->n_hits >= (1u << 16) ? host_threads : 1;
-            std::vector<uint64_t> cut(parts + 1, w->n_hits);
+            const uint64_t n_items = cli_assign ? w->n_assigns : w->n_hits;
+            auto read_of = [&](uint64_t i) { return cli_assign ? w->assigns[i].read : w->hits[i].read; };
+            const unsigned parts = n_items >= (1u << 16) ? host_threads : 1;
+            std::vector<uint64_t> cut(parts + 1, n_items);
             cut[0] = 0;
             for (unsigned k = 1; k < parts; k++) {
-                uint64_t c = std::max(cut[k - 1], w->n_hits * k / parts);
-                while (c > cut[k - 1] && c < w->n_hits && w->hits[c].read == w->hits[c - 1].read) c++;
+                uint64_t c = std::max(cut[k - 1], n_items * k / parts);
+                while (c > cut[k - 1] && c < n_items && read_of(c) == read_of(c - 1)) c++;
                 cut[k] = c;
             }
             // --matched / --unmatched: the batch's records, each to its side, serialised over ranges of reads in parallel and
@@ -1060,6 +1076,14 @@ int main(int argc, char** argv) {
             std::vector<std::string> msg(parts);
             auto fmt = [&](unsigned k) {
                 if (out_fd < 0) return;  // (no results file: --matched / --unmatched alone)
+                if (cli_assign) {
+                    if (w->read_first)
+                        for (uint64_t i = cut[k]; i < cut[k + 1]; i++) w->assigns[i].read -= w->read_first;
+                    rc[k] = mtsv_format_assignments(w->assigns + cut[k], cut[k + 1] - cut[k], w->rb->ids.data(), w->rb->id_off.data(), n_reads, &text[k],
+                                                    &len[k]);
+                    if (rc[k] != MTSV_OK) msg[k] = mtsv_last_error();  // thread-local
+                    return;
+                }
                 if (w->read_first)
                     for (uint64_t i = cut[k]; i < cut[k + 1]; i++) w->hits[i].read -= w->read_first;
                 rc[k] = mtsv_format_results(w->hits + cut[k], cut[k + 1] - cut[k], w->rb->ids.data(), w->rb->id_off.data(), n_reads,
@@ -1074,6 +1098,7 @@ int main(int argc, char** argv) {
                 fmt(0);
             }
             w->hits_owner.reset();  // (the array goes back to the library's pool with the last batch of its call)
+            w->assigns_owner.reset();
             acc(t_fmt, now() - t_f0);
             bool ok = true;
             for (unsigned k = 0; k < parts; k++)
@@ -1156,6 +1181,8 @@ int main(int argc, char** argv) {
             int rc;
             mtsv_hit* hits = nullptr;
             uint64_t n_hits = 0;
+            mtsv_assignment* assigns = nullptr;
+            uint64_t n_assigns = 0;
             if (merged) {
                 auto& w = group[0];
                 if (w->rb->n() > merge_reads || w->rb->bases.size() > merge_bases) {
@@ -1170,7 +1197,7 @@ int main(int argc, char** argv) {
                 for (size_t c = 1; c < cw.size() && rc == MTSV_OK; c++) rc = mtsv_batch_copy_reads(cw[c], cw[0], nullptr);
                 for (size_t c = 0; c < cw.size() && rc == MTSV_OK; c++) rc = mtsv_batch_run(cw[c], &p);
                 if (rc == MTSV_OK) rc = mtsv_batch_merge_runs(ws, cw.data(), (int)cw.size(), nullptr);
-                if (rc == MTSV_OK) rc = mtsv_batch_download(ws, &hits, &n_hits);
+                if (rc == MTSV_OK) rc = cli_assign ? mtsv_batch_download_assignments(ws, &assigns, &n_assigns, nullptr) : mtsv_batch_download(ws, &hits, &n_hits);
             } else if (chunked) {
                 auto& w = group[0];
                 rc = mtsv_bin_batch_chunks(idx.data(), chunk_dev.data(), (int)idx.size(), w->rb->bases.data(), w->rb->off.data(), w->rb->n(), &p,
@@ -1201,7 +1228,8 @@ int main(int argc, char** argv) {
                         rc = mtsv_batch_run(next, &p);
                     }
                 }
-                if (rc == MTSV_OK && match_mode != MTSV_MATCH_ONLY) rc = mtsv_batch_download(ws, &hits, &n_hits);  // (flags only: there are none)
+                if (rc == MTSV_OK && cli_assign) rc = mtsv_batch_download_assignments(ws, &assigns, &n_assigns, nullptr);
+                else if (rc == MTSV_OK && match_mode != MTSV_MATCH_ONLY) rc = mtsv_batch_download(ws, &hits, &n_hits);  // (flags only: there are none)
             }
             std::shared_ptr<uint64_t> flags;
             if (rc == MTSV_OK && partition) {
@@ -1233,9 +1261,17 @@ int main(int argc, char** argv) {
             // (the boundaries by bisection, the renumbering on the formatting threads: a pass over a million hits between two
             //  calls was 1.7 ms of every 8 the worker spent per megaread)
             std::shared_ptr<void> owner(hits, [](void* q) { mtsv_hits_free((mtsv_hit*)q); });
-            uint64_t first = 0, at = 0;
+            std::shared_ptr<void> a_owner(assigns, [](void* q) { mtsv_free(q); });
+            uint64_t first = 0, at = 0, a_at = 0;
             for (auto& w : group) {
                 const uint64_t nr = w->rb->n();
+                if (cli_assign) {
+                    const uint64_t a_end = (uint64_t)(std::partition_point(assigns + a_at, assigns + n_assigns, [&](const mtsv_assignment& x) { return x.read < first + nr; }) - assigns);
+                    w->assigns = assigns + a_at;
+                    w->n_assigns = a_end - a_at;
+                    w->assigns_owner = a_owner;
+                    a_at = a_end;
+                }
                 const uint64_t end = (uint64_t)(std::partition_point(hits + at, hits + n_hits, [&](const mtsv_hit& h) { return h.read < first + nr; }) - hits);
                 w->hits = hits + at;
                 w->n_hits = end - at;

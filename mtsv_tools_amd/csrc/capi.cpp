@@ -463,6 +463,16 @@ int mtsv_format_taxa_report(const mtsv_taxon_stats* rows, uint64_t n_rows, uint6
     })
 }
 
+int mtsv_batch_set_assignments(mtsv_batch* b, int mode) {
+    if (!b) return fail_arg("null argument");
+    GUARD(b->impl.set_assignments(mode))
+}
+
+int mtsv_batch_download_assignments(mtsv_batch* b, mtsv_assignment** a, uint64_t* n, float* device_ms) {
+    if (!b || !a || !n) return fail_arg("null argument");
+    GUARD(b->impl.download_assignments(a, n, device_ms))
+}
+
 int mtsv_batch_download(mtsv_batch* b, mtsv_hit** hits, uint64_t* n_hits) {
     if (!b || !hits || !n_hits) return fail_arg("null argument");
     GUARD(b->impl.download(hits, n_hits))
@@ -650,7 +660,9 @@ int mtsv_bin_batch_chunks(mtsv_index* const* chunks, const int* devices, int n_c
 void mtsv_hits_free(mtsv_hit* hits) {
     if (hits && !mtsv::pinned_hits_release(hits)) free(hits);
 }
-void mtsv_free(void* p) { free(p); }
+void mtsv_free(void* p) {  // (arrays of the pinned pool go back to it)
+    if (p && !mtsv::pinned_hits_release(p)) free(p);
+}
 
 void* mtsv_host_alloc(size_t bytes) {
     void* p = mtsv::host_pinned_alloc(bytes);
@@ -676,34 +688,38 @@ int mtsv_host_unregister(void* p) {
 }
 
 // ---- write_assignments (src/binner.rs:310-379) ------------------------------------------------
+// the text grows in a malloc'd buffer that is handed to the caller as it is; numbers are written digit by
+// digit (snprintf per TaxID cost more than everything else on the result side of mtsv-binner)
+namespace {
+struct Text {
+    char* p = nullptr;
+    uint64_t n = 0, cap = 0;
+    ~Text() { free(p); }
+    void room(uint64_t more) {
+        if (n + more <= cap) return;
+        const uint64_t ncap = std::max<uint64_t>(n + more, cap + cap / 2 + (1 << 16));
+        char* q = (char*)realloc(p, ncap);
+        if (!q) throw std::bad_alloc();
+        p = q;
+        cap = ncap;
+    }
+    void put(uint64_t v) {  // decimal, as %u / %llu
+        char tmp[20];
+        int k = 0;
+        do {
+            tmp[k++] = (char)('0' + v % 10);
+            v /= 10;
+        } while (v);
+        while (k) p[n++] = tmp[--k];
+    }
+};
+}  // namespace
+
 int mtsv_format_results(const mtsv_hit* hits, uint64_t n_hits, const char* ids, const uint64_t* id_off, uint64_t n_reads,
                         int long_format, char** out, uint64_t* out_len) {
     if ((!hits && n_hits) || !ids || !id_off || !out || !out_len) return fail_arg("null argument");
     GUARD({
-        // the text grows in a malloc'd buffer that is handed to the caller as it is; numbers are written digit by
-        // digit (snprintf per TaxID cost more than everything else on the result side of mtsv-binner)
-        struct Text {
-            char* p = nullptr;
-            uint64_t n = 0, cap = 0;
-            ~Text() { free(p); }
-            void room(uint64_t more) {
-                if (n + more <= cap) return;
-                const uint64_t ncap = std::max<uint64_t>(n + more, cap + cap / 2 + (1 << 16));
-                char* q = (char*)realloc(p, ncap);
-                if (!q) throw std::bad_alloc();
-                p = q;
-                cap = ncap;
-            }
-            void put(uint64_t v) {  // decimal, as %u / %llu
-                char tmp[20];
-                int k = 0;
-                do {
-                    tmp[k++] = (char)('0' + v % 10);
-                    v /= 10;
-                } while (v);
-                while (k) p[n++] = tmp[--k];
-            }
-        } buf;
+        Text buf;
         struct Item {
             uint32_t tax, gi;
             uint64_t off;
@@ -760,6 +776,41 @@ int mtsv_format_results(const mtsv_hit* hits, uint64_t n_hits, const char* ids, 
                 }
                 buf.p[buf.n++] = '=';
                 buf.put(it.edit);
+            }
+            buf.p[buf.n++] = '\n';
+            i = j;
+        }
+        buf.room(1);
+        buf.p[buf.n] = 0;
+        *out = buf.p;
+        *out_len = buf.n;
+        buf.p = nullptr;  // the caller's now (mtsv_free)
+    })
+}
+
+// the same lines from the device's assignments: already one per (read, TaxID), smallest edit, ascending
+int mtsv_format_assignments(const mtsv_assignment* a, uint64_t n, const char* ids, const uint64_t* id_off, uint64_t n_reads, char** out,
+                            uint64_t* out_len) {
+    if ((!a && n) || !ids || !id_off || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        Text buf;
+        uint64_t i = 0;
+        while (i < n) {
+            const uint64_t r = a[i].read;
+            if (r >= n_reads) throw std::runtime_error("arg: assignment refers to a read outside the batch");
+            if (i && r < a[i - 1].read) throw std::runtime_error("arg: assignments are not ordered by read");
+            uint64_t j = i;
+            while (j < n && a[j].read == r) j++;
+            const uint64_t id_len = strnlen(ids + id_off[r], id_off[r + 1] - id_off[r]);
+            buf.room(id_len + 2 + (j - i) * 22 + 1);  // "tax=edit," is at most 10 + 1 + 10 + 1 characters
+            memcpy(buf.p + buf.n, ids + id_off[r], id_len);
+            buf.n += id_len;
+            buf.p[buf.n++] = ':';
+            for (uint64_t k = i; k < j; k++) {
+                if (k != i) buf.p[buf.n++] = ',';
+                buf.put(a[k].tax_id);
+                buf.p[buf.n++] = '=';
+                buf.put(a[k].edit);
             }
             buf.p[buf.n++] = '\n';
             i = j;

@@ -23,6 +23,7 @@
 //   scan + k_gather  compact per-strand hits into (read, strand, rank) order      binner.rs:128
 //   k_report    (taxa report on) lane per read: per-TaxID read counts of the pass   collapse.rs:120-146
 //   k_match     (match flags on) lane per read: one bit, "the read has a hit"      mtsv-partition.rs:34-54
+//   k_collapse  (assignments on) per read: one (tax_id, smallest edit) per TaxID      binner.rs:355-378
 //
 // All arithmetic is integer; positions are u32 (n < 2^32).  No MFMA: the path is rank queries and
 // small dynamic programs.
@@ -244,5 +245,19 @@ void launch_merge_bounds(hipStream_t s, const MergePart* parts, uint32_t n_parts
 void launch_merge_sum(hipStream_t s, uint32_t n_reads, uint32_t n_srcs, const uint32_t* lo, uint32_t* cnt_base, uint32_t* nout);
 void launch_merge_copy(hipStream_t s, const MergePart* parts, uint32_t n_parts, uint32_t max_part_hits, uint32_t n_reads,
                        const uint32_t* map, const uint32_t* base, const uint32_t* out_off, DevHit* dst, uint32_t n_dst, uint64_t* n_dropped);
+// k_collapse.hip: the assignments of a pass (binner.rs:355-378) from its gathered hits -- per read one record (read, tax_id,
+// smallest edit) per distinct TaxID, ascending by TaxID as unsigned, reads in the order of the hits.  Inputs as for
+// launch_report; n_hits: the pass's hits (known on the host).  keys (n_hits u64), flags and place (n_hits + 1 u32 each),
+// tile_sums (scan_tiles(n_hits) + 1) and list (n_reads u32) are scratch; ctr: kCollapseCounters u64, zeroed here, of which
+// [kCollapseCtrTotal] receives the number of records written to out[0 ..) (at most n_hits; byte-identical to
+// mtsv_assignment) and [kCollapseCtrLane ..] the reads every tier took.  Tiers by a read's hit count: up to lane_max
+// (1 .. kCollapseLaneMax) a lane, up to wave_max (<= 64) its wavefront, up to lds_max (a power of two <= kCollapseLdsKeys) a
+// workgroup sorting in LDS, beyond that a workgroup sorting in `keys` itself.
+constexpr uint32_t kCollapseLaneMax = 16, kCollapseLdsKeys = 4096;
+constexpr uint32_t kCollapseCtrTotal = 0, kCollapseCtrList = 1, kCollapseCtrTicket = 2, kCollapseCtrLane = 3, kCollapseCtrWave = 4,
+                   kCollapseCtrListed = 5, kCollapseCtrLds = 6, kCollapseCtrGlobal = 7, kCollapseCounters = 8;
+void launch_collapse(hipStream_t s, uint32_t n_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits, uint32_t n_hits,
+                     uint32_t lane_max, uint32_t wave_max, uint32_t lds_max, uint64_t* keys, uint32_t* flags, uint32_t* place, uint64_t* tile_sums,
+                     uint32_t* list, uint64_t* ctr, uint4* out);
 
 }  // namespace mtsv
