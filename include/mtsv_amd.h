@@ -387,11 +387,18 @@ int mtsv_batch_download(mtsv_batch *b, mtsv_hit **hits, uint64_t *n_hits);
  *   MTSV_ASSIGN_ONLY       the hits are gathered on the device (the collapse reads them, and so do the taxa report and
  *                          the match flags) but never copied to the host: mtsv_batch_download returns zero hits; the
  *                          stats keep their meaning, n_hits included
- * Limits: the short format only (TAXID-GI-OFFSET=EDIT needs the hits); one run's worth; not together with
+ * Grains (mtsv_batch_set_assignment_grain): the above is MTSV_GRAIN_TAXID.  MTSV_GRAIN_LONG keeps one 24-byte record per
+ * distinct (tax_id, gi, offset) of the read with the triple's smallest edit, ascending by the triple -- the line of
+ * --output-format long, READ_ID:TAXID-GI-OFFSET=EDIT,... (src/binner.rs:320-352); MTSV_GRAIN_TAXID_GI one per distinct
+ * (tax_id, gi) with the lexicographically smallest (edit, offset) of the pair, ascending by the pair -- what mtsv-collapse
+ * --mode taxid-gi makes of long files (src/collapse.rs:603-625), and in a collector over all chunks.  All fields compare as
+ * unsigned.  Everything said of the 16-byte records holds for these.
+ * Limits: one run's worth; offsets below 2^32 (no device index reaches them); not together with
  * MTSV_MATCH_ONLY, which gathers no hits -- whichever of the two is asked for second fails with MTSV_E_ARG; a bad mode is
  * MTSV_E_ARG; mtsv_bin_batch, _multi and _chunks do not produce assignments.  The taxa report and MTSV_MATCH_WITH_HITS
  * work beside every mode.  MTSV_COLLAPSE_LANE_MAX (1..16), MTSV_COLLAPSE_WAVE_MAX (..64) and MTSV_COLLAPSE_LDS_MAX (a power
- * of two, 2..4096) move the kernel's tier edges (tests); they are read when the assignments are switched on. */
+ * of two, 2..4096; 2..2048 in the two wide grains, whose keys are 16 bytes) move the kernel's tier edges (tests); they are
+ * read when the assignments are switched on. */
 typedef struct {
     uint64_t read;
     uint32_t tax_id;
@@ -411,6 +418,20 @@ int mtsv_batch_set_assignments(mtsv_batch *b, int mode);
  * A host batch run in MTSV_ASSIGN_ONLY keeps none of its hits: mtsv_batch_download after leaving that mode, without a new
  * run, is MTSV_E_ARG. */
 int mtsv_batch_download_assignments(mtsv_batch *b, mtsv_assignment **a, uint64_t *n, float *device_ms);
+/* The grain of the assignments.  Legal only while they are MTSV_ASSIGN_OFF (MTSV_E_ARG otherwise, and nothing changes): the
+ * record arrays of a workspace hold one record size while they are on; switching off, changing the grain and switching on
+ * again is allowed.  A bad grain is MTSV_E_ARG.  mtsv_batch_download_assignments is MTSV_E_ARG unless the grain is
+ * MTSV_GRAIN_TAXID; mtsv_batch_download_assignments_gi is MTSV_E_ARG when it is, and when the mode is off; in everything else
+ * (the pool array, also for *n == 0; mtsv_free; device_ms; a second call) the two calls are alike. */
+#define MTSV_GRAIN_TAXID 0
+#define MTSV_GRAIN_TAXID_GI 1
+#define MTSV_GRAIN_LONG 2
+int mtsv_batch_set_assignment_grain(mtsv_batch *b, int grain);
+typedef struct {
+    uint64_t read;
+    uint32_t tax_id, gi, offset, edit;
+} mtsv_assignment_gi; /* 24 bytes */
+int mtsv_batch_download_assignments_gi(mtsv_batch *b, mtsv_assignment_gi **a, uint64_t *n, float *device_ms);
 void mtsv_batch_free(mtsv_batch *b);
 
 /* ---- result lines (host) ---------------------------------------------------------------- */
@@ -425,6 +446,12 @@ int mtsv_format_results(const mtsv_hit *hits, uint64_t n_hits, const char *ids,
  * on the hits of the same run.  MTSV_E_ARG: reads not in ascending order, a read >= n_reads.  Host only, needs no device. */
 int mtsv_format_assignments(const mtsv_assignment *a, uint64_t n, const char *ids, const uint64_t *id_off,
                             uint64_t n_reads, char **out, uint64_t *out_len);
+/* READ_ID:TAXID-GI-OFFSET=EDIT,... from wide assignments (mtsv_batch_download_assignments_gi), one line per read that has
+ * any, in the order given: nothing is sorted or de-duplicated.  On MTSV_GRAIN_LONG records byte-identical to
+ * mtsv_format_results(long_format = 1) on the hits of the same run.  MTSV_E_ARG: reads not in ascending order, a read
+ * >= n_reads.  Host only, needs no device. */
+int mtsv_format_assignments_gi(const mtsv_assignment_gi *a, uint64_t n, const char *ids, const uint64_t *id_off,
+                               uint64_t n_reads, char **out, uint64_t *out_len);
 /* frees what the library malloc'd, and returns arrays of its page-locked pool (mtsv_batch_download_assignments) to it */
 void mtsv_free(void *p);
 

@@ -8,9 +8,13 @@ when the library or a device is missing.
 """
 from ._lib import (  # noqa: F401
     ASSIGN_DTYPE,
+    ASSIGN_GI_DTYPE,
     ASSIGN_OFF,
     ASSIGN_ONLY,
     ASSIGN_WITH_HITS,
+    GRAIN_LONG,
+    GRAIN_TAXID,
+    GRAIN_TAXID_GI,
     HIT_DTYPE,
     KEEP_MATCHED,
     KEEP_UNMATCHED,
@@ -31,6 +35,7 @@ from ._lib import (  # noqa: F401
     default_params,
     device_count,
     format_assignments,
+    format_assignments_gi,
     format_results,
     format_taxa_report,
     merge_taxa_reports,

@@ -21,6 +21,7 @@ class MtsvError(RuntimeError):
 E_ARG, E_IO, E_FORMAT, E_DEVICE, E_LIMIT, E_NOMEM = -1, -2, -3, -4, -5, -6
 MATCH_OFF, MATCH_WITH_HITS, MATCH_ONLY = 0, 1, 2  # MTSV_MATCH_*
 ASSIGN_OFF, ASSIGN_WITH_HITS, ASSIGN_ONLY = 0, 1, 2  # MTSV_ASSIGN_*
+GRAIN_TAXID, GRAIN_TAXID_GI, GRAIN_LONG = 0, 1, 2  # MTSV_GRAIN_*
 KEEP_UNMATCHED, KEEP_MATCHED = 0, 1  # MTSV_KEEP_*
 
 
@@ -70,6 +71,10 @@ TAXON_STATS_DTYPE = np.dtype({"names": ["tax_id", "only_hit", "only_best", "tied
 # mtsv_assignment: 8 + 4 + 4 = 16 bytes
 ASSIGN_DTYPE = np.dtype({"names": ["read", "tax_id", "edit"], "formats": ["<u8", "<u4", "<u4"], "offsets": [0, 8, 12], "itemsize": 16})
 
+# mtsv_assignment_gi: 8 + 4 * 4 = 24 bytes
+ASSIGN_GI_DTYPE = np.dtype({"names": ["read", "tax_id", "gi", "offset", "edit"], "formats": ["<u8", "<u4", "<u4", "<u4", "<u4"],
+                            "offsets": [0, 8, 12, 16, 20], "itemsize": 24})
+
 EXPORTS = [
     "mtsv_last_error", "mtsv_version", "mtsv_params_default", "mtsv_device_count",
     "mtsv_index_load", "mtsv_index_build", "mtsv_index_build_fasta", "mtsv_index_write",
@@ -85,6 +90,7 @@ EXPORTS = [
     "mtsv_batch_take_reads", "mtsv_batch_read_map", "mtsv_batch_download_reads",
     "mtsv_batch_copy_reads", "mtsv_batch_merge_runs",
     "mtsv_batch_set_assignments", "mtsv_batch_download_assignments", "mtsv_format_assignments",
+    "mtsv_batch_set_assignment_grain", "mtsv_batch_download_assignments_gi", "mtsv_format_assignments_gi",
 ]
 
 _lib = None
@@ -159,6 +165,9 @@ def lib():
         L.mtsv_batch_set_assignments.argtypes = [vp, i32]
         L.mtsv_batch_download_assignments.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_format_assignments.argtypes = [vp, u64, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_batch_set_assignment_grain.argtypes = [vp, i32]
+        L.mtsv_batch_download_assignments_gi.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_format_assignments_gi.argtypes = [vp, u64, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -441,6 +450,25 @@ class Batch:
         finally:
             lib().mtsv_free(out)
 
+    def set_assignment_grain(self, grain):
+        """mtsv_batch_set_assignment_grain: GRAIN_TAXID (16-byte records, download_assignments), GRAIN_TAXID_GI or
+        GRAIN_LONG (24-byte records, download_assignments_gi); only while the assignments are ASSIGN_OFF"""
+        _check(lib().mtsv_batch_set_assignment_grain(self.h, int(grain)))
+
+    def download_assignments_gi(self):
+        """(the last run's assignments as an ASSIGN_GI_DTYPE array -- per read one record per distinct (TaxID, GI, offset)
+        with the smallest edit (GRAIN_LONG) or per distinct (TaxID, GI) with the smallest (edit, offset) (GRAIN_TAXID_GI),
+        ascending --, device ms of the collapse kernels)"""
+        out, n, ms = C.c_void_p(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_batch_download_assignments_gi(self.h, C.byref(out), C.byref(n), C.byref(ms)))
+        try:
+            if n.value == 0:
+                return np.zeros(0, dtype=ASSIGN_GI_DTYPE), ms.value
+            raw = (C.c_ubyte * (n.value * ASSIGN_GI_DTYPE.itemsize)).from_address(out.value)
+            return np.frombuffer(raw, dtype=ASSIGN_GI_DTYPE).copy(), ms.value
+        finally:
+            lib().mtsv_free(out)
+
     def take_reads(self, src, keep=KEEP_UNMATCHED):
         """mtsv_batch_take_reads: this workspace's resident batch := the reads of src's last run whose match flag is clear
         (KEEP_MATCHED: set), handed over on the device; returns (n_kept, bases_kept, device ms of the kernels)"""
@@ -522,6 +550,21 @@ def format_assignments(a, read_ids):
     np.cumsum([len(i.encode()) + 1 for i in read_ids], out=off[1:])
     out, n = C.c_void_p(), C.c_uint64()
     _check(lib().mtsv_format_assignments(a.ctypes.data, len(a), blob, off.ctypes.data, len(read_ids), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value).decode()
+    finally:
+        lib().mtsv_free(out)
+
+
+def format_assignments_gi(a, read_ids):
+    """mtsv_format_assignments_gi: the long-format result lines (READ_ID:TAX-GI-OFFSET=EDIT,...) from wide assignments,
+    as one str"""
+    a = np.ascontiguousarray(a, dtype=ASSIGN_GI_DTYPE)
+    blob = b"".join(i.encode() + b"\0" for i in read_ids)
+    off = np.zeros(len(read_ids) + 1, dtype=np.uint64)
+    np.cumsum([len(i.encode()) + 1 for i in read_ids], out=off[1:])
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_assignments_gi(a.ctypes.data, len(a), blob, off.ctypes.data, len(read_ids), C.byref(out), C.byref(n)))
     try:
         return C.string_at(out.value, n.value).decode()
     finally:

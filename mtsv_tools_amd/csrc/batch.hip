@@ -548,7 +548,9 @@ void Batch::set_assignments(int mode) {
         };
         assign.lane_max = env_u("MTSV_COLLAPSE_LANE_MAX", kCollapseLaneMax, 1, kCollapseLaneMax);
         assign.wave_max = env_u("MTSV_COLLAPSE_WAVE_MAX", 64, 1, 64);
-        uint32_t lds = env_u("MTSV_COLLAPSE_LDS_MAX", kCollapseLdsKeys, 2, kCollapseLdsKeys);
+        // (a 16-byte key halves what the 32 KiB of the LDS tier hold)
+        const uint32_t lds_keys = assign.grain == MTSV_GRAIN_TAXID ? kCollapseLdsKeys : kCollapseLdsKeysWide;
+        uint32_t lds = env_u("MTSV_COLLAPSE_LDS_MAX", lds_keys, 2, lds_keys);
         while (lds & (lds - 1)) lds &= lds - 1;  // (a power of two: the largest one not above what was asked for)
         assign.lds_max = lds;
         assign.trace = getenv("MTSV_TRACE") != nullptr;
@@ -557,6 +559,20 @@ void Batch::set_assignments(int mode) {
         for (auto& t : assign.tiers) t = 0;
     }
     assign.mode = mode;
+}
+
+void Batch::set_assignment_grain(int grain) {
+    if (parent) throw std::runtime_error("internal: the assignments belong to the workspace's owner");
+    if (grain != MTSV_GRAIN_TAXID && grain != MTSV_GRAIN_TAXID_GI && grain != MTSV_GRAIN_LONG) throw std::runtime_error("arg: bad assignment grain");
+    if (assign.mode != MTSV_ASSIGN_OFF)
+        throw std::runtime_error("arg: the grain changes only while the assignments are off (mtsv_batch_set_assignments): the record arrays hold one record size");
+    if (grain == assign.grain) return;
+    assign.grain = grain;
+    // the pinned array a host batch left was sized in the old records
+    if (h_assign_stage) pinned_hits_release(h_assign_stage);
+    h_assign_stage = nullptr;
+    h_assign_cap = staged_assign = last_total_assign = 0;
+    assign_staged_valid = false;
 }
 
 void Batch::collapse_begin() {
@@ -571,28 +587,31 @@ void Batch::collapse_trace(const char* what) {
     for (auto& sg : segments) n_a += sg.a_count, n_h += sg.count;
     std::lock_guard<std::mutex> lk(assign.mu);
     fprintf(stderr, "[collapse] %s: %llu launches, %.3f ms, %llu hits -> %llu assignments; reads by tier: lane %llu, wavefront %llu, lds %llu, global %llu "
-                    "(tiers end at %u / %u / %u hits)\n",
+                    "(tiers end at %u / %u / %u hits)%s\n",
             what, (unsigned long long)assign.launches, assign.ms, (unsigned long long)n_h, (unsigned long long)n_a, (unsigned long long)assign.tiers[0],
             (unsigned long long)assign.tiers[1], (unsigned long long)assign.tiers[3], (unsigned long long)assign.tiers[4], assign.lane_max, assign.wave_max,
-            assign.lds_max);
+            assign.lds_max, assign.grain == MTSV_GRAIN_LONG ? " [grain long]" : assign.grain == MTSV_GRAIN_TAXID_GI ? " [grain taxid-gi]" : "");
 }
 
 void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
     CollapseScratch& c = collapse;
+    const Assignments& as = (parent ? parent : this)->assign;
+    const uint64_t rec = as.rec_bytes(), key_bytes = as.key_bytes();
     uint64_t dummy = 0;
     if (n_hits >= (1ull << 32)) throw std::runtime_error("limit: 2^32 hits or more in one pass of the collapse");
     if (!c.d_ctr) dev_alloc(&c.d_ctr, kCollapseCounters, &dummy);
     if (!c.h_ctr) HIP_CHECK(hipHostMalloc((void**)&c.h_ctr, kCollapseCounters * sizeof(uint64_t), hipHostMallocMapped));
     for (auto& e : c.ev)
         if (!e) HIP_CHECK(hipEventCreate(&e));
-    if (n_hits > c.cap_hits || !c.keys) {
+    if (n_hits > c.cap_hits || !c.keys || c.key_bytes != key_bytes) {
         HIP_CHECK(hipStreamSynchronize(stream));
         for (void* p : {(void*)c.keys, (void*)c.flags, (void*)c.place, (void*)c.tiles}) (void)hipFree(p);
         c.keys = c.tiles = nullptr;
         c.flags = c.place = nullptr;
         c.cap_hits = 0;
         const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(n_hits + n_hits / 8, 1ull << 16), 0xffffffffull);
-        dev_alloc(&c.keys, cap, &dummy);
+        dev_alloc(&c.keys, cap * (key_bytes / 8), &dummy);
+        c.key_bytes = key_bytes;
         dev_alloc(&c.flags, cap + 1, &dummy);
         dev_alloc(&c.place, cap + 1, &dummy);
         dev_alloc(&c.tiles, (uint64_t)scan_tiles((uint32_t)cap) + 1, &dummy);
@@ -607,12 +626,12 @@ void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
         dev_alloc(&c.list, cap, &dummy);
         c.cap_reads = cap;
     }
-    if (n_assign_total + n_hits > assign_cap || !d_assign) {
+    if ((n_assign_total + n_hits) * rec > assign_cap_bytes || !d_assign) {
         // grow the result array, keeping what earlier passes produced
-        const uint64_t ncap = std::max<uint64_t>(std::max(assign_cap * 2, n_assign_total + n_hits), 1ull << 16);
-        uint4* na = nullptr;
+        const uint64_t ncap = std::max<uint64_t>(std::max(assign_cap_bytes * 2, (n_assign_total + n_hits) * rec), (1ull << 16) * rec);
+        uint8_t* na = nullptr;
         dev_alloc(&na, ncap, &dummy);
-        if (n_assign_total) HIP_CHECK(hipMemcpyAsync(na, d_assign, n_assign_total * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
+        if (n_assign_total) HIP_CHECK(hipMemcpyAsync(na, d_assign, n_assign_total * rec, hipMemcpyDeviceToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         // run_host may be copying an earlier range's assignments out of the old array on the owner's copy stream (and another
         // lane's thread may be issuing such a copy right now: the commit mutex covers the pointer swap), as with d_hits
@@ -622,7 +641,7 @@ void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
         if (root->commit_mu && root->copy_stream2) HIP_CHECK(hipStreamSynchronize(root->copy_stream2));
         (void)hipFree(d_assign);
         d_assign = na;
-        assign_cap = ncap;
+        assign_cap_bytes = ncap;
     }
 }
 
@@ -632,8 +651,8 @@ void Batch::collapse_enqueue(uint32_t n_pass_reads, const uint32_t* strand_nout,
     CollapseScratch& c = collapse;
     c.pending_hits = n_hits;
     HIP_CHECK(hipEventRecord(c.ev[0], stream));
-    launch_collapse(stream, n_pass_reads, strand_nout, out_off, hits, (uint32_t)n_hits, as.lane_max, as.wave_max, as.lds_max, c.keys, c.flags, c.place,
-                    c.tiles, c.list, c.d_ctr, d_assign + n_assign_total);
+    launch_collapse(stream, as.grain, n_pass_reads, strand_nout, out_off, hits, (uint32_t)n_hits, as.lane_max, as.wave_max, as.lds_max, c.keys, c.flags,
+                    c.place, c.tiles, c.list, c.d_ctr, d_assign + n_assign_total * as.rec_bytes());
     HIP_CHECK(hipEventRecord(c.ev[1], stream));
     // the pass's record count reaches the host with the synchronise the pass ends with anyway
     launch_publish(stream, c.d_ctr, c.h_ctr, kCollapseCounters);
@@ -654,14 +673,18 @@ uint64_t Batch::collapse_commit() {
     return cnt;
 }
 
-void Batch::download_assignments(mtsv_assignment** a, uint64_t* n, float* device_ms) {
+void Batch::download_assignments(void** a, uint64_t* n, float* device_ms, bool wide) {
     if (parent) throw std::runtime_error("internal: the assignments belong to the workspace's owner");
     if (assign.mode == MTSV_ASSIGN_OFF) throw std::runtime_error("arg: the assignments of this workspace are not switched on (mtsv_batch_set_assignments)");
+    if (wide != (assign.grain != MTSV_GRAIN_TAXID))
+        throw std::runtime_error(wide ? "arg: the grain of this workspace is MTSV_GRAIN_TAXID: its records are mtsv_assignment (mtsv_batch_download_assignments)"
+                                      : "arg: the grain of this workspace is not MTSV_GRAIN_TAXID: its records are mtsv_assignment_gi (mtsv_batch_download_assignments_gi)");
+    const uint64_t rec = assign.rec_bytes();
     HIP_CHECK(hipSetDevice(di->device));
     uint64_t total = 0;
     for (auto& sg : segments) total += sg.a_count;
     last_total_assign = total;
-    mtsv_assignment* out = nullptr;
+    uint8_t* out = nullptr;
     if (assign_staged_valid && h_assign_stage && staged_assign == total) {  // run_host already brought them over
         out = h_assign_stage;
         h_assign_stage = nullptr;
@@ -669,12 +692,12 @@ void Batch::download_assignments(mtsv_assignment** a, uint64_t* n, float* device
         assign_staged_valid = false;
     } else {
         uint64_t cap = 0;
-        out = (mtsv_assignment*)pinned_hits_alloc((total + 1) / 2, &cap);  // (the pool counts in 32-byte hits)
+        out = (uint8_t*)pinned_hits_alloc((total * rec + 31) / 32, &cap);  // (the pool counts in 32-byte hits)
         uint64_t at = 0;
         // (every run is synchronous: no lane has a pass in flight)
         for (auto& sg : segments) {
             if (!sg.a_count) continue;
-            const hipError_t e = hipMemcpy(out + at, sg.lane->d_assign + sg.a_offset, sg.a_count * sizeof(mtsv_assignment), hipMemcpyDeviceToHost);
+            const hipError_t e = hipMemcpy(out + at * rec, sg.lane->d_assign + sg.a_offset * rec, sg.a_count * rec, hipMemcpyDeviceToHost);
             if (e != hipSuccess) {
                 pinned_hits_release(out);
                 throw_hip(e, "hipMemcpy(assignments)", __FILE__, __LINE__);
@@ -1887,10 +1910,11 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
         h_hits_stage = pinned_hits_alloc(last_total_hits ? last_total_hits + last_total_hits / 64 : n + n / 8, &h_hits_cap);
     }
     const bool stage_assign = assign.mode != MTSV_ASSIGN_OFF;
+    const uint64_t a_rec = assign.rec_bytes();
     if (stage_assign && !h_assign_stage) {
-        uint64_t cap = 0;  // (in 32-byte hits: two records each)
-        h_assign_stage = (mtsv_assignment*)pinned_hits_alloc(((last_total_assign ? last_total_assign + last_total_assign / 64 : n + n / 8) + 1) / 2, &cap);
-        h_assign_cap = 2 * cap;
+        uint64_t cap = 0;  // (in 32-byte hits: two 16-byte records each, or four 24-byte ones in three)
+        h_assign_stage = (uint8_t*)pinned_hits_alloc(((last_total_assign ? last_total_assign + last_total_assign / 64 : n + n / 8) * a_rec + 31) / 32, &cap);
+        h_assign_cap = cap * 32 / a_rec;
     }
     if (trace) fprintf(stderr, "[run_host] result array of %llu hits ready at %.2f ms\n", (unsigned long long)h_hits_cap, (now_s() - t_entry) * 1e3);
     const uint64_t n_lanes_used = n >= ls.size() * kLaneMinReads ? ls.size() : 1;
@@ -2084,7 +2108,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
             }
             if (rg.a_cnt && stage_assign) {
                 assign_stage_reserve(staged_assign + rg.a_cnt);
-                HIP_CHECK(hipMemcpyAsync(h_assign_stage + staged_assign, rg.lane->d_assign + rg.a_off, rg.a_cnt * sizeof(mtsv_assignment),
+                HIP_CHECK(hipMemcpyAsync(h_assign_stage + staged_assign * a_rec, rg.lane->d_assign + rg.a_off * a_rec, rg.a_cnt * a_rec,
                                          hipMemcpyDeviceToHost, copy_stream2));
                 staged_assign += rg.a_cnt;
             }
@@ -2229,17 +2253,18 @@ void Batch::stage_reserve(uint64_t n_hits_needed) {
     h_hits_cap = ncap;
 }
 
-// the same for the assignments' pinned array (two 16-byte records per pool unit of 32 bytes)
+// the same for the assignments' pinned array (records of the grain's size in pool units of 32 bytes)
 void Batch::assign_stage_reserve(uint64_t n_needed) {
     if (n_needed <= h_assign_cap) return;
     if (getenv("MTSV_TRACE")) fprintf(stderr, "[run_host] assignment array grows %llu -> %llu records\n", (unsigned long long)h_assign_cap, (unsigned long long)n_needed);
     HIP_CHECK(hipStreamSynchronize(copy_stream2));
     uint64_t ncap = 0;
-    auto* na = (mtsv_assignment*)pinned_hits_alloc((std::max<uint64_t>(2 * h_assign_cap, n_needed) + 1) / 2, &ncap);
-    if (staged_assign) memcpy(na, h_assign_stage, staged_assign * sizeof(mtsv_assignment));
+    const uint64_t rec = assign.rec_bytes();
+    auto* na = (uint8_t*)pinned_hits_alloc((std::max<uint64_t>(2 * h_assign_cap, n_needed) * rec + 31) / 32, &ncap);
+    if (staged_assign) memcpy(na, h_assign_stage, staged_assign * rec);
     if (h_assign_stage) pinned_hits_release(h_assign_stage);
     h_assign_stage = na;
-    h_assign_cap = 2 * ncap;
+    h_assign_cap = ncap * 32 / rec;
 }
 
 // The result array is pinned host memory from the pool; the caller owns it until mtsv_hits_free.

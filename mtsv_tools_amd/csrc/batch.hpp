@@ -237,9 +237,15 @@ struct Batch {
     // Assignments (k_collapse.hip): per read of the last run one (read, tax_id, smallest edit) record per distinct TaxID,
     // ascending by TaxID -- the default results line of mtsv-binner, reduced on the device.  The mode, the thresholds and the
     // times belong to the owner; every lane has a result array and a scratch of its own, created by its first pass with the
-    // assignments on.  Like the flags they describe one run.
+    // assignments on.  Like the flags they describe one run.  The grain (mtsv_batch_set_assignment_grain) decides what a
+    // record is: MTSV_GRAIN_TAXID the 16-byte one above, MTSV_GRAIN_TAXID_GI and MTSV_GRAIN_LONG the 24-byte mtsv_assignment_gi,
+    // one per (TaxID, GI) or per (TaxID, GI, offset).  It changes only while the mode is off, so the record arrays of a
+    // workspace hold records of one size while they are in use; every count and offset of assignments is in records.
     struct Assignments {
         int mode = MTSV_ASSIGN_OFF;
+        int grain = MTSV_GRAIN_TAXID;
+        uint64_t rec_bytes() const { return grain == MTSV_GRAIN_TAXID ? sizeof(mtsv_assignment) : sizeof(mtsv_assignment_gi); }
+        uint64_t key_bytes() const { return grain == MTSV_GRAIN_TAXID ? 8 : 16; }
         // a read of up to lane_max hits is reduced by one lane, up to wave_max by its wavefront, up to lds_max by a workgroup
         // in LDS, a larger one by a workgroup in global memory (MTSV_COLLAPSE_LANE_MAX, _WAVE_MAX, _LDS_MAX: tests)
         uint32_t lane_max = kCollapseLaneMax, wave_max = 64, lds_max = kCollapseLdsKeys;
@@ -252,15 +258,16 @@ struct Batch {
     Assignments assign;
     // run_host: a finished range's assignments leave for this pinned array (pool) on the result copy stream, in read order,
     // like its hits; mtsv_batch_download_assignments hands the array out.  (owner only)
-    mtsv_assignment* h_assign_stage = nullptr;
+    uint8_t* h_assign_stage = nullptr;  // records of assign.rec_bytes()
     uint64_t h_assign_cap = 0, staged_assign = 0, last_total_assign = 0;
     bool assign_staged_valid = false;
     bool host_hits_dropped = false;  // the last run was a host batch in MTSV_ASSIGN_ONLY: its hits were never staged and the lanes' arrays were recycled
     void assign_stage_reserve(uint64_t n_needed);
-    uint4* d_assign = nullptr;  // the lane's assignments (mtsv_assignment), those of a pass behind those of the passes before
-    uint64_t assign_cap = 0, n_assign_total = 0;
+    uint8_t* d_assign = nullptr;  // the lane's assignments (records of the grain), those of a pass behind those of the passes before
+    uint64_t assign_cap_bytes = 0, n_assign_total = 0;
     struct CollapseScratch {
-        uint64_t* keys = nullptr;   // cap_hits sort keys, mirroring a pass's hits
+        uint64_t* keys = nullptr;   // cap_hits sort keys of key_bytes each, mirroring a pass's hits
+        uint64_t key_bytes = 0;
         uint32_t *flags = nullptr, *place = nullptr;  // cap_hits + 1 each
         uint64_t* tiles = nullptr;  // the scan's tile sums
         uint32_t* list = nullptr;   // cap_reads: the reads left to k_collapse_heavy
@@ -273,8 +280,10 @@ struct Batch {
     CollapseScratch collapse;
     bool assign_only() const { return (parent ? parent : this)->assign.mode == MTSV_ASSIGN_ONLY; }
     void set_assignments(int mode);
+    void set_assignment_grain(int grain);
     // the assignments of the last run, in read order, in a pinned array of the pool (*n may be 0: *a is still to be freed)
-    void download_assignments(mtsv_assignment** a, uint64_t* n, float* device_ms);
+    // (grain: the one the caller's record type belongs to -- MTSV_GRAIN_TAXID, or anything else for the 24-byte records)
+    void download_assignments(void** a, uint64_t* n, float* device_ms, bool wide);
     void merge_runs(Batch* const* srcs, int n_srcs, float* device_ms);
     void read_map(std::vector<uint64_t>& map);
     void download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& read_off);

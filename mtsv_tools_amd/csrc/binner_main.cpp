@@ -25,6 +25,7 @@
 //   --merge-on-gpu    with --index a,b,.. and ONE device: every chunk resident there, and a call's hits merged per read in
 //                     HBM (mtsv_batch_copy_reads, mtsv_batch_merge_runs) -- the reads go up once per call, and --report,
 //                     --matched / --unmatched work on the merged hits as they do for one index
+#include <cstddef>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -594,11 +595,22 @@ int main(int argc, char** argv) {
     // MTSV_CLI_ASSIGN=1: the default results format is written from assignments -- the smallest edit per read and TaxID,
     // reduced on the device (mtsv_batch_set_assignments, MTSV_ASSIGN_ONLY: no hit crosses to the host) -- where one workspace
     // per worker holds a call's hits: a single index (behind --filter-index: the database's workspace) or the collector of
-    // --merge-on-gpu.  The file is the same byte for byte.  --output-format long needs the hits and stays on them.
+    // --merge-on-gpu.  The file is the same byte for byte.  --output-format long stays on the hits under this switch.
     // The default is 0 (profiles/README.md r14: the measurement and what it decided).
     bool cli_assign = false;
     if (const char* e = getenv("MTSV_CLI_ASSIGN")) cli_assign = atoi(e) != 0;
     cli_assign = cli_assign && have_results && !long_fmt && (!chunked || merged) && match_mode != MTSV_MATCH_ONLY;
+    // MTSV_CLI_ASSIGN_LONG=1: the same for --output-format long -- the workspace in MTSV_GRAIN_LONG, one 24-byte record per read
+    // and (TaxID, GI, offset) with the smallest edit, the file written by mtsv_format_assignments_gi, byte for byte the same.
+    // A switch of its own: MTSV_CLI_ASSIGN alone leaves long output on the hits.  Default 0, not measured yet.
+    bool cli_assign_long = false;
+    if (const char* e = getenv("MTSV_CLI_ASSIGN_LONG")) cli_assign_long = atoi(e) != 0;
+    cli_assign_long = cli_assign_long && have_results && long_fmt && (!chunked || merged) && match_mode != MTSV_MATCH_ONLY;
+    const bool cli_records = cli_assign || cli_assign_long;  // the results file is written from assignment records
+    const uint64_t a_rec = cli_assign_long ? sizeof(mtsv_assignment_gi) : sizeof(mtsv_assignment);
+    // (both record types begin with the 8-byte read: the one place that relies on it)
+    static_assert(offsetof(mtsv_assignment, read) == 0 && offsetof(mtsv_assignment_gi, read) == 0, "records begin with the read");
+    auto record_read = [a_rec](uint8_t* records, uint64_t i) -> uint64_t& { return *reinterpret_cast<uint64_t*>(records + i * a_rec); };
     std::vector<std::string> filter_paths;
     for (size_t at = 0; filtered && at <= a.filter_index.size();) {
         size_t c = a.filter_index.find(',', at);
@@ -738,7 +750,8 @@ int main(int argc, char** argv) {
                 }
                 if (rc == MTSV_OK && !a.report.empty()) rc = mtsv_batch_set_taxa_report(ws_ready[wk], 1);
                 if (rc == MTSV_OK && partition) rc = mtsv_batch_set_match_flags(ws_ready[wk], match_mode);
-                if (rc == MTSV_OK && cli_assign) rc = mtsv_batch_set_assignments(ws_ready[wk], MTSV_ASSIGN_ONLY);
+                if (rc == MTSV_OK && cli_assign_long) rc = mtsv_batch_set_assignment_grain(ws_ready[wk], MTSV_GRAIN_LONG);
+                if (rc == MTSV_OK && cli_records) rc = mtsv_batch_set_assignments(ws_ready[wk], MTSV_ASSIGN_ONLY);
                 ws_rc[wk] = rc;
                 if (rc != MTSV_OK) ws_msg[wk] = mtsv_last_error();  // (thread-local)
                 return;
@@ -757,7 +770,8 @@ int main(int argc, char** argv) {
             }
             if (rc == MTSV_OK && !a.report.empty()) rc = mtsv_batch_set_taxa_report(ws_ready[wk], 1);  // (after the warm-up reads)
             if (rc == MTSV_OK && partition) rc = mtsv_batch_set_match_flags(ws_ready[wk], match_mode);
-            if (rc == MTSV_OK && cli_assign) rc = mtsv_batch_set_assignments(ws_ready[wk], MTSV_ASSIGN_ONLY);  // (after the warm-up reads)
+            if (rc == MTSV_OK && cli_assign_long) rc = mtsv_batch_set_assignment_grain(ws_ready[wk], MTSV_GRAIN_LONG);
+            if (rc == MTSV_OK && cli_records) rc = mtsv_batch_set_assignments(ws_ready[wk], MTSV_ASSIGN_ONLY);  // (after the warm-up reads)
             ws_rc[wk] = rc;
             if (rc != MTSV_OK) ws_msg[wk] = mtsv_last_error();  // (thread-local)
         };
@@ -807,8 +821,9 @@ int main(int argc, char** argv) {
         uint64_t n_hits = 0;
         uint64_t read_first = 0;  // the batch's first read in the numbering of its call (the formatter subtracts it)
         std::shared_ptr<void> hits_owner;  // the result array of the library call the batch was part of
-        // MTSV_CLI_ASSIGN=1: the batch's assignments instead (the same slicing and numbering), and their array
-        mtsv_assignment* assigns = nullptr;
+        // MTSV_CLI_ASSIGN=1, MTSV_CLI_ASSIGN_LONG=1: the batch's assignments instead (the same slicing and numbering; records of
+        // a_rec bytes that begin with the read), and their array
+        uint8_t* assigns = nullptr;
         uint64_t n_assigns = 0;
         std::shared_ptr<void> assigns_owner;
         std::shared_ptr<uint64_t> flags;   // --matched / --unmatched: the match flags of that call; read i of the batch is bit read_first + i
@@ -1009,8 +1024,8 @@ int main(int argc, char** argv) {
             const double t_f0 = now();
             // write_assignments over slices of the batch's hits (cut between reads), one thread each
             const uint64_t n_reads = w->rb->n();
-            const uint64_t n_items = cli_assign ? w->n_assigns : w->n_hits;
-            auto read_of = [&](uint64_t i) { return cli_assign ? w->assigns[i].read : w->hits[i].read; };
+            const uint64_t n_items = cli_records ? w->n_assigns : w->n_hits;
+            auto read_of = [&](uint64_t i) { return cli_records ? record_read(w->assigns, i) : w->hits[i].read; };
             const unsigned parts = n_items >= (1u << 16) ? host_threads : 1;
             std::vector<uint64_t> cut(parts + 1, n_items);
             cut[0] = 0;
@@ -1076,11 +1091,13 @@ int main(int argc, char** argv) {
             std::vector<std::string> msg(parts);
             auto fmt = [&](unsigned k) {
                 if (out_fd < 0) return;  // (no results file: --matched / --unmatched alone)
-                if (cli_assign) {
+                if (cli_records) {
                     if (w->read_first)
-                        for (uint64_t i = cut[k]; i < cut[k + 1]; i++) w->assigns[i].read -= w->read_first;
-                    rc[k] = mtsv_format_assignments(w->assigns + cut[k], cut[k + 1] - cut[k], w->rb->ids.data(), w->rb->id_off.data(), n_reads, &text[k],
-                                                    &len[k]);
+                        for (uint64_t i = cut[k]; i < cut[k + 1]; i++) record_read(w->assigns, i) -= w->read_first;
+                    rc[k] = cli_assign_long ? mtsv_format_assignments_gi((const mtsv_assignment_gi*)(w->assigns + cut[k] * a_rec), cut[k + 1] - cut[k],
+                                                                         w->rb->ids.data(), w->rb->id_off.data(), n_reads, &text[k], &len[k])
+                                            : mtsv_format_assignments((const mtsv_assignment*)(w->assigns + cut[k] * a_rec), cut[k + 1] - cut[k],
+                                                                      w->rb->ids.data(), w->rb->id_off.data(), n_reads, &text[k], &len[k]);
                     if (rc[k] != MTSV_OK) msg[k] = mtsv_last_error();  // thread-local
                     return;
                 }
@@ -1181,8 +1198,12 @@ int main(int argc, char** argv) {
             int rc;
             mtsv_hit* hits = nullptr;
             uint64_t n_hits = 0;
-            mtsv_assignment* assigns = nullptr;
+            uint8_t* assigns = nullptr;  // records of a_rec bytes
             uint64_t n_assigns = 0;
+            auto download_records = [&](mtsv_batch* from) {
+                return cli_assign_long ? mtsv_batch_download_assignments_gi(from, (mtsv_assignment_gi**)&assigns, &n_assigns, nullptr)
+                                       : mtsv_batch_download_assignments(from, (mtsv_assignment**)&assigns, &n_assigns, nullptr);
+            };
             if (merged) {
                 auto& w = group[0];
                 if (w->rb->n() > merge_reads || w->rb->bases.size() > merge_bases) {
@@ -1197,7 +1218,7 @@ int main(int argc, char** argv) {
                 for (size_t c = 1; c < cw.size() && rc == MTSV_OK; c++) rc = mtsv_batch_copy_reads(cw[c], cw[0], nullptr);
                 for (size_t c = 0; c < cw.size() && rc == MTSV_OK; c++) rc = mtsv_batch_run(cw[c], &p);
                 if (rc == MTSV_OK) rc = mtsv_batch_merge_runs(ws, cw.data(), (int)cw.size(), nullptr);
-                if (rc == MTSV_OK) rc = cli_assign ? mtsv_batch_download_assignments(ws, &assigns, &n_assigns, nullptr) : mtsv_batch_download(ws, &hits, &n_hits);
+                if (rc == MTSV_OK) rc = cli_records ? download_records(ws) : mtsv_batch_download(ws, &hits, &n_hits);
             } else if (chunked) {
                 auto& w = group[0];
                 rc = mtsv_bin_batch_chunks(idx.data(), chunk_dev.data(), (int)idx.size(), w->rb->bases.data(), w->rb->off.data(), w->rb->n(), &p,
@@ -1228,7 +1249,7 @@ int main(int argc, char** argv) {
                         rc = mtsv_batch_run(next, &p);
                     }
                 }
-                if (rc == MTSV_OK && cli_assign) rc = mtsv_batch_download_assignments(ws, &assigns, &n_assigns, nullptr);
+                if (rc == MTSV_OK && cli_records) rc = download_records(ws);
                 else if (rc == MTSV_OK && match_mode != MTSV_MATCH_ONLY) rc = mtsv_batch_download(ws, &hits, &n_hits);  // (flags only: there are none)
             }
             std::shared_ptr<uint64_t> flags;
@@ -1265,9 +1286,15 @@ int main(int argc, char** argv) {
             uint64_t first = 0, at = 0, a_at = 0;
             for (auto& w : group) {
                 const uint64_t nr = w->rb->n();
-                if (cli_assign) {
-                    const uint64_t a_end = (uint64_t)(std::partition_point(assigns + a_at, assigns + n_assigns, [&](const mtsv_assignment& x) { return x.read < first + nr; }) - assigns);
-                    w->assigns = assigns + a_at;
+                if (cli_records) {
+                    uint64_t lo = a_at, hi = n_assigns;  // the first record of a later batch
+                    while (lo < hi) {
+                        const uint64_t mid = lo + (hi - lo) / 2;
+                        if (record_read(assigns, mid) < first + nr) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    const uint64_t a_end = lo;
+                    w->assigns = assigns + a_at * a_rec;
                     w->n_assigns = a_end - a_at;
                     w->assigns_owner = a_owner;
                     a_at = a_end;

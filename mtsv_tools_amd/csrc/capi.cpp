@@ -470,7 +470,18 @@ int mtsv_batch_set_assignments(mtsv_batch* b, int mode) {
 
 int mtsv_batch_download_assignments(mtsv_batch* b, mtsv_assignment** a, uint64_t* n, float* device_ms) {
     if (!b || !a || !n) return fail_arg("null argument");
-    GUARD(b->impl.download_assignments(a, n, device_ms))
+    GUARD(b->impl.download_assignments((void**)a, n, device_ms, false))
+}
+
+static_assert(sizeof(mtsv_assignment) == 16 && sizeof(mtsv_assignment_gi) == 24, "the record sizes of the grains");
+int mtsv_batch_set_assignment_grain(mtsv_batch* b, int grain) {
+    if (!b) return fail_arg("null argument");
+    GUARD(b->impl.set_assignment_grain(grain))
+}
+
+int mtsv_batch_download_assignments_gi(mtsv_batch* b, mtsv_assignment_gi** a, uint64_t* n, float* device_ms) {
+    if (!b || !a || !n) return fail_arg("null argument");
+    GUARD(b->impl.download_assignments((void**)a, n, device_ms, true))
 }
 
 int mtsv_batch_download(mtsv_batch* b, mtsv_hit** hits, uint64_t* n_hits) {
@@ -809,6 +820,45 @@ int mtsv_format_assignments(const mtsv_assignment* a, uint64_t n, const char* id
             for (uint64_t k = i; k < j; k++) {
                 if (k != i) buf.p[buf.n++] = ',';
                 buf.put(a[k].tax_id);
+                buf.p[buf.n++] = '=';
+                buf.put(a[k].edit);
+            }
+            buf.p[buf.n++] = '\n';
+            i = j;
+        }
+        buf.room(1);
+        buf.p[buf.n] = 0;
+        *out = buf.p;
+        *out_len = buf.n;
+        buf.p = nullptr;  // the caller's now (mtsv_free)
+    })
+}
+
+// the long lines from the device's wide assignments: already one per key of the grain, in the grain's order
+int mtsv_format_assignments_gi(const mtsv_assignment_gi* a, uint64_t n, const char* ids, const uint64_t* id_off, uint64_t n_reads, char** out,
+                               uint64_t* out_len) {
+    if ((!a && n) || !ids || !id_off || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        Text buf;
+        uint64_t i = 0;
+        while (i < n) {
+            const uint64_t r = a[i].read;
+            if (r >= n_reads) throw std::runtime_error("arg: assignment refers to a read outside the batch");
+            if (i && r < a[i - 1].read) throw std::runtime_error("arg: assignments are not ordered by read");
+            uint64_t j = i;
+            while (j < n && a[j].read == r) j++;
+            const uint64_t id_len = strnlen(ids + id_off[r], id_off[r + 1] - id_off[r]);
+            buf.room(id_len + 2 + (j - i) * 44 + 1);  // "tax-gi-offset=edit," is at most 10 + 1 + 10 + 1 + 10 + 1 + 10 + 1 characters
+            memcpy(buf.p + buf.n, ids + id_off[r], id_len);
+            buf.n += id_len;
+            buf.p[buf.n++] = ':';
+            for (uint64_t k = i; k < j; k++) {
+                if (k != i) buf.p[buf.n++] = ',';
+                buf.put(a[k].tax_id);
+                buf.p[buf.n++] = '-';
+                buf.put(a[k].gi);
+                buf.p[buf.n++] = '-';
+                buf.put(a[k].offset);
                 buf.p[buf.n++] = '=';
                 buf.put(a[k].edit);
             }

@@ -253,11 +253,17 @@ void launch_merge_copy(hipStream_t s, const MergePart* parts, uint32_t n_parts, 
 // mtsv_assignment) and [kCollapseCtrLane ..] the reads every tier took.  Tiers by a read's hit count: up to lane_max
 // (1 .. kCollapseLaneMax) a lane, up to wave_max (<= 64) its wavefront, up to lds_max (a power of two <= kCollapseLdsKeys) a
 // workgroup sorting in LDS, beyond that a workgroup sorting in `keys` itself.
-constexpr uint32_t kCollapseLaneMax = 16, kCollapseLdsKeys = 4096;
+// grain (the values of MTSV_GRAIN_*): kCollapseGrainTaxid is the above.  The wide grains keep GI and offset: per read one
+// 24-byte record (mtsv_assignment_gi) per distinct (tax_id, gi, offset) with the smallest edit, ascending by the triple
+// (kCollapseGrainLong, binner.rs:320-352), or per distinct (tax_id, gi) with the smallest (edit, offset), ascending by the pair
+// (kCollapseGrainTaxidGi, collapse.rs:603-625).  Their keys are 16 bytes (keys: n_hits of those, 16-byte aligned) and their
+// lds_max ends at kCollapseLdsKeysWide.
+constexpr uint32_t kCollapseLaneMax = 16, kCollapseLdsKeys = 4096, kCollapseLdsKeysWide = 2048;
+constexpr int kCollapseGrainTaxid = 0, kCollapseGrainTaxidGi = 1, kCollapseGrainLong = 2;
 constexpr uint32_t kCollapseCtrTotal = 0, kCollapseCtrList = 1, kCollapseCtrTicket = 2, kCollapseCtrLane = 3, kCollapseCtrWave = 4,
                    kCollapseCtrListed = 5, kCollapseCtrLds = 6, kCollapseCtrGlobal = 7, kCollapseCounters = 8;
-void launch_collapse(hipStream_t s, uint32_t n_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits, uint32_t n_hits,
-                     uint32_t lane_max, uint32_t wave_max, uint32_t lds_max, uint64_t* keys, uint32_t* flags, uint32_t* place, uint64_t* tile_sums,
-                     uint32_t* list, uint64_t* ctr, uint4* out);
+void launch_collapse(hipStream_t s, int grain, uint32_t n_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits,
+                     uint32_t n_hits, uint32_t lane_max, uint32_t wave_max, uint32_t lds_max, void* keys, uint32_t* flags, uint32_t* place,
+                     uint64_t* tile_sums, uint32_t* list, uint64_t* ctr, void* out);
 
 }  // namespace mtsv
