@@ -434,6 +434,64 @@ typedef struct {
 int mtsv_batch_download_assignments_gi(mtsv_batch *b, mtsv_assignment_gi **a, uint64_t *n, float *device_ms);
 void mtsv_batch_free(mtsv_batch *b);
 
+/* ---- folding runs: a chunked database larger than HBM, one chunk resident at a time -----------------------------------
+ * mtsv_batch_merge_runs needs every chunk of a database resident at once, a workspace each and one more.  A database that
+ * mtsv-chunk cut because it does not fit goes chunk by chunk instead: make chunk c resident, run the reads against it with
+ * the assignments on, fold the run's assignment records into an mtsv_fold, free the workspace and the index, load chunk
+ * c + 1.  The fold holds RECORDS, not hits: the sorted union of every list folded so far with one record per key -- what
+ * mtsv-collapse makes of the per-chunk result files (src/collapse.rs:269-297, :603-625) -- so it is bounded by what the
+ * final results file holds, at 16 or 24 bytes a record, and not by the sum of the chunks' hits.
+ *   grain                key                           kept for a key that two lists hold
+ *   MTSV_GRAIN_TAXID     (read, tax_id)                the smaller edit
+ *   MTSV_GRAIN_LONG      (read, tax_id, gi, offset)    the smaller edit
+ *   MTSV_GRAIN_TAXID_GI  (read, tax_id, gi)            the lexicographically smaller (edit, offset)
+ * All fields compare as unsigned.  The merge is global (k_fold.hip: a merge path over both lists), not per read: it does not
+ * depend on the reads' numbering or count, and a read with thousands of records costs what thousands of reads with one do.
+ * The order in which lists are folded does not change the result.  Everything counted per read is derived from the
+ * accumulated records when asked for: the match flags (a read is matched when it has a record) and the taxa report
+ * ({tax_id -> smallest edit} per read, the categories of mtsv_taxon_stats).
+ * A fold is bound to a device and a grain, not to an index, and keeps no pointer to a workspace: after mtsv_fold_add_run
+ * returns, src and its index may be freed.  The accumulator lies in two arrays that take turns and grow together, by
+ * reallocation, when a fold needs more room; 2^32 records or more before equal keys are joined is MTSV_E_LIMIT (the scan's
+ * offsets are 32 bits, as in a pass).  Every refusal leaves the fold as it was.  MTSV_FOLD_TILE (a power of two, 2..1024),
+ * read by mtsv_fold_create, moves the merge's tile size (tests).  With no fold created nothing is allocated or launched.
+ *
+ * mtsv_fold_create: MTSV_E_ARG for a bad grain, MTSV_E_DEVICE when hip_device is no usable device.
+ * mtsv_fold_reset: the fold is empty, its reads are numbered below n_reads (the caller's numbering: the flags have n_reads
+ *   bits), its TaxID union is empty.  A new fold is as after mtsv_fold_reset(f, 0).
+ * mtsv_fold_add_run: folds the assignments of src's last run.  src: a workspace of the fold's device whose assignments are
+ *   on, in either mode, at the fold's grain, and whose last run was mtsv_batch_run on a resident batch or
+ *   mtsv_batch_merge_runs (a host batch of mtsv_batch_run_host* is refused: its records left for the host range by range);
+ *   anything else is MTSV_E_ARG.  The records, which may lie in several stretches of the workspace's lanes, are put next to
+ *   each other in HBM first.  On a workspace filled by mtsv_batch_take_reads / _copy_reads they carry the caller's numbers,
+ *   which is all a chain needs.  The TaxIDs of src's index join the fold's union, the list the report's rows come from; a
+ *   merged collector's records come from every chunk of its merge, so there the TaxIDs are read from the records (they
+ *   cross to the host once).
+ * mtsv_fold_add_records: uploads and folds n host records of the fold's grain (mtsv_assignment, or mtsv_assignment_gi in
+ *   the two wide grains) -- from an earlier run, another device, a file parsed elsewhere.  Checked on the host: keys
+ *   strictly ascending and read < n_reads, MTSV_E_ARG otherwise.  Their TaxIDs join the union.
+ * device_ms (may be NULL): device time of the fold's kernels (count, scan, write).
+ * mtsv_fold_download / _download_gi: the accumulated records in key order.  *a is page-locked memory from the library's pool
+ *   of result arrays, also when *n is 0; the caller returns it with mtsv_free.  mtsv_fold_download on a wide grain and
+ *   mtsv_fold_download_gi on MTSV_GRAIN_TAXID are MTSV_E_ARG.  mtsv_format_assignments* write the result lines.
+ * mtsv_fold_taxa_report: rows as mtsv_batch_taxa_report gives them (non-zero rows, ascending tax_id, mtsv_free), equal to
+ *   those of a collector that merged the same runs; *total_reads: the reads with a record.  Reports of several folds over
+ *   disjoint reads add up with mtsv_merge_taxa_reports.  A record whose TaxID is not in the union is counted on the device
+ *   and makes the call fail, MTSV_E_DEVICE (an internal error: every way in adds its TaxIDs).
+ * mtsv_fold_match_flags: as mtsv_batch_match_flags, over the n_reads of the reset; *n_matched is counted on the device.  A
+ *   record whose read is at or above n_reads (only mtsv_fold_add_run can bring one) makes the call fail, MTSV_E_DEVICE. */
+typedef struct mtsv_fold mtsv_fold;
+int mtsv_fold_create(int hip_device, int grain, mtsv_fold **out);
+void mtsv_fold_free(mtsv_fold *f);
+int mtsv_fold_reset(mtsv_fold *f, uint64_t n_reads);
+int mtsv_fold_add_run(mtsv_fold *f, mtsv_batch *src, float *device_ms);
+int mtsv_fold_add_records(mtsv_fold *f, const void *records, uint64_t n, float *device_ms);
+int mtsv_fold_count(const mtsv_fold *f, uint64_t *n);
+int mtsv_fold_download(mtsv_fold *f, mtsv_assignment **a, uint64_t *n);
+int mtsv_fold_download_gi(mtsv_fold *f, mtsv_assignment_gi **a, uint64_t *n);
+int mtsv_fold_taxa_report(mtsv_fold *f, mtsv_taxon_stats **rows, uint64_t *n_rows, uint64_t *total_reads, float *device_ms);
+int mtsv_fold_match_flags(mtsv_fold *f, uint64_t **words, uint64_t *n_reads, uint64_t *n_matched);
+
 /* ---- result lines (host) ---------------------------------------------------------------- */
 /* write_assignments for a whole batch: hits ordered by read; ids = NUL-separated read ids,
  * id_off[n_reads+1].  Lines are appended to a malloc'd buffer (*out, *out_len), one per read with

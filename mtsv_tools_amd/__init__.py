@@ -26,6 +26,7 @@ from ._lib import (  # noqa: F401
     host_register,
     host_unregister,
     Batch,
+    Fold,
     MGIndex,
     MtsvError,
     Params,

@@ -91,6 +91,8 @@ EXPORTS = [
     "mtsv_batch_copy_reads", "mtsv_batch_merge_runs",
     "mtsv_batch_set_assignments", "mtsv_batch_download_assignments", "mtsv_format_assignments",
     "mtsv_batch_set_assignment_grain", "mtsv_batch_download_assignments_gi", "mtsv_format_assignments_gi",
+    "mtsv_fold_create", "mtsv_fold_free", "mtsv_fold_reset", "mtsv_fold_add_run", "mtsv_fold_add_records", "mtsv_fold_count",
+    "mtsv_fold_download", "mtsv_fold_download_gi", "mtsv_fold_taxa_report", "mtsv_fold_match_flags",
 ]
 
 _lib = None
@@ -168,6 +170,17 @@ def lib():
         L.mtsv_batch_set_assignment_grain.argtypes = [vp, i32]
         L.mtsv_batch_download_assignments_gi.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_format_assignments_gi.argtypes = [vp, u64, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_fold_create.argtypes = [i32, i32, C.POINTER(vp)]
+        L.mtsv_fold_free.argtypes = [vp]
+        L.mtsv_fold_free.restype = None
+        L.mtsv_fold_reset.argtypes = [vp, u64]
+        L.mtsv_fold_add_run.argtypes = [vp, vp, C.POINTER(C.c_float)]
+        L.mtsv_fold_add_records.argtypes = [vp, vp, u64, C.POINTER(C.c_float)]
+        L.mtsv_fold_count.argtypes = [vp, C.POINTER(u64)]
+        L.mtsv_fold_download.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_fold_download_gi.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_fold_taxa_report.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_fold_match_flags.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -518,6 +531,96 @@ class Batch:
     def close(self):
         if self.h is not None and _lib is not None:
             _lib.mtsv_batch_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _records_from(ptr, n, dtype):
+    try:
+        if n == 0:
+            return np.zeros(0, dtype=dtype)
+        raw = (C.c_ubyte * (n * dtype.itemsize)).from_address(ptr.value)
+        return np.frombuffer(raw, dtype=dtype).copy()
+    finally:
+        lib().mtsv_free(ptr)
+
+
+class Fold:
+    """Owning handle of an mtsv_fold: assignment records of one grain accumulated in HBM across runs -- the sorted union
+    of everything folded so far, one record per key with the better value.  Bound to a device and a grain, not to an
+    index: the workspaces and indexes whose runs it took may be closed."""
+
+    def __init__(self, device=0, grain=GRAIN_TAXID, n_reads=None):
+        self.grain = int(grain)
+        self.h = C.c_void_p()
+        _check(lib().mtsv_fold_create(device, self.grain, C.byref(self.h)))
+        if n_reads is not None:
+            self.reset(n_reads)
+
+    def reset(self, n_reads):
+        """mtsv_fold_reset: empty, for reads numbered below n_reads, TaxID union cleared"""
+        _check(lib().mtsv_fold_reset(self.h, int(n_reads)))
+
+    def add_run(self, src):
+        """mtsv_fold_add_run: folds the assignments of the last run of the Batch src; returns the device ms of the fold"""
+        ms = C.c_float()
+        _check(lib().mtsv_fold_add_run(self.h, src.h, C.byref(ms)))
+        return ms.value
+
+    def add_records(self, records):
+        """mtsv_fold_add_records: folds host records (ASSIGN_DTYPE, or ASSIGN_GI_DTYPE in the wide grains), keys strictly
+        ascending; returns the device ms of the fold"""
+        dt = ASSIGN_DTYPE if self.grain == GRAIN_TAXID else ASSIGN_GI_DTYPE
+        records = np.ascontiguousarray(records, dtype=dt)
+        ms = C.c_float()
+        _check(lib().mtsv_fold_add_records(self.h, records.ctypes.data, len(records), C.byref(ms)))
+        return ms.value
+
+    def count(self):
+        n = C.c_uint64()
+        _check(lib().mtsv_fold_count(self.h, C.byref(n)))
+        return n.value
+
+    def download(self):
+        """the accumulated records as an ASSIGN_DTYPE array (GRAIN_TAXID)"""
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(lib().mtsv_fold_download(self.h, C.byref(out), C.byref(n)))
+        return _records_from(out, n.value, ASSIGN_DTYPE)
+
+    def download_gi(self):
+        """the accumulated records as an ASSIGN_GI_DTYPE array (GRAIN_TAXID_GI, GRAIN_LONG)"""
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(lib().mtsv_fold_download_gi(self.h, C.byref(out), C.byref(n)))
+        return _records_from(out, n.value, ASSIGN_GI_DTYPE)
+
+    def taxa_report(self):
+        """(rows as a TAXON_STATS_DTYPE array ascending by tax_id, total_reads, device_ms) of the accumulated records"""
+        out, n, total, ms = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_fold_taxa_report(self.h, C.byref(out), C.byref(n), C.byref(total), C.byref(ms)))
+        return _taxon_rows_from(out, n.value), total.value, ms.value
+
+    def match_flags(self):
+        """(bool array over the n_reads of reset: the read has a record, n_matched)"""
+        out, n, m = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(lib().mtsv_fold_match_flags(self.h, C.byref(out), C.byref(n), C.byref(m)))
+        try:
+            nw = max((n.value + 63) // 64, 1)
+            words = np.frombuffer((C.c_ubyte * (nw * 8)).from_address(out.value), dtype="<u8").copy()
+        finally:
+            lib().mtsv_free(out)
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little").astype(bool)
+        if bits[n.value:].any():
+            raise MtsvError(E_DEVICE, "match flags set beyond the fold's reads")
+        return bits[:n.value], m.value
+
+    def close(self):
+        if self.h is not None and _lib is not None:
+            _lib.mtsv_fold_free(self.h)
         self.h = None
 
     def __del__(self):

@@ -25,6 +25,11 @@
 //   --merge-on-gpu    with --index a,b,.. and ONE device: every chunk resident there, and a call's hits merged per read in
 //                     HBM (mtsv_batch_copy_reads, mtsv_batch_merge_runs) -- the reads go up once per call, and --report,
 //                     --matched / --unmatched work on the merged hits as they do for one index
+//   --fold-on-gpu     with --index a,b,.. and ONE device: ONE chunk resident at a time -- a database whose chunks do not fit
+//                     the device together.  The reads are taken in super-batches (--fold-reads N); per super-batch every
+//                     chunk in turn is loaded, made resident, run against the reads and freed, and what outlives it is an
+//                     accumulator of collapsed assignment records in HBM (mtsv_fold_add_run); results, --report and
+//                     --matched / --unmatched come from the accumulated records, byte for byte what --merge-on-gpu writes
 #include <cstddef>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -123,7 +128,8 @@ struct Args {
     std::string fasta, fastq, index, results, report, matched, unmatched, filter_index, output_format = "default";
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
-    bool verbose = false, force = false, parse_only = false, merge_gpu = false;
+    bool verbose = false, force = false, parse_only = false, merge_gpu = false, fold_gpu = false;
+    uint64_t fold_reads = 16ull << 20;  // --fold-reads: reads per super-batch of --fold-on-gpu (every chunk is loaded once per super-batch)
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
 };
@@ -228,6 +234,16 @@ int main(int argc, char** argv) {
         else if (key == "--filter-index") a.filter_index = val();
         else if (key == "--parse-only") a.parse_only = true;
         else if (key == "--merge-on-gpu") a.merge_gpu = true;
+        else if (key == "--fold-on-gpu") a.fold_gpu = true;
+        else if (key == "--fold-reads") {
+            const std::string v = val();
+            char* e = nullptr;
+            errno = 0;
+            const unsigned long long n = strtoull(v.c_str(), &e, 10);
+            if (v.empty() || v[0] == '-' || *e || errno || n < 1 || n > 0xffffffffull)
+                usage_error("Invalid value for '--fold-reads <N>': a number of reads between 1 and 4294967295 is expected");
+            a.fold_reads = n;
+        }
         else if (key == "-h" || key == "--help") {
             printf("mtsv-binner (MI355X) -- flags as the reference: --fasta|--fastq, -i/--index, -m/--results, -t/--threads,\n"
                    "-e/--edit-rate, --seed-size, --seed-interval, --min-seed, --max-hits, --tune-max-hits, --max-assignments,\n"
@@ -250,7 +266,13 @@ int main(int argc, char** argv) {
                    "--merge-on-gpu (with --index a,b,.. of two or more chunks and one --devices entry: every chunk is made resident on\n"
                    "that device, a call's reads go up once and are copied from chunk to chunk on the GPU, and the chunks' hits are merged\n"
                    "per read on the GPU; the results file is the same, and --report and --matched / --unmatched are accepted: they are\n"
-                   "counted from the merged hits.  Each worker holds a workspace per chunk and one more.  Not with --filter-index)\n");
+                   "counted from the merged hits.  Each worker holds a workspace per chunk and one more.  Not with --filter-index),\n"
+                   "--fold-on-gpu (with --index a,b,.. of two or more chunks and one --devices entry, for a database whose chunks do not\n"
+                   "fit the device together: one chunk is resident at a time.  The reads are taken in super-batches of at most\n"
+                   "--fold-reads N reads (default 16777216); per super-batch every chunk in turn is loaded, made resident, run and freed,\n"
+                   "and its collapsed assignments are folded into an accumulator of records on the GPU; the results file, --report and\n"
+                   "--matched / --unmatched are the same as with --merge-on-gpu.  Not with --merge-on-gpu, --filter-index or\n"
+                   "--parse-only; a run that would resume an existing results file is refused)\n");
             return 0;
         } else if (key == "-V" || key == "--version") {
             printf("mtsv 2.1.0 (%s)\n", mtsv_version());
@@ -281,15 +303,37 @@ int main(int argc, char** argv) {
         }
         if (a.parse_only) usage_error("The argument '--parse-only' cannot be used with '--merge-on-gpu'");
     }
+    if (a.fold_gpu) {
+        // (decided here, before any file or device is touched)
+        if (a.merge_gpu) usage_error("The argument '--merge-on-gpu' cannot be used with '--fold-on-gpu'");
+        if (!a.filter_index.empty()) usage_error("The argument '--filter-index <INDEX>' cannot be used with '--fold-on-gpu'");
+        size_t n_chunks = 0;
+        for (size_t at = 0; at <= a.index.size();) {
+            size_t c = a.index.find(',', at);
+            if (c == std::string::npos) c = a.index.size();
+            n_chunks += c > at;
+            at = c + 1;
+        }
+        if (n_chunks < 2) {
+            fprintf(stderr, "error: '--fold-on-gpu' needs a list of two or more index chunks ('--index a,b,..')\n");
+            return 1;
+        }
+        if (a.devices.size() != 1) {
+            fprintf(stderr, "error: '--fold-on-gpu' needs exactly one '--devices' entry: the chunks take turns on that device\n");
+            return 1;
+        }
+        if (a.parse_only) usage_error("The argument '--parse-only' cannot be used with '--fold-on-gpu'");
+    }
+    const bool folded = a.fold_gpu;
     const bool merged = a.merge_gpu;
-    if (!merged && !a.report.empty() && a.index.find(',') != std::string::npos) {
+    if (!merged && !folded && !a.report.empty() && a.index.find(',') != std::string::npos) {
         // a read's taxa come from several chunks there and per-chunk counters do not add up
         fprintf(stderr, "error: '--report <TSV>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-collapse --report on the results file instead, or give '--merge-on-gpu' (one device)\n");
         return 1;
     }
     const bool partition = !a.matched.empty() || !a.unmatched.empty();
     if (partition && a.parse_only) usage_error("The argument '--parse-only' cannot be used with '--matched <PATH>' / '--unmatched <PATH>'");
-    if (!merged && partition && a.index.find(',') != std::string::npos) {
+    if (!merged && !folded && partition && a.index.find(',') != std::string::npos) {
         // (the flags of the chunks would have to be OR-ed per read)
         fprintf(stderr, "error: '--matched <PATH>' / '--unmatched <PATH>' cannot be used with a list of index chunks ('--index a,b,..'): run mtsv-partition on the results file instead, or give '--merge-on-gpu' (one device)\n");
         return 1;
@@ -302,7 +346,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "error: '--filter-index <INDEX>' cannot be used with a list of index chunks ('--index a,b,..'): filter first with '--unmatched <PATH>', then bin the chunks\n");
         return 1;
     }
-    if (!merged && partition && !a.report.empty() && a.results.empty())
+    if (!merged && !folded && partition && !a.report.empty() && a.results.empty())
         usage_error("The argument '--report <TSV>' requires '-m/--results <RESULTS>': the report is counted from gathered hits, and '--matched' / '--unmatched' without a results file gather none");
     if (a.output_format != "default" && a.output_format != "long")
         usage_error("'" + a.output_format + "' isn't a valid value for '--output-format <OUTPUT_FORMAT>'");
@@ -353,6 +397,10 @@ int main(int argc, char** argv) {
     } else if (exists && partition) {
         // a resumed run sees only the reads after the last one in the results file: the partition files would be incomplete
         fprintf(stderr, "error: results file %s exists and the run would resume it; '--matched' / '--unmatched' need the whole input: give --force-overwrite or another results path\n", a.results.c_str());
+        return 1;
+    } else if (exists && folded) {
+        // (the accumulators hold a super-batch of the whole input's numbering; a resumed run is not what this path is for)
+        fprintf(stderr, "error: results file %s exists and the run would resume it; '--fold-on-gpu' does not resume: give --force-overwrite or another results path\n", a.results.c_str());
         return 1;
     } else if (exists && !a.parse_only) {
         logmsg("INFO", "Existing results detected at " + a.results + "; resuming previous run.");
@@ -656,6 +704,235 @@ int main(int argc, char** argv) {
                 if (len >= 32) warm_len = (uint32_t)std::min<size_t>(len, 1000);
             }
         }
+    }
+    if (folded) {
+        // --fold-on-gpu: one chunk resident at a time.  A super-batch of reads is held on the host, in the (page-locked) blocks
+        // the parser filled, each block a PIECE with a fold of its own; per chunk: load, make resident, one workspace in
+        // MTSV_ASSIGN_ONLY, per piece upload + run + mtsv_fold_add_run, then the workspace and the index are freed.  After the
+        // last chunk a piece's records are its result lines (numbered from 0 within the piece, like its IDs: nothing to offset),
+        // its flags split its reads, its report adds to the run's.  Sequential on purpose: loading chunk c + 1 while chunk c
+        // runs is a follow-up.
+        const int dev = a.devices[0];
+        const int grain = long_fmt ? MTSV_GRAIN_LONG : MTSV_GRAIN_TAXID;
+        const uint64_t piece_reads = a.batch_reads + a.batch_reads / 2;
+        const uint64_t piece_bases = std::min<uint64_t>(3ull << 30, std::max<uint64_t>(piece_reads * std::max<uint64_t>(512, 2 * (uint64_t)warm_len), 1 << 22));
+        if (!getenv("MTSV_CLI_PAGEABLE") && (uint64_t)a.batch_reads * 320 <= (128ull << 20)) {
+            mtsv_ingest::byte_alloc().alloc = [](size_t n) { return mtsv_host_alloc(n); };
+            mtsv_ingest::byte_alloc().release = [](void* q) { mtsv_host_free(q); };
+        }
+        if (!getenv("MTSV_VERIFY")) mtsv_set_default_verify_mode(MTSV_VERIFY_EDIT_FIRST);
+        logmsg("INFO", "Beginning queries.");
+        struct timespec w0;
+        clock_gettime(CLOCK_MONOTONIC, &w0);
+        auto now = [] {
+            struct timespec t;
+            clock_gettime(CLOCK_MONOTONIC, &t);
+            return t.tv_sec + t.tv_nsec * 1e-9;
+        };
+        double t_load = 0, t_resident = 0, t_run = 0, t_fold = 0, t_out = 0;
+        float fold_device_ms = 0;
+        std::vector<std::unique_ptr<ReadBlock>> pieces;
+        std::vector<mtsv_fold*> folds;  // one per piece of a super-batch, kept from super-batch to super-batch
+        uint64_t super_reads = 0, n_super = 0, reads_done = 0, reads_matched = 0;
+        mtsv_taxon_stats* sum = nullptr;
+        uint64_t n_sum = 0, report_reads = 0;
+        int code = 0;
+        auto lib_error = [&] {
+            logmsg("ERROR", std::string("Error running query: ") + mtsv_last_error());
+            code = 2;
+            return false;
+        };
+        auto write_all = [&](int fd, const char* q, uint64_t len) {
+            uint64_t done = 0;
+            while (done < len) {
+                const ssize_t r = ::write(fd, q + done, len - done);
+                if (r <= 0) return false;
+                done += (uint64_t)r;
+            }
+            return true;
+        };
+        auto flush = [&]() -> bool {  // the super-batch collected so far, through every chunk
+            if (pieces.empty()) return true;
+            while (folds.size() < pieces.size()) {
+                mtsv_fold* f = nullptr;
+                if (mtsv_fold_create(dev, grain, &f) != MTSV_OK) return lib_error();
+                folds.push_back(f);
+            }
+            for (size_t k = 0; k < pieces.size(); k++)
+                if (mtsv_fold_reset(folds[k], pieces[k]->n()) != MTSV_OK) return lib_error();
+            for (size_t c = 0; c < index_paths.size(); c++) {
+                mtsv_index* ix = nullptr;
+                mtsv_batch* ws = nullptr;
+                double t0 = now();
+                int rc = mtsv_index_load(index_paths[c].c_str(), &ix);
+                t_load += now() - t0;
+                t0 = now();
+                if (rc == MTSV_OK) rc = mtsv_index_to_device(ix, dev, MTSV_DEV_DEFAULT);
+                t_resident += now() - t0;
+                if (rc == MTSV_OK) rc = mtsv_batch_create_lanes(ix, dev, piece_reads, piece_bases, 0, 1, &ws);
+                if (rc == MTSV_OK) rc = mtsv_batch_set_assignment_grain(ws, grain);
+                if (rc == MTSV_OK) rc = mtsv_batch_set_assignments(ws, MTSV_ASSIGN_ONLY);
+                for (size_t k = 0; k < pieces.size() && rc == MTSV_OK; k++) {
+                    const ReadBlock& rb = *pieces[k];
+                    t0 = now();
+                    rc = mtsv_batch_upload(ws, rb.bases.data(), rb.off.data(), rb.n());
+                    if (rc == MTSV_OK) rc = mtsv_batch_run(ws, &p);
+                    t_run += now() - t0;
+                    t0 = now();
+                    float ms = 0;
+                    if (rc == MTSV_OK) rc = mtsv_fold_add_run(folds[k], ws, &ms);
+                    fold_device_ms += ms;
+                    t_fold += now() - t0;
+                }
+                if (rc != MTSV_OK) lib_error();  // (before the frees: the message is the failing call's)
+                mtsv_batch_free(ws);
+                mtsv_index_free(ix);
+                if (rc != MTSV_OK) return false;
+                logmsg("DEBUG", "chunk " + index_paths[c] + " folded into " + std::to_string(pieces.size()) + " pieces");
+            }
+            const double t0 = now();
+            for (size_t k = 0; k < pieces.size(); k++) {
+                ReadBlock& rb = *pieces[k];
+                mtsv_fold* f = folds[k];
+                if (out_fd >= 0) {
+                    void* recs = nullptr;
+                    uint64_t n_recs = 0;
+                    char* text = nullptr;
+                    uint64_t len = 0;
+                    int rc = long_fmt ? mtsv_fold_download_gi(f, (mtsv_assignment_gi**)&recs, &n_recs) : mtsv_fold_download(f, (mtsv_assignment**)&recs, &n_recs);
+                    if (rc == MTSV_OK)
+                        rc = long_fmt ? mtsv_format_assignments_gi((const mtsv_assignment_gi*)recs, n_recs, rb.ids.data(), rb.id_off.data(), rb.n(), &text, &len)
+                                      : mtsv_format_assignments((const mtsv_assignment*)recs, n_recs, rb.ids.data(), rb.id_off.data(), rb.n(), &text, &len);
+                    if (rc != MTSV_OK) lib_error();
+                    mtsv_free(recs);
+                    const bool written = rc == MTSV_OK && write_all(out_fd, text, len);
+                    mtsv_free(text);
+                    if (rc != MTSV_OK) return false;
+                    if (!written) {
+                        logmsg("ERROR", "Error writing to result file");
+                        code = 11;
+                        return false;
+                    }
+                }
+                if (!a.report.empty()) {
+                    mtsv_taxon_stats *rows = nullptr, *both = nullptr;
+                    uint64_t n_rows = 0, n_both = 0, reads = 0;
+                    const bool ok = mtsv_fold_taxa_report(f, &rows, &n_rows, &reads, nullptr) == MTSV_OK &&
+                                    mtsv_merge_taxa_reports(sum, n_sum, rows, n_rows, &both, &n_both) == MTSV_OK;
+                    if (!ok) lib_error();
+                    mtsv_free(rows);
+                    if (!ok) return false;
+                    mtsv_free(sum);
+                    sum = both;
+                    n_sum = n_both;
+                    report_reads += reads;
+                }
+                if (partition) {
+                    uint64_t *words = nullptr, n_flagged = 0, n_match = 0;
+                    if (mtsv_fold_match_flags(f, &words, &n_flagged, &n_match) != MTSV_OK) return lib_error();
+                    std::string side[2];
+                    for (uint64_t i = 0; i < rb.n(); i++) {
+                        const int sd = (words[i >> 6] >> (i & 63)) & 1 ? 0 : 1;
+                        if (part_fd[sd] >= 0) mtsv_ingest::write_block_record(side[sd], fastq, rb, i);
+                    }
+                    mtsv_free(words);
+                    reads_matched += n_match;
+                    for (int sd = 0; sd < 2; sd++)
+                        if (part_fd[sd] >= 0 && !write_all(part_fd[sd], side[sd].data(), side[sd].size())) {
+                            logmsg("ERROR", std::string("Error writing to ") + (sd ? a.unmatched : a.matched));
+                            code = 11;
+                            return false;
+                        }
+                }
+                reads_done += rb.n();
+                pool.put(std::move(pieces[k]));
+            }
+            t_out += now() - t0;
+            pieces.clear();
+            super_reads = 0;
+            n_super++;
+            logmsg("DEBUG", "taxonomic binning: " + std::to_string(reads_done) + " reads done");
+            return true;
+        };
+        auto take_piece = [&](std::unique_ptr<ReadBlock> rb) {
+            if (rb->n() > piece_reads || rb->bases.size() > piece_bases) {
+                logmsg("ERROR", "Error running query: a batch of reads holds more than " + std::to_string(piece_reads) + " reads or " + std::to_string(piece_bases) +
+                                    " bases, which the chunks' workspaces are sized for: give a smaller --batch-reads");
+                code = 2;
+                return false;
+            }
+            if (!pieces.empty() && super_reads + rb->n() > a.fold_reads && !flush()) return false;
+            super_reads += rb->n();
+            pieces.push_back(std::move(rb));
+            return true;
+        };
+        const bool parsed = produce(std::min<uint64_t>(a.batch_reads, a.fold_reads), [&](std::unique_ptr<ReadBlock> rb) {
+            // (the parser hands out blocks of up to one and a half batches: a super-batch holds at most --fold-reads reads)
+            if (rb->n() <= a.fold_reads) return take_piece(std::move(rb));
+            for (uint64_t from = 0; from < rb->n(); from += a.fold_reads) {
+                auto part = pool.get();
+                part->append(*rb, from, std::min<uint64_t>(from + a.fold_reads, rb->n()));
+                if (!take_piece(std::move(part))) return false;
+            }
+            pool.put(std::move(rb));
+            return true;
+        });
+        // every way out of the folded run ends alike: the process leaves at once, or (MTSV_CLI_CLEAN_EXIT=1) frees what it holds
+        auto leave = [&](int c) {
+            mtsv_free(sum);
+            sum = nullptr;
+            if (!getenv("MTSV_CLI_CLEAN_EXIT")) {
+                fflush(nullptr);
+                _exit(c);
+            }
+            for (auto* f : folds) mtsv_fold_free(f);
+            folds.clear();
+            return c;
+        };
+        if (!parsed && !code) {
+            logmsg("ERROR", "Unable to read from input file: " + rd.err_msg);
+            code = 12;  // binner.rs:81-84
+        }
+        if (!code) flush();
+        if (code) return leave(code);
+        if (out_fd >= 0 && ::close(out_fd) != 0) {
+            logmsg("ERROR", "Error writing to result file");
+            return leave(11);
+        }
+        for (int k = 0; k < 2; k++)
+            if (part_fd[k] >= 0 && ::close(part_fd[k]) != 0) {
+                logmsg("ERROR", std::string("Error writing to ") + (k ? a.unmatched : a.matched));
+                return leave(11);
+            }
+        if (partition)
+            logmsg("INFO", "Partitioned " + std::to_string(reads_done) + " reads: " + std::to_string(reads_matched) + " matched, " + std::to_string(reads_done - reads_matched) +
+                               " unmatched.");
+        if (!a.report.empty()) {
+            char* text = nullptr;
+            uint64_t text_len = 0;
+            if (mtsv_format_taxa_report(sum, n_sum, report_reads, &text, &text_len) != MTSV_OK) {
+                logmsg("ERROR", std::string("Error running query: ") + mtsv_last_error());
+                return leave(2);
+            }
+            FILE* rf = fopen(a.report.c_str(), "wb");
+            const bool written = rf && fwrite(text, 1, text_len, rf) == text_len;
+            if ((rf && fclose(rf) != 0) || !written) {
+                logmsg("ERROR", "Error writing to taxa report file");
+                return leave(11);
+            }
+            mtsv_free(text);
+        }
+        struct timespec w1;
+        clock_gettime(CLOCK_MONOTONIC, &w1);
+        char msg[160];
+        snprintf(msg, sizeof msg, "All worker and result consumer threads terminated. Took %.3f seconds.", (w1.tv_sec - w0.tv_sec) + (w1.tv_nsec - w0.tv_nsec) * 1e-9);
+        logmsg("INFO", msg);
+        // MTSV_CLI_TIMING=1: where a folded run spends its time (seconds; tools/fold_ab.py reads this line)
+        if (getenv("MTSV_CLI_TIMING"))
+            fprintf(stderr, "[cli fold timing] super_batches %llu chunks %zu reads %llu; index_load %.3f s, index_to_device %.3f s, upload_and_run %.3f s, fold %.3f s "
+                            "(device %.3f ms), results_report_flags %.3f s\n",
+                    (unsigned long long)n_super, index_paths.size(), (unsigned long long)reads_done, t_load, t_resident, t_run, t_fold, fold_device_ms, t_out);
+        return leave(0);
     }
     // (batches too large for one parser block are put together from several blocks by appending: those stay in ordinary
     //  memory -- growing a page-locked buffer means allocating another one -- and are staged by the library)

@@ -12,6 +12,7 @@
 #include "../../include/mtsv_amd.h"
 #include "batch.hpp"
 #include "dev_index.hpp"
+#include "fold.hpp"
 #include "mgindex.hpp"
 
 using namespace mtsv;
@@ -482,6 +483,70 @@ int mtsv_batch_set_assignment_grain(mtsv_batch* b, int grain) {
 int mtsv_batch_download_assignments_gi(mtsv_batch* b, mtsv_assignment_gi** a, uint64_t* n, float* device_ms) {
     if (!b || !a || !n) return fail_arg("null argument");
     GUARD(b->impl.download_assignments((void**)a, n, device_ms, true))
+}
+
+// ---- mtsv_fold: assignment records accumulated across runs (fold.hip, k_fold.hip) ----
+int mtsv_fold_create(int hip_device, int grain, mtsv_fold** out) {
+    if (!out) return fail_arg("null argument");
+    GUARD(*out = new mtsv_fold(hip_device, grain))
+}
+
+void mtsv_fold_free(mtsv_fold* f) { delete f; }
+
+int mtsv_fold_reset(mtsv_fold* f, uint64_t n_reads) {
+    if (!f) return fail_arg("null argument");
+    GUARD(f->impl.reset(n_reads))
+}
+
+int mtsv_fold_add_run(mtsv_fold* f, mtsv_batch* src, float* device_ms) {
+    if (!f || !src) return fail_arg("null argument");
+    GUARD(f->impl.add_run(src->impl, device_ms))
+}
+
+int mtsv_fold_add_records(mtsv_fold* f, const void* records, uint64_t n, float* device_ms) {
+    if (!f || (n && !records)) return fail_arg("null argument");
+    GUARD(f->impl.add_records(records, n, device_ms))
+}
+
+int mtsv_fold_count(const mtsv_fold* f, uint64_t* n) {
+    if (!f || !n) return fail_arg("null argument");
+    *n = f->impl.n;
+    return MTSV_OK;
+}
+
+int mtsv_fold_download(mtsv_fold* f, mtsv_assignment** a, uint64_t* n) {
+    if (!f || !a || !n) return fail_arg("null argument");
+    GUARD(f->impl.download((void**)a, n, false))
+}
+
+int mtsv_fold_download_gi(mtsv_fold* f, mtsv_assignment_gi** a, uint64_t* n) {
+    if (!f || !a || !n) return fail_arg("null argument");
+    GUARD(f->impl.download((void**)a, n, true))
+}
+
+int mtsv_fold_taxa_report(mtsv_fold* f, mtsv_taxon_stats** rows, uint64_t* n_rows, uint64_t* total_reads, float* device_ms) {
+    if (!f || !rows || !n_rows || !total_reads) return fail_arg("null argument");
+    GUARD({
+        std::vector<mtsv_taxon_stats> r;
+        f->impl.taxa_report(r, total_reads, device_ms);
+        auto* out = (mtsv_taxon_stats*)malloc(std::max<size_t>(r.size(), 1) * sizeof(mtsv_taxon_stats));
+        if (!out) throw std::bad_alloc();
+        if (!r.empty()) memcpy(out, r.data(), r.size() * sizeof(mtsv_taxon_stats));
+        *rows = out;
+        *n_rows = r.size();
+    })
+}
+
+int mtsv_fold_match_flags(mtsv_fold* f, uint64_t** words, uint64_t* n_reads, uint64_t* n_matched) {
+    if (!f || !words || !n_reads || !n_matched) return fail_arg("null argument");
+    GUARD({
+        std::vector<uint64_t> w;
+        f->impl.match_flags(w, n_reads, n_matched);
+        auto* out = (uint64_t*)malloc(w.size() * sizeof(uint64_t));
+        if (!out) throw std::bad_alloc();
+        memcpy(out, w.data(), w.size() * sizeof(uint64_t));
+        *words = out;
+    })
 }
 
 int mtsv_batch_download(mtsv_batch* b, mtsv_hit** hits, uint64_t* n_hits) {

@@ -1,0 +1,305 @@
+// fold.hip -- the accumulator of assignment records that outlives a chunk (mtsv_fold, include/mtsv_amd.h).
+//
+// A database cut with mtsv-chunk that does not fit the device is binned chunk by chunk: a chunk's index and workspace
+// are resident, the reads run, and what has to survive the chunk is folded into this accumulator -- the collapsed
+// assignment records of the run, 16 or 24 bytes each, not its hits.  The accumulator is the sorted union of everything
+// folded so far with one record per key (k_fold.hip), so it is bounded by what the final results file holds.  The results
+// lines, the match flags and the taxa report are all derived from it.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
+#include "fold.hpp"
+#include "fold_records.hpp"
+#include "mgindex.hpp"
+
+namespace mtsv {
+
+namespace {
+template <class T>
+T* fold_alloc(uint64_t count) {
+    T* p = nullptr;
+    HIP_CHECK(hipMalloc((void**)&p, std::max<uint64_t>(count, 1) * sizeof(T)));
+    return p;
+}
+void sort_unique(std::vector<uint32_t>& v) {
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+}
+}  // namespace
+
+Fold::Fold(int device_, int grain_) : device(device_), grain(grain_) {
+    if (grain != MTSV_GRAIN_TAXID && grain != MTSV_GRAIN_TAXID_GI && grain != MTSV_GRAIN_LONG) throw std::runtime_error("arg: bad assignment grain");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess) {
+        (void)hipGetLastError();
+        n_dev = 0;
+    }
+    if (device < 0 || device >= n_dev) throw std::runtime_error("device: no HIP device " + std::to_string(device) + " (" + std::to_string(n_dev) + " visible)");
+    if (const char* e = getenv("MTSV_FOLD_TILE")) {  // (tests: tile edges within reach of small lists)
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 2), kFoldTileMax);
+        tile = 2;
+        while (tile * 2 <= want) tile *= 2;
+    }
+    trace = getenv("MTSV_TRACE") != nullptr;
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+}
+
+Fold::~Fold() {
+    if (hipSetDevice(device) != hipSuccess) (void)hipGetLastError();
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (void* p : {(void*)d_rec[0], (void*)d_rec[1], (void*)d_in, (void*)d_tile_cnt, (void*)d_tile_off, (void*)d_tile_sums, (void*)d_flags,
+                    (void*)d_taxa, (void*)d_counts})
+        if (p) (void)hipFree(p);
+    for (auto& e : ev)
+        if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
+void Fold::reset(uint64_t n_reads_) {
+    n = 0;
+    n_reads = n_reads_;
+    taxa.clear();
+}
+
+void Fold::in_room(uint64_t n_b) {
+    if (n_b <= in_cap && d_in) return;
+    HIP_CHECK(hipStreamSynchronize(stream));
+    const uint64_t ncap = std::max<uint64_t>(n_b + n_b / 8, 1ull << 16);
+    uint8_t* p = fold_alloc<uint8_t>(ncap * rec_bytes());
+    if (d_in) (void)hipFree(d_in);
+    d_in = p;
+    in_cap = ncap;
+}
+
+void Fold::fold_in(uint64_t n_b, std::vector<uint32_t>& new_taxa, float* device_ms) {
+    const uint64_t rec = rec_bytes(), n_tot = n + n_b;
+    if (n_tot >= (1ull << 32)) throw std::runtime_error("limit: the fold would hold " + std::to_string(n_tot) + " records before equal keys are joined, 2^32 or more");
+    std::vector<uint32_t> u = taxa;
+    u.insert(u.end(), new_taxa.begin(), new_taxa.end());
+    sort_unique(u);
+    if (u.size() >= (1ull << 30)) throw std::runtime_error("limit: taxa report of 2^30 TaxIDs or more");
+    if (device_ms) *device_ms = 0;
+    if (!n_b) {  // (nothing to merge: the source's TaxIDs still join the union)
+        taxa.swap(u);
+        return;
+    }
+    // ---- room; whatever fails here leaves the fold as it was ----
+    if (n_tot > cap || !d_rec[0]) {
+        const uint64_t ncap = std::min<uint64_t>(std::max<uint64_t>(std::max<uint64_t>(2 * cap, n_tot), 1ull << 16), 0xffffffffull);
+        uint8_t* a = fold_alloc<uint8_t>(ncap * rec);
+        uint8_t* b = nullptr;
+        if (hipMalloc((void**)&b, ncap * rec) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(a);
+            throw std::runtime_error("device: no memory for an accumulator of " + std::to_string(ncap) + " records (two arrays)");
+        }
+        if (n) {
+            const hipError_t e1 = hipMemcpyAsync(a, d_rec[cur], n * rec, hipMemcpyDeviceToDevice, stream);
+            const hipError_t e2 = hipStreamSynchronize(stream);
+            if (e1 != hipSuccess || e2 != hipSuccess) {
+                (void)hipFree(a);
+                (void)hipFree(b);
+                throw_hip(e1 != hipSuccess ? e1 : e2, "hipMemcpyAsync(accumulator)", __FILE__, __LINE__);
+            }
+        }
+        if (trace) fprintf(stderr, "[fold] accumulator grown from %llu to %llu records (two arrays of %llu bytes)\n", (unsigned long long)cap, (unsigned long long)ncap, (unsigned long long)(ncap * rec));
+        if (d_rec[0]) (void)hipFree(d_rec[0]);
+        if (d_rec[1]) (void)hipFree(d_rec[1]);
+        d_rec[0] = a;
+        d_rec[1] = b;
+        cur = 0;
+        cap = ncap;
+    }
+    const uint32_t tiles = fold_tiles(n_tot, tile);
+    if (tiles > tiles_cap || !d_tile_cnt) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        for (void* p : {(void*)d_tile_cnt, (void*)d_tile_off, (void*)d_tile_sums})
+            if (p) (void)hipFree(p);
+        d_tile_cnt = d_tile_off = nullptr;
+        d_tile_sums = nullptr;
+        tiles_cap = 0;
+        const uint64_t tc = std::min<uint64_t>(std::max<uint64_t>(2ull * tiles, 1024), 0xffffffffull);
+        d_tile_cnt = fold_alloc<uint32_t>(tc);
+        d_tile_off = fold_alloc<uint32_t>(tc + 1);
+        sums_cap = (uint64_t)scan_tiles((uint32_t)tc) + 1;
+        d_tile_sums = fold_alloc<uint64_t>(sums_cap + 1);
+        tiles_cap = tc;
+    }
+    // ---- the fold: count, scan, write into the other array ----
+    uint64_t total = 0;
+    uint8_t* out = d_rec[cur ^ 1];
+    HIP_CHECK(hipEventRecord(ev[0], stream));
+    launch_fold_count(stream, grain, d_rec[cur], (uint32_t)n, d_in, (uint32_t)n_b, tile, d_tile_cnt);
+    launch_scan(stream, d_tile_cnt, tiles, d_tile_sums, d_tile_sums + sums_cap, d_tile_off);
+    launch_fold_write(stream, grain, d_rec[cur], (uint32_t)n, d_in, (uint32_t)n_b, tile, d_tile_off, out);
+    HIP_CHECK(hipEventRecord(ev[1], stream));
+    HIP_CHECK(hipMemcpyAsync(&total, d_tile_sums + sums_cap, sizeof total, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipGetLastError());
+    if (total > n_tot || total < std::max(n, n_b))
+        throw std::runtime_error("internal: the fold of " + std::to_string(n) + " and " + std::to_string(n_b) + " records counted " + std::to_string(total));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    if (trace)
+        fprintf(stderr, "[fold] %llu + %llu records -> %llu in %u tiles of %u: %.3f ms\n", (unsigned long long)n, (unsigned long long)n_b, (unsigned long long)total,
+                tiles, tile, ms);
+    n = total;
+    cur ^= 1;
+    taxa.swap(u);
+    if (device_ms) *device_ms = ms;
+}
+
+void Fold::add_run(Batch& src, float* device_ms) {
+    if (src.parent) throw std::runtime_error("internal: fold of a lane");
+    if (src.di->device != device) throw std::runtime_error("arg: the workspace is on device " + std::to_string(src.di->device) + ", the fold on device " + std::to_string(device));
+    if (src.assign.mode == MTSV_ASSIGN_OFF) throw std::runtime_error("arg: the assignments of the workspace are not switched on (mtsv_batch_set_assignments)");
+    if (src.assign.grain != grain) throw std::runtime_error("arg: the workspace's assignment grain is " + std::to_string(src.assign.grain) + ", the fold's " + std::to_string(grain));
+    if (src.last_run == Batch::kRunHostOneSegment || src.last_run == Batch::kRunHostSegments)
+        throw std::runtime_error("arg: the workspace's last run was a host batch (a fold takes runs on a resident batch: mtsv_batch_upload / _take_reads / _copy_reads + mtsv_batch_run, or mtsv_batch_merge_runs)");
+    if (src.last_run != Batch::kRunResident && src.last_run != Batch::kRunMerged)
+        throw std::runtime_error("arg: the workspace has no completed run on a resident batch whose assignments are still in HBM");
+    uint64_t n_b = 0;
+    for (const auto& sg : src.segments) n_b += sg.a_count;
+    if (n + n_b >= (1ull << 32)) throw std::runtime_error("limit: the fold would hold " + std::to_string(n + n_b) + " records before equal keys are joined, 2^32 or more");
+    // the TaxIDs the source brings: a run's come from its index's bins; a merged collector's records come from every chunk of
+    // the merge while its index is one chunk's, so theirs are read from the records themselves, below
+    const bool from_records = src.last_run == Batch::kRunMerged;
+    std::vector<uint32_t> t;
+    if (!from_records)
+        for (const Bin& b : src.ix->host.bins) t.push_back(b.tax_id);
+    HIP_CHECK(hipSetDevice(device));
+    const uint64_t rec = rec_bytes();
+    if (n_b) {
+        in_room(n_b);
+        // the run's records, which lie in its lanes' arrays stretch by stretch, next to each other (the run has returned: nothing
+        // of the workspace is in flight)
+        uint64_t at = 0;
+        for (const auto& sg : src.segments) {
+            if (!sg.a_count) continue;
+            HIP_CHECK(hipMemcpyAsync(d_in + at * rec, sg.lane->d_assign + sg.a_offset * rec, sg.a_count * rec, hipMemcpyDeviceToDevice, stream));
+            at += sg.a_count;
+        }
+        if (from_records) {  // (a collector is the rare source: its gathered records come to the host once, for the word behind the 8-byte read)
+            std::vector<uint8_t> h(n_b * rec);
+            HIP_CHECK(hipMemcpyAsync(h.data(), d_in, n_b * rec, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            t.resize(n_b);
+            for (uint64_t i = 0; i < n_b; i++) memcpy(&t[i], &h[i * rec + 8], 4);
+        }
+    }
+    sort_unique(t);
+    fold_in(n_b, t, device_ms);
+    // (the gather has completed with the fold: the workspace may be freed)
+    HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+void Fold::add_records(const void* records, uint64_t n_b, float* device_ms) {
+    std::vector<uint32_t> t;
+    check_fold_records(grain, records, n_b, n_reads, t);  // (keys strictly ascending, reads below n_reads)
+    sort_unique(t);
+    if (n + n_b >= (1ull << 32)) throw std::runtime_error("limit: the fold would hold " + std::to_string(n + n_b) + " records before equal keys are joined, 2^32 or more");
+    HIP_CHECK(hipSetDevice(device));
+    if (n_b) {
+        in_room(n_b);
+        HIP_CHECK(hipMemcpyAsync(d_in, records, n_b * rec_bytes(), hipMemcpyHostToDevice, stream));
+    }
+    fold_in(n_b, t, device_ms);
+    HIP_CHECK(hipStreamSynchronize(stream));  // (the caller's array has been read)
+}
+
+void Fold::download(void** a, uint64_t* n_out, bool wide) {
+    if (wide != (grain != MTSV_GRAIN_TAXID))
+        throw std::runtime_error(wide ? "arg: the grain of this fold is MTSV_GRAIN_TAXID: its records are mtsv_assignment (mtsv_fold_download)"
+                                      : "arg: the grain of this fold is not MTSV_GRAIN_TAXID: its records are mtsv_assignment_gi (mtsv_fold_download_gi)");
+    HIP_CHECK(hipSetDevice(device));
+    const uint64_t rec = rec_bytes();
+    uint64_t pool_cap = 0;
+    uint8_t* out = (uint8_t*)pinned_hits_alloc((n * rec + 31) / 32, &pool_cap);  // (the pool counts in 32-byte hits)
+    if (n) {
+        const hipError_t e = hipMemcpy(out, d_rec[cur], n * rec, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            pinned_hits_release(out);
+            throw_hip(e, "hipMemcpy(fold records)", __FILE__, __LINE__);
+        }
+    }
+    *a = out;
+    *n_out = n;
+}
+
+void Fold::match_flags(std::vector<uint64_t>& words, uint64_t* n_reads_out, uint64_t* n_matched) {
+    const uint64_t nw = std::max<uint64_t>((n_reads + 63) / 64, 1);
+    words.assign(nw, 0);
+    *n_reads_out = n_reads;
+    *n_matched = 0;
+    if (!n) return;
+    HIP_CHECK(hipSetDevice(device));
+    if (nw + 2 > flags_cap || !d_flags) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        uint64_t* p = fold_alloc<uint64_t>(nw + 2);
+        if (d_flags) (void)hipFree(d_flags);
+        d_flags = p;
+        flags_cap = nw + 2;
+    }
+    uint64_t ctr[2] = {0, 0};
+    HIP_CHECK(hipMemsetAsync(d_flags, 0, (nw + 2) * 8, stream));
+    launch_fold_flags(stream, grain, d_rec[cur], (uint32_t)n, n_reads, d_flags, d_flags + nw);
+    HIP_CHECK(hipMemcpyAsync(words.data(), d_flags, nw * 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(ctr, d_flags + nw, sizeof ctr, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipGetLastError());
+    if (ctr[1]) throw std::runtime_error("internal: " + std::to_string(ctr[1]) + " reads of the fold are numbered at or above its " + std::to_string(n_reads) + " reads");
+    *n_matched = ctr[0];
+}
+
+void Fold::taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_reads, float* device_ms) {
+    rows.clear();
+    *total_reads = 0;
+    if (device_ms) *device_ms = 0;
+    if (!n) return;
+    HIP_CHECK(hipSetDevice(device));
+    const uint64_t n_taxa = taxa.size(), n_cnt = 4 * n_taxa + 2;
+    if (n_taxa > taxa_cap || !d_counts) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        uint32_t* t = fold_alloc<uint32_t>(n_taxa);
+        uint64_t* c = nullptr;
+        if (hipMalloc((void**)&c, n_cnt * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(t);
+            throw std::runtime_error("device: no memory for the counters of " + std::to_string(n_taxa) + " taxa");
+        }
+        if (d_taxa) (void)hipFree(d_taxa);
+        if (d_counts) (void)hipFree(d_counts);
+        d_taxa = t;
+        d_counts = c;
+        taxa_cap = n_taxa;
+    }
+    std::vector<uint64_t> c(n_cnt);
+    if (n_taxa) HIP_CHECK(hipMemcpyAsync(d_taxa, taxa.data(), n_taxa * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemsetAsync(d_counts, 0, n_cnt * 8, stream));
+    HIP_CHECK(hipEventRecord(ev[0], stream));
+    launch_fold_report(stream, grain, d_rec[cur], (uint32_t)n, d_taxa, (uint32_t)n_taxa, d_counts);
+    HIP_CHECK(hipEventRecord(ev[1], stream));
+    HIP_CHECK(hipMemcpyAsync(c.data(), d_counts, n_cnt * 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipGetLastError());
+    if (c[n_cnt - 1])
+        throw std::runtime_error("internal: " + std::to_string(c[n_cnt - 1]) + " (read, TaxID) pairs of the fold carry a TaxID that is not in its union of " + std::to_string(n_taxa) + " TaxIDs");
+    rows.clear();
+    for (uint64_t k = 0; k < n_taxa; k++) {
+        const uint64_t* q = &c[4 * k];
+        if (q[0] | q[1] | q[2] | q[3]) rows.push_back(mtsv_taxon_stats{taxa[k], 0, q[0], q[1], q[2], q[3]});
+    }
+    *total_reads = c[n_cnt - 2];
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    if (device_ms) *device_ms = ms;
+    if (trace) fprintf(stderr, "[fold] report of %llu records over %llu taxa: %.3f ms\n", (unsigned long long)n, (unsigned long long)n_taxa, ms);
+}
+
+}  // namespace mtsv

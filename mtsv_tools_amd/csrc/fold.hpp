@@ -1,0 +1,62 @@
+// fold.hpp -- an accumulator of assignment records in HBM that outlives the workspaces whose runs are folded into it (fold.hip).
+#pragma once
+#include <vector>
+
+#include "../../include/mtsv_amd.h"
+#include "batch.hpp"
+
+namespace mtsv {
+
+// The sorted union of the assignment lists folded so far, one record per key (k_fold.hip), in one of two arrays that take
+// turns: a fold reads the current one and the incoming list and writes the other.  Bound to a device and a grain; it keeps
+// no pointer to a workspace or an index.  What is counted per read -- the match flags, the taxa report -- is derived from
+// the records when it is asked for.
+struct Fold {
+    int device;
+    int grain;
+    uint32_t tile = kFoldTile;  // MTSV_FOLD_TILE, read at creation (tests)
+    bool trace = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint8_t* d_rec[2] = {nullptr, nullptr};  // cap records each; they grow together
+    uint64_t cap = 0, n = 0;
+    int cur = 0;
+    uint8_t* d_in = nullptr;  // the incoming list: a run's records gathered from its lanes' arrays, or uploaded ones
+    uint64_t in_cap = 0;
+    uint32_t *d_tile_cnt = nullptr, *d_tile_off = nullptr;
+    uint64_t* d_tile_sums = nullptr;  // the scan's tile sums, then its total
+    uint64_t tiles_cap = 0, sums_cap = 0;
+    uint64_t n_reads = 0;             // the caller's numbering (reset)
+    std::vector<uint32_t> taxa;       // the TaxIDs of every source folded so far, ascending
+    uint64_t* d_flags = nullptr;      // flag words, then two counters
+    uint64_t flags_cap = 0;
+    uint32_t* d_taxa = nullptr;
+    uint64_t* d_counts = nullptr;
+    uint64_t taxa_cap = 0;
+
+    Fold(int device, int grain);
+    ~Fold();
+    Fold(const Fold&) = delete;
+    Fold& operator=(const Fold&) = delete;
+
+    uint64_t rec_bytes() const { return grain == MTSV_GRAIN_TAXID ? sizeof(mtsv_assignment) : sizeof(mtsv_assignment_gi); }
+    void reset(uint64_t n_reads);
+    void add_run(Batch& src, float* device_ms);
+    void add_records(const void* records, uint64_t n, float* device_ms);
+    void download(void** a, uint64_t* n, bool wide);
+    void taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_reads, float* device_ms);
+    void match_flags(std::vector<uint64_t>& words, uint64_t* n_reads, uint64_t* n_matched);
+
+   private:
+    void in_room(uint64_t n_b);
+    // d_in[0 .. n_b) folded into the accumulator; new_taxa (ascending) joins the union when it has succeeded
+    void fold_in(uint64_t n_b, std::vector<uint32_t>& new_taxa, float* device_ms);
+};
+
+}  // namespace mtsv
+
+struct mtsv_fold {
+    mtsv::Fold impl;
+    template <class... A>
+    explicit mtsv_fold(A&&... a) : impl(std::forward<A>(a)...) {}
+};

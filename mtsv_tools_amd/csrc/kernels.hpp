@@ -2,7 +2,8 @@
 //
 // The mtsv-binner hot path as gfx950 kernels (k_seed.hip, k_coalesce.hip, k_verify.hip; k_report.hip for the taxa report, k_match.hip for
 // the per-read match flags, k_compact.hip for the hand-over of a run's unmatched or matched reads to another workspace,
-// k_merge.hip for the per-read merge of several runs' hits).
+// k_merge.hip for the per-read merge of several runs' hits, k_fold.hip for the accumulator of assignment records that a
+// chunk's run is folded into before the chunk leaves the device).
 //
 // One batch of reads flows through staged kernels with worklists in HBM:
 //
@@ -24,6 +25,7 @@
 //   k_report    (taxa report on) lane per read: per-TaxID read counts of the pass   collapse.rs:120-146
 //   k_match     (match flags on) lane per read: one bit, "the read has a hit"      mtsv-partition.rs:34-54
 //   k_collapse  (assignments on) per read: one (tax_id, smallest edit) per TaxID      binner.rs:355-378
+//   k_fold      (mtsv_fold) two sorted record lists into one, one record per key       collapse.rs:269-297, :603-625
 //
 // All arithmetic is integer; positions are u32 (n < 2^32).  No MFMA: the path is rank queries and
 // small dynamic programs.
@@ -265,5 +267,25 @@ constexpr uint32_t kCollapseCtrTotal = 0, kCollapseCtrList = 1, kCollapseCtrTick
 void launch_collapse(hipStream_t s, int grain, uint32_t n_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits,
                      uint32_t n_hits, uint32_t lane_max, uint32_t wave_max, uint32_t lds_max, void* keys, uint32_t* flags, uint32_t* place,
                      uint64_t* tile_sums, uint32_t* list, uint64_t* ctr, void* out);
+// k_fold.hip: two assignment lists of one grain (records as launch_collapse writes them, each list ascending by the grain's
+// key -- (read, tax_id), (read, tax_id, gi, offset) or (read, tax_id, gi), unsigned -- with distinct keys) folded into their
+// sorted union, one record per key: for a key both lists hold, a's record with the smaller edit of the two (TAXID_GI: the
+// smaller (edit, offset)).  a and b are 16-byte aligned, n_a + n_b < 2^32.  A workgroup owns `tile` positions (a power of two,
+// 2 .. kFoldTileMax) of the merged sequence; there are fold_tiles(n_a + n_b, tile) of them.
+//   count:  tile_cnt[t] = the records tile t keeps
+//   (launch_scan over tile_cnt: tile_off[0 .. tiles], tile_off[tiles] = the records of the union)
+//   write:  the union to out[0 .. tile_off[tiles]); a tile writes nothing outside [tile_off[t], tile_off[t + 1])
+constexpr uint32_t kFoldTileMax = 1024, kFoldTile = 1024;
+uint32_t fold_tiles(uint64_t n, uint32_t tile);
+void launch_fold_count(hipStream_t s, int grain, const void* a, uint32_t n_a, const void* b, uint32_t n_b, uint32_t tile, uint32_t* tile_cnt);
+void launch_fold_write(hipStream_t s, int grain, const void* a, uint32_t n_a, const void* b, uint32_t n_b, uint32_t tile, const uint32_t* tile_off,
+                       void* out);
+// The match flags of a list: every read that has a record sets bit (read & 63) of words[read >> 6] (zeroed by the caller) and
+// adds one to ctr[0]; a read >= n_reads sets nothing and adds one to ctr[1].  ctr: two u64, zeroed by the caller.
+void launch_fold_flags(hipStream_t s, int grain, const void* rec, uint32_t n, uint64_t n_reads, uint64_t* words, uint64_t* ctr);
+// The taxa report of a list (launch_report's categories, from per read {tax_id -> smallest edit of its records}): counts holds
+// 4 u64 per taxon of the ascending list taxa, then the reads with a record, then the (read, TaxID) pairs whose TaxID the list does
+// not hold (they are counted nowhere else); 4 * n_taxa + 2 u64, zeroed by the caller.
+void launch_fold_report(hipStream_t s, int grain, const void* rec, uint32_t n, const uint32_t* taxa, uint32_t n_taxa, uint64_t* counts);
 
 }  // namespace mtsv
