@@ -492,6 +492,43 @@ int mtsv_fold_download_gi(mtsv_fold *f, mtsv_assignment_gi **a, uint64_t *n);
 int mtsv_fold_taxa_report(mtsv_fold *f, mtsv_taxon_stats **rows, uint64_t *n_rows, uint64_t *total_reads, float *device_ms);
 int mtsv_fold_match_flags(mtsv_fold *f, uint64_t **words, uint64_t *n_reads, uint64_t *n_matched);
 
+/* ---- result lines written on the device: the results file from records that never leave HBM as records ------------------
+ * mtsv_format_assignments* walk downloaded records on a host thread.  These two calls write the same bytes on the device
+ * (k_text.hip) from records that lie in HBM already, and what crosses to the host is the text: one line per read that has a
+ * record, READ_ID:TAXID=EDIT,... from MTSV_GRAIN_TAXID records and READ_ID:TAXID-GI-OFFSET=EDIT,... from the two wide grains,
+ * byte for byte what mtsv_format_assignments / mtsv_format_assignments_gi make of the same records and IDs.  ids and id_off
+ * are what those take: the NUL-separated read IDs and id_off[n_reads + 1]; an ID is strnlen within its slot, which may be
+ * NUL-padded or filled to its last byte with no NUL.
+ * The kernels are record-parallel, not read-parallel: a record's bytes are its read's ID and ':' when it is the first of
+ * its read, its fields, and ',' or '\n'; their lengths are measured (digit counts by comparison), scanned to 64-bit offsets,
+ * and a workgroup writes the text of its tile of records through LDS.  A read with thousands of records costs what
+ * thousands of reads with one record do.  MTSV_TEXT_TILE (a power of two, 2..1024) moves the tile size (tests); it is read
+ * by mtsv_fold_create, and by a workspace's first mtsv_batch_format_text.  With neither call made nothing is allocated or
+ * launched.
+ *
+ * mtsv_fold_format_text: the accumulated records of the fold, in its grain.  n_reads must be the n_reads of the last
+ *   mtsv_fold_reset, MTSV_E_ARG otherwise.  The fold is not changed: its records, report and flags are as before.
+ * mtsv_batch_format_text: the assignments of the workspace's last run, in its grain.  The assignments must be on, in either
+ *   mode, and the last run mtsv_batch_run on a resident batch or mtsv_batch_merge_runs -- the sources mtsv_fold_add_run
+ *   accepts; records that lie in several stretches of the workspace's lanes are put next to each other in HBM first.  A host
+ *   batch of mtsv_batch_run_host* is MTSV_E_ARG (its records left for the host range by range), and so are assignments
+ *   that are off and a workspace with no run yet.  On a workspace filled by mtsv_batch_take_reads / _copy_reads the records
+ *   carry the caller's numbers: ids and n_reads are then the caller's.
+ * Both: *text is page-locked memory from the library's pool of result arrays, also when *len is 0; it holds *len + 1 bytes
+ *   with a NUL at *len, and the caller returns it with mtsv_free.  device_ms (may be NULL): device time of the kernels
+ *   (measure, scan, write).  A null ids, id_off, text or len is MTSV_E_ARG.  Counted on the device, and MTSV_E_ARG with
+ *   nothing returned: a record whose read is at or above n_reads; an ID slot that does not lie inside the ID bytes (id_off
+ *   must ascend, id_off[n_reads] is the length of ids) or is longer than 2^20 bytes.  Every refusal leaves the fold or the
+ *   workspace as it was.  The order of the records is not checked: every source keeps its records in key order.
+ * Limits: one call's worth -- the IDs of all n_reads reads go up with every call, also of reads that have no record, and the
+ *   text of a call lies in HBM before it is copied; fewer than 2^32 records.
+ * Out of scope: text per range of a host batch (mtsv_batch_run_host*).  It needs the IDs on the device before the ranges
+ *   finish and touches the lanes' staging; such a run's lines come from mtsv_format_assignments*. */
+int mtsv_fold_format_text(mtsv_fold *f, const char *ids, const uint64_t *id_off, uint64_t n_reads, char **text, uint64_t *len,
+                          float *device_ms);
+int mtsv_batch_format_text(mtsv_batch *b, const char *ids, const uint64_t *id_off, uint64_t n_reads, char **text, uint64_t *len,
+                           float *device_ms);
+
 /* ---- result lines (host) ---------------------------------------------------------------- */
 /* write_assignments for a whole batch: hits ordered by read; ids = NUL-separated read ids,
  * id_off[n_reads+1].  Lines are appended to a malloc'd buffer (*out, *out_len), one per read with

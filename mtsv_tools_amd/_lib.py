@@ -93,6 +93,7 @@ EXPORTS = [
     "mtsv_batch_set_assignment_grain", "mtsv_batch_download_assignments_gi", "mtsv_format_assignments_gi",
     "mtsv_fold_create", "mtsv_fold_free", "mtsv_fold_reset", "mtsv_fold_add_run", "mtsv_fold_add_records", "mtsv_fold_count",
     "mtsv_fold_download", "mtsv_fold_download_gi", "mtsv_fold_taxa_report", "mtsv_fold_match_flags",
+    "mtsv_fold_format_text", "mtsv_batch_format_text",
 ]
 
 _lib = None
@@ -181,6 +182,8 @@ def lib():
         L.mtsv_fold_download_gi.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_fold_taxa_report.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_fold_match_flags.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+        L.mtsv_fold_format_text.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_batch_format_text.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -482,6 +485,11 @@ class Batch:
         finally:
             lib().mtsv_free(out)
 
+    def format_text(self, read_ids):
+        """mtsv_batch_format_text: (the result lines of the last run's assignments as bytes, written on the device; device ms).
+        read_ids: the IDs of the reads the records number -- a list of str, or a (bytes, offsets) table"""
+        return _format_text(lib().mtsv_batch_format_text, self.h, read_ids)
+
     def take_reads(self, src, keep=KEEP_UNMATCHED):
         """mtsv_batch_take_reads: this workspace's resident batch := the reads of src's last run whose match flag is clear
         (KEEP_MATCHED: set), handed over on the device; returns (n_kept, bases_kept, device ms of the kernels)"""
@@ -538,6 +546,31 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+def _id_table(read_ids):
+    """(blob, id_off) as mtsv_format_assignments takes them: from a list of IDs, the NUL-terminated IDs back to back, as
+    format_assignments builds them; a (bytes, offsets) pair is a table already and passes through (its slots may be NUL-padded
+    or filled to the last byte)"""
+    if isinstance(read_ids, tuple):
+        blob, off = read_ids
+        return bytes(blob), np.ascontiguousarray(off, dtype=np.uint64)
+    blob = b"".join(i.encode() + b"\0" for i in read_ids)
+    off = np.zeros(len(read_ids) + 1, dtype=np.uint64)
+    np.cumsum([len(i.encode()) + 1 for i in read_ids], out=off[1:])
+    return blob, off
+
+
+def _format_text(call, handle, read_ids):
+    blob, off = _id_table(read_ids)
+    out, n, ms = C.c_void_p(), C.c_uint64(), C.c_float()
+    _check(call(handle, blob, off.ctypes.data, len(off) - 1, C.byref(out), C.byref(n), C.byref(ms)))
+    try:
+        if C.string_at(out.value + n.value, 1) != b"\0":
+            raise MtsvError(E_DEVICE, "the text does not end with a NUL")
+        return C.string_at(out.value, n.value), ms.value
+    finally:
+        lib().mtsv_free(out)
 
 
 def _records_from(ptr, n, dtype):
@@ -617,6 +650,11 @@ class Fold:
         if bits[n.value:].any():
             raise MtsvError(E_DEVICE, "match flags set beyond the fold's reads")
         return bits[:n.value], m.value
+
+    def format_text(self, read_ids):
+        """mtsv_fold_format_text: (the result lines of the accumulated records as bytes, written on the device; device ms).
+        read_ids: the IDs of the n_reads reads of reset -- a list of str, or a (bytes, offsets) table"""
+        return _format_text(lib().mtsv_fold_format_text, self.h, read_ids)
 
     def close(self):
         if self.h is not None and _lib is not None:

@@ -284,6 +284,10 @@ struct Batch {
     // the assignments of the last run, in read order, in a pinned array of the pool (*n may be 0: *a is still to be freed)
     // (grain: the one the caller's record type belongs to -- MTSV_GRAIN_TAXID, or anything else for the 24-byte records)
     void download_assignments(void** a, uint64_t* n, float* device_ms, bool wide);
+    // the result lines of the last run's assignments, written on the device (text.hip: mtsv_batch_format_text); the
+    // formatter is created by the first call.  (owner only)
+    std::shared_ptr<struct TextFormatter> text;
+    void format_text(const char* ids, const uint64_t* id_off, uint64_t n_reads, char** text_out, uint64_t* len, float* device_ms);
     void merge_runs(Batch* const* srcs, int n_srcs, float* device_ms);
     void read_map(std::vector<uint64_t>& map);
     void download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& read_off);

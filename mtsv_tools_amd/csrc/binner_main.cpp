@@ -30,6 +30,9 @@
 //                     chunk in turn is loaded, made resident, run against the reads and freed, and what outlives it is an
 //                     accumulator of collapsed assignment records in HBM (mtsv_fold_add_run); results, --report and
 //                     --matched / --unmatched come from the accumulated records, byte for byte what --merge-on-gpu writes
+//   --text-on-gpu     with --fold-on-gpu: a piece's result lines are written on the device from the accumulated records
+//                     (mtsv_fold_format_text, k_text.hip) -- the read IDs go up and the text comes down, where otherwise the
+//                     records come down and a host thread formats them; the results file is the same byte for byte
 #include <cstddef>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -128,7 +131,7 @@ struct Args {
     std::string fasta, fastq, index, results, report, matched, unmatched, filter_index, output_format = "default";
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
-    bool verbose = false, force = false, parse_only = false, merge_gpu = false, fold_gpu = false;
+    bool verbose = false, force = false, parse_only = false, merge_gpu = false, fold_gpu = false, text_gpu = false;
     uint64_t fold_reads = 16ull << 20;  // --fold-reads: reads per super-batch of --fold-on-gpu (every chunk is loaded once per super-batch)
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
@@ -235,6 +238,7 @@ int main(int argc, char** argv) {
         else if (key == "--parse-only") a.parse_only = true;
         else if (key == "--merge-on-gpu") a.merge_gpu = true;
         else if (key == "--fold-on-gpu") a.fold_gpu = true;
+        else if (key == "--text-on-gpu") a.text_gpu = true;
         else if (key == "--fold-reads") {
             const std::string v = val();
             char* e = nullptr;
@@ -272,7 +276,9 @@ int main(int argc, char** argv) {
                    "--fold-reads N reads (default 16777216); per super-batch every chunk in turn is loaded, made resident, run and freed,\n"
                    "and its collapsed assignments are folded into an accumulator of records on the GPU; the results file, --report and\n"
                    "--matched / --unmatched are the same as with --merge-on-gpu.  Not with --merge-on-gpu, --filter-index or\n"
-                   "--parse-only; a run that would resume an existing results file is refused)\n");
+                   "--parse-only; a run that would resume an existing results file is refused),\n"
+                   "--text-on-gpu (only with --fold-on-gpu: the result lines are written on the GPU from the accumulated records, and the\n"
+                   "text is what comes to the host; the results file is the same)\n");
             return 0;
         } else if (key == "-V" || key == "--version") {
             printf("mtsv 2.1.0 (%s)\n", mtsv_version());
@@ -284,6 +290,11 @@ int main(int argc, char** argv) {
         usage_error(a.fasta.empty() ? "The following required arguments were not provided: --fasta <FASTA> | --fastq <FASTQ>"
                                     : "The argument '--fasta <FASTA>' cannot be used with '--fastq <FASTQ>'");
     if (a.index.empty() && !a.parse_only) usage_error("The following required arguments were not provided: --index <INDEX>");
+    if (a.text_gpu) {
+        // (decided here, before any file or device is touched)
+        if (a.merge_gpu && !a.fold_gpu) usage_error("The argument '--text-on-gpu' cannot be used with '--merge-on-gpu': it writes the lines of '--fold-on-gpu'");
+        if (!a.fold_gpu) usage_error("The argument '--text-on-gpu' requires '--fold-on-gpu'");
+    }
     if (a.merge_gpu) {
         // (decided here, before any file or device is touched)
         size_t n_chunks = 0;
@@ -730,7 +741,7 @@ int main(int argc, char** argv) {
             return t.tv_sec + t.tv_nsec * 1e-9;
         };
         double t_load = 0, t_resident = 0, t_run = 0, t_fold = 0, t_out = 0;
-        float fold_device_ms = 0;
+        float fold_device_ms = 0, text_device_ms = 0;
         std::vector<std::unique_ptr<ReadBlock>> pieces;
         std::vector<mtsv_fold*> folds;  // one per piece of a super-batch, kept from super-batch to super-batch
         uint64_t super_reads = 0, n_super = 0, reads_done = 0, reads_matched = 0;
@@ -799,8 +810,15 @@ int main(int argc, char** argv) {
                     uint64_t n_recs = 0;
                     char* text = nullptr;
                     uint64_t len = 0;
-                    int rc = long_fmt ? mtsv_fold_download_gi(f, (mtsv_assignment_gi**)&recs, &n_recs) : mtsv_fold_download(f, (mtsv_assignment**)&recs, &n_recs);
-                    if (rc == MTSV_OK)
+                    int rc = MTSV_OK;
+                    if (a.text_gpu) {  // (--text-on-gpu: the lines are written where the records are)
+                        float ms = 0;
+                        rc = mtsv_fold_format_text(f, rb.ids.data(), rb.id_off.data(), rb.n(), &text, &len, &ms);
+                        text_device_ms += ms;
+                    } else {
+                        rc = long_fmt ? mtsv_fold_download_gi(f, (mtsv_assignment_gi**)&recs, &n_recs) : mtsv_fold_download(f, (mtsv_assignment**)&recs, &n_recs);
+                    }
+                    if (rc == MTSV_OK && !a.text_gpu)
                         rc = long_fmt ? mtsv_format_assignments_gi((const mtsv_assignment_gi*)recs, n_recs, rb.ids.data(), rb.id_off.data(), rb.n(), &text, &len)
                                       : mtsv_format_assignments((const mtsv_assignment*)recs, n_recs, rb.ids.data(), rb.id_off.data(), rb.n(), &text, &len);
                     if (rc != MTSV_OK) lib_error();
@@ -932,6 +950,7 @@ int main(int argc, char** argv) {
             fprintf(stderr, "[cli fold timing] super_batches %llu chunks %zu reads %llu; index_load %.3f s, index_to_device %.3f s, upload_and_run %.3f s, fold %.3f s "
                             "(device %.3f ms), results_report_flags %.3f s\n",
                     (unsigned long long)n_super, index_paths.size(), (unsigned long long)reads_done, t_load, t_resident, t_run, t_fold, fold_device_ms, t_out);
+        if (getenv("MTSV_CLI_TIMING") && a.text_gpu) fprintf(stderr, "[cli text timing] text_on_gpu device %.3f ms\n", text_device_ms);
         return leave(0);
     }
     // (batches too large for one parser block are put together from several blocks by appending: those stay in ordinary

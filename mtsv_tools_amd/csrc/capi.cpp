@@ -549,6 +549,17 @@ int mtsv_fold_match_flags(mtsv_fold* f, uint64_t** words, uint64_t* n_reads, uin
     })
 }
 
+// ---- the result lines written on the device (text.hip, k_text.hip) ----
+int mtsv_fold_format_text(mtsv_fold* f, const char* ids, const uint64_t* id_off, uint64_t n_reads, char** text, uint64_t* len, float* device_ms) {
+    if (!f || !ids || !id_off || !text || !len) return fail_arg("null argument");
+    GUARD(f->impl.format_text(ids, id_off, n_reads, text, len, device_ms))
+}
+
+int mtsv_batch_format_text(mtsv_batch* b, const char* ids, const uint64_t* id_off, uint64_t n_reads, char** text, uint64_t* len, float* device_ms) {
+    if (!b || !ids || !id_off || !text || !len) return fail_arg("null argument");
+    GUARD(b->impl.format_text(ids, id_off, n_reads, text, len, device_ms))
+}
+
 int mtsv_batch_download(mtsv_batch* b, mtsv_hit** hits, uint64_t* n_hits) {
     if (!b || !hits || !n_hits) return fail_arg("null argument");
     GUARD(b->impl.download(hits, n_hits))

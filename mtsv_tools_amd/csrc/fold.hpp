@@ -1,9 +1,11 @@
 // fold.hpp -- an accumulator of assignment records in HBM that outlives the workspaces whose runs are folded into it (fold.hip).
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "../../include/mtsv_amd.h"
 #include "batch.hpp"
+#include "text.hpp"
 
 namespace mtsv {
 
@@ -33,6 +35,8 @@ struct Fold {
     uint32_t* d_taxa = nullptr;
     uint64_t* d_counts = nullptr;
     uint64_t taxa_cap = 0;
+    uint32_t text_tile = kTextTile;       // MTSV_TEXT_TILE, read at creation (tests)
+    std::unique_ptr<TextFormatter> text;  // created by the first format_text
 
     Fold(int device, int grain);
     ~Fold();
@@ -46,6 +50,8 @@ struct Fold {
     void download(void** a, uint64_t* n, bool wide);
     void taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_reads, float* device_ms);
     void match_flags(std::vector<uint64_t>& words, uint64_t* n_reads, uint64_t* n_matched);
+    // the result lines of the accumulated records, written on the device (text.hip); the fold is not changed
+    void format_text(const char* ids, const uint64_t* id_off, uint64_t n_reads, char** text, uint64_t* len, float* device_ms);
 
    private:
     void in_room(uint64_t n_b);

@@ -287,5 +287,24 @@ void launch_fold_flags(hipStream_t s, int grain, const void* rec, uint32_t n, ui
 // 4 u64 per taxon of the ascending list taxa, then the reads with a record, then the (read, TaxID) pairs whose TaxID the list does
 // not hold (they are counted nowhere else); 4 * n_taxa + 2 u64, zeroed by the caller.
 void launch_fold_report(hipStream_t s, int grain, const void* rec, uint32_t n, const uint32_t* taxa, uint32_t n_taxa, uint64_t* counts);
+// k_text.hip: the result lines of n assignment records of one grain (ordered by the grain's key, 4-byte aligned), as
+// mtsv_format_assignments / _gi write them.  ids (4-byte aligned, ids_bytes of them) and id_off[n_reads + 1] are the read
+// IDs on the device; a workgroup owns `tile` records (a power of two, 2 .. kTextTileMax); there are text_tiles(n, tile) tiles.
+//   measure: rec_len[i] = the bytes of record i, tile_cnt[t] = the bytes of tile t; ctr[0] += the reads at or above n_reads,
+//            ctr[1] += the ID slots outside the ID bytes or longer than kTextIdMax (ctr: two u64, zeroed by the caller)
+//   scan:    tile_off[0 .. tiles] = the byte at which a tile's text begins, tile_off[tiles] = *total = the bytes of the text;
+//            sums: text_scan_blocks(tiles) u64 of scratch
+//   write:   the text to out[0 .. total); a tile writes nothing outside [tile_off[t], tile_off[t + 1]).  Only after a
+//            measure pass that left both counters at zero.
+constexpr uint32_t kTextTileMax = 1024, kTextTile = 1024;
+constexpr uint64_t kTextIdMax = 1ull << 20;
+uint32_t text_tiles(uint64_t n, uint32_t tile);
+uint32_t text_scan_blocks(uint32_t tiles);
+uint32_t text_window_bytes(uint32_t tile);  // the LDS image of a tile: longer texts leave in several windows
+void launch_text_measure(hipStream_t s, int grain, const void* rec, uint32_t n, const uint8_t* ids, const uint64_t* id_off, uint64_t n_reads,
+                         uint64_t ids_bytes, uint32_t tile, uint32_t* rec_len, uint32_t* tile_cnt, uint64_t* ctr);
+void launch_text_scan(hipStream_t s, const uint32_t* tile_cnt, uint32_t tiles, uint64_t* sums, uint64_t* total, uint64_t* tile_off);
+void launch_text_write(hipStream_t s, int grain, const void* rec, uint32_t n, const uint8_t* ids, const uint64_t* id_off, uint32_t tile,
+                       const uint32_t* rec_len, const uint64_t* tile_off, uint8_t* out);
 
 }  // namespace mtsv
