@@ -156,7 +156,52 @@ void mtsv_index_free(mtsv_index *ix);
 #define MTSV_DEV_DEFAULT 0u
 #define MTSV_DEV_SAMPLED_SA_ONLY 1u /* keep the file's row-sampled SA only (LF-walk locate) */
 #define MTSV_DEV_NO_KMER_TABLE 2u   /* no seed-suffix interval table */
+#define MTSV_DEV_PACK_ON_DEVICE 4u /* pack on the device, below; combines freely with the other two */
 int mtsv_index_to_device(mtsv_index *ix, int hip_device, uint32_t flags);
+
+/* ---- packing on the device (k_pack.hip) ----------------------------------------------------------------------------
+ * By default the host re-packs the file's BWT into rank blocks and its text into codes, on its threads, before the first
+ * byte is uploaded.  With MTSV_DEV_PACK_ON_DEVICE the file's raw bytes cross instead -- bwt (n bytes), the six Occ arrays of
+ * A C G T N $, then the text (n bytes), as temporaries in HBM -- and kernels pack them: per tile of 64 rank blocks a count, a
+ * scan of the tiles' counts, the blocks, a check of every Occ checkpoint of the file against the blocks just written, and
+ * the text's codes.  What is resident afterwards is byte for byte what the host pack uploads -- rank blocks, text codes,
+ * every scalar, device_bytes -- and so is everything built on top of it by the same kernels: the full suffix array, the
+ * k-mer table, its width, its kept levels and tags.  Every temporary is freed before the table's width is decided from
+ * the free HBM.  The SA samples, the bins and the bin lookup table are prepared on the host in both cases.
+ * Errors are the host pack's, text and code: "format: bwt holds a symbol outside ACGTN$", "format: bwt holds no sentinel",
+ * "format: Occ checkpoint J disagrees with the bwt" with J the smallest such checkpoint; nothing stays allocated then.
+ * Environment, read at every upload: MTSV_DEV_PACK=device packs on the device without the flag (for an A/B of the command
+ * line and the tools; the flag an index is resident with is the one that was passed); MTSV_PACK_TILE=1..64 (a power of
+ * two) moves the tile edges, for tests. */
+
+/* For tests, like mtsv_batch_download_reads: a look inside the index resident on `hip_device`.  *out is malloc'd
+ * (mtsv_free) and holds *bytes bytes: the device's array as it is, or for MTSV_DEVPART_HEADER one mtsv_device_header.
+ * MTSV_E_ARG when the index is not resident there or the part is unknown. */
+#define MTSV_DEVPART_HEADER 0   /* mtsv_device_header, below */
+#define MTSV_DEVPART_BLOCKS 1   /* n_blocks rank blocks of 64 bytes */
+#define MTSV_DEVPART_TEXT 2     /* (n + 15) / 16 * 16 + 32 codes, 7 behind n */
+#define MTSV_DEVPART_SA_SAMPLE 3
+#define MTSV_DEVPART_BINS 4     /* n_bins x {start, end, tax_id, gi} u32 */
+#define MTSV_DEVPART_BIN_END 5
+#define MTSV_DEVPART_BIN_LUT 6
+typedef struct {
+    uint32_t n, n_blocks;
+    uint32_t C[5];             /* less[] of A, C, G, T, N */
+    uint32_t sentinel_row;
+    uint32_t sa_s, sa_pow2_shift;
+    uint32_t n_bins, bin_lut_shift;
+    uint32_t kmer_k;           /* 0: no table */
+    uint32_t sa_full;          /* 1 when the full suffix array is resident */
+    uint32_t packed_on_device; /* 1 when this upload packed on the device (by the flag or by MTSV_DEV_PACK) */
+    uint32_t _pad;
+    uint64_t device_bytes;
+    /* times of the upload in ms.  pack_ms: the host pack by the host's clock, or the pack kernels by device events;
+     * copy_ms: the host-to-device copies by the host's clock around the synchronous calls; accel_build_ms: the full
+     * suffix array and the k-mer table, by device events */
+    float pack_ms, copy_ms, accel_build_ms;
+    float _pad2;
+} mtsv_device_header;
+int mtsv_index_download_device(mtsv_index *ix, int hip_device, int part, void **out, uint64_t *bytes);
 
 /* ---- the hot path ----------------------------------------------------------------------- */
 /* bases: concatenated raw read bytes (any case, any byte), read_off[n_reads+1].

@@ -12,6 +12,14 @@ from ._lib import (  # noqa: F401
     ASSIGN_OFF,
     ASSIGN_ONLY,
     ASSIGN_WITH_HITS,
+    DEVPART_BIN_END,
+    DEVPART_BIN_LUT,
+    DEVPART_BINS,
+    DEVPART_BLOCKS,
+    DEVPART_HEADER,
+    DEVPART_SA_SAMPLE,
+    DEVPART_TEXT,
+    DeviceHeader,
     GRAIN_LONG,
     GRAIN_TAXID,
     GRAIN_TAXID_GI,
@@ -51,3 +59,4 @@ from ._lib import (  # noqa: F401
 DEV_DEFAULT = 0
 DEV_SAMPLED_SA_ONLY = 1
 DEV_NO_KMER_TABLE = 2
+DEV_PACK_ON_DEVICE = 4

@@ -23,6 +23,8 @@ MATCH_OFF, MATCH_WITH_HITS, MATCH_ONLY = 0, 1, 2  # MTSV_MATCH_*
 ASSIGN_OFF, ASSIGN_WITH_HITS, ASSIGN_ONLY = 0, 1, 2  # MTSV_ASSIGN_*
 GRAIN_TAXID, GRAIN_TAXID_GI, GRAIN_LONG = 0, 1, 2  # MTSV_GRAIN_*
 KEEP_UNMATCHED, KEEP_MATCHED = 0, 1  # MTSV_KEEP_*
+# MTSV_DEVPART_*
+DEVPART_HEADER, DEVPART_BLOCKS, DEVPART_TEXT, DEVPART_SA_SAMPLE, DEVPART_BINS, DEVPART_BIN_END, DEVPART_BIN_LUT = range(7)
 
 
 class Params(C.Structure):  # mtsv_params
@@ -35,6 +37,14 @@ class IndexInfo(C.Structure):  # mtsv_index_info_t
     _fields_ = [("n", C.c_uint64), ("n_bins", C.c_uint64), ("occ_k", C.c_uint32),
                 ("sa_s", C.c_uint64), ("file_bytes", C.c_uint64), ("device_bytes", C.c_uint64),
                 ("kmer_k", C.c_uint32), ("sa_full", C.c_uint32)]
+
+
+class DeviceHeader(C.Structure):  # mtsv_device_header
+    _fields_ = [("n", C.c_uint32), ("n_blocks", C.c_uint32), ("C", C.c_uint32 * 5), ("sentinel_row", C.c_uint32),
+                ("sa_s", C.c_uint32), ("sa_pow2_shift", C.c_uint32), ("n_bins", C.c_uint32), ("bin_lut_shift", C.c_uint32),
+                ("kmer_k", C.c_uint32), ("sa_full", C.c_uint32), ("packed_on_device", C.c_uint32), ("_pad", C.c_uint32),
+                ("device_bytes", C.c_uint64), ("pack_ms", C.c_float), ("copy_ms", C.c_float), ("accel_build_ms", C.c_float),
+                ("_pad2", C.c_float)]
 
 
 N_STAGES = 8
@@ -94,6 +104,7 @@ EXPORTS = [
     "mtsv_fold_create", "mtsv_fold_free", "mtsv_fold_reset", "mtsv_fold_add_run", "mtsv_fold_add_records", "mtsv_fold_count",
     "mtsv_fold_download", "mtsv_fold_download_gi", "mtsv_fold_taxa_report", "mtsv_fold_match_flags",
     "mtsv_fold_format_text", "mtsv_batch_format_text",
+    "mtsv_index_download_device",
 ]
 
 _lib = None
@@ -120,6 +131,7 @@ def lib():
         L.mtsv_index_free.argtypes = [vp]
         L.mtsv_index_free.restype = None
         L.mtsv_index_to_device.argtypes = [vp, i32, u32]
+        L.mtsv_index_download_device.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_bin_batch.argtypes = [vp, i32, vp, vp, u64, C.POINTER(Params), C.POINTER(vp),
                                      C.POINTER(u64)]
         L.mtsv_hits_free.argtypes = [vp]
@@ -342,6 +354,26 @@ class MGIndex:
 
     def to_device(self, device=0, flags=0):
         _check(lib().mtsv_index_to_device(self.h, device, flags))
+
+    def download_device(self, device=0, part=DEVPART_HEADER):
+        """mtsv_index_download_device (for tests): the resident array `part` as bytes; DEVPART_HEADER as a dict of the
+        scalars of mtsv_device_header (C as a list)"""
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(lib().mtsv_index_download_device(self.h, device, part, C.byref(out), C.byref(n)))
+        try:
+            raw = C.string_at(out.value, n.value)
+        finally:
+            lib().mtsv_free(out)
+        if part != DEVPART_HEADER:
+            return raw
+        h = DeviceHeader.from_buffer_copy(raw)
+        d = {}
+        for name, t in h._fields_:
+            if name.startswith("_"):
+                continue
+            v = getattr(h, name)
+            d[name] = list(v) if name == "C" else float(v) if t is C.c_float else int(v)
+        return d
 
     def bin_batch(self, bases, read_off, params=None, device=0):
         """mtsv_bin_batch: hits ordered by (read, strand, rank)."""

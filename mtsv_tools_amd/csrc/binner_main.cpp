@@ -31,6 +31,7 @@
 //                     accumulator of collapsed assignment records in HBM (mtsv_fold_add_run); results, --report and
 //                     --matched / --unmatched come from the accumulated records, byte for byte what --merge-on-gpu writes
 //   --text-on-gpu     with --fold-on-gpu: a piece's result lines are written on the device from the accumulated records
+//   --fold-prefetch   with --fold-on-gpu: the next chunk's file is read by a loader thread while the resident chunk runs
 //                     (mtsv_fold_format_text, k_text.hip) -- the read IDs go up and the text comes down, where otherwise the
 //                     records come down and a host thread formats them; the results file is the same byte for byte
 #include <cstddef>
@@ -131,7 +132,7 @@ struct Args {
     std::string fasta, fastq, index, results, report, matched, unmatched, filter_index, output_format = "default";
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
-    bool verbose = false, force = false, parse_only = false, merge_gpu = false, fold_gpu = false, text_gpu = false;
+    bool verbose = false, force = false, parse_only = false, merge_gpu = false, fold_gpu = false, text_gpu = false, fold_prefetch = false;
     uint64_t fold_reads = 16ull << 20;  // --fold-reads: reads per super-batch of --fold-on-gpu (every chunk is loaded once per super-batch)
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
@@ -239,6 +240,7 @@ int main(int argc, char** argv) {
         else if (key == "--merge-on-gpu") a.merge_gpu = true;
         else if (key == "--fold-on-gpu") a.fold_gpu = true;
         else if (key == "--text-on-gpu") a.text_gpu = true;
+        else if (key == "--fold-prefetch") a.fold_prefetch = true;
         else if (key == "--fold-reads") {
             const std::string v = val();
             char* e = nullptr;
@@ -278,7 +280,10 @@ int main(int argc, char** argv) {
                    "--matched / --unmatched are the same as with --merge-on-gpu.  Not with --merge-on-gpu, --filter-index or\n"
                    "--parse-only; a run that would resume an existing results file is refused),\n"
                    "--text-on-gpu (only with --fold-on-gpu: the result lines are written on the GPU from the accumulated records, and the\n"
-                   "text is what comes to the host; the results file is the same)\n");
+                   "text is what comes to the host; the results file is the same),\n"
+                   "--fold-prefetch (only with --fold-on-gpu: a loader thread reads chunk c + 1 from its file while chunk c is made\n"
+                   "resident, run and folded, and the chunks are packed into the device layout on the GPU; still one chunk resident\n"
+                   "at a time, at most two in host memory; the files are the same)\n");
             return 0;
         } else if (key == "-V" || key == "--version") {
             printf("mtsv 2.1.0 (%s)\n", mtsv_version());
@@ -295,6 +300,7 @@ int main(int argc, char** argv) {
         if (a.merge_gpu && !a.fold_gpu) usage_error("The argument '--text-on-gpu' cannot be used with '--merge-on-gpu': it writes the lines of '--fold-on-gpu'");
         if (!a.fold_gpu) usage_error("The argument '--text-on-gpu' requires '--fold-on-gpu'");
     }
+    if (a.fold_prefetch && !a.fold_gpu) usage_error("The argument '--fold-prefetch' requires '--fold-on-gpu'");  // (likewise)
     if (a.merge_gpu) {
         // (decided here, before any file or device is touched)
         size_t n_chunks = 0;
@@ -721,8 +727,13 @@ int main(int argc, char** argv) {
         // the parser filled, each block a PIECE with a fold of its own; per chunk: load, make resident, one workspace in
         // MTSV_ASSIGN_ONLY, per piece upload + run + mtsv_fold_add_run, then the workspace and the index are freed.  After the
         // last chunk a piece's records are its result lines (numbered from 0 within the piece, like its IDs: nothing to offset),
-        // its flags split its reads, its report adds to the run's.  Sequential on purpose: loading chunk c + 1 while chunk c
-        // runs is a follow-up.
+        // its flags split its reads, its report adds to the run's.
+        // --fold-prefetch: one loader thread runs mtsv_index_load of chunk c + 1 (after the last chunk: of chunk 0 for the next
+        // super-batch, when one is known to follow) while this thread makes chunk c resident, runs it over the pieces and folds.
+        // The chunks' uploads then pack on the device (MTSV_DEV_PACK_ON_DEVICE), which the measurement found 8 times faster.
+        // Depth 1: at most two host indexes are alive, and still one chunk is resident -- c + 1 goes up after c's workspace
+        // and index are freed.  mtsv_last_error is thread-local: the loader hands its message over with its return code, and
+        // a chunk that failed to load is reported when its turn comes.  flush() joins the loader on every way out.
         const int dev = a.devices[0];
         const int grain = long_fmt ? MTSV_GRAIN_LONG : MTSV_GRAIN_TAXID;
         const uint64_t piece_reads = a.batch_reads + a.batch_reads / 2;
@@ -740,7 +751,28 @@ int main(int argc, char** argv) {
             clock_gettime(CLOCK_MONOTONIC, &t);
             return t.tv_sec + t.tv_nsec * 1e-9;
         };
-        double t_load = 0, t_resident = 0, t_run = 0, t_fold = 0, t_out = 0;
+        double t_load = 0, t_resident = 0, t_run = 0, t_fold = 0, t_out = 0, t_loader = 0;
+        struct Prefetch {  // the loader's chunk: `chunk` is index_paths.size() when there is none
+            std::thread th;
+            size_t chunk;
+            mtsv_index* ix = nullptr;
+            int rc = MTSV_OK;
+            std::string err;
+            double secs = 0;
+        } pre;
+        pre.chunk = index_paths.size();
+        auto pre_start = [&](size_t c) {
+            pre.chunk = c;
+            pre.th = std::thread([&pre, &now, path = index_paths[c]] {
+                const double t0 = now();
+                pre.rc = mtsv_index_load(path.c_str(), &pre.ix);
+                if (pre.rc != MTSV_OK) pre.err = mtsv_last_error();
+                pre.secs = now() - t0;
+            });
+        };
+        auto pre_join = [&] {
+            if (pre.th.joinable()) pre.th.join();
+        };
         float fold_device_ms = 0, text_device_ms = 0;
         std::vector<std::unique_ptr<ReadBlock>> pieces;
         std::vector<mtsv_fold*> folds;  // one per piece of a super-batch, kept from super-batch to super-batch
@@ -762,8 +794,12 @@ int main(int argc, char** argv) {
             }
             return true;
         };
-        auto flush = [&]() -> bool {  // the super-batch collected so far, through every chunk
+        auto flush = [&](bool more) -> bool {  // the super-batch collected so far, through every chunk; more: another one follows
             if (pieces.empty()) return true;
+            struct JoinLoader {  // (no loader thread outlives flush())
+                decltype(pre_join)& join;
+                ~JoinLoader() { join(); }
+            } join_loader{pre_join};
             while (folds.size() < pieces.size()) {
                 mtsv_fold* f = nullptr;
                 if (mtsv_fold_create(dev, grain, &f) != MTSV_OK) return lib_error();
@@ -775,10 +811,33 @@ int main(int argc, char** argv) {
                 mtsv_index* ix = nullptr;
                 mtsv_batch* ws = nullptr;
                 double t0 = now();
-                int rc = mtsv_index_load(index_paths[c].c_str(), &ix);
+                int rc;
+                if (a.fold_prefetch && pre.chunk == c) {  // the loader has it, or is on it: t_load counts the wait
+                    pre_join();
+                    rc = pre.rc;
+                    ix = pre.ix;
+                    t_loader += pre.secs;
+                    pre.ix = nullptr;
+                    pre.chunk = index_paths.size();
+                    if (rc != MTSV_OK) {
+                        logmsg("ERROR", "Error running query: " + pre.err);
+                        code = 2;
+                        return false;
+                    }
+                } else {
+                    rc = mtsv_index_load(index_paths[c].c_str(), &ix);
+                }
                 t_load += now() - t0;
+                if (a.fold_prefetch && rc == MTSV_OK) {
+                    if (c + 1 < index_paths.size())
+                        pre_start(c + 1);
+                    else if (more)
+                        pre_start(0);
+                }
                 t0 = now();
-                if (rc == MTSV_OK) rc = mtsv_index_to_device(ix, dev, MTSV_DEV_DEFAULT);
+                // (under --fold-prefetch the chunk is packed on the device: 63 ms against 527 ms a chunk of 3.45e8 symbols,
+                //  profiles/README.md r18; without the flag the upload is the one it was)
+                if (rc == MTSV_OK) rc = mtsv_index_to_device(ix, dev, a.fold_prefetch ? MTSV_DEV_PACK_ON_DEVICE : MTSV_DEV_DEFAULT);
                 t_resident += now() - t0;
                 if (rc == MTSV_OK) rc = mtsv_batch_create_lanes(ix, dev, piece_reads, piece_bases, 0, 1, &ws);
                 if (rc == MTSV_OK) rc = mtsv_batch_set_assignment_grain(ws, grain);
@@ -879,7 +938,7 @@ int main(int argc, char** argv) {
                 code = 2;
                 return false;
             }
-            if (!pieces.empty() && super_reads + rb->n() > a.fold_reads && !flush()) return false;
+            if (!pieces.empty() && super_reads + rb->n() > a.fold_reads && !flush(true)) return false;
             super_reads += rb->n();
             pieces.push_back(std::move(rb));
             return true;
@@ -899,19 +958,22 @@ int main(int argc, char** argv) {
         auto leave = [&](int c) {
             mtsv_free(sum);
             sum = nullptr;
+            pre_join();  // (joined by flush() already; a chunk it loaded for a super-batch that never came is freed below)
             if (!getenv("MTSV_CLI_CLEAN_EXIT")) {
                 fflush(nullptr);
                 _exit(c);
             }
             for (auto* f : folds) mtsv_fold_free(f);
             folds.clear();
+            mtsv_index_free(pre.ix);
+            pre.ix = nullptr;
             return c;
         };
         if (!parsed && !code) {
             logmsg("ERROR", "Unable to read from input file: " + rd.err_msg);
             code = 12;  // binner.rs:81-84
         }
-        if (!code) flush();
+        if (!code) flush(false);
         if (code) return leave(code);
         if (out_fd >= 0 && ::close(out_fd) != 0) {
             logmsg("ERROR", "Error writing to result file");
@@ -946,10 +1008,15 @@ int main(int argc, char** argv) {
         snprintf(msg, sizeof msg, "All worker and result consumer threads terminated. Took %.3f seconds.", (w1.tv_sec - w0.tv_sec) + (w1.tv_nsec - w0.tv_nsec) * 1e-9);
         logmsg("INFO", msg);
         // MTSV_CLI_TIMING=1: where a folded run spends its time (seconds; tools/fold_ab.py reads this line)
+        // (--fold-prefetch: index_load is the time this thread waited for the loader -- and the first chunk's load -- and the
+        //  loader's own time, which ran beside the other figures, follows)
+        char prefetch_note[96] = "";
+        if (a.fold_prefetch) snprintf(prefetch_note, sizeof prefetch_note, "; prefetch: loader %.3f s, waited_for_loader %.3f s", t_loader, t_load);
         if (getenv("MTSV_CLI_TIMING"))
             fprintf(stderr, "[cli fold timing] super_batches %llu chunks %zu reads %llu; index_load %.3f s, index_to_device %.3f s, upload_and_run %.3f s, fold %.3f s "
-                            "(device %.3f ms), results_report_flags %.3f s\n",
-                    (unsigned long long)n_super, index_paths.size(), (unsigned long long)reads_done, t_load, t_resident, t_run, t_fold, fold_device_ms, t_out);
+                            "(device %.3f ms), results_report_flags %.3f s%s\n",
+                    (unsigned long long)n_super, index_paths.size(), (unsigned long long)reads_done, t_load, t_resident, t_run, t_fold, fold_device_ms, t_out,
+                    prefetch_note);
         if (getenv("MTSV_CLI_TIMING") && a.text_gpu) fprintf(stderr, "[cli text timing] text_on_gpu device %.3f ms\n", text_device_ms);
         return leave(0);
     }

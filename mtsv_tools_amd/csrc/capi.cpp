@@ -227,6 +227,60 @@ static DeviceIndex* device_index(mtsv_index* ix, int dev) {
     return it->second.get();
 }
 
+int mtsv_index_download_device(mtsv_index* ix, int hip_device, int part, void** out, uint64_t* bytes) {
+    if (!ix || !out || !bytes) return fail_arg("null argument");
+    GUARD({
+        std::lock_guard<std::mutex> lk(ix->mu);
+        const DeviceIndex* di = device_index(ix, hip_device);
+        const DevIndexView& v = di->view;
+        mtsv_device_header h;
+        memset(&h, 0, sizeof h);
+        const void* src = nullptr;
+        uint64_t len = 0;
+        switch (part) {
+        case MTSV_DEVPART_HEADER:
+            h.n = v.n;
+            h.n_blocks = v.n_blocks;
+            for (int a = 0; a < 5; a++) h.C[a] = v.C[a];
+            h.sentinel_row = v.sentinel_row;
+            h.sa_s = v.sa_s;
+            h.sa_pow2_shift = v.sa_pow2_shift;
+            h.n_bins = v.n_bins;
+            h.bin_lut_shift = v.bin_lut_shift;
+            h.kmer_k = v.kmer_tab ? v.kmer_k : 0;
+            h.sa_full = v.sa_full ? 1 : 0;
+            h.packed_on_device = di->packed_on_device ? 1 : 0;
+            h.device_bytes = di->bytes;
+            h.pack_ms = di->pack_ms;
+            h.copy_ms = di->copy_ms;
+            h.accel_build_ms = di->accel_build_ms;
+            len = sizeof h;
+            break;
+        case MTSV_DEVPART_BLOCKS: src = di->d_blocks, len = (uint64_t)v.n_blocks * sizeof(RankBlock); break;
+        case MTSV_DEVPART_TEXT: src = di->d_text, len = di->text_bytes; break;
+        case MTSV_DEVPART_SA_SAMPLE: src = di->d_sa_sample, len = di->sa_sample_bytes; break;
+        case MTSV_DEVPART_BINS: src = di->d_bins, len = (uint64_t)v.n_bins * sizeof(DevBin); break;
+        case MTSV_DEVPART_BIN_END: src = di->d_bin_end, len = (uint64_t)v.n_bins * 4; break;
+        case MTSV_DEVPART_BIN_LUT: src = di->d_bin_lut, len = di->bin_lut_bytes; break;
+        default: throw std::runtime_error("arg: unknown MTSV_DEVPART_* " + std::to_string(part));
+        }
+        void* p = malloc(len ? len : 1);
+        if (!p) throw std::bad_alloc();
+        if (part == MTSV_DEVPART_HEADER) {
+            memcpy(p, &h, sizeof h);
+        } else if (len) {
+            hipError_t e = hipSetDevice(hip_device);
+            if (e == hipSuccess) e = hipMemcpy(p, src, len, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                free(p);
+                throw std::runtime_error(std::string("device: ") + hipGetErrorString(e) + " at mtsv_index_download_device");
+            }
+        }
+        *out = p;
+        *bytes = len;
+    })
+}
+
 int mtsv_batch_create(mtsv_index* ix, int hip_device, uint64_t max_reads, uint64_t max_bases, uint64_t max_hits_ws,
                       mtsv_batch** out) {
     if (!ix || !out) return fail_arg("null argument");

@@ -7,6 +7,7 @@
 //     steps of FMIndex::backward_search (call site src/index.rs:305) become one 8-byte gather.
 // Both hold exactly the values the reference's primitives would compute; results are unchanged.
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "dev_index.hpp"
+#include "kernels.hpp"
 
 namespace mtsv {
 
@@ -143,23 +145,14 @@ void parallel_ranges(uint64_t n, int threads, F fn) {
 
 }  // namespace
 
-std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint32_t flags) {
-    const uint64_t n64 = hx.n();
-    if (n64 >= 0xFFFFFF00ull)
-        throw std::runtime_error("limit: index of 2^32 symbols or more does not fit the u32 device layout; chunk the database (mtsv-chunk)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw std::runtime_error("device: no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) throw std::runtime_error("device: invalid device ordinal " + std::to_string(device));
-    HIP_CHECK(hipSetDevice(device));
-
-    const uint32_t n = (uint32_t)n64;
-    const uint32_t n_blocks = (n >> kBlockShift) + 1;
+// The host pack: the rank blocks, the sentinel's row and the padded text codes of hx.
+static void pack_on_host(const HostIndex& hx, const uint32_t n, const uint32_t n_blocks, std::vector<RankBlock>& blocks, uint64_t& sentinel_row,
+                         std::vector<uint8_t>& codes) {
     int threads = (int)std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
     if (n_blocks < 4096) threads = 1;
 
     // ---- pack rank blocks (two passes: per-range symbol counts, then blocks) ----------------
-    std::vector<RankBlock> blocks(n_blocks);
+    blocks.resize(n_blocks);
     std::vector<std::array<uint64_t, 6>> range_cnt(threads);
     // ranges are block-aligned
     uint64_t blocks_per = ((uint64_t)n_blocks + threads - 1) / threads;
@@ -224,16 +217,143 @@ std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint3
     });
     for (auto& e : errs)
         if (!e.empty()) throw std::runtime_error(e);
-    uint64_t sentinel_row = UINT64_MAX;
+    sentinel_row = UINT64_MAX;
     for (uint64_t s : sentinel_rows)
         if (s != UINT64_MAX) sentinel_row = s;
     if (sentinel_row == UINT64_MAX) throw std::runtime_error("format: bwt holds no sentinel");
 
-    // ---- text codes, SA samples, bins ---------------------------------------------------------
-    std::vector<uint8_t> codes(((uint64_t)n + 15) / 16 * 16 + 32, (uint8_t)7);  // padded for load16(): two aligned 16-byte loads from any position
+    // ---- text codes ---------------------------------------------------------------------------
+    codes.assign(((uint64_t)n + 15) / 16 * 16 + 32, (uint8_t)7);  // padded for load16(): two aligned 16-byte loads from any position
     parallel_ranges(n, threads, [&](uint64_t lo, uint64_t hi, int) {
         for (uint64_t i = lo; i < hi; i++) codes[i] = (uint8_t)sym_code(hx.text[i]);
     });
+}
+
+// The device pack (k_pack.hip): d_blocks and d_text of di from the file's raw bytes, to the bytes pack_on_host makes, with its
+// errors.  Uploaded raw, as temporaries: the bwt, the six Occ arrays of A C G T N $, then the text; all are freed before this
+// returns (the bwt's before the text is uploaded).  The counters are read once, after the pack.  Returns the sentinel's row.
+namespace {
+struct DevTemp {  // hipFree on every way out
+    void* p = nullptr;
+    ~DevTemp() { (void)hipFree(p); }
+    void alloc(uint64_t bytes) { HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16)); }
+    void release() {
+        HIP_CHECK(hipFree(p));
+        p = nullptr;
+    }
+};
+struct DevEvents {
+    hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevEvents() {
+        for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
+    }
+    ~DevEvents() {
+        for (auto& x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+}  // namespace
+
+static uint64_t pack_on_device(const HostIndex& hx, const uint32_t n, const uint32_t n_blocks, DeviceIndex& di, double& copy_ms) {
+    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    uint32_t tile = kPackTile;
+    if (const char* e = getenv("MTSV_PACK_TILE")) {  // (moves the tile edges, for tests)
+        const int t = atoi(e);
+        if (t >= 1 && t <= (int)kPackTileMax && !(t & (t - 1))) tile = (uint32_t)t;
+    }
+    static const uint8_t syms[6] = {'A', 'C', 'G', 'T', 'N', '$'};
+    const uint64_t n_chk = ((uint64_t)n - 1) / hx.k + 1;
+    for (uint8_t a : syms)
+        if (hx.occ[a].size() < n_chk) throw std::runtime_error("format: occ checkpoint count != floor((n-1)/k)+1");
+    const uint32_t tiles = pack_tiles(n_blocks, tile);
+    const uint64_t raw_bytes = ((uint64_t)n + 15) / 16 * 16;
+    DevEvents ev;
+    DevTemp d_bwt, d_occ, d_tiles, d_ctr, d_raw_text;
+
+    HIP_CHECK(hipMalloc((void**)&di.d_blocks, (uint64_t)n_blocks * sizeof(RankBlock)));
+    di.bytes += (uint64_t)n_blocks * sizeof(RankBlock);
+    d_bwt.alloc(raw_bytes);
+    d_occ.alloc(6 * n_chk * 8);
+    d_tiles.alloc((uint64_t)tiles * sizeof(uint4));
+    d_ctr.alloc(kPackCounters * 4);
+    uint32_t ctr[kPackCounters] = {0};
+    ctr[kPackCtrForeignRow] = ctr[kPackCtrOccBadFirst] = 0xffffffffu;
+    double t0 = now_ms();
+    HIP_CHECK(hipMemcpy(d_bwt.p, hx.bwt.data(), n, hipMemcpyHostToDevice));
+    for (int a = 0; a < 6; a++)
+        HIP_CHECK(hipMemcpy((uint64_t*)d_occ.p + a * n_chk, hx.occ[syms[a]].data(), n_chk * 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_ctr.p, ctr, sizeof ctr, hipMemcpyHostToDevice));
+    copy_ms += now_ms() - t0;
+
+    HIP_CHECK(hipEventRecord(ev.e[0], 0));
+    launch_pack_count(0, (const uint8_t*)d_bwt.p, n, n_blocks, tile, (uint4*)d_tiles.p, (uint32_t*)d_ctr.p);
+    HIP_CHECK(hipEventRecord(ev.e[1], 0));
+    launch_pack_scan(0, (uint4*)d_tiles.p, tiles);
+    HIP_CHECK(hipEventRecord(ev.e[2], 0));
+    launch_pack_blocks(0, (const uint8_t*)d_bwt.p, n, n_blocks, tile, (const uint4*)d_tiles.p, di.d_blocks);
+    HIP_CHECK(hipEventRecord(ev.e[3], 0));
+    launch_pack_check_occ(0, di.d_blocks, n, hx.k, (uint32_t)n_chk, (const uint64_t*)d_occ.p, (uint32_t*)d_ctr.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[4], 0));
+    HIP_CHECK(hipMemcpy(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));  // (after the kernels: the null stream orders them)
+    d_bwt.release();
+    d_occ.release();
+    d_tiles.release();
+    d_ctr.release();
+    // the host's order: the error of the lowest row wins, and at one row the foreign symbol comes before the checkpoint
+    const uint64_t occ_row = ctr[kPackCtrOccBad] ? (uint64_t)ctr[kPackCtrOccBadFirst] * hx.k : UINT64_MAX;
+    if (ctr[kPackCtrForeign] && ctr[kPackCtrForeignRow] <= occ_row) throw std::runtime_error("format: bwt holds a symbol outside ACGTN$");
+    if (ctr[kPackCtrOccBad])
+        throw std::runtime_error("format: Occ checkpoint " + std::to_string(ctr[kPackCtrOccBadFirst]) + " disagrees with the bwt");
+    if (!ctr[kPackCtrSentinels]) throw std::runtime_error("format: bwt holds no sentinel");
+
+    HIP_CHECK(hipMalloc((void**)&di.d_text, di.text_bytes));
+    di.bytes += di.text_bytes;
+    d_raw_text.alloc(raw_bytes);
+    t0 = now_ms();
+    HIP_CHECK(hipMemcpy(d_raw_text.p, hx.text.data(), n, hipMemcpyHostToDevice));
+    copy_ms += now_ms() - t0;
+    HIP_CHECK(hipEventRecord(ev.e[5], 0));
+    launch_pack_text(0, (const uint8_t*)d_raw_text.p, n, di.d_text, di.text_bytes);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ev.e[6], 0));
+    HIP_CHECK(hipEventSynchronize(ev.e[6]));
+    d_raw_text.release();
+    float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // count, scan, blocks, check_occ, text
+    for (int k = 0; k < 4; k++) HIP_CHECK(hipEventElapsedTime(&ms[k], ev.e[k], ev.e[k + 1]));
+    HIP_CHECK(hipEventElapsedTime(&ms[4], ev.e[5], ev.e[6]));
+    di.pack_ms = ms[0] + ms[1] + ms[2] + ms[3] + ms[4];
+    if (getenv("MTSV_TRACE"))
+        fprintf(stderr, "[upload] pack on device, tile %u: k_pack_count %.3f k_pack_scan %.3f k_pack_blocks %.3f k_pack_check_occ %.3f k_pack_text %.3f ms\n",
+                tile, ms[0], ms[1], ms[2], ms[3], ms[4]);
+    return ctr[kPackCtrSentinelRow];
+}
+
+std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint32_t flags) {
+    const uint64_t n64 = hx.n();
+    if (n64 >= 0xFFFFFF00ull)
+        throw std::runtime_error("limit: index of 2^32 symbols or more does not fit the u32 device layout; chunk the database (mtsv-chunk)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        throw std::runtime_error("device: no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) throw std::runtime_error("device: invalid device ordinal " + std::to_string(device));
+    HIP_CHECK(hipSetDevice(device));
+
+    const uint32_t n = (uint32_t)n64;
+    const uint32_t n_blocks = (n >> kBlockShift) + 1;
+    // MTSV_DEV_PACK=device: uploads that do not pass the flag pack on the device too (read at every upload: an A/B switch)
+    const char* pack_env = getenv("MTSV_DEV_PACK");
+    const bool on_device = (flags & 4u /* MTSV_DEV_PACK_ON_DEVICE */) || (pack_env && !strcmp(pack_env, "device"));
+    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+
+    std::vector<RankBlock> blocks;
+    std::vector<uint8_t> codes;
+    uint64_t sentinel_row = UINT64_MAX;
+    const double pack_t0 = now_ms();
+    if (!on_device) pack_on_host(hx, n, n_blocks, blocks, sentinel_row, codes);
+    const double host_pack_ms = now_ms() - pack_t0;
+
+    // ---- SA samples, bins (on the host for both packs: n / s elements or fewer) ----------------
     std::vector<uint32_t> samp(hx.sample.size());
     for (size_t i = 0; i < samp.size(); i++) samp[i] = (uint32_t)hx.sample[i];
     std::vector<DevBin> bins(hx.bins.size());
@@ -259,14 +379,29 @@ std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint3
     auto di = std::make_unique<DeviceIndex>();
     di->device = device;
     di->flags = flags;
+    double copy_ms = 0;
     auto up = [&](auto** dptr, const void* src, uint64_t bytes) {
         HIP_CHECK(hipMalloc((void**)dptr, bytes ? bytes : 16));
+        const double t0 = now_ms();
         if (bytes) HIP_CHECK(hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice));
+        copy_ms += now_ms() - t0;
         di->bytes += bytes;
     };
-    up(&di->d_blocks, blocks.data(), (uint64_t)n_blocks * sizeof(RankBlock));
-    up(&di->d_sa_sample, samp.data(), samp.size() * 4);
-    up(&di->d_text, codes.data(), codes.size());
+    di->text_bytes = ((uint64_t)n + 15) / 16 * 16 + 32;
+    di->sa_sample_bytes = samp.size() * 4;
+    di->bin_lut_bytes = bin_lut.size() * 4;
+    di->packed_on_device = on_device;
+    if (on_device) {
+        // d_blocks and d_text from the raw bytes; every temporary is freed in there, before the k-mer table below asks
+        // hipMemGetInfo what is free
+        sentinel_row = pack_on_device(hx, n, n_blocks, *di, copy_ms);
+        up(&di->d_sa_sample, samp.data(), samp.size() * 4);
+    } else {
+        di->pack_ms = (float)host_pack_ms;
+        up(&di->d_blocks, blocks.data(), (uint64_t)n_blocks * sizeof(RankBlock));
+        up(&di->d_sa_sample, samp.data(), samp.size() * 4);
+        up(&di->d_text, codes.data(), codes.size());
+    }
     up(&di->d_bin_end, bin_end.data(), bin_end.size() * 4);
     up(&di->d_bins, bins.data(), bins.size() * sizeof(DevBin));
     up(&di->d_bin_lut, bin_lut.data(), bin_lut.size() * 4);
@@ -413,6 +548,7 @@ std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint3
     HIP_CHECK(hipEventElapsedTime(&di->accel_build_ms, e0, e1));
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    di->copy_ms = (float)copy_ms;
     return di;
 }
 

@@ -32,6 +32,11 @@ struct DeviceIndex {
     uint64_t bytes = 0;
     uint32_t flags = 0;
     float accel_build_ms = 0.f;
+    // mtsv_index_download_device: the sizes of the arrays the view does not carry, how the upload packed, and its times --
+    // pack_ms: the host pack (host clock) or the pack kernels (device events); copy_ms: the host-to-device copies (host clock)
+    uint64_t text_bytes = 0, sa_sample_bytes = 0, bin_lut_bytes = 0;
+    bool packed_on_device = false;
+    float pack_ms = 0.f, copy_ms = 0.f;
 
     DeviceIndex() = default;
     DeviceIndex(const DeviceIndex&) = delete;
@@ -39,7 +44,8 @@ struct DeviceIndex {
     ~DeviceIndex();
 };
 
-// Pack (host, multi-threaded) + upload + build the HBM-only acceleration structures.
+// Pack (host, multi-threaded; with flag 4, MTSV_DEV_PACK_ON_DEVICE, or MTSV_DEV_PACK=device in the environment: the raw
+// bytes are uploaded and packed by k_pack.hip, to the same bytes) + upload + build the HBM-only acceleration structures.
 // Throws std::runtime_error ("device: ...", "limit: ...", "format: ...").
 std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint32_t flags);
 

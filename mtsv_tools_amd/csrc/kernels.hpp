@@ -306,5 +306,27 @@ void launch_text_measure(hipStream_t s, int grain, const void* rec, uint32_t n, 
 void launch_text_scan(hipStream_t s, const uint32_t* tile_cnt, uint32_t tiles, uint64_t* sums, uint64_t* total, uint64_t* tile_off);
 void launch_text_write(hipStream_t s, int grain, const void* rec, uint32_t n, const uint8_t* ids, const uint64_t* id_off, uint32_t tile,
                        const uint32_t* rec_len, const uint64_t* tile_off, uint8_t* out);
+// k_pack.hip: the file's raw bytes into the HBM layout, for upload_index under MTSV_DEV_PACK_ON_DEVICE.  bwt: n raw bytes;
+// blocks: n_blocks = (n >> 7) + 1 rank blocks; a workgroup owns `tile` blocks (a power of two, 1 .. kPackTileMax); there are
+// pack_tiles(n_blocks, tile) tiles.  ctr: kPackCounters u32, set by the caller to 0 except the two *First/*Row minima
+// (0xffffffff).
+//   count:  tile_cnt[t] = the A, C, G, T of tile t; ctr[kPackCtrForeign] += bytes outside ACGTN$ ([kPackCtrForeignRow]: the
+//           first such row), ctr[kPackCtrSentinels] += sentinels ([kPackCtrSentinelRow]: the last one's row)
+//   scan:   tile_cnt to its exclusive prefixes, in place
+//   blocks: every block of every tile, byte for byte what the host packs; rows at and beyond n hold code 7
+//   check_occ: occ holds the file's six Occ arrays of A C G T N $, n_chk = (n - 1) / k + 1 entries each, one after the other;
+//           ctr[kPackCtrOccBad] += checkpoints that disagree with the blocks, [kPackCtrOccBadFirst] = the smallest of them.
+//           Reads the sentinel counters: after count, on the same stream.
+//   text:   codes[0 .. codes_bytes) (a multiple of 16) from text[0 .. n), 7 behind n; text is readable up to the next
+//           multiple of 16 bytes
+constexpr uint32_t kPackTileMax = 64, kPackTile = 64;
+constexpr uint32_t kPackCtrForeign = 0, kPackCtrForeignRow = 1, kPackCtrSentinels = 2, kPackCtrSentinelRow = 3, kPackCtrOccBad = 4,
+                   kPackCtrOccBadFirst = 5, kPackCounters = 8;
+uint32_t pack_tiles(uint32_t n_blocks, uint32_t tile);
+void launch_pack_count(hipStream_t s, const uint8_t* bwt, uint32_t n, uint32_t n_blocks, uint32_t tile, uint4* tile_cnt, uint32_t* ctr);
+void launch_pack_scan(hipStream_t s, uint4* tile_cnt, uint32_t n_tiles);
+void launch_pack_blocks(hipStream_t s, const uint8_t* bwt, uint32_t n, uint32_t n_blocks, uint32_t tile, const uint4* tile_off, RankBlock* blocks);
+void launch_pack_check_occ(hipStream_t s, const RankBlock* blocks, uint32_t n, uint32_t k, uint32_t n_chk, const uint64_t* occ, uint32_t* ctr);
+void launch_pack_text(hipStream_t s, const uint8_t* text, uint32_t n, uint8_t* codes, uint64_t codes_bytes);
 
 }  // namespace mtsv
