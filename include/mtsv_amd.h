@@ -537,6 +537,40 @@ int mtsv_fold_download_gi(mtsv_fold *f, mtsv_assignment_gi **a, uint64_t *n);
 int mtsv_fold_taxa_report(mtsv_fold *f, mtsv_taxon_stats **rows, uint64_t *n_rows, uint64_t *total_reads, float *device_ms);
 int mtsv_fold_match_flags(mtsv_fold *f, uint64_t **words, uint64_t *n_reads, uint64_t *n_matched);
 
+/* ---- result text folded on the device: per-chunk result files that already exist ------------------------------------------
+ * The documented way to run a chunked database is one mtsv-binner job per chunk, often on other nodes or days, and
+ * mtsv-collapse over the per-chunk result files.  mtsv_fold_add_run needs the run in this process; this call takes the
+ * run's TEXT: it is the inverse of mtsv_fold_format_text, and what mtsv-collapse --on-gpu is built on.
+ *   hits                 the hit parts of n_lines result lines laid end to end -- what stands behind the last ':' of a line,
+ *                        without ID, ':' or line end
+ *   line_off[n_lines+1]  ascending from 0: line j is hits[line_off[j] .. line_off[j + 1]), TOKEN(,TOKEN)* or nothing
+ *   line_read[n_lines]   the number the caller gave the line's read ID, strictly ascending over the non-empty lines and
+ *                        below the n_reads of the last mtsv_fold_reset (a file that names an ID on several lines, or whose
+ *                        lines are not in the order of the numbering, is the caller's to cut and reorder)
+ * A token is T=E, T-G=E or T-G-O=E, every number 1 to 10 decimal digits with value <= 4294967295, as the binners and
+ * mtsv-collapse write them.  A fold of MTSV_GRAIN_TAXID takes all three shapes and uses T and E; the two wide grains need
+ * T-G-O=E.  Inside a line the tokens ascend by the key of the fold's grain (equal keys may follow each other) -- long-format
+ * lines are ordered by (tax, gi, offset), so they do, at every grain.  A run of adjacent tokens with one key becomes one
+ * record with the smallest edit, at MTSV_GRAIN_TAXID_GI the smallest (edit, offset): the list is what k_collapse leaves of a
+ * run, and it goes the way mtsv_fold_add_run's list goes.  No record crosses to the host or comes from it.
+ * The kernels (k_parse.hip) are byte-parallel, then record-parallel: a workgroup owns a tile of bytes, a byte starts a token
+ * when it begins a non-empty line or follows a ',', every token is parsed by the lane of its first byte, the runs of equal
+ * keys are found by comparing neighbours, scanned, and reduced with one 64-bit atomic minimum per token.  A line of
+ * thousands of tokens costs what thousands of short lines do.  MTSV_PARSE_TILE (a power of two, 64..16384 bytes), read by
+ * mtsv_fold_create, moves the tile size (tests).  The arrays of the call grow by reallocation and are kept by the fold.
+ * *n_tokens, *n_records (may be NULL): the tokens of the call and the records they made.  device_ms (may be NULL): device
+ * time of the parse kernels and of the fold's.  The records' TaxIDs join the union (they cross to the host, 4 bytes each).
+ * Refusals, all before the accumulator is touched -- the fold is as it was, mtsv_last_error names the first such line:
+ *   MTSV_E_FORMAT  a token outside the grammar above (a trailing or doubled ',' makes an empty one), or, in a wide grain,
+ *                  without GI and offset; offsets of 2^32 and above are outside it
+ *   MTSV_E_ARG     a line whose keys descend; a line_read not above the previous non-empty line's, or at or above n_reads;
+ *                  line_off that does not start at 0 or descends; a null array
+ *   MTSV_E_LIMIT   2^32 tokens or more in one call; a fold that would hold 2^32 records or more
+ * n_lines == 0 and empty lines fold nothing.  Not done here: mtsv-binner --fold-on-gpu starting from an earlier results file,
+ * which this call makes possible. */
+int mtsv_fold_add_text(mtsv_fold *f, const char *hits, const uint64_t *line_off, const uint32_t *line_read, uint64_t n_lines,
+                       uint64_t *n_tokens, uint64_t *n_records, float *device_ms);
+
 /* ---- result lines written on the device: the results file from records that never leave HBM as records ------------------
  * mtsv_format_assignments* walk downloaded records on a host thread.  These two calls write the same bytes on the device
  * (k_text.hip) from records that lie in HBM already, and what crosses to the host is the text: one line per read that has a

@@ -105,6 +105,7 @@ EXPORTS = [
     "mtsv_fold_download", "mtsv_fold_download_gi", "mtsv_fold_taxa_report", "mtsv_fold_match_flags",
     "mtsv_fold_format_text", "mtsv_batch_format_text",
     "mtsv_index_download_device",
+    "mtsv_fold_add_text",
 ]
 
 _lib = None
@@ -196,6 +197,7 @@ def lib():
         L.mtsv_fold_match_flags.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.mtsv_fold_format_text.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_batch_format_text.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_fold_add_text.argtypes = [vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -645,6 +647,21 @@ class Fold:
         ms = C.c_float()
         _check(lib().mtsv_fold_add_records(self.h, records.ctypes.data, len(records), C.byref(ms)))
         return ms.value
+
+    def add_text(self, hits, line_off, line_read):
+        """mtsv_fold_add_text: parses the hit parts of result lines on the device and folds their records.  hits: bytes (or a
+        uint8 array), line_off: n_lines + 1 offsets into it, line_read: the lines' read numbers; returns (tokens, records,
+        device ms)"""
+        hits = np.frombuffer(hits, dtype=np.uint8) if isinstance(hits, (bytes, bytearray)) else np.ascontiguousarray(hits, dtype=np.uint8)
+        line_off = np.ascontiguousarray(line_off, dtype=np.uint64)
+        line_read = np.ascontiguousarray(line_read, dtype=np.uint32)
+        n_lines = len(line_read)
+        if n_lines and len(line_off) != n_lines + 1:
+            raise ValueError("line_off must hold one more entry than line_read")
+        n_tok, n_rec, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_fold_add_text(self.h, hits.ctypes.data if len(hits) else None, line_off.ctypes.data if n_lines else None,
+                                        line_read.ctypes.data if n_lines else None, n_lines, C.byref(n_tok), C.byref(n_rec), C.byref(ms)))
+        return n_tok.value, n_rec.value, ms.value
 
     def count(self):
         n = C.c_uint64()

@@ -562,6 +562,12 @@ int mtsv_fold_add_records(mtsv_fold* f, const void* records, uint64_t n, float* 
     GUARD(f->impl.add_records(records, n, device_ms))
 }
 
+int mtsv_fold_add_text(mtsv_fold* f, const char* hits, const uint64_t* line_off, const uint32_t* line_read, uint64_t n_lines, uint64_t* n_tokens,
+                       uint64_t* n_records, float* device_ms) {
+    if (!f || (n_lines && (!line_off || !line_read)) || (n_lines && line_off[n_lines] && !hits)) return fail_arg("null argument");
+    GUARD(f->impl.add_text(hits, line_off, line_read, n_lines, n_tokens, n_records, device_ms))
+}
+
 int mtsv_fold_count(const mtsv_fold* f, uint64_t* n) {
     if (!f || !n) return fail_arg("null argument");
     *n = f->impl.n;

@@ -5,6 +5,13 @@
 // report (collapse.rs:717-753).  Host-side text processing: SURVEY 8(f) rank 2, needed to score
 // BASELINE config 5 (one index chunk per GPU, reads broadcast).  Inputs are sorted externally in runs of
 // 128 MiB (collapse.rs:427-475,665), so result files larger than memory collapse too.
+//
+// --on-gpu [--device N]: the same output from the device.  The files are mapped and cut into lines, the distinct read IDs
+// sorted into a dictionary (collapse_lines.hpp), and the hit parts go, piece by piece through page-locked staging, to
+// mtsv_fold_add_text: k_parse.hip turns the text into records in HBM, k_fold.hip merges them, k_fold_report counts the
+// report and k_text.hip writes the lines.  Input the device path refuses -- a token outside the canonical grammar, a line
+// whose keys do not ascend, taxid-gi mode on tokens without an offset -- goes to the host path below as a whole, before the
+// output file is created, so every error text and exit code stays this file's.  Without --on-gpu no device is opened.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +23,11 @@
 #include <vector>
 
 #include <unistd.h>
+
+#include <chrono>
+
+#include "../../include/mtsv_amd.h"
+#include "collapse_lines.hpp"
 
 namespace {
 
@@ -80,11 +92,158 @@ struct Stats {
     uint64_t only_hit = 0, only_best = 0, tied_best = 0, not_best = 0;
 };
 
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+constexpr int kGpuFallBack = -1000;  // run_on_gpu: the input is the host path's
+
+// mtsv-collapse --on-gpu.  Returns the exit code, or kGpuFallBack with nothing written.
+int run_on_gpu(const std::vector<std::string>& files, const std::string& out_path, const std::string& report, bool by_gi, int device, bool verbose) {
+    namespace mc = mtsv_collapse;
+    const bool timing = getenv("MTSV_COLLAPSE_TIMING") != nullptr;
+    auto fall_back = [&](const std::string& why) {
+        if (verbose) fprintf(stderr, "mtsv-collapse: --on-gpu: %s; the host path takes the input\n", why.c_str());
+        return kGpuFallBack;
+    };
+    auto device_error = [&](const char* what) {
+        fprintf(stderr, "mtsv-collapse: --on-gpu: %s: %s\n", what, mtsv_last_error());
+        return 2;
+    };
+    uint64_t piece_bytes = 64ull << 20;
+    if (const char* e = getenv("MTSV_COLLAPSE_PIECE_BYTES")) piece_bytes = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    // ---- lines and dictionary ----
+    const double t0 = now_ms();
+    std::vector<mc::FileBytes> bytes(files.size());
+    std::vector<std::vector<mc::Line>> lines(files.size());
+    for (size_t f = 0; f < files.size(); f++) {
+        if (!bytes[f].open(files[f])) return fall_back("cannot read " + files[f]);
+        std::string bad;
+        if (!mc::split_lines(bytes[f].p, bytes[f].n, lines[f], &bad)) return fall_back("a line of " + files[f] + " has no read ID");
+        for (const auto& l : lines[f])
+            if (l.id_len > (1ull << 20) || memchr(l.id, 0, (size_t)l.id_len)) return fall_back("a read ID of " + files[f] + " holds a NUL or more than 2^20 bytes");
+    }
+    std::vector<const mc::Line*> dict;
+    if (!mc::build_dictionary(lines, dict)) return fall_back("2^32 read IDs or more");
+    const uint64_t n_reads = dict.size();
+    const double t1 = now_ms();
+    // ---- the fold ----
+    mtsv_fold* fold = nullptr;
+    if (mtsv_fold_create(device, by_gi ? MTSV_GRAIN_TAXID_GI : MTSV_GRAIN_TAXID, &fold) != MTSV_OK) return device_error("no fold on the device");
+    struct Closer {
+        mtsv_fold* f;
+        char* stage = nullptr;
+        ~Closer() {
+            if (stage) mtsv_host_free(stage);
+            mtsv_fold_free(f);
+        }
+    } hold{fold};
+    if (mtsv_fold_reset(fold, n_reads) != MTSV_OK) return device_error("mtsv_fold_reset");
+    double stage_ms = 0, add_ms = 0;
+    uint64_t stage_cap = 0, n_calls = 0, n_tokens = 0, n_bytes = 0;
+    std::vector<const mc::Line*> order;
+    std::vector<mc::Piece> pieces;
+    std::vector<uint64_t> line_off;
+    std::vector<uint32_t> line_read;
+    for (size_t f = 0; f < files.size(); f++) {
+        const double ta = now_ms();
+        mc::cut_pieces(lines[f], piece_bytes, order, pieces);
+        stage_ms += now_ms() - ta;
+        for (const auto& p : pieces) {
+            const double tb = now_ms();
+            if (p.bytes > stage_cap || !hold.stage) {
+                if (hold.stage) mtsv_host_free(hold.stage);
+                // (room for the largest piece of this file: page-locking memory costs by the byte, and files are of a size)
+                stage_cap = 4096;
+                for (const auto& q : pieces) stage_cap = std::max(stage_cap, q.bytes + q.bytes / 8);
+                hold.stage = (char*)mtsv_host_alloc((size_t)stage_cap);
+                if (!hold.stage) return device_error("no page-locked staging");
+            }
+            mc::stage_piece(order, p, hold.stage, line_off, line_read);
+            const double tc = now_ms();
+            uint64_t tok = 0, rec = 0;
+            const int rc = mtsv_fold_add_text(fold, hold.stage, line_off.data(), line_read.data(), line_read.size(), &tok, &rec, nullptr);
+            stage_ms += tc - tb;
+            add_ms += now_ms() - tc;
+            n_calls++;
+            n_tokens += tok;
+            n_bytes += p.bytes;
+            if (rc == MTSV_OK) continue;
+            const std::string why = mtsv_last_error();
+            if (rc == MTSV_E_FORMAT || rc == MTSV_E_LIMIT || (rc == MTSV_E_ARG && why.find("a key below") != std::string::npos))
+                return fall_back(files[f] + ": " + why);
+            return device_error("mtsv_fold_add_text");
+        }
+    }
+    // ---- the lines and the report come from the fold ----
+    const double t2 = now_ms();
+    std::string ids;
+    std::vector<uint64_t> id_off(n_reads + 1, 0);
+    for (uint64_t r = 0; r < n_reads; r++) {
+        ids.append(dict[r]->id, (size_t)dict[r]->id_len);
+        id_off[r + 1] = ids.size();
+    }
+    if (ids.empty()) ids.push_back('\0');  // (a pointer the library accepts)
+    char* text = nullptr;
+    uint64_t text_len = 0;
+    if (mtsv_fold_format_text(fold, ids.data(), id_off.data(), n_reads, &text, &text_len, nullptr) != MTSV_OK) return device_error("mtsv_fold_format_text");
+    const double t3 = now_ms();
+    char* rep_text = nullptr;
+    uint64_t rep_len = 0;
+    if (!report.empty()) {
+        mtsv_taxon_stats* rows = nullptr;
+        uint64_t n_rows = 0, total_reads = 0;
+        if (mtsv_fold_taxa_report(fold, &rows, &n_rows, &total_reads, nullptr) != MTSV_OK) {
+            mtsv_free(text);
+            return device_error("mtsv_fold_taxa_report");
+        }
+        const int rc = mtsv_format_taxa_report(rows, n_rows, total_reads, &rep_text, &rep_len);
+        mtsv_free(rows);
+        if (rc != MTSV_OK) {
+            mtsv_free(text);
+            return device_error("mtsv_format_taxa_report");
+        }
+    }
+    const double t4 = now_ms();
+    FILE* out = fopen(out_path.c_str(), "wb");
+    if (!out) {
+        fprintf(stderr, "thread 'main' panicked: Unable to create output file.\n");
+        mtsv_free(text);
+        mtsv_free(rep_text);
+        return 101;
+    }
+    const bool wrote = fwrite(text, 1, (size_t)text_len, out) == text_len;
+    mtsv_free(text);
+    if (fclose(out) != 0 || !wrote) {
+        mtsv_free(rep_text);
+        die("write error");
+    }
+    if (!report.empty()) {
+        FILE* r = fopen(report.c_str(), "wb");
+        if (!r) {
+            fprintf(stderr, "thread 'main' panicked: Unable to write taxa report\n");
+            mtsv_free(rep_text);
+            return 101;
+        }
+        fwrite(rep_text, 1, (size_t)rep_len, r);
+        fclose(r);
+        mtsv_free(rep_text);
+    }
+    const double t5 = now_ms();
+    // MTSV_COLLAPSE_TIMING=1: where the device path spends its time (tools/collapse_ab.py reads this line)
+    if (timing)
+        fprintf(stderr, "[collapse timing] files %zu reads %llu calls %llu hit_bytes %llu tokens %llu text_bytes %llu; read_split_dictionary %.3f ms, staging %.3f ms, "
+                        "add_text %.3f ms, id_table_and_text %.3f ms, report %.3f ms, write %.3f ms\n",
+                files.size(), (unsigned long long)n_reads, (unsigned long long)n_calls, (unsigned long long)n_bytes, (unsigned long long)n_tokens,
+                (unsigned long long)text_len, t1 - t0, stage_ms, add_ms, t3 - t2, t4 - t3, t5 - t4);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     std::string out_path, mode = "taxid", report;
     std::vector<std::string> files;
+    bool on_gpu = false, verbose = false, device_given = false;
+    int device = 0;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         auto val = [&]() -> std::string {
@@ -98,9 +257,20 @@ int main(int argc, char** argv) {
         else if (k == "--mode") mode = val();
         else if (k == "-t" || k == "--threads") (void)val();
         else if (k == "--report") report = val();
-        else if (k == "-v") {
+        else if (k == "-v") verbose = true;
+        else if (k == "--on-gpu") on_gpu = true;
+        else if (k == "--device") {
+            const std::string v = val();
+            char* end = nullptr;
+            const long d = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || d < 0 || d > 1 << 20) {
+                fprintf(stderr, "error: Invalid value for '--device <N>': %s\n", v.c_str());
+                return 1;
+            }
+            device = (int)d;
+            device_given = true;
         } else if (k == "-h" || k == "--help") {
-            printf("mtsv-collapse -o <OUTPUT> [--mode taxid|taxid-gi] [--report <TSV>] [-t N] <FILES>...\n");
+            printf("mtsv-collapse -o <OUTPUT> [--mode taxid|taxid-gi] [--report <TSV>] [-t N] [--on-gpu [--device N]] <FILES>...\n");
             return 0;
         } else if (!k.empty() && k[0] == '-') {
             fprintf(stderr, "error: Found argument '%s' which wasn't expected\n", k.c_str());
@@ -112,7 +282,15 @@ int main(int argc, char** argv) {
         fprintf(stderr, "error: required: -o <OUTPUT> <FILES>..., --mode taxid|taxid-gi\n");
         return 1;
     }
+    if (device_given && !on_gpu) {
+        fprintf(stderr, "error: The argument '--device <N>' requires '--on-gpu'\n");
+        return 1;
+    }
     const bool by_gi = mode == "taxid-gi";
+    if (on_gpu) {
+        const int rc = run_on_gpu(files, out_path, report, by_gi, device, verbose);
+        if (rc != kGpuFallBack) return rc;
+    }
 
     // External sort like collapse.rs:427-475,665: every input is cut into runs of at most `chunk_bytes` of
     // lines (128 MiB there and here; MTSV_COLLAPSE_CHUNK_BYTES for tests), each run is sorted by read id and

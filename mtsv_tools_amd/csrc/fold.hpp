@@ -5,6 +5,7 @@
 
 #include "../../include/mtsv_amd.h"
 #include "batch.hpp"
+#include "parse.hpp"
 #include "text.hpp"
 
 namespace mtsv {
@@ -37,6 +38,8 @@ struct Fold {
     uint64_t taxa_cap = 0;
     uint32_t text_tile = kTextTile;       // MTSV_TEXT_TILE, read at creation (tests)
     std::unique_ptr<TextFormatter> text;  // created by the first format_text
+    uint32_t parse_tile = kParseTile;     // MTSV_PARSE_TILE, read at creation (tests)
+    std::unique_ptr<TextParser> parser;   // created by the first add_text
 
     Fold(int device, int grain);
     ~Fold();
@@ -47,6 +50,9 @@ struct Fold {
     void reset(uint64_t n_reads);
     void add_run(Batch& src, float* device_ms);
     void add_records(const void* records, uint64_t n, float* device_ms);
+    // the hit parts of result lines, parsed on the device (parse.hip) and folded like a run's list
+    void add_text(const char* hits, const uint64_t* line_off, const uint32_t* line_read, uint64_t n_lines, uint64_t* n_tokens, uint64_t* n_records,
+                  float* device_ms);
     void download(void** a, uint64_t* n, bool wide);
     void taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_reads, float* device_ms);
     void match_flags(std::vector<uint64_t>& words, uint64_t* n_reads, uint64_t* n_matched);

@@ -3,7 +3,7 @@
 // The mtsv-binner hot path as gfx950 kernels (k_seed.hip, k_coalesce.hip, k_verify.hip; k_report.hip for the taxa report, k_match.hip for
 // the per-read match flags, k_compact.hip for the hand-over of a run's unmatched or matched reads to another workspace,
 // k_merge.hip for the per-read merge of several runs' hits, k_fold.hip for the accumulator of assignment records that a
-// chunk's run is folded into before the chunk leaves the device).
+// chunk's run is folded into before the chunk leaves the device, k_parse.hip for result text parsed back into such records).
 //
 // One batch of reads flows through staged kernels with worklists in HBM:
 //
@@ -26,6 +26,7 @@
 //   k_match     (match flags on) lane per read: one bit, "the read has a hit"      mtsv-partition.rs:34-54
 //   k_collapse  (assignments on) per read: one (tax_id, smallest edit) per TaxID      binner.rs:355-378
 //   k_fold      (mtsv_fold) two sorted record lists into one, one record per key       collapse.rs:269-297, :603-625
+//   k_parse     (mtsv_fold_add_text) result text back into a sorted, reduced record list     collapse.rs:198-255
 //
 // All arithmetic is integer; positions are u32 (n < 2^32).  No MFMA: the path is rank queries and
 // small dynamic programs.
@@ -328,5 +329,31 @@ void launch_pack_scan(hipStream_t s, uint4* tile_cnt, uint32_t n_tiles);
 void launch_pack_blocks(hipStream_t s, const uint8_t* bwt, uint32_t n, uint32_t n_blocks, uint32_t tile, const uint4* tile_off, RankBlock* blocks);
 void launch_pack_check_occ(hipStream_t s, const RankBlock* blocks, uint32_t n, uint32_t k, uint32_t n_chk, const uint64_t* occ, uint32_t* ctr);
 void launch_pack_text(hipStream_t s, const uint8_t* text, uint32_t n, uint8_t* codes, uint64_t codes_bytes);
+// k_parse.hip: the hit parts of result lines (hits[0 .. n_bytes), 16-byte aligned; line j = hits[line_off[j] .. line_off[j + 1]),
+// line_off[0] = 0 and ascending -- the caller has checked -- line_off[n_lines] = n_bytes; line_read[j] the line's read) into a
+// list of assignment records of one grain, ordered by the grain's key with distinct keys.  A workgroup owns `tile` bytes (a
+// power of two, 64 .. kParseTileMax); there are parse_tiles(n_bytes, tile) tiles.
+//   count:   tile_cnt[t] = the tokens that start in tile t
+//   (launch_scan over tile_cnt: tile_off[0 .. tiles], tile_off[tiles] = n_tok, which must be below 2^32)
+//   tokens:  raw_key[i] (read, tax, gi, offset), raw_val[i] (edit, first of its line, line as two words): n_tok uint4 each.
+//            ctr: kParseCounters u64 as pairs (how many, the smallest line), set by the caller to (0, all ones);
+//            [kParseCtrFormat] the tokens outside the grammar or, in a wide grain, without GI and offset
+//   heads:   flag[i] = token i begins a record; [kParseCtrKeyOrder] keys that descend inside a line, [kParseCtrReadOrder]
+//            lines whose read is not above the previous non-empty line's, [kParseCtrReadRange] reads at or above n_reads
+//   (launch_scan over flag: place[0 .. n_tok], place[n_tok] = n_rec)
+//   reduce:  out[0 .. n_rec): the records (mtsv_assignment / mtsv_assignment_gi), every one with the smallest edit of its
+//            run -- kCollapseGrainTaxidGi: the smallest (edit, offset); tax_out[0 .. n_rec): their TaxIDs.  Only after counters
+//            that are all zero.
+constexpr uint32_t kParseTileMax = 16384, kParseTile = 4096;
+constexpr uint32_t kParseCtrFormat = 0, kParseCtrKeyOrder = 2, kParseCtrReadOrder = 4, kParseCtrReadRange = 6, kParseCounters = 8;
+uint32_t parse_tiles(uint64_t n_bytes, uint32_t tile);
+void launch_parse_count(hipStream_t s, const uint8_t* hits, uint64_t n_bytes, const uint64_t* line_off, uint64_t n_lines, uint32_t tile,
+                        uint32_t* tile_cnt);
+void launch_parse_tokens(hipStream_t s, int grain, const uint8_t* hits, uint64_t n_bytes, const uint64_t* line_off, const uint32_t* line_read,
+                         uint64_t n_lines, uint32_t tile, const uint32_t* tile_off, uint32_t n_tok, void* raw_key, void* raw_val, uint64_t* ctr);
+void launch_parse_heads(hipStream_t s, int grain, const void* raw_key, const void* raw_val, uint32_t n_tok, uint64_t n_reads, uint32_t* flag,
+                        uint64_t* ctr);
+void launch_parse_reduce(hipStream_t s, int grain, const void* raw_key, const void* raw_val, const uint32_t* flag, const uint32_t* place,
+                         uint32_t n_tok, uint32_t n_rec, void* out, uint32_t* tax_out);
 
 }  // namespace mtsv
