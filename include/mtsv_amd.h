@@ -608,6 +608,75 @@ int mtsv_fold_format_text(mtsv_fold *f, const char *ids, const uint64_t *id_off,
 int mtsv_batch_format_text(mtsv_batch *b, const char *ids, const uint64_t *id_off, uint64_t n_reads, char **text, uint64_t *len,
                            float *device_ms);
 
+/* ---- taxonomy: per-read LCA and reads per clade ----------------------------------------------------------------------------
+ * A fold answers "which TaxIDs did this read touch"; with a taxonomy it answers "which taxon IS this read, and how many reads
+ * per species, genus or family".
+ *
+ * mtsv_taxonomy (host only, needs no device): an NCBI nodes.dmp.  Every line is split at '|', blanks and tabs around a field
+ * are dropped, the first three fields are TaxID, parent TaxID and rank; further fields and a trailing '|' are ignored, so
+ * `1 | 1 | no rank` loads like NCBI's `1\t|\t1\t|\tno rank\t|\t...\t|`.  Empty lines are skipped.  A node whose parent is
+ * itself is a root; a parent that has no line of its own becomes an implied root of unknown rank; every root hangs under a
+ * super-root with TaxID 0, so the LCA is total: taxa of different trees meet in 0.  Rank codes are the place of the rank
+ * string among the file's distinct rank strings ascending by bytes; MTSV_RANK_UNKNOWN (printed "-") is the rank of the
+ * super-root, of implied roots and of TaxIDs the file does not know.
+ * mtsv_taxonomy_load: MTSV_E_IO for a file that cannot be read; MTSV_E_FORMAT, with mtsv_last_error naming the line or the
+ *   TaxID, for a line of fewer than three fields, an ID that is not 1 to 10 digits or is above 4294967295, TaxID 0 (in either
+ *   field), a TaxID listed twice, a cycle other than a self-parent.
+ * mtsv_taxonomy_parent: the parent's TaxID -- 0 for roots, implied roots and the super-root itself -- and the rank code.  A
+ *   TaxID the file does not know is a child of the super-root, as mtsv_fold_lca treats it: *parent 0, *rank
+ *   MTSV_RANK_UNKNOWN.
+ * mtsv_taxonomy_rank_name: the rank string of a code, "-" for MTSV_RANK_UNKNOWN and codes the file does not have; it lives
+ *   as long as tx.
+ *
+ * mtsv_fold_lca: per read that has a record in f, with m the read's smallest edit, the TaxIDs of the records with
+ * edit <= m + edit_slack (the sum saturates: 0 is the best taxa, 0xffffffff all taxa) ENTER, and the read's LCA is the deepest
+ * node that is an ancestor-or-self of every entered TaxID.  A TaxID of f's union that tx does not know is a child of the
+ * super-root: alone it is its own LCA, with anything else the LCA is 0.  All three grains; f is not changed.
+ *   out (may be NULL): another fold of the same device at MTSV_GRAIN_TAXID.  It becomes a fold as after
+ *     mtsv_fold_reset(out, n_reads of f) that holds exactly one record (read, LCA TaxID, m) per read with a record, its union
+ *     the LCA TaxIDs present.  Everything a fold offers works on it: mtsv_fold_download, mtsv_fold_format_text (lines
+ *     READ_ID:LCA=EDIT, a results file every tool reads), mtsv_fold_taxa_report (every row only_hit), mtsv_fold_match_flags
+ *     (equal to f's).
+ *   rows (may be NULL; needs n_rows and total_reads): one row per node with clade > 0, in preorder of the taxonomy -- a parent
+ *     before its children, children ascending by TaxID as unsigned, the super-root first.  direct: the reads whose LCA is the
+ *     node; clade: the sum of direct over its subtree; depth 0 for the super-root, 1 for roots.  *total_reads: the reads with
+ *     a record, the super-root's clade.  malloc'd, mtsv_free.  The abundance at a rank is the rows of that rank.
+ *   device_ms (may be NULL): device time of the kernels.
+ * On the device (k_lca.hip): the host builds, per call and only when f's union or the taxonomy changed, the part of the
+ * taxonomy the union needs -- the super-root, the union's TaxIDs, their ancestors -- numbered in preorder with the last node
+ * of every subtree; then the LCA of a set is a walk up from its smallest member until the interval holds its largest, and a
+ * clade is the difference of two prefix sums.  Five steps: heads, segmented minimum of edit, segmented min and max of the
+ * entered node numbers, the walk, scan and clade.  MTSV_LCA_TILE (a power of two, 64..1024), read by mtsv_fold_create, moves
+ * the tile size (tests); MTSV_LCA_TIMING=1 prints the steps' times to stderr.
+ * MTSV_E_ARG, with both folds as they were: out == f, out on another device, out of a wide grain, a null f or tx, rows
+ * without n_rows or total_reads.  An empty f gives an empty out and zero rows.  A record whose TaxID is not in f's union, or a
+ * walk that does not end within the tree's depth, is an internal error, MTSV_E_DEVICE.
+ * Not done here: mtsv-binner --fold-on-gpu, whose super-batches would need clade rows added across pieces.
+ * mtsv_format_clade_report (host only): the TSV `taxid parent rank depth direct direct_pct clade clade_pct`, the rank as its
+ * name; percentages of max(total_reads, 1) with two decimals, as mtsv_format_taxa_report computes its own.  tx may be NULL:
+ * every rank is printed "-" then.  *out malloc'd, mtsv_free. */
+#define MTSV_RANK_UNKNOWN 0xffffffffu
+typedef struct mtsv_taxonomy mtsv_taxonomy;
+typedef struct {
+    uint64_t n_nodes;         /* lines of the file */
+    uint64_t n_implied_roots; /* parents without a line */
+    uint32_t n_ranks;         /* distinct rank strings */
+    uint32_t max_depth;       /* the super-root is at 0, roots at 1 */
+} mtsv_taxonomy_info_t;
+int mtsv_taxonomy_load(const char *nodes_dmp, mtsv_taxonomy **out);
+void mtsv_taxonomy_free(mtsv_taxonomy *tx);
+int mtsv_taxonomy_info(const mtsv_taxonomy *tx, mtsv_taxonomy_info_t *info);
+int mtsv_taxonomy_parent(const mtsv_taxonomy *tx, uint32_t tax_id, uint32_t *parent, uint32_t *rank);
+const char *mtsv_taxonomy_rank_name(const mtsv_taxonomy *tx, uint32_t rank);
+typedef struct {
+    uint32_t tax_id, parent_tax_id, rank, depth;
+    uint64_t direct, clade;
+} mtsv_clade_stats; /* 32 bytes */
+int mtsv_fold_lca(mtsv_fold *f, const mtsv_taxonomy *tx, uint32_t edit_slack, mtsv_fold *out, mtsv_clade_stats **rows,
+                  uint64_t *n_rows, uint64_t *total_reads, float *device_ms);
+int mtsv_format_clade_report(const mtsv_clade_stats *rows, uint64_t n_rows, uint64_t total_reads, const mtsv_taxonomy *tx,
+                             char **out, uint64_t *out_len);
+
 /* ---- result lines (host) ---------------------------------------------------------------- */
 /* write_assignments for a whole batch: hits ordered by read; ids = NUL-separated read ids,
  * id_off[n_reads+1].  Lines are appended to a malloc'd buffer (*out, *out_len), one per read with

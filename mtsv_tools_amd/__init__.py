@@ -12,6 +12,7 @@ from ._lib import (  # noqa: F401
     ASSIGN_OFF,
     ASSIGN_ONLY,
     ASSIGN_WITH_HITS,
+    CLADE_STATS_DTYPE,
     DEVPART_BIN_END,
     DEVPART_BIN_LUT,
     DEVPART_BINS,
@@ -29,7 +30,10 @@ from ._lib import (  # noqa: F401
     MATCH_OFF,
     MATCH_ONLY,
     MATCH_WITH_HITS,
+    RANK_UNKNOWN,
+    SLACK_ALL,
     TAXON_STATS_DTYPE,
+    Taxonomy,
     HostBuffer,
     host_register,
     host_unregister,
@@ -45,6 +49,7 @@ from ._lib import (  # noqa: F401
     device_count,
     format_assignments,
     format_assignments_gi,
+    format_clade_report,
     format_results,
     format_taxa_report,
     merge_taxa_reports,

@@ -85,6 +85,17 @@ ASSIGN_DTYPE = np.dtype({"names": ["read", "tax_id", "edit"], "formats": ["<u8",
 ASSIGN_GI_DTYPE = np.dtype({"names": ["read", "tax_id", "gi", "offset", "edit"], "formats": ["<u8", "<u4", "<u4", "<u4", "<u4"],
                             "offsets": [0, 8, 12, 16, 20], "itemsize": 24})
 
+# mtsv_clade_stats: 4 * 4 + 2 * 8 = 32 bytes
+CLADE_STATS_DTYPE = np.dtype({"names": ["tax_id", "parent_tax_id", "rank", "depth", "direct", "clade"],
+                              "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8"], "offsets": [0, 4, 8, 12, 16, 24], "itemsize": 32})
+RANK_UNKNOWN = 0xffffffff  # MTSV_RANK_UNKNOWN
+SLACK_ALL = 0xffffffff  # edit_slack of mtsv_fold_lca: every TaxID of a read enters
+
+
+class TaxonomyInfo(C.Structure):  # mtsv_taxonomy_info_t
+    _fields_ = [("n_nodes", C.c_uint64), ("n_implied_roots", C.c_uint64), ("n_ranks", C.c_uint32), ("max_depth", C.c_uint32)]
+
+
 EXPORTS = [
     "mtsv_last_error", "mtsv_version", "mtsv_params_default", "mtsv_device_count",
     "mtsv_index_load", "mtsv_index_build", "mtsv_index_build_fasta", "mtsv_index_write",
@@ -106,6 +117,8 @@ EXPORTS = [
     "mtsv_fold_format_text", "mtsv_batch_format_text",
     "mtsv_index_download_device",
     "mtsv_fold_add_text",
+    "mtsv_taxonomy_load", "mtsv_taxonomy_free", "mtsv_taxonomy_info", "mtsv_taxonomy_parent", "mtsv_taxonomy_rank_name",
+    "mtsv_fold_lca", "mtsv_format_clade_report",
 ]
 
 _lib = None
@@ -198,6 +211,15 @@ def lib():
         L.mtsv_fold_format_text.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_batch_format_text.argtypes = [vp, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_fold_add_text.argtypes = [vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_taxonomy_load.argtypes = [C.c_char_p, C.POINTER(vp)]
+        L.mtsv_taxonomy_free.argtypes = [vp]
+        L.mtsv_taxonomy_free.restype = None
+        L.mtsv_taxonomy_info.argtypes = [vp, C.POINTER(TaxonomyInfo)]
+        L.mtsv_taxonomy_parent.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.mtsv_taxonomy_rank_name.argtypes = [vp, u32]
+        L.mtsv_taxonomy_rank_name.restype = C.c_char_p
+        L.mtsv_fold_lca.argtypes = [vp, vp, u32, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_format_clade_report.argtypes = [vp, u64, u64, vp, C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -705,6 +727,16 @@ class Fold:
         read_ids: the IDs of the n_reads reads of reset -- a list of str, or a (bytes, offsets) table"""
         return _format_text(lib().mtsv_fold_format_text, self.h, read_ids)
 
+    def lca(self, tx, slack=0, out=None, rows=True):
+        """mtsv_fold_lca: per read with a record the LCA, in the Taxonomy tx, of its TaxIDs within `slack` edits of its
+        smallest edit (SLACK_ALL: all of them).  out: another Fold of this device at GRAIN_TAXID that takes one record
+        (read, LCA, smallest edit) per read.  Returns (clade rows as a CLADE_STATS_DTYPE array in preorder, or None without
+        rows; total_reads; device ms)"""
+        ptr, n, total, ms = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_fold_lca(self.h, tx.h, int(slack), out.h if out is not None else None, C.byref(ptr) if rows else None,
+                                   C.byref(n), C.byref(total), C.byref(ms)))
+        return (_records_from(ptr, n.value, CLADE_STATS_DTYPE) if rows else None), total.value, ms.value
+
     def close(self):
         if self.h is not None and _lib is not None:
             _lib.mtsv_fold_free(self.h)
@@ -715,6 +747,54 @@ class Fold:
             self.close()
         except Exception:
             pass
+
+
+class Taxonomy:
+    """Owning handle of an mtsv_taxonomy: an NCBI nodes.dmp as a tree on the host (no device needed)"""
+
+    def __init__(self, path):
+        self.h = C.c_void_p()
+        _check(lib().mtsv_taxonomy_load(os.fsencode(path), C.byref(self.h)))
+
+    def info(self):
+        """{n_nodes, n_implied_roots, n_ranks, max_depth}"""
+        i = TaxonomyInfo()
+        _check(lib().mtsv_taxonomy_info(self.h, C.byref(i)))
+        return {n: int(getattr(i, n)) for n, _ in TaxonomyInfo._fields_}
+
+    def parent(self, tax_id):
+        """(the parent's TaxID, the rank code) of a TaxID; (0, RANK_UNKNOWN) for one the file does not know"""
+        p, r = C.c_uint32(), C.c_uint32()
+        _check(lib().mtsv_taxonomy_parent(self.h, int(tax_id), C.byref(p), C.byref(r)))
+        return p.value, r.value
+
+    def rank_name(self, rank):
+        return lib().mtsv_taxonomy_rank_name(self.h, int(rank)).decode()
+
+    def close(self):
+        if self.h is not None and _lib is not None:
+            _lib.mtsv_taxonomy_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def format_clade_report(rows, total_reads, tx=None):
+    """mtsv_format_clade_report: the TSV of mtsv-collapse --clade-report, as bytes; without tx every rank is '-'"""
+    out_rows = np.zeros(len(rows), dtype=CLADE_STATS_DTYPE)
+    for f in CLADE_STATS_DTYPE.names:
+        out_rows[f] = rows[f]
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_clade_report(out_rows.ctypes.data, len(out_rows), int(total_reads), tx.h if tx is not None else None,
+                                          C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value)
+    finally:
+        lib().mtsv_free(out)
 
 
 def format_results(hits, read_ids, long_format=False):

@@ -609,6 +609,74 @@ int mtsv_fold_match_flags(mtsv_fold* f, uint64_t** words, uint64_t* n_reads, uin
     })
 }
 
+// ---- taxonomy, per-read LCA and clade report (taxonomy.cpp, lca.hip, k_lca.hip) ----
+int mtsv_taxonomy_load(const char* nodes_dmp, mtsv_taxonomy** out) {
+    if (!nodes_dmp || !out) return fail_arg("null argument");
+    GUARD(*out = new mtsv_taxonomy{Taxonomy::load(nodes_dmp)})
+}
+
+void mtsv_taxonomy_free(mtsv_taxonomy* tx) { delete tx; }
+
+int mtsv_taxonomy_info(const mtsv_taxonomy* tx, mtsv_taxonomy_info_t* info) {
+    if (!tx || !info) return fail_arg("null argument");
+    info->n_nodes = tx->impl.ids.size();
+    info->n_implied_roots = tx->impl.implied.size();
+    info->n_ranks = (uint32_t)tx->impl.rank_names.size();
+    info->max_depth = tx->impl.max_depth;
+    return MTSV_OK;
+}
+
+int mtsv_taxonomy_parent(const mtsv_taxonomy* tx, uint32_t tax_id, uint32_t* parent, uint32_t* rank) {
+    if (!tx || !parent || !rank) return fail_arg("null argument");
+    (void)tx->impl.lookup(tax_id, parent, rank);
+    return MTSV_OK;
+}
+
+const char* mtsv_taxonomy_rank_name(const mtsv_taxonomy* tx, uint32_t rank) { return tx ? tx->impl.rank_name(rank) : "-"; }
+
+static_assert(sizeof(mtsv_clade_stats) == 32, "the clade row");
+int mtsv_fold_lca(mtsv_fold* f, const mtsv_taxonomy* tx, uint32_t edit_slack, mtsv_fold* out, mtsv_clade_stats** rows, uint64_t* n_rows,
+                  uint64_t* total_reads, float* device_ms) {
+    if (!f || !tx) return fail_arg("null argument");
+    if (rows && (!n_rows || !total_reads)) return fail_arg("rows without n_rows or total_reads");
+    GUARD({
+        std::vector<mtsv_clade_stats> r;
+        mtsv_clade_stats* mem = nullptr;
+        f->impl.lca(tx->impl, edit_slack, out ? &out->impl : nullptr, rows ? &r : nullptr, total_reads, device_ms);
+        if (rows) {
+            mem = (mtsv_clade_stats*)malloc(std::max<size_t>(r.size(), 1) * sizeof(mtsv_clade_stats));
+            if (!mem) throw std::bad_alloc();
+            if (!r.empty()) memcpy(mem, r.data(), r.size() * sizeof(mtsv_clade_stats));
+            *rows = mem;
+            *n_rows = r.size();
+        }
+    })
+}
+
+int mtsv_format_clade_report(const mtsv_clade_stats* rows, uint64_t n_rows, uint64_t total_reads, const mtsv_taxonomy* tx, char** out,
+                             uint64_t* out_len) {
+    if ((!rows && n_rows) || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        std::string text = "taxid\tparent\trank\tdepth\tdirect\tdirect_pct\tclade\tclade_pct\n";
+        const double denom = (double)std::max<uint64_t>(total_reads, 1);
+        char line[256];
+        for (uint64_t i = 0; i < n_rows; i++) {
+            const mtsv_clade_stats& s = rows[i];
+            snprintf(line, sizeof line, "%u\t%u\t", s.tax_id, s.parent_tax_id);
+            text += line;
+            text += tx ? tx->impl.rank_name(s.rank) : "-";
+            snprintf(line, sizeof line, "\t%u\t%llu\t%.2f\t%llu\t%.2f\n", s.depth, (unsigned long long)s.direct, s.direct / denom * 100.0,
+                     (unsigned long long)s.clade, s.clade / denom * 100.0);
+            text += line;
+        }
+        char* p = (char*)malloc(text.size() + 1);
+        if (!p) throw std::bad_alloc();
+        memcpy(p, text.c_str(), text.size() + 1);
+        *out = p;
+        *out_len = text.size();
+    })
+}
+
 // ---- the result lines written on the device (text.hip, k_text.hip) ----
 int mtsv_fold_format_text(mtsv_fold* f, const char* ids, const uint64_t* id_off, uint64_t n_reads, char** text, uint64_t* len, float* device_ms) {
     if (!f || !ids || !id_off || !text || !len) return fail_arg("null argument");

@@ -12,6 +12,13 @@
 // report and k_text.hip writes the lines.  Input the device path refuses -- a token outside the canonical grammar, a line
 // whose keys do not ascend, taxid-gi mode on tokens without an offset -- goes to the host path below as a whole, before the
 // output file is created, so every error text and exit code stays this file's.  Without --on-gpu no device is opened.
+//
+// --taxonomy <nodes.dmp> with --lca-output and/or --clade-report (only with --on-gpu): what the reads ARE.  mtsv_fold_lca
+// (k_lca.hip) takes the fold the -o lines come from and gives a second fold with one record per read -- the lowest common
+// ancestor of the read's best taxa (--lca-slack N: of the taxa within N edits of the best; all: of all of them) -- whose
+// lines, READ_ID:LCA=EDIT in the order of -o's, are --lca-output, and the reads per clade, --clade-report.  -o and --report
+// are what they are without these options.  The host path has no such step: where --on-gpu alone would hand the input to
+// it, a run with --taxonomy ends with the reason on stderr, exit code 2 and none of the two files.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -96,11 +103,29 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 constexpr int kGpuFallBack = -1000;  // run_on_gpu: the input is the host path's
 
+struct LcaOptions {
+    std::string taxonomy, lca_output, clade_report;
+    uint32_t slack = 0;
+    bool on() const { return !taxonomy.empty(); }
+};
+
+bool write_file(const std::string& path, const char* p, uint64_t len) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool wrote = fwrite(p, 1, (size_t)len, f) == len;
+    return (fclose(f) == 0) && wrote;
+}
+
 // mtsv-collapse --on-gpu.  Returns the exit code, or kGpuFallBack with nothing written.
-int run_on_gpu(const std::vector<std::string>& files, const std::string& out_path, const std::string& report, bool by_gi, int device, bool verbose) {
+int run_on_gpu(const std::vector<std::string>& files, const std::string& out_path, const std::string& report, bool by_gi, int device, bool verbose,
+               const LcaOptions& lca) {
     namespace mc = mtsv_collapse;
     const bool timing = getenv("MTSV_COLLAPSE_TIMING") != nullptr;
     auto fall_back = [&](const std::string& why) {
+        if (lca.on()) {  // (the host path has no LCA step)
+            fprintf(stderr, "mtsv-collapse: --on-gpu: %s; --taxonomy needs the device path\n", why.c_str());
+            return 2;
+        }
         if (verbose) fprintf(stderr, "mtsv-collapse: --on-gpu: %s; the host path takes the input\n", why.c_str());
         return kGpuFallBack;
     };
@@ -110,6 +135,18 @@ int run_on_gpu(const std::vector<std::string>& files, const std::string& out_pat
     };
     uint64_t piece_bytes = 64ull << 20;
     if (const char* e = getenv("MTSV_COLLAPSE_PIECE_BYTES")) piece_bytes = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    struct TaxonomyCloser {
+        mtsv_taxonomy* tx = nullptr;
+        mtsv_fold* per_read = nullptr;  // the fold of the reads' LCA records
+        ~TaxonomyCloser() {
+            mtsv_fold_free(per_read);
+            mtsv_taxonomy_free(tx);
+        }
+    } tax;
+    if (lca.on() && mtsv_taxonomy_load(lca.taxonomy.c_str(), &tax.tx) != MTSV_OK) {
+        fprintf(stderr, "mtsv-collapse: --taxonomy: %s\n", mtsv_last_error());
+        return 2;
+    }
     // ---- lines and dictionary ----
     const double t0 = now_ms();
     std::vector<mc::FileBytes> bytes(files.size());
@@ -202,6 +239,36 @@ int run_on_gpu(const std::vector<std::string>& files, const std::string& out_pat
             return device_error("mtsv_format_taxa_report");
         }
     }
+    // ---- the reads' LCAs and the clades, from the same fold; both texts are complete before a file is created ----
+    char *lca_text = nullptr, *clade_text = nullptr;
+    uint64_t lca_len = 0, clade_len = 0;
+    struct TextCloser {
+        char *&a, *&b;
+        ~TextCloser() {
+            mtsv_free(a);
+            mtsv_free(b);
+        }
+    } lca_hold{lca_text, clade_text};
+    if (lca.on()) {
+        auto lca_error = [&](const char* what) {
+            mtsv_free(text);
+            mtsv_free(rep_text);
+            return device_error(what);
+        };
+        const bool want_lines = !lca.lca_output.empty(), want_clades = !lca.clade_report.empty();
+        if (want_lines && mtsv_fold_create(device, MTSV_GRAIN_TAXID, &tax.per_read) != MTSV_OK) return lca_error("no fold for the reads' LCAs");
+        mtsv_clade_stats* rows = nullptr;
+        uint64_t n_rows = 0, lca_reads = 0;
+        if (mtsv_fold_lca(fold, tax.tx, lca.slack, tax.per_read, want_clades ? &rows : nullptr, &n_rows, &lca_reads, nullptr) != MTSV_OK)
+            return lca_error("mtsv_fold_lca");
+        if (want_clades) {
+            const int rc = mtsv_format_clade_report(rows, n_rows, lca_reads, tax.tx, &clade_text, &clade_len);
+            mtsv_free(rows);
+            if (rc != MTSV_OK) return lca_error("mtsv_format_clade_report");
+        }
+        if (want_lines && mtsv_fold_format_text(tax.per_read, ids.data(), id_off.data(), n_reads, &lca_text, &lca_len, nullptr) != MTSV_OK)
+            return lca_error("mtsv_fold_format_text (LCA lines)");
+    }
     const double t4 = now_ms();
     FILE* out = fopen(out_path.c_str(), "wb");
     if (!out) {
@@ -227,6 +294,16 @@ int run_on_gpu(const std::vector<std::string>& files, const std::string& out_pat
         fclose(r);
         mtsv_free(rep_text);
     }
+    if (lca.on()) {
+        const bool ok = (lca.lca_output.empty() || write_file(lca.lca_output, lca_text, lca_len)) &&
+                        (lca.clade_report.empty() || write_file(lca.clade_report, clade_text, clade_len));
+        if (!ok) {
+            if (!lca.lca_output.empty()) remove(lca.lca_output.c_str());
+            if (!lca.clade_report.empty()) remove(lca.clade_report.c_str());
+            fprintf(stderr, "thread 'main' panicked: Unable to write the LCA output or the clade report\n");
+            return 101;
+        }
+    }
     const double t5 = now_ms();
     // MTSV_COLLAPSE_TIMING=1: where the device path spends its time (tools/collapse_ab.py reads this line)
     if (timing)
@@ -244,6 +321,8 @@ int main(int argc, char** argv) {
     std::vector<std::string> files;
     bool on_gpu = false, verbose = false, device_given = false;
     int device = 0;
+    LcaOptions lca;
+    bool slack_given = false;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         auto val = [&]() -> std::string {
@@ -259,6 +338,20 @@ int main(int argc, char** argv) {
         else if (k == "--report") report = val();
         else if (k == "-v") verbose = true;
         else if (k == "--on-gpu") on_gpu = true;
+        else if (k == "--taxonomy") lca.taxonomy = val();
+        else if (k == "--lca-output") lca.lca_output = val();
+        else if (k == "--clade-report") lca.clade_report = val();
+        else if (k == "--lca-slack") {
+            const std::string v = val();
+            uint64_t n = 0;
+            if (v == "all") n = 0xffffffffull;
+            else if (!parse_u64(v, 0xffffffffull, &n)) {
+                fprintf(stderr, "error: Invalid value for '--lca-slack <N|all>': %s\n", v.c_str());
+                return 1;
+            }
+            lca.slack = (uint32_t)n;
+            slack_given = true;
+        }
         else if (k == "--device") {
             const std::string v = val();
             char* end = nullptr;
@@ -270,7 +363,8 @@ int main(int argc, char** argv) {
             device = (int)d;
             device_given = true;
         } else if (k == "-h" || k == "--help") {
-            printf("mtsv-collapse -o <OUTPUT> [--mode taxid|taxid-gi] [--report <TSV>] [-t N] [--on-gpu [--device N]] <FILES>...\n");
+            printf("mtsv-collapse -o <OUTPUT> [--mode taxid|taxid-gi] [--report <TSV>] [-t N] [--on-gpu [--device N] [--taxonomy <nodes.dmp> "
+                   "[--lca-output <PATH>] [--clade-report <TSV>] [--lca-slack <N|all>]]] <FILES>...\n");
             return 0;
         } else if (!k.empty() && k[0] == '-') {
             fprintf(stderr, "error: Found argument '%s' which wasn't expected\n", k.c_str());
@@ -286,9 +380,23 @@ int main(int argc, char** argv) {
         fprintf(stderr, "error: The argument '--device <N>' requires '--on-gpu'\n");
         return 1;
     }
+    if (lca.on() && !on_gpu) {
+        fprintf(stderr, "error: The argument '--taxonomy <nodes.dmp>' requires '--on-gpu'\n");
+        return 1;
+    }
+    if (lca.on() && lca.lca_output.empty() && lca.clade_report.empty()) {
+        fprintf(stderr, "error: The argument '--taxonomy <nodes.dmp>' requires '--lca-output <PATH>' or '--clade-report <TSV>'\n");
+        return 1;
+    }
+    for (const auto& o : {std::make_pair("--lca-output <PATH>", !lca.lca_output.empty()), std::make_pair("--clade-report <TSV>", !lca.clade_report.empty()),
+                          std::make_pair("--lca-slack <N|all>", slack_given)})
+        if (o.second && !lca.on()) {
+            fprintf(stderr, "error: The argument '%s' requires '--taxonomy <nodes.dmp>'\n", o.first);
+            return 1;
+        }
     const bool by_gi = mode == "taxid-gi";
     if (on_gpu) {
-        const int rc = run_on_gpu(files, out_path, report, by_gi, device, verbose);
+        const int rc = run_on_gpu(files, out_path, report, by_gi, device, verbose, lca);
         if (rc != kGpuFallBack) return rc;
     }
 

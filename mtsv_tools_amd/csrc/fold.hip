@@ -46,6 +46,7 @@ Fold::Fold(int device_, int grain_) : device(device_), grain(grain_) {
     }
     text_tile = TextFormatter::tile_from_env();
     parse_tile = TextParser::tile_from_env();
+    lca_tile = LcaState::tile_from_env();
     trace = getenv("MTSV_TRACE") != nullptr;
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -57,6 +58,7 @@ Fold::~Fold() {
     if (stream) (void)hipStreamSynchronize(stream);
     text.reset();
     parser.reset();
+    lca_state.reset();
     for (void* p : {(void*)d_rec[0], (void*)d_rec[1], (void*)d_in, (void*)d_tile_cnt, (void*)d_tile_off, (void*)d_tile_sums, (void*)d_flags,
                     (void*)d_taxa, (void*)d_counts})
         if (p) (void)hipFree(p);

@@ -5,6 +5,7 @@
 
 #include "../../include/mtsv_amd.h"
 #include "batch.hpp"
+#include "lca.hpp"
 #include "parse.hpp"
 #include "text.hpp"
 
@@ -40,6 +41,8 @@ struct Fold {
     std::unique_ptr<TextFormatter> text;  // created by the first format_text
     uint32_t parse_tile = kParseTile;     // MTSV_PARSE_TILE, read at creation (tests)
     std::unique_ptr<TextParser> parser;   // created by the first add_text
+    uint32_t lca_tile = kLcaTile;         // MTSV_LCA_TILE, read at creation (tests)
+    std::unique_ptr<LcaState> lca_state;  // created by the first lca
 
     Fold(int device, int grain);
     ~Fold();
@@ -58,6 +61,11 @@ struct Fold {
     void match_flags(std::vector<uint64_t>& words, uint64_t* n_reads, uint64_t* n_matched);
     // the result lines of the accumulated records, written on the device (text.hip); the fold is not changed
     void format_text(const char* ids, const uint64_t* id_off, uint64_t n_reads, char** text, uint64_t* len, float* device_ms);
+    // per read with a record the LCA of its taxa within edit_slack of its smallest edit (lca.hip, k_lca.hip): one record
+    // (read, LCA TaxID, smallest edit) per read into `out` (may be null; a fold of this device at MTSV_GRAIN_TAXID, not this
+    // one), which becomes as after reset(n_reads) with those records; the clade rows in preorder (rows may be null); this
+    // fold is not changed
+    void lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<mtsv_clade_stats>* rows, uint64_t* total_reads, float* device_ms);
 
    private:
     void in_room(uint64_t n_b);

@@ -356,4 +356,32 @@ void launch_parse_heads(hipStream_t s, int grain, const void* raw_key, const voi
 void launch_parse_reduce(hipStream_t s, int grain, const void* raw_key, const void* raw_val, const uint32_t* flag, const uint32_t* place,
                          uint32_t n_tok, uint32_t n_rec, void* out, uint32_t* tax_out);
 
+// k_lca.hip: per read of a sorted assignment list (n records of 4 or 6 words: read in words 0 and 1, tax_id in word 2, edit in
+// the last) the lowest common ancestor of the TaxIDs whose edit is within `slack` of the read's smallest, on a tree numbered in
+// preorder: node 0 is the super-root, parent[i] < i for i > 0, last[i] is the last node of i's subtree, tax[i] its TaxID;
+// u_tax[0 .. n_union) ascending with u_node beside it maps a record's TaxID to its node.  A workgroup owns `tile` records (a power
+// of two, 64 .. kLcaTileMax); there are lca_tiles(n, tile) tiles.  A HEAD is a record whose read differs from its predecessor's;
+// the reads with a record are numbered by their heads (slots).  ctr: kLcaCounters u64, zeroed by the caller.
+//   heads:  tile_cnt[t] = the heads of tile t
+//   (launch_scan over tile_cnt: tile_off[0 .. tiles], tile_off[tiles] = n_slots)
+//   min:    m[slot] = the smallest edit of the read (m set to all ones by the caller); out[slot].read (16-byte records)
+//   span:   lo[slot] / hi[slot] = the smallest / largest node number among the records with edit <= m[slot] + slack, saturating
+//           (lo set to all ones, hi to zero by the caller); ctr[kLcaCtrMissing] += records whose TaxID u_tax does not hold
+//   walk:   out[slot] = (read, tax of the LCA, m[slot]); direct[node] += 1 (direct: n_nodes u32, zeroed by the caller); a walk
+//           of more than max_depth steps, or a span outside the tree, adds to ctr[kLcaCtrWalk] and writes nothing
+//   (launch_scan over direct: prefix[0 .. n_nodes])
+//   clade:  clade[i] = prefix[last[i] + 1] - prefix[i]
+constexpr uint32_t kLcaTileMax = 1024, kLcaTile = 1024;
+constexpr uint32_t kLcaCtrMissing = 0, kLcaCtrWalk = 1, kLcaCounters = 2;
+uint32_t lca_tiles(uint64_t n, uint32_t tile);
+void launch_lca_heads(hipStream_t s, int grain, const void* rec, uint32_t n, uint32_t tile, uint32_t* tile_cnt);
+void launch_lca_min(hipStream_t s, int grain, const void* rec, uint32_t n, uint32_t tile, const uint32_t* tile_off, uint32_t n_slots, uint32_t* m,
+                    void* out);
+void launch_lca_span(hipStream_t s, int grain, const void* rec, uint32_t n, uint32_t tile, const uint32_t* tile_off, uint32_t n_slots,
+                     const uint32_t* m, uint32_t slack, const uint32_t* u_tax, const uint32_t* u_node, uint32_t n_union, uint32_t* lo, uint32_t* hi,
+                     uint64_t* ctr);
+void launch_lca_walk(hipStream_t s, uint32_t n_slots, uint32_t n_nodes, uint32_t max_depth, const uint32_t* lo, const uint32_t* hi, const uint32_t* m,
+                     const uint32_t* parent, const uint32_t* last, const uint32_t* tax, void* out, uint32_t* direct, uint64_t* ctr);
+void launch_lca_clade(hipStream_t s, uint32_t n_nodes, const uint32_t* last, const uint32_t* prefix, uint32_t* clade);
+
 }  // namespace mtsv
