@@ -147,6 +147,49 @@ def test_tile_edges_at_every_block(written, name, tile, monkeypatch):
         ix.close()
 
 
+def traced_tiles(capfd):
+    """the tiles of the device packs traced since the last look"""
+    return re.findall(r"\[upload\] pack on device, tile (\d+):", capfd.readouterr().err)
+
+
+@pytest.mark.parametrize("tile", ["4", "8", "16", "32"])
+def test_tiles_between_two_blocks_and_the_default(written, tile, monkeypatch, capfd):
+    w = written("random-8193")                                                     # 65 blocks: 17, 9, 5 and 3 tiles, the last of one block
+    ix = M.MGIndex.load(w.path)
+    try:
+        monkeypatch.setenv("MTSV_PACK_TILE", tile)
+        monkeypatch.setenv("MTSV_TRACE", "1")
+        ix.to_device(0, PACK)
+        h, _ = check_against_restatement(w, ix, 0, 1)
+        assert h["n_blocks"] == 65 and traced_tiles(capfd) == [tile]
+    finally:
+        ix.close()
+
+
+# ---- 2b. the carry of k_pack_scan: one workgroup walks PACK_ROUND tiles per round and carries their sums into the next ----
+
+PACK_ROUND = 1024
+# (rung, tile, rounds, tiles of the last round): random-524161 has 4096 blocks, random-131073 has 1025 -- a second round of one
+# tile behind a full one.  The rounds are asserted from the resident header's n_blocks, not from the rung's name.
+CARRY_CASES = [("random-524161", 4, 1, 1024), ("random-524161", 2, 2, 1024), ("random-524161", 1, 4, 1024), ("random-131073", 1, 2, 1)]
+
+
+@pytest.mark.parametrize("name,tile,n_rounds,last", CARRY_CASES, ids=[f"{c[0]}-tile{c[1]}" for c in CARRY_CASES])
+def test_scan_carry_over_rounds_of_1024_tiles(written, name, tile, n_rounds, last, monkeypatch, capfd):
+    w = written(name)
+    ix = M.MGIndex.load(w.path)
+    try:
+        monkeypatch.setenv("MTSV_PACK_TILE", str(tile))
+        monkeypatch.setenv("MTSV_TRACE", "1")
+        ix.to_device(0, PACK)
+        h, _ = check_against_restatement(w, ix, 0, 1)
+        assert traced_tiles(capfd) == [str(tile)]
+        tiles = -(-h["n_blocks"] // tile)
+        assert (-(-tiles // PACK_ROUND), tiles - (n_rounds - 1) * PACK_ROUND) == (n_rounds, last)
+    finally:
+        ix.close()
+
+
 # ---- 3. what is built on the device-packed blocks: the full suffix array, the table, its levels and tags ----
 
 @pytest.mark.parametrize("name", ["random-129", "random-8193", "sentinel-res0", "nrun-20000", "ACG-4096"])
