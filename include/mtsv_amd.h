@@ -608,6 +608,43 @@ int mtsv_fold_format_text(mtsv_fold *f, const char *ids, const uint64_t *id_off,
 int mtsv_batch_format_text(mtsv_batch *b, const char *ids, const uint64_t *id_off, uint64_t n_reads, char **text, uint64_t *len,
                            float *device_ms);
 
+/* ---- identical reads binned once (dedup.hip, k_dedup.hip) ----------------------------------------------------------------
+ * The result of binning is a function of a read's normalised codes and the parameters, so a batch that holds a sequence many
+ * times (PCR and optical duplicates, rRNA, amplicons) needs the search once per distinct sequence.  Two reads are IDENTICAL
+ * when their lengths are equal and every code (0..4 after normalisation: `acgt` equals `ACGT`, `R` equals `N`) is equal; no
+ * reverse complement, no prefix relation.  For every resident read j, rep(j) is the smallest resident index whose read is
+ * identical to j: exact and deterministic, whatever the hash function does.
+ * An mtsv_dupmap is bound to a device and holds what the last mtsv_batch_take_unique found.  MTSV_DEDUP_HASH_BITS (0..64,
+ * default 64: only that many low bits of the hash are used, for the start slot and the tag alike; 0 puts every read on one
+ * probe chain) and MTSV_FAN_TILE (a power of two, 64..1024: the output records a workgroup of the expansion owns) are read by
+ * mtsv_dupmap_create (tests); results do not depend on either.  With no map created nothing is allocated or launched.
+ *
+ * mtsv_dupmap_create: MTSV_E_DEVICE when hip_device is no usable device.
+ * mtsv_batch_take_unique: dst's resident batch becomes the representatives (the reads with rep(j) == j) of src's resident batch,
+ *   in order, as if they had been uploaded, held as codes; its read map (survivor -> the caller's number) is composed with
+ *   src's when src is mapped, exactly as mtsv_batch_take_reads does.  src needs a resident batch under the conditions of
+ *   mtsv_batch_copy_reads; no run and no match flags.  m then holds, per resident read j of src, read[j], the caller's number
+ *   of j (strictly ascending; the identity when src is unmapped), and rep[j], the caller's number of rep(j).  MTSV_E_ARG, with
+ *   dst and m as they were: dst == src; different devices, or m of another device; nothing resident in src; more
+ *   representatives or bases than dst was created for; NULL handles.  The host receives five counters and the survivors'
+ *   offsets, no codes and no flags.  device_ms (may be NULL): hash, insert, resolve, scan and copy.  More than 2^30 reads is
+ *   MTSV_E_LIMIT.  With MTSV_TRACE set when the map was created: one stderr line, `[dedup] ...`.
+ * mtsv_dupmap_download: both arrays, malloc'd (mtsv_free), *n_reads entries each; *n_reads is 0 before any take.
+ * mtsv_fold_expand: dst becomes a fold as after mtsv_fold_reset(dst, n_reads of src) that holds, for every entry j of m, the
+ *   records src holds for read rep[j] with `read` replaced by read[j] (key order holds because read[] ascends); its TaxID union
+ *   is src's.  All three grains; src is not changed.  Everything a fold offers then works on dst.  Every record of src must
+ *   belong to a read that is a representative in m: the records found for self-representing entries are counted, and a count
+ *   that differs from src's is MTSV_E_ARG before anything is written.  Also MTSV_E_ARG, with dst as it was: dst == src,
+ *   different grains or devices, an m that holds no take.  2^32 expanded records or more: MTSV_E_LIMIT.  device_ms (may be
+ *   NULL): count, scan and write. */
+typedef struct mtsv_dupmap mtsv_dupmap;
+int mtsv_dupmap_create(int hip_device, mtsv_dupmap **out);
+void mtsv_dupmap_free(mtsv_dupmap *m);
+int mtsv_batch_take_unique(mtsv_batch *dst, mtsv_batch *src, mtsv_dupmap *m, uint64_t *n_unique, uint64_t *bases_kept,
+                           float *device_ms);
+int mtsv_dupmap_download(const mtsv_dupmap *m, uint64_t **read, uint64_t **rep, uint64_t *n_reads, uint64_t *n_unique);
+int mtsv_fold_expand(mtsv_fold *dst, mtsv_fold *src, const mtsv_dupmap *m, float *device_ms);
+
 /* ---- taxonomy: per-read LCA and reads per clade ----------------------------------------------------------------------------
  * A fold answers "which TaxIDs did this read touch"; with a taxonomy it answers "which taxon IS this read, and how many reads
  * per species, genus or family".

@@ -38,6 +38,7 @@ from ._lib import (  # noqa: F401
     host_register,
     host_unregister,
     Batch,
+    DupMap,
     Fold,
     MGIndex,
     MtsvError,

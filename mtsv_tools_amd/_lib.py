@@ -119,6 +119,7 @@ EXPORTS = [
     "mtsv_fold_add_text",
     "mtsv_taxonomy_load", "mtsv_taxonomy_free", "mtsv_taxonomy_info", "mtsv_taxonomy_parent", "mtsv_taxonomy_rank_name",
     "mtsv_fold_lca", "mtsv_format_clade_report",
+    "mtsv_dupmap_create", "mtsv_dupmap_free", "mtsv_batch_take_unique", "mtsv_dupmap_download", "mtsv_fold_expand",
 ]
 
 _lib = None
@@ -220,6 +221,12 @@ def lib():
         L.mtsv_taxonomy_rank_name.restype = C.c_char_p
         L.mtsv_fold_lca.argtypes = [vp, vp, u32, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_format_clade_report.argtypes = [vp, u64, u64, vp, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_dupmap_create.argtypes = [i32, C.POINTER(vp)]
+        L.mtsv_dupmap_free.argtypes = [vp]
+        L.mtsv_dupmap_free.restype = None
+        L.mtsv_batch_take_unique.argtypes = [vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_dupmap_download.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+        L.mtsv_fold_expand.argtypes = [vp, vp, vp, C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -570,6 +577,14 @@ class Batch:
         _check(lib().mtsv_batch_merge_runs(self.h, arr, len(srcs), C.byref(ms)))
         return ms.value
 
+    def take_unique(self, src, dupmap):
+        """mtsv_batch_take_unique: this workspace's resident batch := the first read of every group of identical reads of
+        src's resident batch, handed over on the device; dupmap (a DupMap) then holds the groups.  Returns (n_unique,
+        bases_kept, device ms of the kernels)"""
+        n, nb, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_batch_take_unique(self.h, src.h, dupmap.h, C.byref(n), C.byref(nb), C.byref(ms)))
+        return n.value, nb.value, ms.value
+
     def read_map(self):
         """the caller's read number of every resident read (uint64 array; the identity after upload)"""
         out, n = C.c_void_p(), C.c_uint64()
@@ -737,9 +752,50 @@ class Fold:
                                    C.byref(n), C.byref(total), C.byref(ms)))
         return (_records_from(ptr, n.value, CLADE_STATS_DTYPE) if rows else None), total.value, ms.value
 
+    def expand(self, src, dupmap):
+        """mtsv_fold_expand: this fold := for every read of dupmap's last take the records the Fold src holds for the read's
+        representative, numbered as that read; returns the device ms of the kernels"""
+        ms = C.c_float()
+        _check(lib().mtsv_fold_expand(self.h, src.h, dupmap.h, C.byref(ms)))
+        return ms.value
+
     def close(self):
         if self.h is not None and _lib is not None:
             _lib.mtsv_fold_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DupMap:
+    """Owning handle of an mtsv_dupmap: which reads of the last Batch.take_unique are identical.  MTSV_DEDUP_HASH_BITS and
+    MTSV_FAN_TILE are read when it is created."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _check(lib().mtsv_dupmap_create(device, C.byref(self.h)))
+
+    def download(self):
+        """(read, rep, n_unique): per resident read of the take's source the caller's number of the read and of the first
+        read identical to it, as uint64 arrays; empty before any take"""
+        a, b, n, u = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(lib().mtsv_dupmap_download(self.h, C.byref(a), C.byref(b), C.byref(n), C.byref(u)))
+        try:
+            nbytes = max(n.value, 1) * 8
+            read = np.frombuffer((C.c_ubyte * nbytes).from_address(a.value), dtype="<u8")[:n.value].copy()
+            rep = np.frombuffer((C.c_ubyte * nbytes).from_address(b.value), dtype="<u8")[:n.value].copy()
+        finally:
+            lib().mtsv_free(a)
+            lib().mtsv_free(b)
+        return read, rep, u.value
+
+    def close(self):
+        if self.h is not None and _lib is not None:
+            _lib.mtsv_dupmap_free(self.h)
         self.h = None
 
     def __del__(self):

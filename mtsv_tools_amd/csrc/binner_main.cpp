@@ -34,6 +34,9 @@
 //   --fold-prefetch   with --fold-on-gpu: the next chunk's file is read by a loader thread while the resident chunk runs
 //                     (mtsv_fold_format_text, k_text.hip) -- the read IDs go up and the text comes down, where otherwise the
 //                     records come down and a host thread formats them; the results file is the same byte for byte
+//   --dedup           with --fold-on-gpu: identical reads of a piece are binned once (mtsv_batch_take_unique, k_dedup.hip) and
+//                     the records of the one read that ran are fanned out to its copies before anything is derived from them
+//                     (mtsv_fold_expand): every output file is the same byte for byte
 #include <cstddef>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -132,7 +135,7 @@ struct Args {
     std::string fasta, fastq, index, results, report, matched, unmatched, filter_index, output_format = "default";
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
-    bool verbose = false, force = false, parse_only = false, merge_gpu = false, fold_gpu = false, text_gpu = false, fold_prefetch = false;
+    bool verbose = false, force = false, parse_only = false, merge_gpu = false, fold_gpu = false, text_gpu = false, fold_prefetch = false, dedup = false;
     uint64_t fold_reads = 16ull << 20;  // --fold-reads: reads per super-batch of --fold-on-gpu (every chunk is loaded once per super-batch)
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
@@ -241,6 +244,7 @@ int main(int argc, char** argv) {
         else if (key == "--fold-on-gpu") a.fold_gpu = true;
         else if (key == "--text-on-gpu") a.text_gpu = true;
         else if (key == "--fold-prefetch") a.fold_prefetch = true;
+        else if (key == "--dedup") a.dedup = true;
         else if (key == "--fold-reads") {
             const std::string v = val();
             char* e = nullptr;
@@ -283,7 +287,10 @@ int main(int argc, char** argv) {
                    "text is what comes to the host; the results file is the same),\n"
                    "--fold-prefetch (only with --fold-on-gpu: a loader thread reads chunk c + 1 from its file while chunk c is made\n"
                    "resident, run and folded, and the chunks are packed into the device layout on the GPU; still one chunk resident\n"
-                   "at a time, at most two in host memory; the files are the same)\n");
+                   "at a time, at most two in host memory; the files are the same),\n"
+                   "--dedup (only with --fold-on-gpu: reads of a batch that are identical base for base after normalisation are binned\n"
+                   "once, on the GPU, and the records of the one that ran are copied to the others on the GPU before results, --report\n"
+                   "and --matched / --unmatched are derived; every read keeps its own ID and every file is the same)\n");
             return 0;
         } else if (key == "-V" || key == "--version") {
             printf("mtsv 2.1.0 (%s)\n", mtsv_version());
@@ -301,6 +308,7 @@ int main(int argc, char** argv) {
         if (!a.fold_gpu) usage_error("The argument '--text-on-gpu' requires '--fold-on-gpu'");
     }
     if (a.fold_prefetch && !a.fold_gpu) usage_error("The argument '--fold-prefetch' requires '--fold-on-gpu'");  // (likewise)
+    if (a.dedup && !a.fold_gpu) usage_error("The argument '--dedup' requires '--fold-on-gpu'");                  // (likewise)
     if (a.merge_gpu) {
         // (decided here, before any file or device is touched)
         size_t n_chunks = 0;
@@ -773,9 +781,18 @@ int main(int argc, char** argv) {
         auto pre_join = [&] {
             if (pre.th.joinable()) pre.th.join();
         };
-        float fold_device_ms = 0, text_device_ms = 0;
+        float fold_device_ms = 0, text_device_ms = 0, dedup_device_ms = 0, expand_device_ms = 0;
         std::vector<std::unique_ptr<ReadBlock>> pieces;
         std::vector<mtsv_fold*> folds;  // one per piece of a super-batch, kept from super-batch to super-batch
+        // --dedup: a chunk's run sees the distinct sequences of a piece.  Per chunk and piece the reads go up into an intake
+        // workspace, mtsv_batch_take_unique packs the first read of every group of identical reads into the chunk's workspace,
+        // and the run is folded into the piece's fold of REPRESENTATIVES; after the last chunk mtsv_fold_expand fans those
+        // records out into the piece's fold proper, which everything below is derived from as without the flag.  The map is
+        // computed again for every chunk, into the piece's mtsv_dupmap, with the same content every time: hashing the piece
+        // once per chunk is the price of keeping no reads resident between chunks (a chunk's index may need that room).
+        std::vector<mtsv_fold*> rep_folds;
+        std::vector<mtsv_dupmap*> dupmaps;
+        uint64_t dedup_reads = 0, dedup_distinct = 0;
         uint64_t super_reads = 0, n_super = 0, reads_done = 0, reads_matched = 0;
         mtsv_taxon_stats* sum = nullptr;
         uint64_t n_sum = 0, report_reads = 0;
@@ -805,11 +822,19 @@ int main(int argc, char** argv) {
                 if (mtsv_fold_create(dev, grain, &f) != MTSV_OK) return lib_error();
                 folds.push_back(f);
             }
+            while (a.dedup && rep_folds.size() < pieces.size()) {
+                mtsv_fold* f = nullptr;
+                mtsv_dupmap* m = nullptr;
+                if (mtsv_fold_create(dev, grain, &f) != MTSV_OK) return lib_error();
+                rep_folds.push_back(f);
+                if (mtsv_dupmap_create(dev, &m) != MTSV_OK) return lib_error();
+                dupmaps.push_back(m);
+            }
             for (size_t k = 0; k < pieces.size(); k++)
-                if (mtsv_fold_reset(folds[k], pieces[k]->n()) != MTSV_OK) return lib_error();
+                if (mtsv_fold_reset(a.dedup ? rep_folds[k] : folds[k], pieces[k]->n()) != MTSV_OK) return lib_error();
             for (size_t c = 0; c < index_paths.size(); c++) {
                 mtsv_index* ix = nullptr;
-                mtsv_batch* ws = nullptr;
+                mtsv_batch *ws = nullptr, *intake = nullptr;
                 double t0 = now();
                 int rc;
                 if (a.fold_prefetch && pre.chunk == c) {  // the loader has it, or is on it: t_load counts the wait
@@ -842,20 +867,32 @@ int main(int argc, char** argv) {
                 if (rc == MTSV_OK) rc = mtsv_batch_create_lanes(ix, dev, piece_reads, piece_bases, 0, 1, &ws);
                 if (rc == MTSV_OK) rc = mtsv_batch_set_assignment_grain(ws, grain);
                 if (rc == MTSV_OK) rc = mtsv_batch_set_assignments(ws, MTSV_ASSIGN_ONLY);
+                if (rc == MTSV_OK && a.dedup) rc = mtsv_batch_create_lanes(ix, dev, piece_reads, piece_bases, 1, 1, &intake);  // (it never runs)
                 for (size_t k = 0; k < pieces.size() && rc == MTSV_OK; k++) {
                     const ReadBlock& rb = *pieces[k];
                     t0 = now();
-                    rc = mtsv_batch_upload(ws, rb.bases.data(), rb.off.data(), rb.n());
+                    rc = mtsv_batch_upload(a.dedup ? intake : ws, rb.bases.data(), rb.off.data(), rb.n());
+                    if (rc == MTSV_OK && a.dedup) {
+                        uint64_t n_distinct = 0, bases_kept = 0;
+                        float ms = 0;
+                        rc = mtsv_batch_take_unique(ws, intake, dupmaps[k], &n_distinct, &bases_kept, &ms);
+                        dedup_device_ms += ms;
+                        if (rc == MTSV_OK && c == 0) {
+                            dedup_reads += rb.n();
+                            dedup_distinct += n_distinct;
+                        }
+                    }
                     if (rc == MTSV_OK) rc = mtsv_batch_run(ws, &p);
                     t_run += now() - t0;
                     t0 = now();
                     float ms = 0;
-                    if (rc == MTSV_OK) rc = mtsv_fold_add_run(folds[k], ws, &ms);
+                    if (rc == MTSV_OK) rc = mtsv_fold_add_run(a.dedup ? rep_folds[k] : folds[k], ws, &ms);
                     fold_device_ms += ms;
                     t_fold += now() - t0;
                 }
                 if (rc != MTSV_OK) lib_error();  // (before the frees: the message is the failing call's)
                 mtsv_batch_free(ws);
+                mtsv_batch_free(intake);
                 mtsv_index_free(ix);
                 if (rc != MTSV_OK) return false;
                 logmsg("DEBUG", "chunk " + index_paths[c] + " folded into " + std::to_string(pieces.size()) + " pieces");
@@ -864,6 +901,11 @@ int main(int argc, char** argv) {
             for (size_t k = 0; k < pieces.size(); k++) {
                 ReadBlock& rb = *pieces[k];
                 mtsv_fold* f = folds[k];
+                if (a.dedup) {  // (the piece's map is the last chunk's, equal to every chunk's)
+                    float ms = 0;
+                    if (mtsv_fold_expand(f, rep_folds[k], dupmaps[k], &ms) != MTSV_OK) return lib_error();
+                    expand_device_ms += ms;
+                }
                 if (out_fd >= 0) {
                     void* recs = nullptr;
                     uint64_t n_recs = 0;
@@ -965,6 +1007,10 @@ int main(int argc, char** argv) {
             }
             for (auto* f : folds) mtsv_fold_free(f);
             folds.clear();
+            for (auto* f : rep_folds) mtsv_fold_free(f);
+            rep_folds.clear();
+            for (auto* m : dupmaps) mtsv_dupmap_free(m);
+            dupmaps.clear();
             mtsv_index_free(pre.ix);
             pre.ix = nullptr;
             return c;
@@ -987,6 +1033,7 @@ int main(int argc, char** argv) {
         if (partition)
             logmsg("INFO", "Partitioned " + std::to_string(reads_done) + " reads: " + std::to_string(reads_matched) + " matched, " + std::to_string(reads_done - reads_matched) +
                                " unmatched.");
+        if (a.dedup) logmsg("INFO", "Collapsed " + std::to_string(dedup_reads) + " reads to " + std::to_string(dedup_distinct) + " distinct sequences.");
         if (!a.report.empty()) {
             char* text = nullptr;
             uint64_t text_len = 0;
@@ -1018,6 +1065,8 @@ int main(int argc, char** argv) {
                     (unsigned long long)n_super, index_paths.size(), (unsigned long long)reads_done, t_load, t_resident, t_run, t_fold, fold_device_ms, t_out,
                     prefetch_note);
         if (getenv("MTSV_CLI_TIMING") && a.text_gpu) fprintf(stderr, "[cli text timing] text_on_gpu device %.3f ms\n", text_device_ms);
+        if (getenv("MTSV_CLI_TIMING") && a.dedup)
+            fprintf(stderr, "[cli dedup timing] take_unique device %.3f ms, expand device %.3f ms\n", dedup_device_ms, expand_device_ms);
         return leave(0);
     }
     // (batches too large for one parser block are put together from several blocks by appending: those stay in ordinary

@@ -11,6 +11,7 @@
 
 #include "../../include/mtsv_amd.h"
 #include "batch.hpp"
+#include "dedup.hpp"
 #include "dev_index.hpp"
 #include "fold.hpp"
 #include "mgindex.hpp"
@@ -607,6 +608,45 @@ int mtsv_fold_match_flags(mtsv_fold* f, uint64_t** words, uint64_t* n_reads, uin
         memcpy(out, w.data(), w.size() * sizeof(uint64_t));
         *words = out;
     })
+}
+
+// ---- mtsv_dupmap: identical reads binned once (dedup.hip, k_dedup.hip) ----
+int mtsv_dupmap_create(int hip_device, mtsv_dupmap** out) {
+    if (!out) return fail_arg("null argument");
+    GUARD(*out = new mtsv_dupmap(hip_device))
+}
+
+void mtsv_dupmap_free(mtsv_dupmap* m) { delete m; }
+
+int mtsv_batch_take_unique(mtsv_batch* dst, mtsv_batch* src, mtsv_dupmap* m, uint64_t* n_unique, uint64_t* bases_kept, float* device_ms) {
+    if (!dst || !src || !m || !n_unique || !bases_kept) return fail_arg("null argument");
+    GUARD(m->impl.take_unique(dst->impl, src->impl, n_unique, bases_kept, device_ms))
+}
+
+int mtsv_dupmap_download(const mtsv_dupmap* m, uint64_t** read, uint64_t** rep, uint64_t* n_reads, uint64_t* n_unique) {
+    if (!m || !read || !rep || !n_reads || !n_unique) return fail_arg("null argument");
+    GUARD({
+        std::vector<uint64_t> a, b;
+        m->impl.download(a, b);
+        auto* oa = (uint64_t*)malloc(std::max<size_t>(a.size(), 1) * sizeof(uint64_t));
+        auto* ob = (uint64_t*)malloc(std::max<size_t>(b.size(), 1) * sizeof(uint64_t));
+        if (!oa || !ob) {
+            free(oa);
+            free(ob);
+            throw std::bad_alloc();
+        }
+        if (!a.empty()) memcpy(oa, a.data(), a.size() * sizeof(uint64_t));
+        if (!b.empty()) memcpy(ob, b.data(), b.size() * sizeof(uint64_t));
+        *read = oa;
+        *rep = ob;
+        *n_reads = a.size();
+        *n_unique = m->impl.valid ? m->impl.n_unique : 0;
+    })
+}
+
+int mtsv_fold_expand(mtsv_fold* dst, mtsv_fold* src, const mtsv_dupmap* m, float* device_ms) {
+    if (!dst || !src || !m) return fail_arg("null argument");
+    GUARD(m->impl.expand(dst->impl, src->impl, device_ms))
 }
 
 // ---- taxonomy, per-read LCA and clade report (taxonomy.cpp, lca.hip, k_lca.hip) ----

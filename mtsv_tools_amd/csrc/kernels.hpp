@@ -383,5 +383,30 @@ void launch_lca_span(hipStream_t s, int grain, const void* rec, uint32_t n, uint
 void launch_lca_walk(hipStream_t s, uint32_t n_slots, uint32_t n_nodes, uint32_t max_depth, const uint32_t* lo, const uint32_t* hi, const uint32_t* m,
                      const uint32_t* parent, const uint32_t* last, const uint32_t* tax, void* out, uint32_t* direct, uint64_t* ctr);
 void launch_lca_clade(hipStream_t s, uint32_t n_nodes, const uint32_t* last, const uint32_t* prefix, uint32_t* clade);
+// k_dedup.hip: the identical reads of a resident batch (codes 0..4, read_off[n_reads + 1]; codes readable to the end of the
+// aligned dword of its last base).  rep(j) = the smallest index of a read with j's length and codes.
+//   hash:     hash[j], 64 bits of the read's codes and length, independent of where the read lies
+//   insert:   table: n_slots u64 (a power of two >= 2 n_reads, < 2^32), set to all ones by the caller; only the low hash_bits
+//             (0..64) of a hash are used; slot_of[j] = the slot of j's sequence; ctr[1] += the reads that found none (none,
+//             unless the table is too small).  ctr: two u64, zeroed by the caller
+//   resolve:  words: ceil(n_reads / 64) u64, bit j = "rep(j) == j"; read[j] = src_map[j], rep[j] = src_map[rep(j)] (src_map
+//             null: the identity); ctr[0] += the representatives
+// (launch_compact_scan / _copy with words and keep_matched = 1 then pack the representatives)
+void launch_dedup_hash(hipStream_t s, uint32_t n_reads, const uint32_t* read_off, const uint8_t* codes, uint64_t* hash);
+void launch_dedup_insert(hipStream_t s, uint32_t n_reads, const uint32_t* read_off, const uint8_t* codes, const uint64_t* hash, uint32_t hash_bits,
+                         uint64_t* table, uint32_t n_slots, uint32_t* slot_of, uint64_t* ctr);
+void launch_dedup_resolve(hipStream_t s, uint32_t n_reads, const uint64_t* table, const uint32_t* slot_of, const uint32_t* src_map, uint64_t* words,
+                          uint32_t* read, uint32_t* rep, uint64_t* ctr);
+// The fan: n_entries map entries (read[] strictly ascending); rec: n_rec records of the grain ordered by its key.
+//   count:  first[j] / cnt[j] = where the records of read rep[j] begin in rec / how many there are; *ctr (one u64, zeroed by the
+//           caller) += cnt[j] of the entries with rep[j] == read[j]
+//   (launch_scan over cnt: off[0 .. n_entries], off[n_entries] = total, which must be below 2^32)
+//   write:  out[off[j] .. off[j + 1]) = those records with `read` replaced by read[j].  A workgroup owns `tile` output records (a
+//           power of two, 64 .. kFanTileMax)
+constexpr uint32_t kFanTileMax = 1024, kFanTile = 1024;
+void launch_fan_count(hipStream_t s, int grain, uint32_t n_entries, const uint32_t* read, const uint32_t* rep, const void* rec, uint32_t n_rec,
+                      uint32_t* first, uint32_t* cnt, uint64_t* ctr);
+void launch_fan_write(hipStream_t s, int grain, uint32_t n_entries, const uint32_t* read, const uint32_t* first, const uint32_t* off, const void* rec,
+                      uint32_t tile, uint32_t total, void* out);
 
 }  // namespace mtsv
