@@ -719,6 +719,22 @@ void Batch::run(const mtsv_params& p) {
     last_run = kRunResident;
 }
 
+// d_compact for `tiles` tiles of the compaction kernels, and d_read_map (take_reads, and DupMap::take_unique of dedup.hip)
+void Batch::compact_room(uint64_t tiles) {
+    if (!d_compact || compact_cap < tiles) {
+        (void)hipFree(d_compact);
+        d_compact = nullptr;
+        compact_cap = 0;
+        uint64_t b = 0;
+        dev_alloc(&d_compact, 3 + 2 * (tiles + tiles / 16), &b);
+        compact_cap = tiles + tiles / 16;
+    }
+    if (!d_read_map) {
+        uint64_t b = 0;
+        dev_alloc(&d_read_map, max_reads, &b);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Chaining: the unmatched (matched) reads of src's last run become this workspace's resident batch.  The bases go from
 // HBM to HBM, the flags are read where k_match wrote them; the host sees the 24-byte result block (the capacity check
@@ -743,19 +759,7 @@ void Batch::take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_k
     const uint32_t* s_off = host_batch ? src.arena[0].d_off : src.d_read_off;
     const uint32_t* s_map = src.mapped ? src.d_read_map : nullptr;
     HIP_CHECK(hipSetDevice(di->device));
-    const uint64_t tiles = compact_tiles(n);
-    if (!d_compact || compact_cap < tiles) {
-        (void)hipFree(d_compact);
-        d_compact = nullptr;
-        compact_cap = 0;
-        uint64_t b = 0;
-        dev_alloc(&d_compact, 3 + 2 * (tiles + tiles / 16), &b);
-        compact_cap = tiles + tiles / 16;
-    }
-    if (!d_read_map) {
-        uint64_t b = 0;
-        dev_alloc(&d_read_map, max_reads, &b);
-    }
+    compact_room(compact_tiles(n));
     if (!compact_ev[0])
         for (auto& e : compact_ev) HIP_CHECK(hipEventCreate(&e));
     uint64_t* result = d_compact;

@@ -217,6 +217,7 @@ struct Batch {
     uint64_t* d_compact = nullptr;    // the result block (3 words), then two arrays of tile sums
     uint64_t compact_cap = 0;         // ... entries each
     hipEvent_t compact_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the scan and around the copy
+    void compact_room(uint64_t tiles);  // d_compact for that many tiles, and d_read_map; on the workspace's device
     void take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_kept, float* device_ms);
     // this workspace's resident batch := a copy of src's (codes or bases, offsets, longest read, read map), HBM to HBM
     void copy_reads(Batch& src, float* device_ms);

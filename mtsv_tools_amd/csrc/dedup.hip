@@ -18,48 +18,18 @@
 
 namespace mtsv {
 
-namespace {
-template <class T>
-T* dedup_alloc(uint64_t count) {
-    T* p = nullptr;
-    HIP_CHECK(hipMalloc((void**)&p, std::max<uint64_t>(count, 1) * sizeof(T)));
-    return p;
-}
-template <class T>
-void dedup_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-}  // namespace
-
 DupMap::DupMap(int device_) : device(device_) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess) {
-        (void)hipGetLastError();
-        n_dev = 0;
-    }
-    if (device < 0 || device >= n_dev) throw std::runtime_error("device: no HIP device " + std::to_string(device) + " (" + std::to_string(n_dev) + " visible)");
+    require_device(device);
     if (const char* e = getenv("MTSV_DEDUP_HASH_BITS")) hash_bits = (uint32_t)std::min<uint64_t>(strtoull(e, nullptr, 10), 64);  // (tests: long chains, equal tags)
-    if (const char* e = getenv("MTSV_FAN_TILE")) {  // (tests: tile edges within reach of small lists)
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 64), kFanTileMax);
-        fan_tile = 64;
-        while (fan_tile * 2 <= want) fan_tile *= 2;
-    }
+    fan_tile = tile_from_env("MTSV_FAN_TILE", kFanTile, 64, kFanTileMax);
     trace = getenv("MTSV_TRACE") != nullptr;
     HIP_CHECK(hipSetDevice(device));
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    for (auto& e : fan.ev) HIP_CHECK(hipEventCreate(&e));
+    ev.create();
+    fan.ev.create();
 }
 
 DupMap::~DupMap() {
     if (hipSetDevice(device) != hipSuccess) (void)hipGetLastError();
-    for (void* p : {(void*)d_read[0], (void*)d_read[1], (void*)d_rep[0], (void*)d_rep[1], (void*)d_hash, (void*)d_table, (void*)d_words, (void*)d_ctr,
-                    (void*)d_slot, (void*)fan.d_first, (void*)fan.d_cnt, (void*)fan.d_off, (void*)fan.d_sums})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : fan.ev)
-        if (e) (void)hipEventDestroy(e);
 }
 
 void DupMap::take_unique(Batch& dst, Batch& src, uint64_t* n_unique_out, uint64_t* bases_kept, float* device_ms) {
@@ -83,82 +53,51 @@ void DupMap::take_unique(Batch& dst, Batch& src, uint64_t* n_unique_out, uint64_
     // ---- room: the map's (a refusal from here on leaves both the map and dst as they were) ----
     uint64_t slots = 2;
     while (slots < 2 * n_src) slots *= 2;
-    if (n_src > cap || !d_read[0]) {
-        const uint64_t ncap = std::max<uint64_t>(n_src + n_src / 8, 1024);
-        uint32_t* a[4] = {nullptr, nullptr, nullptr, nullptr};
-        try {
-            for (auto& p : a) p = dedup_alloc<uint32_t>(ncap);
-            if (valid && n) {
-                HIP_CHECK(hipMemcpyAsync(a[0], d_read[cur], n * 4, hipMemcpyDeviceToDevice, stream));
-                HIP_CHECK(hipMemcpyAsync(a[2], d_rep[cur], n * 4, hipMemcpyDeviceToDevice, stream));
-                HIP_CHECK(hipStreamSynchronize(stream));
-            }
-        } catch (...) {
-            for (auto& p : a) dedup_free(p);
-            throw;
+    if (n_src > d_read[0].cap || !d_read[0].p) {
+        // (four new arrays; the map's entries move to the first of each pair, and the old arrays leave with `fresh`)
+        DevBuf<uint32_t> fresh[4];
+        for (auto& b : fresh) b.room(stream, n_src, "the map");
+        if (valid && n) {
+            HIP_CHECK(hipMemcpyAsync(fresh[0].p, d_read[cur].p, n * 4, hipMemcpyDeviceToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(fresh[2].p, d_rep[cur].p, n * 4, hipMemcpyDeviceToDevice, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
         }
         for (int k = 0; k < 2; k++) {
-            dedup_free(d_read[k]);
-            dedup_free(d_rep[k]);
+            d_read[k].swap(fresh[k]);
+            d_rep[k].swap(fresh[2 + k]);
         }
-        d_read[0] = a[0];
-        d_read[1] = a[1];
-        d_rep[0] = a[2];
-        d_rep[1] = a[3];
         cur = 0;
-        cap = ncap;
     }
-    if (n_src > reads_cap || !d_hash) {
-        const uint64_t ncap = std::max<uint64_t>(n_src + n_src / 8, 1024);
-        dedup_free(d_hash);
-        dedup_free(d_slot);
-        dedup_free(d_words);
-        reads_cap = 0;
-        d_hash = dedup_alloc<uint64_t>(ncap);
-        d_slot = dedup_alloc<uint32_t>(ncap);
-        d_words = dedup_alloc<uint64_t>((ncap + 63) / 64);
-        reads_cap = ncap;
-    }
-    if (slots > table_cap || !d_table) {
-        dedup_free(d_table);
-        table_cap = 0;
-        d_table = dedup_alloc<uint64_t>(slots);
-        table_cap = slots;
-    }
-    if (!d_ctr) d_ctr = dedup_alloc<uint64_t>(2);
+    d_hash.room(stream, n_src, "the reads' hashes");
+    d_slot.room(stream, n_src, "the reads' slots");
+    d_words.room(stream, (n_src + 63) / 64, "the representatives' bitmap");
+    d_table.room(stream, slots, "the table");
+    d_ctr.room(stream, 2, "the counters");
     // ---- room: dst's, as take_reads makes it ----
-    const uint64_t tiles = compact_tiles(n_src);
-    if (!dst.d_compact || dst.compact_cap < tiles) {
-        (void)hipFree(dst.d_compact);
-        dst.d_compact = nullptr;
-        dst.compact_cap = 0;
-        dst.d_compact = dedup_alloc<uint64_t>(3 + 2 * (tiles + tiles / 16));
-        dst.compact_cap = tiles + tiles / 16;
-    }
-    if (!dst.d_read_map) dst.d_read_map = dedup_alloc<uint32_t>(dst.max_reads);
+    dst.compact_room(compact_tiles(n_src));
     uint64_t* result = dst.d_compact;
     uint64_t *tile_cnt = dst.d_compact + 3, *tile_bases = dst.d_compact + 3 + dst.compact_cap;
-    uint32_t *new_read = d_read[cur ^ 1], *new_rep = d_rep[cur ^ 1];
+    uint32_t *new_read = d_read[cur ^ 1].p, *new_rep = d_rep[cur ^ 1].p;
     // ---- which reads are identical ----
     // (a batch as uploaded is normalised into the source's d_codes first, as run() would do it)
     if (!codes && nb_src) launch_normalise(stream, src.d_bases, src.d_codes, 0, nb_src);
     HIP_CHECK(hipMemsetAsync(result, 0, 3 * sizeof(uint64_t), stream));
-    HIP_CHECK(hipMemsetAsync(d_ctr, 0, 2 * sizeof(uint64_t), stream));
-    HIP_CHECK(hipMemsetAsync(d_words, 0, std::max<uint64_t>((n_src + 63) / 64, 1) * sizeof(uint64_t), stream));
+    HIP_CHECK(hipMemsetAsync(d_ctr.p, 0, 2 * sizeof(uint64_t), stream));
+    HIP_CHECK(hipMemsetAsync(d_words.p, 0, std::max<uint64_t>((n_src + 63) / 64, 1) * sizeof(uint64_t), stream));
     HIP_CHECK(hipEventRecord(ev[0], stream));
-    launch_dedup_hash(stream, (uint32_t)n_src, s_off, s_codes, d_hash);
+    launch_dedup_hash(stream, (uint32_t)n_src, s_off, s_codes, d_hash.p);
     HIP_CHECK(hipEventRecord(ev[1], stream));
-    HIP_CHECK(hipMemsetAsync(d_table, 0xff, slots * sizeof(uint64_t), stream));
-    launch_dedup_insert(stream, (uint32_t)n_src, s_off, s_codes, d_hash, hash_bits, d_table, (uint32_t)slots, d_slot, d_ctr);
+    HIP_CHECK(hipMemsetAsync(d_table.p, 0xff, slots * sizeof(uint64_t), stream));
+    launch_dedup_insert(stream, (uint32_t)n_src, s_off, s_codes, d_hash.p, hash_bits, d_table.p, (uint32_t)slots, d_slot.p, d_ctr.p);
     HIP_CHECK(hipEventRecord(ev[2], stream));
-    launch_dedup_resolve(stream, (uint32_t)n_src, d_table, d_slot, s_map, d_words, new_read, new_rep, d_ctr);
+    launch_dedup_resolve(stream, (uint32_t)n_src, d_table.p, d_slot.p, s_map, d_words.p, new_read, new_rep, d_ctr.p);
     HIP_CHECK(hipEventRecord(ev[3], stream));
     // ---- the representatives, packed by the kernels of take_reads (bitmap, keep = set) ----
-    launch_compact_scan(stream, (uint32_t)n_src, d_words, s_off, MTSV_KEEP_MATCHED, tile_cnt, tile_bases, result);
+    launch_compact_scan(stream, (uint32_t)n_src, d_words.p, s_off, MTSV_KEEP_MATCHED, tile_cnt, tile_bases, result);
     HIP_CHECK(hipEventRecord(ev[4], stream));
     uint64_t h_result[3] = {0, 0, 0}, h_ctr[2] = {0, 0};
     HIP_CHECK(hipMemcpyAsync(h_result, result, sizeof h_result, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync(h_ctr, d_ctr, sizeof h_ctr, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(h_ctr, d_ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     const uint64_t m = h_result[0], nb = h_result[1];
@@ -172,7 +111,7 @@ void DupMap::take_unique(Batch& dst, Batch& src, uint64_t* n_unique_out, uint64_
     dst.resident = false;
     dst.last_run = Batch::kRunNone;
     HIP_CHECK(hipEventRecord(ev[5], stream));
-    launch_compact_copy(stream, (uint32_t)n_src, d_words, s_off, s_codes, MTSV_KEEP_MATCHED, s_map, tile_cnt, tile_bases, result, dst.d_codes, dst.d_read_off,
+    launch_compact_copy(stream, (uint32_t)n_src, d_words.p, s_off, s_codes, MTSV_KEEP_MATCHED, s_map, tile_cnt, tile_bases, result, dst.d_codes, dst.d_read_off,
                         dst.d_read_map);
     HIP_CHECK(hipEventRecord(ev[6], stream));
     dst.h_read_off.resize(m + 1);
@@ -212,8 +151,8 @@ void DupMap::download(std::vector<uint64_t>& read, std::vector<uint64_t>& rep) c
     if (!valid || !n) return;
     std::vector<uint32_t> a(n), b(n);
     HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipMemcpy(a.data(), d_read[cur], n * 4, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(b.data(), d_rep[cur], n * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(a.data(), d_read[cur].p, n * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(b.data(), d_rep[cur].p, n * 4, hipMemcpyDeviceToHost));
     read.assign(a.begin(), a.end());
     rep.assign(b.begin(), b.end());
 }
@@ -239,27 +178,17 @@ void DupMap::expand(Fold& dst, Fold& src, float* device_ms) const {
     HIP_CHECK(hipSetDevice(device));
     hipStream_t stream = dst.stream;
     Fan& f = fan;
-    if (n > f.cap || !f.d_first) {
-        const uint64_t ncap = std::max<uint64_t>(n + n / 8, 1024);
-        dedup_free(f.d_first);
-        dedup_free(f.d_cnt);
-        dedup_free(f.d_off);
-        dedup_free(f.d_sums);
-        f.cap = 0;
-        f.d_first = dedup_alloc<uint32_t>(ncap);
-        f.d_cnt = dedup_alloc<uint32_t>(ncap);
-        f.d_off = dedup_alloc<uint32_t>(ncap + 1);
-        f.sums_cap = (uint64_t)scan_tiles((uint32_t)ncap) + 1;
-        f.d_sums = dedup_alloc<uint64_t>(f.sums_cap + 2);
-        f.cap = ncap;
-    }
-    const uint32_t *rd = d_read[cur], *rp = d_rep[cur];
-    uint64_t *d_total = f.d_sums + f.sums_cap, *d_own = d_total + 1;
-    const uint64_t rec = src.rec_bytes();
+    f.d_first.room(stream, n, "the reads' first records");
+    f.d_cnt.room(stream, n, "the reads' record counts");
+    f.d_off.room(stream, n + 1, "the reads' offsets");
+    f.d_sums.room(stream, (uint64_t)scan_tiles((uint32_t)n) + 3, "the scan's sums");
+    f.sums_cap = f.d_sums.cap - 2;  // (the total and the counter lie behind the sums)
+    const uint32_t *rd = d_read[cur].p, *rp = d_rep[cur].p;
+    uint64_t *d_total = f.d_sums.p + f.sums_cap, *d_own = d_total + 1;
     HIP_CHECK(hipMemsetAsync(d_total, 0, 2 * sizeof(uint64_t), stream));
     HIP_CHECK(hipEventRecord(f.ev[0], stream));
-    launch_fan_count(stream, src.grain, (uint32_t)n, rd, rp, src.d_rec[src.cur], (uint32_t)src.n, f.d_first, f.d_cnt, d_own);
-    launch_scan(stream, f.d_cnt, (uint32_t)n, f.d_sums, d_total, f.d_off);
+    launch_fan_count(stream, src.grain, (uint32_t)n, rd, rp, src.d_rec[src.cur].p, (uint32_t)src.n, f.d_first.p, f.d_cnt.p, d_own);
+    launch_scan(stream, f.d_cnt.p, (uint32_t)n, f.d_sums.p, d_total, f.d_off.p);
     HIP_CHECK(hipEventRecord(f.ev[1], stream));
     uint64_t h[2] = {0, 0};
     HIP_CHECK(hipMemcpyAsync(h, d_total, sizeof h, hipMemcpyDeviceToHost, stream));
@@ -271,49 +200,18 @@ void DupMap::expand(Fold& dst, Fold& src, float* device_ms) const {
                                  " records belong to reads that are no representatives in the map");
     if (total >= (1ull << 32)) throw std::runtime_error("limit: the expanded fold would hold " + std::to_string(total) + " records, 2^32 or more");
     if (total < own) throw std::runtime_error("internal: " + std::to_string(own) + " records of representatives, " + std::to_string(total) + " after the fan");
-    uint8_t *grown_a = nullptr, *grown_b = nullptr, *out = nullptr;
-    uint64_t grown_cap = 0;
-    if (total > dst.cap || !dst.d_rec[0]) {
-        grown_cap = std::min<uint64_t>(std::max<uint64_t>(total, 1ull << 16), 0xffffffffull);
-        const bool ok_a = hipMalloc((void**)&grown_a, grown_cap * rec) == hipSuccess;
-        const bool ok_b = ok_a && hipMalloc((void**)&grown_b, grown_cap * rec) == hipSuccess;
-        if (!ok_b) {
-            (void)hipGetLastError();
-            if (grown_a) (void)hipFree(grown_a);
-            throw std::runtime_error("device: no memory for an output fold of " + std::to_string(grown_cap) + " records (two arrays)");
-        }
-        out = grown_a;
-    } else {
-        out = dst.d_rec[dst.cur ^ 1];
-    }
+    Fold::Staged st = dst.stage_write(total, "an output fold");  // (an error below frees a pair it holds: dst stays as it was)
     float ms_count = 0, ms_write = 0;
-    std::vector<uint32_t> taxa;
-    try {
-        taxa = src.taxa;
-        HIP_CHECK(hipEventRecord(f.ev[2], stream));
-        launch_fan_write(stream, src.grain, (uint32_t)n, rd, f.d_first, f.d_off, src.d_rec[src.cur], fan_tile, (uint32_t)total, out);
-        HIP_CHECK(hipEventRecord(f.ev[3], stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventElapsedTime(&ms_count, f.ev[0], f.ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&ms_write, f.ev[2], f.ev[3]));
-    } catch (...) {
-        if (grown_a) (void)hipFree(grown_a);
-        if (grown_b) (void)hipFree(grown_b);
-        throw;
-    }
+    std::vector<uint32_t> taxa = src.taxa;
+    HIP_CHECK(hipEventRecord(f.ev[2], stream));
+    launch_fan_write(stream, src.grain, (uint32_t)n, rd, f.d_first.p, f.d_off.p, src.d_rec[src.cur].p, fan_tile, (uint32_t)total, st.dst);
+    HIP_CHECK(hipEventRecord(f.ev[3], stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventElapsedTime(&ms_count, f.ev[0], f.ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms_write, f.ev[2], f.ev[3]));
     // ---- nothing can fail from here ----
-    if (grown_a) {
-        if (dst.d_rec[0]) (void)hipFree(dst.d_rec[0]);
-        if (dst.d_rec[1]) (void)hipFree(dst.d_rec[1]);
-        dst.d_rec[0] = grown_a;
-        dst.d_rec[1] = grown_b;
-        dst.cur = 0;
-        dst.cap = grown_cap;
-    } else {
-        dst.cur ^= 1;
-    }
-    dst.n = total;
+    dst.commit(st, total);
     dst.n_reads = src.n_reads;
     dst.taxa.swap(taxa);
     if (device_ms) *device_ms = ms_count + ms_write;

@@ -16,23 +16,21 @@ struct DupMap {
     uint32_t hash_bits = 64;      // MTSV_DEDUP_HASH_BITS, read at creation (tests)
     uint32_t fan_tile = kFanTile;  // MTSV_FAN_TILE, read at creation (tests)
     bool trace = false;
-    uint32_t *d_read[2] = {nullptr, nullptr}, *d_rep[2] = {nullptr, nullptr};  // cap entries each
-    uint64_t cap = 0;
+    DevBuf<uint32_t> d_read[2], d_rep[2];  // the same capacity each
     int cur = 0;
     bool valid = false;  // a take has succeeded
     uint64_t n = 0, n_unique = 0;
     // scratch of a take
-    uint64_t *d_hash = nullptr, *d_table = nullptr, *d_words = nullptr, *d_ctr = nullptr;
-    uint32_t* d_slot = nullptr;
-    uint64_t reads_cap = 0, table_cap = 0;
-    hipEvent_t ev[8] = {};
+    DevBuf<uint64_t> d_hash, d_table, d_words, d_ctr;
+    DevBuf<uint32_t> d_slot;
+    DevEvents<8> ev;
     float ms_hash = 0, ms_insert = 0, ms_resolve = 0, ms_scan = 0, ms_copy = 0;  // of the last take
     // scratch of an expansion (the map itself is not changed by one)
     struct Fan {
-        uint32_t *d_first = nullptr, *d_cnt = nullptr, *d_off = nullptr;  // cap, cap, cap + 1 entries
-        uint64_t* d_sums = nullptr;                                      // the scan's tile sums, then its total, then the counter
-        uint64_t cap = 0, sums_cap = 0;
-        hipEvent_t ev[4] = {};  // around count + scan, around write
+        DevBuf<uint32_t> d_first, d_cnt, d_off;  // n, n, n + 1 entries
+        DevBuf<uint64_t> d_sums;                 // the scan's tile sums, then (at sums_cap) its total, then the counter
+        uint64_t sums_cap = 0;
+        DevEvents<4> ev;  // around count + scan, around write
     };
     mutable Fan fan;
 

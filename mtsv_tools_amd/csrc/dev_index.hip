@@ -15,7 +15,7 @@
 #include <thread>
 #include <vector>
 
-#include "dev_index.hpp"
+#include "dev_mem.hpp"
 #include "kernels.hpp"
 
 namespace mtsv {
@@ -232,30 +232,7 @@ static void pack_on_host(const HostIndex& hx, const uint32_t n, const uint32_t n
 // The device pack (k_pack.hip): d_blocks and d_text of di from the file's raw bytes, to the bytes pack_on_host makes, with its
 // errors.  Uploaded raw, as temporaries: the bwt, the six Occ arrays of A C G T N $, then the text; all are freed before this
 // returns (the bwt's before the text is uploaded).  The counters are read once, after the pack.  Returns the sentinel's row.
-namespace {
-struct DevTemp {  // hipFree on every way out
-    void* p = nullptr;
-    ~DevTemp() { (void)hipFree(p); }
-    void alloc(uint64_t bytes) { HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16)); }
-    void release() {
-        HIP_CHECK(hipFree(p));
-        p = nullptr;
-    }
-};
-struct DevEvents {
-    hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    DevEvents() {
-        for (auto& x : e) HIP_CHECK(hipEventCreate(&x));
-    }
-    ~DevEvents() {
-        for (auto& x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-}  // namespace
-
 static uint64_t pack_on_device(const HostIndex& hx, const uint32_t n, const uint32_t n_blocks, DeviceIndex& di, double& copy_ms) {
-    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     uint32_t tile = kPackTile;
     if (const char* e = getenv("MTSV_PACK_TILE")) {  // (moves the tile edges, for tests)
         const int t = atoi(e);
@@ -267,32 +244,36 @@ static uint64_t pack_on_device(const HostIndex& hx, const uint32_t n, const uint
         if (hx.occ[a].size() < n_chk) throw std::runtime_error("format: occ checkpoint count != floor((n-1)/k)+1");
     const uint32_t tiles = pack_tiles(n_blocks, tile);
     const uint64_t raw_bytes = ((uint64_t)n + 15) / 16 * 16;
-    DevEvents ev;
-    DevTemp d_bwt, d_occ, d_tiles, d_ctr, d_raw_text;
+    DevEvents<7> ev;  // (the temporaries are sized exactly and freed on every way out)
+    DevBuf<uint8_t> d_bwt, d_raw_text;
+    DevBuf<uint64_t> d_occ;
+    DevBuf<uint4> d_tiles;
+    DevBuf<uint32_t> d_ctr;
+    ev.create();
 
     HIP_CHECK(hipMalloc((void**)&di.d_blocks, (uint64_t)n_blocks * sizeof(RankBlock)));
     di.bytes += (uint64_t)n_blocks * sizeof(RankBlock);
-    d_bwt.alloc(raw_bytes);
-    d_occ.alloc(6 * n_chk * 8);
-    d_tiles.alloc((uint64_t)tiles * sizeof(uint4));
-    d_ctr.alloc(kPackCounters * 4);
+    d_bwt.alloc(raw_bytes, "the raw bwt");
+    d_occ.alloc(6 * n_chk, "the raw Occ arrays");
+    d_tiles.alloc(tiles, "the pack's tiles");
+    d_ctr.alloc(kPackCounters, "the pack's counters");
     uint32_t ctr[kPackCounters] = {0};
     ctr[kPackCtrForeignRow] = ctr[kPackCtrOccBadFirst] = 0xffffffffu;
     double t0 = now_ms();
     HIP_CHECK(hipMemcpy(d_bwt.p, hx.bwt.data(), n, hipMemcpyHostToDevice));
     for (int a = 0; a < 6; a++)
-        HIP_CHECK(hipMemcpy((uint64_t*)d_occ.p + a * n_chk, hx.occ[syms[a]].data(), n_chk * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_occ.p + a * n_chk, hx.occ[syms[a]].data(), n_chk * 8, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(d_ctr.p, ctr, sizeof ctr, hipMemcpyHostToDevice));
     copy_ms += now_ms() - t0;
 
     HIP_CHECK(hipEventRecord(ev.e[0], 0));
-    launch_pack_count(0, (const uint8_t*)d_bwt.p, n, n_blocks, tile, (uint4*)d_tiles.p, (uint32_t*)d_ctr.p);
+    launch_pack_count(0, d_bwt.p, n, n_blocks, tile, d_tiles.p, d_ctr.p);
     HIP_CHECK(hipEventRecord(ev.e[1], 0));
-    launch_pack_scan(0, (uint4*)d_tiles.p, tiles);
+    launch_pack_scan(0, d_tiles.p, tiles);
     HIP_CHECK(hipEventRecord(ev.e[2], 0));
-    launch_pack_blocks(0, (const uint8_t*)d_bwt.p, n, n_blocks, tile, (const uint4*)d_tiles.p, di.d_blocks);
+    launch_pack_blocks(0, d_bwt.p, n, n_blocks, tile, d_tiles.p, di.d_blocks);
     HIP_CHECK(hipEventRecord(ev.e[3], 0));
-    launch_pack_check_occ(0, di.d_blocks, n, hx.k, (uint32_t)n_chk, (const uint64_t*)d_occ.p, (uint32_t*)d_ctr.p);
+    launch_pack_check_occ(0, di.d_blocks, n, hx.k, (uint32_t)n_chk, d_occ.p, d_ctr.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ev.e[4], 0));
     HIP_CHECK(hipMemcpy(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));  // (after the kernels: the null stream orders them)
@@ -309,12 +290,12 @@ static uint64_t pack_on_device(const HostIndex& hx, const uint32_t n, const uint
 
     HIP_CHECK(hipMalloc((void**)&di.d_text, di.text_bytes));
     di.bytes += di.text_bytes;
-    d_raw_text.alloc(raw_bytes);
+    d_raw_text.alloc(raw_bytes, "the raw text");
     t0 = now_ms();
     HIP_CHECK(hipMemcpy(d_raw_text.p, hx.text.data(), n, hipMemcpyHostToDevice));
     copy_ms += now_ms() - t0;
     HIP_CHECK(hipEventRecord(ev.e[5], 0));
-    launch_pack_text(0, (const uint8_t*)d_raw_text.p, n, di.d_text, di.text_bytes);
+    launch_pack_text(0, d_raw_text.p, n, di.d_text, di.text_bytes);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ev.e[6], 0));
     HIP_CHECK(hipEventSynchronize(ev.e[6]));
@@ -344,7 +325,6 @@ std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint3
     // MTSV_DEV_PACK=device: uploads that do not pass the flag pack on the device too (read at every upload: an A/B switch)
     const char* pack_env = getenv("MTSV_DEV_PACK");
     const bool on_device = (flags & 4u /* MTSV_DEV_PACK_ON_DEVICE */) || (pack_env && !strcmp(pack_env, "device"));
-    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 
     std::vector<RankBlock> blocks;
     std::vector<uint8_t> codes;

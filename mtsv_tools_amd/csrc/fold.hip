@@ -19,12 +19,6 @@
 namespace mtsv {
 
 namespace {
-template <class T>
-T* fold_alloc(uint64_t count) {
-    T* p = nullptr;
-    HIP_CHECK(hipMalloc((void**)&p, std::max<uint64_t>(count, 1) * sizeof(T)));
-    return p;
-}
 void sort_unique(std::vector<uint32_t>& v) {
     std::sort(v.begin(), v.end());
     v.erase(std::unique(v.begin(), v.end()), v.end());
@@ -33,24 +27,15 @@ void sort_unique(std::vector<uint32_t>& v) {
 
 Fold::Fold(int device_, int grain_) : device(device_), grain(grain_) {
     if (grain != MTSV_GRAIN_TAXID && grain != MTSV_GRAIN_TAXID_GI && grain != MTSV_GRAIN_LONG) throw std::runtime_error("arg: bad assignment grain");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess) {
-        (void)hipGetLastError();
-        n_dev = 0;
-    }
-    if (device < 0 || device >= n_dev) throw std::runtime_error("device: no HIP device " + std::to_string(device) + " (" + std::to_string(n_dev) + " visible)");
-    if (const char* e = getenv("MTSV_FOLD_TILE")) {  // (tests: tile edges within reach of small lists)
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 2), kFoldTileMax);
-        tile = 2;
-        while (tile * 2 <= want) tile *= 2;
-    }
-    text_tile = TextFormatter::tile_from_env();
-    parse_tile = TextParser::tile_from_env();
-    lca_tile = LcaState::tile_from_env();
+    require_device(device);
+    tile = tile_from_env("MTSV_FOLD_TILE", kFoldTile, 2, kFoldTileMax);
+    text_tile = tile_from_env("MTSV_TEXT_TILE", kTextTile, 2, kTextTileMax);
+    parse_tile = tile_from_env("MTSV_PARSE_TILE", kParseTile, 64, kParseTileMax);
+    lca_tile = tile_from_env("MTSV_LCA_TILE", kLcaTile, 64, kLcaTileMax);
     trace = getenv("MTSV_TRACE") != nullptr;
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    ev.create();
 }
 
 Fold::~Fold() {
@@ -59,11 +44,6 @@ Fold::~Fold() {
     text.reset();
     parser.reset();
     lca_state.reset();
-    for (void* p : {(void*)d_rec[0], (void*)d_rec[1], (void*)d_in, (void*)d_tile_cnt, (void*)d_tile_off, (void*)d_tile_sums, (void*)d_flags,
-                    (void*)d_taxa, (void*)d_counts})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -73,14 +53,34 @@ void Fold::reset(uint64_t n_reads_) {
     taxa.clear();
 }
 
-void Fold::in_room(uint64_t n_b) {
-    if (n_b <= in_cap && d_in) return;
-    HIP_CHECK(hipStreamSynchronize(stream));
-    const uint64_t ncap = std::max<uint64_t>(n_b + n_b / 8, 1ull << 16);
-    uint8_t* p = fold_alloc<uint8_t>(ncap * rec_bytes());
-    if (d_in) (void)hipFree(d_in);
-    d_in = p;
-    in_cap = ncap;
+void Fold::in_room(uint64_t n_b) { d_in.room(stream, n_b * rec_bytes(), "the incoming records", (1ull << 16) * rec_bytes()); }
+
+Fold::Staged Fold::stage_write(uint64_t n_records, const char* what) {
+    Staged s;
+    if (n_records <= cap && d_rec[0].p) {
+        s.dst = d_rec[cur ^ 1].p;
+        return s;
+    }
+    const uint64_t ncap = std::min<uint64_t>(std::max<uint64_t>(std::max<uint64_t>(2 * cap, n_records), 1ull << 16), 0xffffffffull);
+    try {
+        for (auto& b : s.pair) b.alloc(ncap * rec_bytes(), what);
+    } catch (const std::runtime_error&) {
+        throw std::runtime_error(std::string("device: no memory for ") + what + " of " + std::to_string(ncap) + " records (two arrays)");
+    }
+    s.dst = s.pair[0].p;
+    s.cap = ncap;
+    return s;
+}
+
+void Fold::commit(Staged& s, uint64_t n_records) {
+    if (s.cap) {
+        for (int k = 0; k < 2; k++) d_rec[k].swap(s.pair[k]);
+        cur = 0;
+        cap = s.cap;
+    } else {
+        cur ^= 1;
+    }
+    n = n_records;
 }
 
 void Fold::fold_in(uint64_t n_b, std::vector<uint32_t>& new_taxa, float* device_ms) {
@@ -96,56 +96,21 @@ void Fold::fold_in(uint64_t n_b, std::vector<uint32_t>& new_taxa, float* device_
         return;
     }
     // ---- room; whatever fails here leaves the fold as it was ----
-    if (n_tot > cap || !d_rec[0]) {
-        const uint64_t ncap = std::min<uint64_t>(std::max<uint64_t>(std::max<uint64_t>(2 * cap, n_tot), 1ull << 16), 0xffffffffull);
-        uint8_t* a = fold_alloc<uint8_t>(ncap * rec);
-        uint8_t* b = nullptr;
-        if (hipMalloc((void**)&b, ncap * rec) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(a);
-            throw std::runtime_error("device: no memory for an accumulator of " + std::to_string(ncap) + " records (two arrays)");
-        }
-        if (n) {
-            const hipError_t e1 = hipMemcpyAsync(a, d_rec[cur], n * rec, hipMemcpyDeviceToDevice, stream);
-            const hipError_t e2 = hipStreamSynchronize(stream);
-            if (e1 != hipSuccess || e2 != hipSuccess) {
-                (void)hipFree(a);
-                (void)hipFree(b);
-                throw_hip(e1 != hipSuccess ? e1 : e2, "hipMemcpyAsync(accumulator)", __FILE__, __LINE__);
-            }
-        }
-        if (trace) fprintf(stderr, "[fold] accumulator grown from %llu to %llu records (two arrays of %llu bytes)\n", (unsigned long long)cap, (unsigned long long)ncap, (unsigned long long)(ncap * rec));
-        if (d_rec[0]) (void)hipFree(d_rec[0]);
-        if (d_rec[1]) (void)hipFree(d_rec[1]);
-        d_rec[0] = a;
-        d_rec[1] = b;
-        cur = 0;
-        cap = ncap;
-    }
+    Staged st = stage_write(n_tot, "an accumulator");
+    if (trace && st.cap) fprintf(stderr, "[fold] accumulator grown from %llu to %llu records (two arrays of %llu bytes)\n", (unsigned long long)cap, (unsigned long long)st.cap, (unsigned long long)(st.cap * rec));
     const uint32_t tiles = fold_tiles(n_tot, tile);
-    if (tiles > tiles_cap || !d_tile_cnt) {
-        HIP_CHECK(hipStreamSynchronize(stream));
-        for (void* p : {(void*)d_tile_cnt, (void*)d_tile_off, (void*)d_tile_sums})
-            if (p) (void)hipFree(p);
-        d_tile_cnt = d_tile_off = nullptr;
-        d_tile_sums = nullptr;
-        tiles_cap = 0;
-        const uint64_t tc = std::min<uint64_t>(std::max<uint64_t>(2ull * tiles, 1024), 0xffffffffull);
-        d_tile_cnt = fold_alloc<uint32_t>(tc);
-        d_tile_off = fold_alloc<uint32_t>(tc + 1);
-        sums_cap = (uint64_t)scan_tiles((uint32_t)tc) + 1;
-        d_tile_sums = fold_alloc<uint64_t>(sums_cap + 1);
-        tiles_cap = tc;
-    }
-    // ---- the fold: count, scan, write into the other array ----
+    d_tile_cnt.room(stream, tiles, "the tiles' survivors");
+    d_tile_off.room(stream, (uint64_t)tiles + 1, "the tiles' offsets");
+    d_tile_sums.room(stream, (uint64_t)scan_tiles(tiles) + 2, "the scan's sums");
+    sums_cap = d_tile_sums.cap - 1;  // (the total lies behind the sums)
+    // ---- the fold: count, scan, write into the staged array (a new pair is read from the old one: no copy) ----
     uint64_t total = 0;
-    uint8_t* out = d_rec[cur ^ 1];
     HIP_CHECK(hipEventRecord(ev[0], stream));
-    launch_fold_count(stream, grain, d_rec[cur], (uint32_t)n, d_in, (uint32_t)n_b, tile, d_tile_cnt);
-    launch_scan(stream, d_tile_cnt, tiles, d_tile_sums, d_tile_sums + sums_cap, d_tile_off);
-    launch_fold_write(stream, grain, d_rec[cur], (uint32_t)n, d_in, (uint32_t)n_b, tile, d_tile_off, out);
+    launch_fold_count(stream, grain, d_rec[cur].p, (uint32_t)n, d_in.p, (uint32_t)n_b, tile, d_tile_cnt.p);
+    launch_scan(stream, d_tile_cnt.p, tiles, d_tile_sums.p, d_tile_sums.p + sums_cap, d_tile_off.p);
+    launch_fold_write(stream, grain, d_rec[cur].p, (uint32_t)n, d_in.p, (uint32_t)n_b, tile, d_tile_off.p, st.dst);
     HIP_CHECK(hipEventRecord(ev[1], stream));
-    HIP_CHECK(hipMemcpyAsync(&total, d_tile_sums + sums_cap, sizeof total, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(&total, d_tile_sums.p + sums_cap, sizeof total, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     if (total > n_tot || total < std::max(n, n_b))
@@ -155,8 +120,7 @@ void Fold::fold_in(uint64_t n_b, std::vector<uint32_t>& new_taxa, float* device_
     if (trace)
         fprintf(stderr, "[fold] %llu + %llu records -> %llu in %u tiles of %u: %.3f ms\n", (unsigned long long)n, (unsigned long long)n_b, (unsigned long long)total,
                 tiles, tile, ms);
-    n = total;
-    cur ^= 1;
+    commit(st, total);
     taxa.swap(u);
     if (device_ms) *device_ms = ms;
 }
@@ -188,12 +152,12 @@ void Fold::add_run(Batch& src, float* device_ms) {
         uint64_t at = 0;
         for (const auto& sg : src.segments) {
             if (!sg.a_count) continue;
-            HIP_CHECK(hipMemcpyAsync(d_in + at * rec, sg.lane->d_assign + sg.a_offset * rec, sg.a_count * rec, hipMemcpyDeviceToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(d_in.p + at * rec, sg.lane->d_assign + sg.a_offset * rec, sg.a_count * rec, hipMemcpyDeviceToDevice, stream));
             at += sg.a_count;
         }
         if (from_records) {  // (a collector is the rare source: its gathered records come to the host once, for the word behind the 8-byte read)
             std::vector<uint8_t> h(n_b * rec);
-            HIP_CHECK(hipMemcpyAsync(h.data(), d_in, n_b * rec, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(h.data(), d_in.p, n_b * rec, hipMemcpyDeviceToHost, stream));
             HIP_CHECK(hipStreamSynchronize(stream));
             t.resize(n_b);
             for (uint64_t i = 0; i < n_b; i++) memcpy(&t[i], &h[i * rec + 8], 4);
@@ -213,7 +177,7 @@ void Fold::add_records(const void* records, uint64_t n_b, float* device_ms) {
     HIP_CHECK(hipSetDevice(device));
     if (n_b) {
         in_room(n_b);
-        HIP_CHECK(hipMemcpyAsync(d_in, records, n_b * rec_bytes(), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(d_in.p, records, n_b * rec_bytes(), hipMemcpyHostToDevice, stream));
     }
     fold_in(n_b, t, device_ms);
     HIP_CHECK(hipStreamSynchronize(stream));  // (the caller's array has been read)
@@ -228,7 +192,7 @@ void Fold::download(void** a, uint64_t* n_out, bool wide) {
     uint64_t pool_cap = 0;
     uint8_t* out = (uint8_t*)pinned_hits_alloc((n * rec + 31) / 32, &pool_cap);  // (the pool counts in 32-byte hits)
     if (n) {
-        const hipError_t e = hipMemcpy(out, d_rec[cur], n * rec, hipMemcpyDeviceToHost);
+        const hipError_t e = hipMemcpy(out, d_rec[cur].p, n * rec, hipMemcpyDeviceToHost);
         if (e != hipSuccess) {
             pinned_hits_release(out);
             throw_hip(e, "hipMemcpy(fold records)", __FILE__, __LINE__);
@@ -245,18 +209,12 @@ void Fold::match_flags(std::vector<uint64_t>& words, uint64_t* n_reads_out, uint
     *n_matched = 0;
     if (!n) return;
     HIP_CHECK(hipSetDevice(device));
-    if (nw + 2 > flags_cap || !d_flags) {
-        HIP_CHECK(hipStreamSynchronize(stream));
-        uint64_t* p = fold_alloc<uint64_t>(nw + 2);
-        if (d_flags) (void)hipFree(d_flags);
-        d_flags = p;
-        flags_cap = nw + 2;
-    }
+    d_flags.room(stream, nw + 2, "the match flags");
     uint64_t ctr[2] = {0, 0};
-    HIP_CHECK(hipMemsetAsync(d_flags, 0, (nw + 2) * 8, stream));
-    launch_fold_flags(stream, grain, d_rec[cur], (uint32_t)n, n_reads, d_flags, d_flags + nw);
-    HIP_CHECK(hipMemcpyAsync(words.data(), d_flags, nw * 8, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync(ctr, d_flags + nw, sizeof ctr, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemsetAsync(d_flags.p, 0, (nw + 2) * 8, stream));
+    launch_fold_flags(stream, grain, d_rec[cur].p, (uint32_t)n, n_reads, d_flags.p, d_flags.p + nw);
+    HIP_CHECK(hipMemcpyAsync(words.data(), d_flags.p, nw * 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(ctr, d_flags.p + nw, sizeof ctr, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     if (ctr[1]) throw std::runtime_error("internal: " + std::to_string(ctr[1]) + " reads of the fold are numbered at or above its " + std::to_string(n_reads) + " reads");
@@ -270,28 +228,15 @@ void Fold::taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_read
     if (!n) return;
     HIP_CHECK(hipSetDevice(device));
     const uint64_t n_taxa = taxa.size(), n_cnt = 4 * n_taxa + 2;
-    if (n_taxa > taxa_cap || !d_counts) {
-        HIP_CHECK(hipStreamSynchronize(stream));
-        uint32_t* t = fold_alloc<uint32_t>(n_taxa);
-        uint64_t* c = nullptr;
-        if (hipMalloc((void**)&c, n_cnt * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(t);
-            throw std::runtime_error("device: no memory for the counters of " + std::to_string(n_taxa) + " taxa");
-        }
-        if (d_taxa) (void)hipFree(d_taxa);
-        if (d_counts) (void)hipFree(d_counts);
-        d_taxa = t;
-        d_counts = c;
-        taxa_cap = n_taxa;
-    }
+    d_taxa.room(stream, n_taxa, "the TaxIDs");
+    d_counts.room(stream, n_cnt, "the taxa's counters");
     std::vector<uint64_t> c(n_cnt);
-    if (n_taxa) HIP_CHECK(hipMemcpyAsync(d_taxa, taxa.data(), n_taxa * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemsetAsync(d_counts, 0, n_cnt * 8, stream));
+    if (n_taxa) HIP_CHECK(hipMemcpyAsync(d_taxa.p, taxa.data(), n_taxa * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemsetAsync(d_counts.p, 0, n_cnt * 8, stream));
     HIP_CHECK(hipEventRecord(ev[0], stream));
-    launch_fold_report(stream, grain, d_rec[cur], (uint32_t)n, d_taxa, (uint32_t)n_taxa, d_counts);
+    launch_fold_report(stream, grain, d_rec[cur].p, (uint32_t)n, d_taxa.p, (uint32_t)n_taxa, d_counts.p);
     HIP_CHECK(hipEventRecord(ev[1], stream));
-    HIP_CHECK(hipMemcpyAsync(c.data(), d_counts, n_cnt * 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(c.data(), d_counts.p, n_cnt * 8, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     if (c[n_cnt - 1])

@@ -21,22 +21,19 @@ struct Fold {
     uint32_t tile = kFoldTile;  // MTSV_FOLD_TILE, read at creation (tests)
     bool trace = false;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    uint8_t* d_rec[2] = {nullptr, nullptr};  // cap records each; they grow together
+    DevEvents<2> ev;
+    DevBuf<uint8_t> d_rec[2];  // cap records each; they grow together (stage_write, commit)
     uint64_t cap = 0, n = 0;
     int cur = 0;
-    uint8_t* d_in = nullptr;  // the incoming list: a run's records gathered from its lanes' arrays, or uploaded ones
-    uint64_t in_cap = 0;
-    uint32_t *d_tile_cnt = nullptr, *d_tile_off = nullptr;
-    uint64_t* d_tile_sums = nullptr;  // the scan's tile sums, then its total
-    uint64_t tiles_cap = 0, sums_cap = 0;
+    DevBuf<uint8_t> d_in;  // the incoming list: a run's records gathered from its lanes' arrays, or uploaded ones
+    DevBuf<uint32_t> d_tile_cnt, d_tile_off;
+    DevBuf<uint64_t> d_tile_sums;  // the scan's tile sums, then (at sums_cap) its total
+    uint64_t sums_cap = 0;
     uint64_t n_reads = 0;             // the caller's numbering (reset)
     std::vector<uint32_t> taxa;       // the TaxIDs of every source folded so far, ascending
-    uint64_t* d_flags = nullptr;      // flag words, then two counters
-    uint64_t flags_cap = 0;
-    uint32_t* d_taxa = nullptr;
-    uint64_t* d_counts = nullptr;
-    uint64_t taxa_cap = 0;
+    DevBuf<uint64_t> d_flags;         // flag words, then two counters
+    DevBuf<uint32_t> d_taxa;
+    DevBuf<uint64_t> d_counts;
     uint32_t text_tile = kTextTile;       // MTSV_TEXT_TILE, read at creation (tests)
     std::unique_ptr<TextFormatter> text;  // created by the first format_text
     uint32_t parse_tile = kParseTile;     // MTSV_PARSE_TILE, read at creation (tests)
@@ -66,6 +63,19 @@ struct Fold {
     // one), which becomes as after reset(n_reads) with those records; the clade rows in preorder (rows may be null); this
     // fold is not changed
     void lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<mtsv_clade_stats>* rows, uint64_t* total_reads, float* device_ms);
+
+    // A write of a whole new record list (fold_in, lca, DupMap::expand) is staged: dst is the array that is not current, or,
+    // when that is too small, the first of a new pair, which the fold takes only with commit.  A Staged that is not
+    // committed frees its pair; one that is frees the pair the fold had.
+    struct Staged {
+        uint8_t* dst = nullptr;
+        DevBuf<uint8_t> pair[2];
+        uint64_t cap = 0;  // of the new pair, in records; 0: dst is the fold's other array
+    };
+    // room for n_records; throws "device: no memory for <what> of ... records (two arrays)" and leaves the fold as it was
+    Staged stage_write(uint64_t n_records, const char* what);
+    // the fold holds the n_records written at s.dst: cannot fail (the caller has waited for the writes)
+    void commit(Staged& s, uint64_t n_records);
 
    private:
     void in_room(uint64_t n_b);

@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "dev_index.hpp"
+#include "dev_mem.hpp"
 #include "mgindex.hpp"
 
 namespace mtsv {
@@ -87,16 +87,6 @@ struct MaxOp {
 
 inline uint32_t grid_for(uint64_t n) { return (uint32_t)((n + 255) / 256); }
 
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(uint64_t bytes) { HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16)); }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    template <class T>
-    T* as() const { return (T*)p; }
-};
-
 }  // namespace
 
 // text: normalised "ACGTN...$", n symbols.  Fills bwt (n bytes), sample (ceil(n/s) entries) and the
@@ -107,43 +97,49 @@ void gpu_suffix_sort(const uint8_t* text, uint32_t n, uint64_t s, int device, st
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         throw std::runtime_error("device: no HIP device " + std::to_string(device) + " for the index build");
     HIP_CHECK(hipSetDevice(device));
-    DevBuf d_text(n), d_keys_a((uint64_t)n * 8), d_keys_b((uint64_t)n * 8), d_vals_a((uint64_t)n * 4), d_vals_b((uint64_t)n * 4),
-        d_rank((uint64_t)n * 4), d_head((uint64_t)n * 4), d_cnt(16);
+    DevBuf<uint8_t> d_text, d_tmp;  // (sized exactly: the sort fills the device for a large index)
+    DevBuf<uint64_t> d_keys_a, d_keys_b;
+    DevBuf<unsigned long long> d_cnt;  // the groups of a round; at the end, as 32 bits, the sentinel's row
+    DevBuf<uint32_t> d_vals_a, d_vals_b, d_rank, d_head;
+    d_text.alloc(n, "the text");
+    for (auto* b : {&d_keys_a, &d_keys_b}) b->alloc(n, "the sort keys");
+    for (auto* b : {&d_vals_a, &d_vals_b, &d_rank, &d_head}) b->alloc(n, "the suffixes and their ranks");
+    d_cnt.alloc(2, "the counters");
     HIP_CHECK(hipMemcpy(d_text.p, text, n, hipMemcpyHostToDevice));
     size_t tmp_sort = 0, tmp_scan = 0;
-    rocprim::double_buffer<uint64_t> kb(d_keys_a.as<uint64_t>(), d_keys_b.as<uint64_t>());
-    rocprim::double_buffer<uint32_t> vb(d_vals_a.as<uint32_t>(), d_vals_b.as<uint32_t>());
+    rocprim::double_buffer<uint64_t> kb(d_keys_a.p, d_keys_b.p);
+    rocprim::double_buffer<uint32_t> vb(d_vals_a.p, d_vals_b.p);
     HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_sort, kb, vb, (size_t)n, 0, 64));
-    HIP_CHECK(rocprim::inclusive_scan(nullptr, tmp_scan, d_head.as<uint32_t>(), d_vals_b.as<uint32_t>(), (size_t)n, MaxOp()));
-    DevBuf d_tmp(std::max(tmp_sort, tmp_scan));
+    HIP_CHECK(rocprim::inclusive_scan(nullptr, tmp_scan, d_head.p, d_vals_b.p, (size_t)n, MaxOp()));
+    d_tmp.alloc(std::max(tmp_sort, tmp_scan), "the sort's scratch");
 
-    hipLaunchKernelGGL(k_key0, dim3(grid_for(n)), dim3(256), 0, 0, d_text.as<uint8_t>(), n, kb.current(), vb.current());
+    hipLaunchKernelGGL(k_key0, dim3(grid_for(n)), dim3(256), 0, 0, d_text.p, n, kb.current(), vb.current());
     uint32_t h = 21;
     for (int round = 0;; round++) {
         size_t t1 = tmp_sort;
         // round 0 keys use 63 bits; later rounds 64
         HIP_CHECK(rocprim::radix_sort_pairs(d_tmp.p, t1, kb, vb, (size_t)n, 0, round == 0 ? 63 : 64));
         HIP_CHECK(hipMemset(d_cnt.p, 0, 8));
-        hipLaunchKernelGGL(k_heads, dim3(grid_for(n)), dim3(256), 0, 0, kb.current(), n, d_head.as<uint32_t>(),
-                           d_cnt.as<unsigned long long>());
+        hipLaunchKernelGGL(k_heads, dim3(grid_for(n)), dim3(256), 0, 0, kb.current(), n, d_head.p,
+                           d_cnt.p);
         unsigned long long groups = 0;
         HIP_CHECK(hipMemcpy(&groups, d_cnt.p, 8, hipMemcpyDeviceToHost));
         if (groups == n) break;  // every suffix distinguished: vb.current() is the suffix array
         if (round > 40) throw std::runtime_error("device: suffix sort did not converge");
         size_t t2 = tmp_scan;
         uint32_t* group_start = vb.alternate();  // free after the sort
-        HIP_CHECK(rocprim::inclusive_scan(d_tmp.p, t2, d_head.as<uint32_t>(), group_start, (size_t)n, MaxOp()));
-        hipLaunchKernelGGL(k_scatter_rank, dim3(grid_for(n)), dim3(256), 0, 0, vb.current(), group_start, n, d_rank.as<uint32_t>());
-        hipLaunchKernelGGL(k_key_h, dim3(grid_for(n)), dim3(256), 0, 0, d_rank.as<uint32_t>(), n, h, kb.current(), vb.current());
+        HIP_CHECK(rocprim::inclusive_scan(d_tmp.p, t2, d_head.p, group_start, (size_t)n, MaxOp()));
+        hipLaunchKernelGGL(k_scatter_rank, dim3(grid_for(n)), dim3(256), 0, 0, vb.current(), group_start, n, d_rank.p);
+        hipLaunchKernelGGL(k_key_h, dim3(grid_for(n)), dim3(256), 0, 0, d_rank.p, n, h, kb.current(), vb.current());
         h = h > 0x40000000u ? 0x80000000u : h * 2;
     }
     HIP_CHECK(hipGetLastError());
     const uint32_t* sa = vb.current();
     // BWT into the (now free) alternate key buffer, samples into the head buffer
     uint8_t* d_bwt = (uint8_t*)kb.alternate();
-    uint32_t* d_sample = d_head.as<uint32_t>();
+    uint32_t* d_sample = d_head.p;
     HIP_CHECK(hipMemset(d_cnt.p, 0xff, 4));
-    hipLaunchKernelGGL(k_bwt, dim3(grid_for(n)), dim3(256), 0, 0, d_text.as<uint8_t>(), sa, n, d_bwt, d_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_bwt, dim3(grid_for(n)), dim3(256), 0, 0, d_text.p, sa, n, d_bwt, (uint32_t*)d_cnt.p);
     const uint64_t ns = ((uint64_t)n + s - 1) / s;
     if (s <= 0xffffffffull)
         hipLaunchKernelGGL(k_sample, dim3(grid_for(ns)), dim3(256), 0, 0, sa, n, (uint32_t)s, d_sample);

@@ -233,19 +233,13 @@ __global__ __launch_bounds__(kFoldThreads) void k_fold(const uint32_t* __restric
 }
 
 template <uint32_t W>
-__device__ inline uint64_t fold_read_of(const uint32_t* __restrict__ rec, uint64_t i) {
-    const uint2 v = *reinterpret_cast<const uint2*>(rec + i * W);
-    return (uint64_t)v.x | (uint64_t)v.y << 32;
-}
-
-template <uint32_t W>
 __global__ __launch_bounds__(kFoldThreads) void k_fold_flags(const uint32_t* __restrict__ rec, uint32_t n, uint64_t n_reads,
                                                              unsigned long long* __restrict__ words, unsigned long long* __restrict__ ctr) {
     const uint64_t i = (uint64_t)blockIdx.x * kFoldThreads + threadIdx.x;
     bool head = false, beyond = false;
     if (i < n) {
-        const uint64_t read = fold_read_of<W>(rec, i);
-        head = i == 0 || fold_read_of<W>(rec, i - 1) != read;
+        const uint64_t read = rec_read_of<W>(rec, i);
+        head = i == 0 || rec_read_of<W>(rec, i - 1) != read;
         beyond = head && read >= n_reads;
         head = head && !beyond;
         // (other heads of the wavefront may share the word)
@@ -258,17 +252,6 @@ __global__ __launch_bounds__(kFoldThreads) void k_fold_flags(const uint32_t* __r
     }
 }
 
-// place of t in the ascending list taxa (n_taxa when it is not there)
-__device__ inline uint32_t fold_slot(const uint32_t* __restrict__ taxa, uint32_t n_taxa, uint32_t t) {
-    uint32_t lo = 0, hi = n_taxa;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (taxa[mid] < t) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n_taxa && taxa[lo] == t ? lo : n_taxa;
-}
-
 // counts: 4 per taxon (only_hit, only_best, tied_best, not_best), then the reads with a record, then the (read, TaxID) pairs
 // whose TaxID is not in the list (none, unless the caller's list is incomplete: the host makes an error of them)
 template <uint32_t W>
@@ -278,13 +261,13 @@ __global__ __launch_bounds__(kFoldThreads) void k_fold_report(const uint32_t* __
     const uint64_t i = (uint64_t)blockIdx.x * kFoldThreads + threadIdx.x;
     bool head = false;
     if (i < n) {
-        const uint64_t read = fold_read_of<W>(rec, i);
-        head = i == 0 || fold_read_of<W>(rec, i - 1) != read;
+        const uint64_t read = rec_read_of<W>(rec, i);
+        head = i == 0 || rec_read_of<W>(rec, i - 1) != read;
         if (head) {
             // first walk: the read's smallest edit m, its distinct TaxIDs, and how many of them are at m
             uint64_t end = i;
             uint32_t m = 0xffffffffu, nd = 0, best = 0, cur = 0, cur_min = 0;
-            for (; end < n && fold_read_of<W>(rec, end) == read; end++) {
+            for (; end < n && rec_read_of<W>(rec, end) == read; end++) {
                 const uint32_t t = rec[end * W + 2], e = rec[end * W + kEdit];
                 if (end == i || t != cur) {
                     if (end != i) {
@@ -306,7 +289,7 @@ __global__ __launch_bounds__(kFoldThreads) void k_fold_report(const uint32_t* __
                 uint32_t e = rec[j * W + kEdit];
                 for (j++; j < end && rec[j * W + 2] == t; j++) e = min(e, rec[j * W + kEdit]);
                 const uint32_t cat = nd == 1 ? 0u : e != m ? 3u : best == 1 ? 1u : 2u;
-                const uint32_t slot = fold_slot(taxa, n_taxa, t);
+                const uint32_t slot = find_u32(taxa, n_taxa, t);
                 atomicAdd(slot < n_taxa ? &counts[4ull * slot + cat] : &counts[4ull * n_taxa + 1], 1ull);
             }
         }

@@ -40,12 +40,6 @@ constexpr uint32_t kLcaWaves = kLcaThreads / kWave;
 constexpr uint32_t kLcaStretchMax = kLcaTileMax / kLcaThreads;  // records per lane at the largest tile
 static_assert(kLcaStretchMax <= 32, "the heads of a lane's stretch are kept as bits of one word");
 
-template <uint32_t W>
-__device__ inline uint64_t lca_read_of(const uint32_t* __restrict__ rec, uint64_t i) {
-    const uint2 v = *reinterpret_cast<const uint2*>(rec + i * W);
-    return (uint64_t)v.x | (uint64_t)v.y << 32;
-}
-
 // What a lane knows of its tile: its stretch of positions [p0, p1), which of them are heads (bit k: position p0 + k), the heads
 // of the tile before p0, the heads of the tile
 struct LcaLane {
@@ -66,9 +60,9 @@ __device__ inline LcaLane lca_lane(const uint32_t* __restrict__ rec, uint32_t n,
     t.heads = 0;
     if (t.p0 < t.p1) {
         const uint64_t first = t.i0 + t.p0;
-        uint64_t prev = first ? lca_read_of<W>(rec, first - 1) : 0;
+        uint64_t prev = first ? rec_read_of<W>(rec, first - 1) : 0;
         for (uint32_t p = t.p0; p < t.p1; p++) {
-            const uint64_t read = lca_read_of<W>(rec, t.i0 + p);
+            const uint64_t read = rec_read_of<W>(rec, t.i0 + p);
             if (t.i0 + p == 0 || read != prev) t.heads |= 1u << (p - t.p0);
             prev = read;
         }
@@ -124,7 +118,7 @@ __device__ inline void lca_lds_reduce(uint32_t* cell, bool act, uint32_t r, uint
 template <uint32_t W>
 __device__ inline bool lca_goes_on(const uint32_t* __restrict__ rec, uint32_t n, const LcaLane& t) {
     const uint64_t next = t.i0 + t.nt;
-    return next < n && lca_read_of<W>(rec, next) == lca_read_of<W>(rec, next - 1);
+    return next < n && rec_read_of<W>(rec, next) == rec_read_of<W>(rec, next - 1);
 }
 
 template <uint32_t W>
@@ -168,17 +162,6 @@ __global__ __launch_bounds__(kLcaThreads) void k_lca_min(const uint32_t* __restr
     }
 }
 
-// place of x in the ascending list u (n when it is not there)
-__device__ inline uint32_t lca_find(const uint32_t* __restrict__ u, uint32_t n, uint32_t x) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (u[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && u[lo] == x ? lo : n;
-}
-
 template <uint32_t W>
 __global__ __launch_bounds__(kLcaThreads) void k_lca_span(const uint32_t* __restrict__ rec, uint32_t n, uint32_t tile, const uint32_t* __restrict__ tile_off,
                                                          uint32_t n_slots, const uint32_t* __restrict__ m, uint32_t slack,
@@ -207,7 +190,7 @@ __global__ __launch_bounds__(kLcaThreads) void k_lca_span(const uint32_t* __rest
                 act = rec[i * W + W - 1] <= bound;
             }
             if (act) {
-                const uint32_t j = lca_find(u_tax, n_union, rec[i * W + 2]);
+                const uint32_t j = find_u32(u_tax, n_union, rec[i * W + 2]);
                 if (j < n_union) node = u_node[j];
                 else {
                     n_missing++;

@@ -43,17 +43,6 @@ struct ReportLds {
 // (tax_id, edit) of a hit
 __device__ inline uint2 hit_te(const DevHit* __restrict__ hits, uint64_t i) { return make_uint2(hits[i].tax_id, hits[i].edit); }
 
-// dense slot of a TaxID: its place in the sorted list of the index's TaxIDs (n_taxa if it is not there)
-__device__ inline uint32_t slot_of_taxon(const uint32_t* __restrict__ taxa, uint32_t n_taxa, uint32_t t) {
-    uint32_t lo = 0, hi = n_taxa;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (taxa[mid] < t) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n_taxa && taxa[lo] == t ? lo : n_taxa;
-}
-
 template <bool DENSE>
 __device__ inline void lds_add(const ReportLds& s, unsigned long long* __restrict__ counts, uint32_t key, uint32_t c) {
     if (DENSE) {
@@ -78,7 +67,7 @@ __device__ inline void lds_add(const ReportLds& s, unsigned long long* __restric
 template <bool DENSE>
 __device__ inline void count_one(const ReportLds& s, unsigned long long* __restrict__ counts, const uint32_t* __restrict__ taxa,
                                  uint32_t n_taxa, uint32_t tax_id, uint32_t cat) {
-    const uint32_t slot = slot_of_taxon(taxa, n_taxa, tax_id);
+    const uint32_t slot = find_u32(taxa, n_taxa, tax_id);  // (its dense slot: the place among the index's TaxIDs)
     if (slot >= n_taxa) return;  // (cannot happen: every hit's TaxID comes from the index's bins)
     const uint32_t key = slot * 4 + cat;
     const uint32_t first = __builtin_amdgcn_readfirstlane(key);

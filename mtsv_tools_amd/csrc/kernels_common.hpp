@@ -1,5 +1,6 @@
 // kernels_common.hpp -- device helpers shared by the kernel files of the hot path (k_seed.hip: normalise, search,
-// thin, expand, locate; k_coalesce.hip; k_verify.hip: SW prefilter, edit distance, selection, gather; k_report.hip).
+// thin, expand, locate; k_coalesce.hip; k_verify.hip: SW prefilter, edit distance, selection, gather; k_report.hip),
+// and the two that k_report.hip, k_fold.hip and k_lca.hip share: find_u32, rec_read_of.
 #pragma once
 #include <cstdlib>
 #include <stdexcept>
@@ -41,6 +42,24 @@ __device__ inline int row_sum16(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);  // row_half_mirror
     v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);  // row_mirror
     return v;
+}
+
+// place of x in the ascending list `sorted` (n when it is not there)
+__device__ inline uint32_t find_u32(const uint32_t* __restrict__ sorted, uint32_t n, uint32_t x) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (sorted[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && sorted[lo] == x ? lo : n;
+}
+
+// the 64-bit read of assignment record i of W words (8-byte aligned records: k_text.hip's are not, and it has its own)
+template <uint32_t W>
+__device__ inline uint64_t rec_read_of(const uint32_t* __restrict__ rec, uint64_t i) {
+    const uint2 v = *reinterpret_cast<const uint2*>(rec + i * W);
+    return (uint64_t)v.x | (uint64_t)v.y << 32;
 }
 
 }  // namespace

@@ -2,7 +2,6 @@
 // five steps of k_lca.hip over the fold's records.  What comes down is counters and two words per node of the tree; the
 // records of the reads' LCAs stay in HBM, in the output fold.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <iterator>
@@ -13,25 +12,6 @@
 #include "lca.hpp"
 
 namespace mtsv {
-
-namespace {
-// p[0 .. want) of device memory (what it held is lost); nothing changes when the allocation fails
-template <class T>
-void lca_room(hipStream_t stream, T*& p, uint64_t& cap, uint64_t want, const char* what) {
-    if (want <= cap && p) return;
-    HIP_CHECK(hipStreamSynchronize(stream));
-    const uint64_t ncap = std::max<uint64_t>(want + want / 8, 1024);
-    T* q = nullptr;
-    if (hipMalloc((void**)&q, ncap * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        throw std::runtime_error(std::string("device: no memory for ") + what + " (" + std::to_string(ncap * sizeof(T)) + " bytes)");
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = ncap;
-}
-double lca_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-}  // namespace
 
 LcaTree LcaTree::build(const Taxonomy& tx, const std::vector<uint32_t>& taxa) {
     // ---- the TaxIDs of the tree below the super-root: the union and, level by level, the parents not met yet ----
@@ -112,29 +92,15 @@ LcaTree LcaTree::build(const Taxonomy& tx, const std::vector<uint32_t>& taxa) {
     return T;
 }
 
-uint32_t LcaState::tile_from_env() {
-    uint32_t tile = kLcaTile;
-    if (const char* e = getenv("MTSV_LCA_TILE")) {  // (tests: tile edges within reach of short lists)
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 64), kLcaTileMax);
-        tile = 64;
-        while (tile * 2 <= want) tile *= 2;
-    }
-    return tile;
-}
-
 LcaState::LcaState(int device_, hipStream_t stream_) : device(device_), stream(stream_) {
     timing = getenv("MTSV_LCA_TIMING") != nullptr;
     HIP_CHECK(hipSetDevice(device));
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    ev.create();
 }
 
 LcaState::~LcaState() {
     if (hipSetDevice(device) != hipSuccess) (void)hipGetLastError();
     if (stream) (void)hipStreamSynchronize(stream);
-    for (void* p : {(void*)d_tree, (void*)d_tile_cnt, (void*)d_tile_off, (void*)d_sums, (void*)d_ctr, (void*)d_slot, (void*)d_node, (void*)d_out})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
 }
 
 void Fold::lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<mtsv_clade_stats>* rows, uint64_t* total_reads, float* device_ms) {
@@ -152,7 +118,7 @@ void Fold::lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<m
     if (!lca_state) lca_state.reset(new LcaState(device, stream));
     LcaState& L = *lca_state;
     // ---- the device tree: only when the union or the taxonomy changed ----
-    const double t0 = L.timing ? lca_now() : 0;
+    const double t0 = L.timing ? now_ms() : 0;
     const bool rebuild = L.tree_serial != tx.serial || L.tree_taxa != taxa;
     if (rebuild) {
         LcaTree T = LcaTree::build(tx, taxa);
@@ -161,8 +127,8 @@ void Fold::lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<m
         img.reserve(3 * N + 2 * U);
         for (const auto* v : {&T.parent, &T.last, &T.tax, &T.u_tax, &T.u_node}) img.insert(img.end(), v->begin(), v->end());
         L.tree_serial = 0;  // (the device's copy is being replaced)
-        lca_room(stream, L.d_tree, L.tree_cap, img.size(), "the device tree");
-        HIP_CHECK(hipMemcpyAsync(L.d_tree, img.data(), img.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        L.d_tree.room(stream, img.size(), "the device tree");
+        HIP_CHECK(hipMemcpyAsync(L.d_tree.p, img.data(), img.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         L.tree = std::move(T);
         L.tree_taxa = taxa;
@@ -170,20 +136,20 @@ void Fold::lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<m
     }
     const LcaTree& T = L.tree;
     const uint32_t N = T.nodes(), U = (uint32_t)T.u_tax.size();
-    const uint32_t *d_parent = L.d_tree, *d_last = d_parent + N, *d_tax = d_last + N, *d_u_tax = d_tax + N, *d_u_node = d_u_tax + U;
-    const double t1 = L.timing ? lca_now() : 0;
+    const uint32_t *d_parent = L.d_tree.p, *d_last = d_parent + N, *d_tax = d_last + N, *d_u_tax = d_tax + N, *d_u_node = d_u_tax + U;
+    const double t1 = L.timing ? now_ms() : 0;
     // ---- the reads with a record ----
     const uint32_t tiles = lca_tiles(n, lca_tile);
-    lca_room(stream, L.d_tile_cnt, L.cnt_cap, tiles, "the tiles' heads");
-    lca_room(stream, L.d_tile_off, L.off_cap, (uint64_t)tiles + 1, "the tiles' offsets");
-    lca_room(stream, L.d_sums, L.sums_cap, (uint64_t)std::max(scan_tiles(tiles), scan_tiles(N)) + 1, "the scans' sums");
-    lca_room(stream, L.d_ctr, L.ctr_cap, kLcaCounters + 2, "the counters");
-    lca_room(stream, L.d_node, L.node_cap, 3ull * N + 1, "the nodes' counts");
-    uint64_t* d_n_slots = L.d_ctr + kLcaCounters;
-    HIP_CHECK(hipMemsetAsync(L.d_ctr, 0, (kLcaCounters + 2) * sizeof(uint64_t), stream));
+    L.d_tile_cnt.room(stream, tiles, "the tiles' heads");
+    L.d_tile_off.room(stream, (uint64_t)tiles + 1, "the tiles' offsets");
+    L.d_sums.room(stream, (uint64_t)std::max(scan_tiles(tiles), scan_tiles(N)) + 1, "the scans' sums");
+    L.d_ctr.room(stream, kLcaCounters + 2, "the counters");
+    L.d_node.room(stream, 3ull * N + 1, "the nodes' counts");
+    uint64_t* d_n_slots = L.d_ctr.p + kLcaCounters;
+    HIP_CHECK(hipMemsetAsync(L.d_ctr.p, 0, (kLcaCounters + 2) * sizeof(uint64_t), stream));
     HIP_CHECK(hipEventRecord(L.ev[0], stream));
-    launch_lca_heads(stream, grain, d_rec[cur], (uint32_t)n, lca_tile, L.d_tile_cnt);
-    launch_scan(stream, L.d_tile_cnt, tiles, L.d_sums, d_n_slots, L.d_tile_off);
+    launch_lca_heads(stream, grain, d_rec[cur].p, (uint32_t)n, lca_tile, L.d_tile_cnt.p);
+    launch_scan(stream, L.d_tile_cnt.p, tiles, L.d_sums.p, d_n_slots, L.d_tile_off.p);
     HIP_CHECK(hipEventRecord(L.ev[1], stream));
     uint64_t R = 0;
     HIP_CHECK(hipMemcpyAsync(&R, d_n_slots, sizeof R, hipMemcpyDeviceToHost, stream));
@@ -191,80 +157,49 @@ void Fold::lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<m
     HIP_CHECK(hipGetLastError());
     if (!R || R > n) throw std::runtime_error("internal: " + std::to_string(n) + " records of " + std::to_string(R) + " reads");
     // ---- room for one record per read: the output fold's other array, a new pair when it is too small, or the call's own ----
-    lca_room(stream, L.d_slot, L.slot_cap, 3 * R, "the reads' spans");
-    uint8_t *grown_a = nullptr, *grown_b = nullptr, *dst = nullptr;
-    uint64_t grown_cap = 0;
-    if (!out) {
-        lca_room(stream, L.d_out, L.out_cap, R * sizeof(mtsv_assignment), "the reads' records");
-        dst = L.d_out;
-    } else if (R > out->cap || !out->d_rec[0]) {
-        grown_cap = std::min<uint64_t>(std::max<uint64_t>(R, 1ull << 16), 0xffffffffull);
-        const bool ok_a = hipMalloc((void**)&grown_a, grown_cap * sizeof(mtsv_assignment)) == hipSuccess;
-        const bool ok_b = ok_a && hipMalloc((void**)&grown_b, grown_cap * sizeof(mtsv_assignment)) == hipSuccess;
-        if (!ok_b) {
-            (void)hipGetLastError();
-            if (grown_a) (void)hipFree(grown_a);
-            throw std::runtime_error("device: no memory for an output fold of " + std::to_string(grown_cap) + " records (two arrays)");
-        }
-        dst = grown_a;
-    } else {
-        dst = out->d_rec[out->cur ^ 1];
-    }
+    L.d_slot.room(stream, 3 * R, "the reads' spans");
+    if (!out) L.d_out.room(stream, R * sizeof(mtsv_assignment), "the reads' records");
+    Staged st = out ? out->stage_write(R, "an output fold") : Staged{};  // (an error below frees a pair it holds: the output fold stays as it was)
+    uint8_t* dst = out ? st.dst : L.d_out.p;
     std::vector<uint32_t> direct(N), clade(N);
     uint64_t ctr[kLcaCounters + 2] = {};
     float ms[5] = {0, 0, 0, 0, 0};
     double t2 = 0, t3 = 0;
-    try {
-        uint32_t *d_m = L.d_slot, *d_lo = d_m + R, *d_hi = d_lo + R;
-        uint32_t *d_direct = L.d_node, *d_prefix = d_direct + N, *d_clade = d_prefix + N + 1;
-        HIP_CHECK(hipMemsetAsync(d_m, 0xff, 2 * R * sizeof(uint32_t), stream));  // (m and lo: all ones)
-        HIP_CHECK(hipMemsetAsync(d_hi, 0, R * sizeof(uint32_t), stream));
-        HIP_CHECK(hipMemsetAsync(d_direct, 0, (size_t)N * sizeof(uint32_t), stream));
-        HIP_CHECK(hipEventRecord(L.ev[2], stream));
-        launch_lca_min(stream, grain, d_rec[cur], (uint32_t)n, lca_tile, L.d_tile_off, (uint32_t)R, d_m, dst);
-        HIP_CHECK(hipEventRecord(L.ev[3], stream));
-        launch_lca_span(stream, grain, d_rec[cur], (uint32_t)n, lca_tile, L.d_tile_off, (uint32_t)R, d_m, edit_slack, d_u_tax, d_u_node, U, d_lo, d_hi,
-                        L.d_ctr);
-        HIP_CHECK(hipEventRecord(L.ev[4], stream));
-        launch_lca_walk(stream, (uint32_t)R, N, T.max_depth, d_lo, d_hi, d_m, d_parent, d_last, d_tax, dst, d_direct, L.d_ctr);
-        HIP_CHECK(hipEventRecord(L.ev[5], stream));
-        launch_scan(stream, d_direct, N, L.d_sums, d_n_slots + 1, d_prefix);
-        launch_lca_clade(stream, N, d_last, d_prefix, d_clade);
-        HIP_CHECK(hipEventRecord(L.ev[6], stream));
-        if (L.timing) HIP_CHECK(hipStreamSynchronize(stream));
-        t2 = L.timing ? lca_now() : 0;
-        HIP_CHECK(hipMemcpyAsync(ctr, L.d_ctr, sizeof ctr, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipMemcpyAsync(direct.data(), d_direct, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipMemcpyAsync(clade.data(), d_clade, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipGetLastError());
-        t3 = L.timing ? lca_now() : 0;
-        if (ctr[kLcaCtrMissing])
-            throw std::runtime_error("internal: " + std::to_string(ctr[kLcaCtrMissing]) + " records of the fold carry a TaxID that is not in its union of " + std::to_string(U) + " TaxIDs");
-        if (ctr[kLcaCtrWalk])
-            throw std::runtime_error("internal: the walks of " + std::to_string(ctr[kLcaCtrWalk]) + " reads did not end within the " + std::to_string(T.max_depth) + " levels of the device tree");
-        if (ctr[kLcaCounters + 1] != R || clade[0] != R)
-            throw std::runtime_error("internal: " + std::to_string(R) + " reads, " + std::to_string(ctr[kLcaCounters + 1]) + " counted at their nodes, " + std::to_string(clade[0]) + " under the super-root");
-        HIP_CHECK(hipEventElapsedTime(&ms[0], L.ev[0], L.ev[1]));
-        for (int k = 1; k < 5; k++) HIP_CHECK(hipEventElapsedTime(&ms[k], L.ev[k + 1], L.ev[k + 2]));
-    } catch (...) {
-        if (grown_a) (void)hipFree(grown_a);
-        if (grown_b) (void)hipFree(grown_b);
-        throw;
-    }
+    uint32_t *d_m = L.d_slot.p, *d_lo = d_m + R, *d_hi = d_lo + R;
+    uint32_t *d_direct = L.d_node.p, *d_prefix = d_direct + N, *d_clade = d_prefix + N + 1;
+    HIP_CHECK(hipMemsetAsync(d_m, 0xff, 2 * R * sizeof(uint32_t), stream));  // (m and lo: all ones)
+    HIP_CHECK(hipMemsetAsync(d_hi, 0, R * sizeof(uint32_t), stream));
+    HIP_CHECK(hipMemsetAsync(d_direct, 0, (size_t)N * sizeof(uint32_t), stream));
+    HIP_CHECK(hipEventRecord(L.ev[2], stream));
+    launch_lca_min(stream, grain, d_rec[cur].p, (uint32_t)n, lca_tile, L.d_tile_off.p, (uint32_t)R, d_m, dst);
+    HIP_CHECK(hipEventRecord(L.ev[3], stream));
+    launch_lca_span(stream, grain, d_rec[cur].p, (uint32_t)n, lca_tile, L.d_tile_off.p, (uint32_t)R, d_m, edit_slack, d_u_tax, d_u_node, U, d_lo, d_hi,
+                    L.d_ctr.p);
+    HIP_CHECK(hipEventRecord(L.ev[4], stream));
+    launch_lca_walk(stream, (uint32_t)R, N, T.max_depth, d_lo, d_hi, d_m, d_parent, d_last, d_tax, dst, d_direct, L.d_ctr.p);
+    HIP_CHECK(hipEventRecord(L.ev[5], stream));
+    launch_scan(stream, d_direct, N, L.d_sums.p, d_n_slots + 1, d_prefix);
+    launch_lca_clade(stream, N, d_last, d_prefix, d_clade);
+    HIP_CHECK(hipEventRecord(L.ev[6], stream));
+    if (L.timing) HIP_CHECK(hipStreamSynchronize(stream));
+    t2 = L.timing ? now_ms() : 0;
+    HIP_CHECK(hipMemcpyAsync(ctr, L.d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(direct.data(), d_direct, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(clade.data(), d_clade, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipGetLastError());
+    t3 = L.timing ? now_ms() : 0;
+    if (ctr[kLcaCtrMissing])
+        throw std::runtime_error("internal: " + std::to_string(ctr[kLcaCtrMissing]) + " records of the fold carry a TaxID that is not in its union of " + std::to_string(U) + " TaxIDs");
+    if (ctr[kLcaCtrWalk])
+        throw std::runtime_error("internal: the walks of " + std::to_string(ctr[kLcaCtrWalk]) + " reads did not end within the " + std::to_string(T.max_depth) + " levels of the device tree");
+    if (ctr[kLcaCounters + 1] != R || clade[0] != R)
+        throw std::runtime_error("internal: " + std::to_string(R) + " reads, " + std::to_string(ctr[kLcaCounters + 1]) + " counted at their nodes, " + std::to_string(clade[0]) + " under the super-root");
+    HIP_CHECK(hipEventElapsedTime(&ms[0], L.ev[0], L.ev[1]));
+    for (int k = 1; k < 5; k++) HIP_CHECK(hipEventElapsedTime(&ms[k], L.ev[k + 1], L.ev[k + 2]));
     // ---- nothing can fail from here: the output fold takes the records, the caller the rows ----
     if (out) {
-        if (grown_a) {
-            if (out->d_rec[0]) (void)hipFree(out->d_rec[0]);
-            if (out->d_rec[1]) (void)hipFree(out->d_rec[1]);
-            out->d_rec[0] = grown_a;
-            out->d_rec[1] = grown_b;
-            out->cur = 0;
-            out->cap = grown_cap;
-        } else {
-            out->cur ^= 1;
-        }
-        out->n = R;
+        out->commit(st, R);
         out->n_reads = n_reads;
         out->taxa.clear();
         for (uint32_t i = 0; i < N; i++)
@@ -284,7 +219,7 @@ void Fold::lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<m
     if (L.timing)
         fprintf(stderr, "[lca timing] records %llu reads %llu nodes %u taxa %u rebuilt %d; tree %.3f ms, heads %.3f ms, min %.3f ms, span %.3f ms, walk %.3f ms, "
                         "clade %.3f ms, download %.3f ms, call %.3f ms\n",
-                (unsigned long long)n, (unsigned long long)R, N, U, rebuild ? 1 : 0, t1 - t0, ms[0], ms[1], ms[2], ms[3], ms[4], t3 - t2, lca_now() - t0);
+                (unsigned long long)n, (unsigned long long)R, N, U, rebuild ? 1 : 0, t1 - t0, ms[0], ms[1], ms[2], ms[3], ms[4], t3 - t2, now_ms() - t0);
 }
 
 }  // namespace mtsv

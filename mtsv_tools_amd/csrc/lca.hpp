@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dev_mem.hpp"
 #include "kernels.hpp"
 #include "taxonomy.hpp"
 
@@ -27,32 +28,22 @@ struct LcaState {
     int device;
     hipStream_t stream;  // the fold's
     bool timing = false;
-    hipEvent_t ev[7] = {};
+    DevEvents<7> ev;
     LcaTree tree;
     uint64_t tree_serial = 0;         // the taxonomy's; 0: no tree yet
     std::vector<uint32_t> tree_taxa;  // the union it was built from
-    uint32_t* d_tree = nullptr;       // parent, last, tax (n_nodes each), u_tax, u_node (n_union each)
-    uint64_t tree_cap = 0;
-    uint32_t *d_tile_cnt = nullptr, *d_tile_off = nullptr;
-    uint64_t cnt_cap = 0, off_cap = 0;
-    uint64_t* d_sums = nullptr;  // the scans' tile sums
-    uint64_t sums_cap = 0;
-    uint64_t* d_ctr = nullptr;  // kLcaCounters, then the two scans' totals
-    uint64_t ctr_cap = 0;
-    uint32_t* d_slot = nullptr;  // m, lo, hi: n_slots each
-    uint64_t slot_cap = 0;
-    uint32_t* d_node = nullptr;  // direct (n_nodes), prefix (n_nodes + 1), clade (n_nodes)
-    uint64_t node_cap = 0;
-    uint8_t* d_out = nullptr;  // the records of a call without an output fold
-    uint64_t out_cap = 0;
+    DevBuf<uint32_t> d_tree;          // parent, last, tax (n_nodes each), u_tax, u_node (n_union each)
+    DevBuf<uint32_t> d_tile_cnt, d_tile_off;
+    DevBuf<uint64_t> d_sums;  // the scans' tile sums
+    DevBuf<uint64_t> d_ctr;   // kLcaCounters, then the two scans' totals
+    DevBuf<uint32_t> d_slot;  // m, lo, hi: n_slots each
+    DevBuf<uint32_t> d_node;  // direct (n_nodes), prefix (n_nodes + 1), clade (n_nodes)
+    DevBuf<uint8_t> d_out;    // the records of a call without an output fold
 
     LcaState(int device, hipStream_t stream);
     ~LcaState();
     LcaState(const LcaState&) = delete;
     LcaState& operator=(const LcaState&) = delete;
-
-    // MTSV_LCA_TILE as a tile size: a power of two, 64 .. kLcaTileMax; kLcaTile when it is not set
-    static uint32_t tile_from_env();
 };
 
 }  // namespace mtsv

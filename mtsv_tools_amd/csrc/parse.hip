@@ -3,7 +3,6 @@
 // record crosses to the host or comes from it; what comes down is counters and the records' TaxIDs, four bytes each, for the
 // union the report's rows come from.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
@@ -14,50 +13,16 @@
 
 namespace mtsv {
 
-namespace {
-// p[0 .. want) of device memory (what it held is lost); nothing changes when the allocation fails
-template <class T>
-void parse_room(hipStream_t stream, T*& p, uint64_t& cap, uint64_t want, const char* what) {
-    if (want <= cap && p) return;
-    HIP_CHECK(hipStreamSynchronize(stream));
-    const uint64_t ncap = std::max<uint64_t>(want + want / 8, 1024);
-    T* q = nullptr;
-    if (hipMalloc((void**)&q, ncap * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        throw std::runtime_error(std::string("device: no memory for ") + what + " (" + std::to_string(ncap * sizeof(T)) + " bytes)");
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = ncap;
-}
-double parse_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-}  // namespace
-
-uint32_t TextParser::tile_from_env() {
-    uint32_t tile = kParseTile;
-    if (const char* e = getenv("MTSV_PARSE_TILE")) {  // (tests: tile edges within reach of short texts)
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 64), kParseTileMax);
-        tile = 64;
-        while (tile * 2 <= want) tile *= 2;
-    }
-    return tile;
-}
-
 TextParser::TextParser(int device_, hipStream_t stream_) : device(device_), stream(stream_) {
     trace = getenv("MTSV_TRACE") != nullptr;
     timing = getenv("MTSV_PARSE_TIMING") != nullptr;
     HIP_CHECK(hipSetDevice(device));
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    ev.create();
 }
 
 TextParser::~TextParser() {
     if (hipSetDevice(device) != hipSuccess) (void)hipGetLastError();
     if (stream) (void)hipStreamSynchronize(stream);
-    for (void* p : {(void*)d_hits, (void*)d_line_off, (void*)d_line_read, (void*)d_tile_cnt, (void*)d_tile_off, (void*)d_sums, (void*)d_ctr, (void*)d_raw_key,
-                    (void*)d_raw_val, (void*)d_flag, (void*)d_place, (void*)d_tax})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
 }
 
 void Fold::add_text(const char* hits, const uint64_t* line_off, const uint32_t* line_read, uint64_t n_lines, uint64_t* n_tokens, uint64_t* n_records,
@@ -87,28 +52,28 @@ void Fold::add_text(const char* hits, const uint64_t* line_off, const uint32_t* 
     if (N / P.tile >= 0xfffffff0ull) throw std::runtime_error("limit: " + std::to_string(N) + " bytes of text in tiles of " + std::to_string(P.tile));
     const uint32_t tiles = parse_tiles(N, P.tile);
     // ---- the text goes up; the tokens are counted ----
-    const double t0 = P.timing ? parse_now() : 0;
-    parse_room(stream, P.d_hits, P.hits_cap, N + 16, "the text");
-    parse_room(stream, P.d_line_off, P.off_cap, n_lines + 1, "the lines' offsets");
-    parse_room(stream, P.d_line_read, P.read_cap, n_lines, "the lines' reads");
-    parse_room(stream, P.d_tile_cnt, P.cnt_cap, tiles, "the tiles' tokens");
-    parse_room(stream, P.d_tile_off, P.toff_cap, (uint64_t)tiles + 1, "the tiles' offsets");
-    parse_room(stream, P.d_sums, P.sums_cap, (uint64_t)scan_tiles(tiles) + 1, "the scan's sums");
-    parse_room(stream, P.d_ctr, P.ctr_cap, kParseCounters + 2, "the counters");
+    const double t0 = P.timing ? now_ms() : 0;
+    P.d_hits.room(stream, N + 16, "the text");
+    P.d_line_off.room(stream, n_lines + 1, "the lines' offsets");
+    P.d_line_read.room(stream, n_lines, "the lines' reads");
+    P.d_tile_cnt.room(stream, tiles, "the tiles' tokens");
+    P.d_tile_off.room(stream, (uint64_t)tiles + 1, "the tiles' offsets");
+    P.d_sums.room(stream, (uint64_t)scan_tiles(tiles) + 1, "the scan's sums");
+    P.d_ctr.room(stream, kParseCounters + 2, "the counters");
     uint64_t ctr[kParseCounters + 2];
     for (uint32_t k = 0; k < kParseCounters; k++) ctr[k] = k & 1 ? ~0ull : 0;
     ctr[kParseCounters] = ctr[kParseCounters + 1] = 0;
-    HIP_CHECK(hipMemcpyAsync(P.d_hits, hits, N, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(P.d_line_off, line_off, (n_lines + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(P.d_line_read, line_read, n_lines * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(P.d_ctr, ctr, sizeof ctr, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(P.d_hits.p, hits, N, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(P.d_line_off.p, line_off, (n_lines + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(P.d_line_read.p, line_read, n_lines * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(P.d_ctr.p, ctr, sizeof ctr, hipMemcpyHostToDevice, stream));
     if (P.timing) HIP_CHECK(hipStreamSynchronize(stream));
-    const double t1 = P.timing ? parse_now() : 0;
-    uint64_t* d_n_tok = P.d_ctr + kParseCounters;
+    const double t1 = P.timing ? now_ms() : 0;
+    uint64_t* d_n_tok = P.d_ctr.p + kParseCounters;
     uint64_t* d_n_rec = d_n_tok + 1;
     HIP_CHECK(hipEventRecord(P.ev[0], stream));
-    launch_parse_count(stream, P.d_hits, N, P.d_line_off, n_lines, P.tile, P.d_tile_cnt);
-    launch_scan(stream, P.d_tile_cnt, tiles, P.d_sums, d_n_tok, P.d_tile_off);
+    launch_parse_count(stream, P.d_hits.p, N, P.d_line_off.p, n_lines, P.tile, P.d_tile_cnt.p);
+    launch_scan(stream, P.d_tile_cnt.p, tiles, P.d_sums.p, d_n_tok, P.d_tile_off.p);
     HIP_CHECK(hipEventRecord(P.ev[1], stream));
     uint64_t n_tok = 0;
     HIP_CHECK(hipMemcpyAsync(&n_tok, d_n_tok, sizeof n_tok, hipMemcpyDeviceToHost, stream));
@@ -118,18 +83,18 @@ void Fold::add_text(const char* hits, const uint64_t* line_off, const uint32_t* 
     if (n_tok >= (1ull << 32)) throw std::runtime_error("limit: " + std::to_string(n_tok) + " tokens in one call, 2^32 or more");
     if (!n_tok) throw std::runtime_error("internal: " + std::to_string(N) + " bytes of text hold no token");
     // ---- the tokens are parsed and their runs found; whatever is refused is refused here, with the fold untouched ----
-    parse_room(stream, P.d_raw_key, P.key_cap, n_tok * 16, "the raw tokens");
-    parse_room(stream, P.d_raw_val, P.val_cap, n_tok * 16, "the raw tokens");
-    parse_room(stream, P.d_flag, P.flag_cap, n_tok, "the tokens' flags");
-    parse_room(stream, P.d_place, P.place_cap, n_tok + 1, "the tokens' places");
-    parse_room(stream, P.d_sums, P.sums_cap, (uint64_t)scan_tiles((uint32_t)n_tok) + 1, "the scan's sums");
+    P.d_raw_key.room(stream, n_tok * 16, "the raw tokens");
+    P.d_raw_val.room(stream, n_tok * 16, "the raw tokens");
+    P.d_flag.room(stream, n_tok, "the tokens' flags");
+    P.d_place.room(stream, n_tok + 1, "the tokens' places");
+    P.d_sums.room(stream, (uint64_t)scan_tiles((uint32_t)n_tok) + 1, "the scan's sums");
     HIP_CHECK(hipEventRecord(P.ev[2], stream));
-    launch_parse_tokens(stream, grain, P.d_hits, N, P.d_line_off, P.d_line_read, n_lines, P.tile, P.d_tile_off, (uint32_t)n_tok, P.d_raw_key, P.d_raw_val,
-                        P.d_ctr);
-    launch_parse_heads(stream, grain, P.d_raw_key, P.d_raw_val, (uint32_t)n_tok, n_reads, P.d_flag, P.d_ctr);
-    launch_scan(stream, P.d_flag, (uint32_t)n_tok, P.d_sums, d_n_rec, P.d_place);
+    launch_parse_tokens(stream, grain, P.d_hits.p, N, P.d_line_off.p, P.d_line_read.p, n_lines, P.tile, P.d_tile_off.p, (uint32_t)n_tok, P.d_raw_key.p, P.d_raw_val.p,
+                        P.d_ctr.p);
+    launch_parse_heads(stream, grain, P.d_raw_key.p, P.d_raw_val.p, (uint32_t)n_tok, n_reads, P.d_flag.p, P.d_ctr.p);
+    launch_scan(stream, P.d_flag.p, (uint32_t)n_tok, P.d_sums.p, d_n_rec, P.d_place.p);
     HIP_CHECK(hipEventRecord(P.ev[3], stream));
-    HIP_CHECK(hipMemcpyAsync(ctr, P.d_ctr, sizeof ctr, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(ctr, P.d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     if (ctr[kParseCtrFormat])
@@ -154,12 +119,12 @@ void Fold::add_text(const char* hits, const uint64_t* line_off, const uint32_t* 
     if (n + n_rec >= (1ull << 32)) throw std::runtime_error("limit: the fold would hold " + std::to_string(n + n_rec) + " records before equal keys are joined, 2^32 or more");
     // ---- the records, in the fold's incoming array; their TaxIDs for the union ----
     in_room(n_rec);
-    parse_room(stream, P.d_tax, P.tax_cap, n_rec, "the records' TaxIDs");
+    P.d_tax.room(stream, n_rec, "the records' TaxIDs");
     HIP_CHECK(hipEventRecord(P.ev[4], stream));
-    launch_parse_reduce(stream, grain, P.d_raw_key, P.d_raw_val, P.d_flag, P.d_place, (uint32_t)n_tok, (uint32_t)n_rec, d_in, P.d_tax);
+    launch_parse_reduce(stream, grain, P.d_raw_key.p, P.d_raw_val.p, P.d_flag.p, P.d_place.p, (uint32_t)n_tok, (uint32_t)n_rec, d_in.p, P.d_tax.p);
     HIP_CHECK(hipEventRecord(P.ev[5], stream));
     taxa_in.resize(n_rec);
-    HIP_CHECK(hipMemcpyAsync(taxa_in.data(), P.d_tax, n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(taxa_in.data(), P.d_tax.p, n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     std::sort(taxa_in.begin(), taxa_in.end());
@@ -179,7 +144,7 @@ void Fold::add_text(const char* hits, const uint64_t* line_off, const uint32_t* 
     // MTSV_PARSE_TIMING=1: where a call spends its time (tools/collapse_ab.py reads this line)
     if (P.timing)
         fprintf(stderr, "[parse timing] bytes %llu lines %llu tokens %llu records %llu; upload %.3f ms, kernels %.3f ms, fold %.3f ms, call %.3f ms\n",
-                (unsigned long long)N, (unsigned long long)n_lines, (unsigned long long)n_tok, (unsigned long long)n_rec, t1 - t0, ms, fold_ms, parse_now() - t0);
+                (unsigned long long)N, (unsigned long long)n_lines, (unsigned long long)n_tok, (unsigned long long)n_rec, t1 - t0, ms, fold_ms, now_ms() - t0);
 }
 
 }  // namespace mtsv

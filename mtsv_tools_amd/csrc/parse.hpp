@@ -1,7 +1,7 @@
 // parse.hpp -- result text that lies in HBM turned back into assignment records there (parse.hip, k_parse.hip).
 #pragma once
 #include "../../include/mtsv_amd.h"
-#include "dev_index.hpp"
+#include "dev_mem.hpp"
 #include "kernels.hpp"
 
 namespace mtsv {
@@ -12,31 +12,26 @@ namespace mtsv {
 struct TextParser {
     int device;
     hipStream_t stream;         // the fold's
-    uint32_t tile = kParseTile;  // MTSV_PARSE_TILE (tests)
+    uint32_t tile = kParseTile;  // MTSV_PARSE_TILE (tests): a power of two, 64 .. kParseTileMax
     bool trace = false, timing = false;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // three pairs: count, tokens and heads, reduce
-    uint8_t* d_hits = nullptr;
-    uint64_t* d_line_off = nullptr;
-    uint32_t* d_line_read = nullptr;
-    uint32_t* d_tile_cnt = nullptr;
-    uint32_t* d_tile_off = nullptr;
-    uint64_t* d_sums = nullptr;  // the scans' tile sums
-    uint64_t* d_ctr = nullptr;   // kParseCounters, then the tokens, then the records
-    uint8_t* d_raw_key = nullptr;
-    uint8_t* d_raw_val = nullptr;
-    uint32_t* d_flag = nullptr;
-    uint32_t* d_place = nullptr;
-    uint32_t* d_tax = nullptr;  // the records' TaxIDs, for the host
-    uint64_t hits_cap = 0, off_cap = 0, read_cap = 0, cnt_cap = 0, toff_cap = 0, sums_cap = 0, ctr_cap = 0, key_cap = 0, val_cap = 0, flag_cap = 0,
-             place_cap = 0, tax_cap = 0;
+    DevEvents<6> ev;  // three pairs: count, tokens and heads, reduce
+    DevBuf<uint8_t> d_hits;
+    DevBuf<uint64_t> d_line_off;
+    DevBuf<uint32_t> d_line_read;
+    DevBuf<uint32_t> d_tile_cnt;
+    DevBuf<uint32_t> d_tile_off;
+    DevBuf<uint64_t> d_sums;  // the scans' tile sums
+    DevBuf<uint64_t> d_ctr;   // kParseCounters, then the tokens, then the records
+    DevBuf<uint8_t> d_raw_key;
+    DevBuf<uint8_t> d_raw_val;
+    DevBuf<uint32_t> d_flag;
+    DevBuf<uint32_t> d_place;
+    DevBuf<uint32_t> d_tax;  // the records' TaxIDs, for the host
 
     TextParser(int device, hipStream_t stream);
     ~TextParser();
     TextParser(const TextParser&) = delete;
     TextParser& operator=(const TextParser&) = delete;
-
-    // MTSV_PARSE_TILE as a tile size: a power of two, 64 .. kParseTileMax; kParseTile when it is not set
-    static uint32_t tile_from_env();
 };
 
 }  // namespace mtsv

@@ -2,7 +2,6 @@
 // include/mtsv_amd.h): the records are in HBM already, the read IDs go up, k_text.hip measures, scans and writes, and
 // what crosses to the host is the text.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
@@ -14,51 +13,18 @@
 
 namespace mtsv {
 
-namespace {
-// p[0 .. want) of device memory (what it held is lost); nothing changes when the allocation fails
-template <class T>
-void text_room(hipStream_t stream, T*& p, uint64_t& cap, uint64_t want, const char* what) {
-    if (want <= cap && p) return;
-    HIP_CHECK(hipStreamSynchronize(stream));
-    const uint64_t ncap = std::max<uint64_t>(want + want / 8, 1024);
-    T* q = nullptr;
-    if (hipMalloc((void**)&q, ncap * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        throw std::runtime_error(std::string("device: no memory for ") + what + " (" + std::to_string(ncap * sizeof(T)) + " bytes)");
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = ncap;
-}
-double text_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-}  // namespace
-
-uint32_t TextFormatter::tile_from_env() {
-    uint32_t tile = kTextTile;
-    if (const char* e = getenv("MTSV_TEXT_TILE")) {  // (tests: tile edges and windows within reach of small lists)
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 2), kTextTileMax);
-        tile = 2;
-        while (tile * 2 <= want) tile *= 2;
-    }
-    return tile;
-}
-
 TextFormatter::TextFormatter(int device_) : device(device_) {
-    tile = tile_from_env();
+    tile = tile_from_env("MTSV_TEXT_TILE", kTextTile, 2, kTextTileMax);
     trace = getenv("MTSV_TRACE") != nullptr;
     timing = getenv("MTSV_TEXT_TIMING") != nullptr;
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    ev.create();
 }
 
 TextFormatter::~TextFormatter() {
     if (hipSetDevice(device) != hipSuccess) (void)hipGetLastError();
     if (stream) (void)hipStreamSynchronize(stream);
-    for (void* p : {(void*)d_ids, (void*)d_id_off, (void*)d_gather, (void*)d_rec_len, (void*)d_tile_cnt, (void*)d_tile_off, (void*)d_sums, (void*)d_out})
-        if (p) (void)hipFree(p);
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -81,39 +47,39 @@ void TextFormatter::format(int grain, const std::vector<Stretch>& src, const cha
         return;
     }
     // ---- the IDs go up; the records come to lie next to each other ----
-    const double t0 = timing ? text_now() : 0;
+    const double t0 = timing ? now_ms() : 0;
     const uint64_t ids_bytes = n_reads ? id_off[n_reads] : 0;
-    text_room(stream, d_ids, ids_cap, ids_bytes + 8, "the read IDs");
-    text_room(stream, d_id_off, off_cap, n_reads + 1, "the read IDs' offsets");
-    if (ids_bytes) HIP_CHECK(hipMemcpyAsync(d_ids, ids, ids_bytes, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(d_id_off, id_off, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    d_ids.room(stream, ids_bytes + 8, "the read IDs");
+    d_id_off.room(stream, n_reads + 1, "the read IDs' offsets");
+    if (ids_bytes) HIP_CHECK(hipMemcpyAsync(d_ids.p, ids, ids_bytes, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(d_id_off.p, id_off, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
     if (timing) HIP_CHECK(hipStreamSynchronize(stream));
-    const double t1 = timing ? text_now() : 0;
+    const double t1 = timing ? now_ms() : 0;
     const uint8_t* d_rec = nullptr;
     if (n_src == 1) {
         for (const auto& s : src)
             if (s.n) d_rec = s.rec;
     } else {
-        text_room(stream, d_gather, gather_cap, n * rec, "the gathered records");
+        d_gather.room(stream, n * rec, "the gathered records");
         uint64_t at = 0;
         for (const auto& s : src) {
             if (!s.n) continue;
-            HIP_CHECK(hipMemcpyAsync(d_gather + at * rec, s.rec, s.n * rec, hipMemcpyDeviceToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(d_gather.p + at * rec, s.rec, s.n * rec, hipMemcpyDeviceToDevice, stream));
             at += s.n;
         }
-        d_rec = d_gather;
+        d_rec = d_gather.p;
     }
-    text_room(stream, d_rec_len, len_cap, n, "the records' lengths");
-    text_room(stream, d_tile_cnt, cnt_cap, tiles, "the tiles' lengths");
-    text_room(stream, d_tile_off, toff_cap, (uint64_t)tiles + 1, "the tiles' offsets");
-    text_room(stream, d_sums, sums_cap, (uint64_t)text_scan_blocks(tiles) + 3, "the scan's sums");
-    uint64_t* d_total = d_sums + text_scan_blocks(tiles);
+    d_rec_len.room(stream, n, "the records' lengths");
+    d_tile_cnt.room(stream, tiles, "the tiles' lengths");
+    d_tile_off.room(stream, (uint64_t)tiles + 1, "the tiles' offsets");
+    d_sums.room(stream, (uint64_t)text_scan_blocks(tiles) + 3, "the scan's sums");
+    uint64_t* d_total = d_sums.p + text_scan_blocks(tiles);
     // ---- measure and scan; the host needs the length before the text has a place ----
     uint64_t res[3] = {0, 0, 0};  // the bytes of the text, the reads beyond n_reads, the bad ID slots
     HIP_CHECK(hipMemsetAsync(d_total, 0, sizeof res, stream));
     HIP_CHECK(hipEventRecord(ev[0], stream));
-    launch_text_measure(stream, grain, d_rec, (uint32_t)n, d_ids, d_id_off, n_reads, ids_bytes, tile, d_rec_len, d_tile_cnt, d_total + 1);
-    launch_text_scan(stream, d_tile_cnt, tiles, d_sums, d_total, d_tile_off);
+    launch_text_measure(stream, grain, d_rec, (uint32_t)n, d_ids.p, d_id_off.p, n_reads, ids_bytes, tile, d_rec_len.p, d_tile_cnt.p, d_total + 1);
+    launch_text_scan(stream, d_tile_cnt.p, tiles, d_sums.p, d_total, d_tile_off.p);
     HIP_CHECK(hipEventRecord(ev[1], stream));
     HIP_CHECK(hipMemcpyAsync(res, d_total, sizeof res, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -125,23 +91,23 @@ void TextFormatter::format(int grain, const std::vector<Stretch>& src, const cha
         throw std::runtime_error("arg: " + std::to_string(res[2]) + " ID slots do not lie inside the ID bytes (id_off must ascend) or are longer than " +
                                  std::to_string(kTextIdMax) + " bytes");
     const uint64_t total = res[0];
-    text_room(stream, d_out, out_cap, total + 16, "the text");
+    d_out.room(stream, total + 16, "the text");
     char* out = (char*)pinned_hits_alloc((total + 1 + 31) / 32, &pool_cap);  // (the pool counts in 32-byte hits)
     // ---- write, and the text comes down ----
     float ms = 0, ms2 = 0;
     double t2 = 0, t3 = 0;
     try {
         HIP_CHECK(hipEventRecord(ev[2], stream));
-        launch_text_write(stream, grain, d_rec, (uint32_t)n, d_ids, d_id_off, tile, d_rec_len, d_tile_off, d_out);
+        launch_text_write(stream, grain, d_rec, (uint32_t)n, d_ids.p, d_id_off.p, tile, d_rec_len.p, d_tile_off.p, d_out.p);
         HIP_CHECK(hipEventRecord(ev[3], stream));
         if (timing) {
             HIP_CHECK(hipStreamSynchronize(stream));
-            t2 = text_now();
+            t2 = now_ms();
         }
-        if (total) HIP_CHECK(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, stream));
+        if (total) HIP_CHECK(hipMemcpyAsync(out, d_out.p, total, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipGetLastError());
-        if (timing) t3 = text_now();
+        if (timing) t3 = now_ms();
         HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
         HIP_CHECK(hipEventElapsedTime(&ms2, ev[2], ev[3]));
     } catch (...) {
@@ -171,7 +137,7 @@ void Fold::format_text(const char* ids, const uint64_t* id_off, uint64_t n_reads
         text->tile = text_tile;  // (read when the fold was created)
     }
     HIP_CHECK(hipStreamSynchronize(stream));
-    text->format(grain, {TextFormatter::Stretch{d_rec[cur], n}}, ids, id_off, n_reads, text_out, len, device_ms);
+    text->format(grain, {TextFormatter::Stretch{d_rec[cur].p, n}}, ids, id_off, n_reads, text_out, len, device_ms);
 }
 
 void Batch::format_text(const char* ids, const uint64_t* id_off, uint64_t n_reads_, char** text_out, uint64_t* len, float* device_ms) {

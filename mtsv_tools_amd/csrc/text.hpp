@@ -3,7 +3,7 @@
 #include <vector>
 
 #include "../../include/mtsv_amd.h"
-#include "dev_index.hpp"
+#include "dev_mem.hpp"
 #include "kernels.hpp"
 
 namespace mtsv {
@@ -13,27 +13,23 @@ namespace mtsv {
 // one on its first call and keeps it; its arrays grow by reallocation and are kept from call to call.
 struct TextFormatter {
     int device;
-    uint32_t tile = kTextTile;  // MTSV_TEXT_TILE (tests)
+    uint32_t tile = kTextTile;  // MTSV_TEXT_TILE (tests): a power of two, 2 .. kTextTileMax
     bool trace = false, timing = false;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint8_t* d_ids = nullptr;
-    uint64_t* d_id_off = nullptr;
-    uint8_t* d_gather = nullptr;  // records that lie in several stretches, next to each other
-    uint32_t* d_rec_len = nullptr;
-    uint32_t* d_tile_cnt = nullptr;
-    uint64_t* d_tile_off = nullptr;
-    uint64_t* d_sums = nullptr;  // the scan's sums, then the total, then the two counters of the measure pass
-    uint8_t* d_out = nullptr;
-    uint64_t ids_cap = 0, off_cap = 0, gather_cap = 0, len_cap = 0, cnt_cap = 0, toff_cap = 0, sums_cap = 0, out_cap = 0;
+    DevEvents<4> ev;
+    DevBuf<uint8_t> d_ids;
+    DevBuf<uint64_t> d_id_off;
+    DevBuf<uint8_t> d_gather;  // records that lie in several stretches, next to each other
+    DevBuf<uint32_t> d_rec_len;
+    DevBuf<uint32_t> d_tile_cnt;
+    DevBuf<uint64_t> d_tile_off;
+    DevBuf<uint64_t> d_sums;  // the scan's sums, then the total, then the two counters of the measure pass
+    DevBuf<uint8_t> d_out;
 
     explicit TextFormatter(int device);
     ~TextFormatter();
     TextFormatter(const TextFormatter&) = delete;
     TextFormatter& operator=(const TextFormatter&) = delete;
-
-    // MTSV_TEXT_TILE as a tile size: a power of two, 2 .. kTextTileMax; kTextTile when it is not set
-    static uint32_t tile_from_env();
 
     struct Stretch {
         const uint8_t* rec;  // device memory

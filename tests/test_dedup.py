@@ -331,6 +331,44 @@ def test_fan_equals_the_restatement(ix, gname, tile, bits, monkeypatch, capfd):
         x.close()
 
 
+def test_fan_into_a_fold_that_holds_records_grows_it_then_reuses_it(ix, monkeypatch):
+    """The three ways an expansion finds room in a destination that already holds records, each compared byte for byte with
+    the restatement: a new pair of arrays (one held record gave the fold room for 65 536; 33 000 sequences twice with one
+    record per representative expand to 66 000), the fold's other array (the same expansion again), and the other array
+    again for a result of four records."""
+    set_bits(monkeypatch, None)
+    grain, n_seq = M.GRAIN_TAXID, 33000
+    seqs = [bytes(b"ACGT"[(g >> (2 * k)) & 3] for k in range(20)) for g in range(n_seq)]
+    raws = seqs + seqs
+    random.Random(78).shuffle(raws)
+    bases, off = helpers.reads_to_batch(raws)
+    n = len(raws)
+    reads = D.read_codes(bases, off)
+    read, rep = D.dupmap(reads)
+    reps = D.representatives(reads)
+    recs = [(j, (10 + j % 7) | ((j & 1) << 31), j % 23) for j in reps]
+    two = recs[:1] + recs[-1:]
+    want, want_two = D.expand(recs, read, rep), D.expand(two, read, rep)
+    assert len(reps) == n_seq and len(want) == n > 65536 and len(want_two) == 4
+    src, dst, m = M.Batch(ix, 0, n, len(bases), lanes=1), M.Batch(ix, 0, n, len(bases), lanes=1), M.DupMap(0)
+    src.upload(bases, off)
+    assert dst.take_unique(src, m)[0] == n_seq
+    held = np.array([(n - 1, 4, 4)], dtype=M.ASSIGN_DTYPE)
+    f_rep, f_two, f_dst = M.Fold(0, grain, n), M.Fold(0, grain, n), M.Fold(0, grain, n)
+    f_rep.add_records(to_array(grain, recs))
+    f_two.add_records(to_array(grain, two))
+    f_dst.add_records(held)
+    for source, expected in ((f_rep, want), (f_rep, want), (f_two, want_two)):
+        assert f_dst.expand(source, m) >= 0.0
+        assert f_dst.count() == len(expected) and f_dst.download().tobytes() == to_array(grain, expected).tobytes()
+    assert f_rep.download().tobytes() == to_array(grain, recs).tobytes()   # the source is not changed
+    # the fold goes on as any other: the next list is folded out of the array the last expansion wrote
+    f_dst.add_records(held)
+    assert f_dst.download().tobytes() == to_array(grain, sorted(want_two + [(n - 1, 4, 4)])).tobytes()
+    for x in (src, dst, m, f_rep, f_two, f_dst):
+        x.close()
+
+
 def test_fan_groups_are_what_they_claim():
     raws = fan_reads()
     reads = D.read_codes(*helpers.reads_to_batch(raws))
