@@ -7,28 +7,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <ctime>
 #include <fstream>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/mtsv_amd.h"
+#include "cli_common.hpp"
 
 namespace {
-bool g_verbose = false;
-void logmsg(const char* level, const std::string& msg) {
-    if (!g_verbose && !strcmp(level, "DEBUG")) return;
-    char ts[32];
-    time_t t = time(nullptr);
-    strftime(ts, sizeof ts, "%Y-%m-%d %H:%M:%S", localtime(&t));
-    printf("[%s %s mtsv_build] %s\n", level, ts, msg.c_str());
-    fflush(stdout);
-}
-[[noreturn]] void panic(const std::string& m) {
-    fprintf(stderr, "thread 'main' panicked: %s\n", m.c_str());
-    exit(101);
-}
+void logmsg(const char* level, const std::string& msg) { mtsv_cli::logmsg("mtsv_build", level, msg); }
+using mtsv_cli::panic;
 bool parse_u32(const std::string& s, uint32_t* out) {
     if (s.empty()) return false;
     uint64_t v = 0;
@@ -88,7 +77,7 @@ int main(int argc, char** argv) {
         else if (k == "--sample-interval") fm = val();
         else if (k == "--mapping") mapping = val();
         else if (k == "--skip-missing") skip_missing = true;
-        else if (k == "-v") g_verbose = true;
+        else if (k == "-v") mtsv_cli::verbose() = true;
         else if (k == "--device") device = atoi(val().c_str());
         else if (k == "--threads") threads = atoi(val().c_str());
         else if (k == "-h" || k == "--help") {

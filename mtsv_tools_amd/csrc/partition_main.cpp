@@ -15,24 +15,16 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <ctime>
 #include <string>
 #include <unordered_set>
 #include <vector>
 
+#include "cli_common.hpp"
 #include "fastx_ingest.hpp"
 
 namespace {
 
-bool g_verbose = false;
-void logmsg(const char* level, const std::string& msg) {
-    if (!g_verbose && !strcmp(level, "DEBUG")) return;
-    char ts[32];
-    time_t t = time(nullptr);
-    strftime(ts, sizeof ts, "%Y-%m-%d %H:%M:%S", localtime(&t));
-    printf("[%s %s mtsv_partition] %s\n", level, ts, msg.c_str());
-    fflush(stdout);
-}
+void logmsg(const char* level, const std::string& msg) { mtsv_cli::logmsg("mtsv_partition", level, msg); }
 
 [[noreturn]] void usage_error(const std::string& m) {
     fprintf(stderr,
@@ -121,7 +113,7 @@ int main(int argc, char** argv) {
         else if (k == "--fastq") fastq = val();
         else if (k == "--matched") matched = val();
         else if (k == "--unmatched") unmatched = val();
-        else if (k == "-v") g_verbose = true;
+        else if (k == "-v") mtsv_cli::verbose() = true;
         else if (k == "-h" || k == "--help") {
             printf("mtsv-partition -- split reads into matched / unmatched sets based on mtsv results\n"
                    "    --results R1 [R2 ..]   mtsv results files (the read ID is what stands before the last ':' of a line)\n"

@@ -35,6 +35,59 @@ def test_exit_codes_without_touching_the_gpu(tmp_path):
     assert run("--fasta", "x", "-i", "y", "-m", str(tmp_path / "r"), "--batch-reads", "-5").returncode == 1
 
 
+def test_a_doubly_wrong_command_line_gets_the_message_of_the_first_violation(tmp_path):
+    """Validation order is part of the interface: of two violations the earlier check's message and exit code come out,
+    and a run refused there has touched no output file.  Nothing here opens a device, an index or the input."""
+    r, m, rep = str(tmp_path / "r"), str(tmp_path / "m.fq"), str(tmp_path / "rep.tsv")
+    existing = tmp_path / "existing.results"
+    existing.write_bytes(b"r0:1=0\nr1:2=3\n")
+    missing = str(tmp_path / "missing.fa")
+    table = [
+        # (arguments, exit code, what only the winning message says, what the losing message says)
+        (["--fasta", "x", "-i", "a,b", "-m", r, "--text-on-gpu", "--merge-on-gpu"], 1,
+         "'--text-on-gpu' cannot be used with '--merge-on-gpu'", "requires '--fold-on-gpu'"),
+        (["--fasta", "x", "-i", "a,b", "-m", r, "--fold-on-gpu", "--merge-on-gpu", "--filter-index", "f"], 1,
+         "'--merge-on-gpu' cannot be used with '--fold-on-gpu'", "--filter-index"),
+        (["--fasta", "x", "-i", "a", "-m", r, "--fold-on-gpu", "--filter-index", "f"], 1,
+         "'--filter-index <INDEX>' cannot be used with '--fold-on-gpu'", "two or more index chunks"),
+        (["--fasta", "x", "-i", "a", "-m", r, "--merge-on-gpu", "--devices", "0,1"], 1,
+         "'--merge-on-gpu' needs a list of two or more index chunks", "exactly one '--devices' entry"),
+        (["--fasta", "x", "-i", "a", "-m", r, "--fold-on-gpu", "--devices", "0,1"], 1,
+         "'--fold-on-gpu' needs a list of two or more index chunks", "exactly one '--devices' entry"),
+        (["--fasta", "x", "-i", "a,b", "-m", r, "--merge-on-gpu", "--devices", "0,1", "--parse-only"], 1,
+         "'--merge-on-gpu' needs exactly one '--devices' entry", "--parse-only"),
+        (["--fasta", "x", "--matched", m, "--parse-only", "--filter-index", "f"], 1,
+         "'--parse-only' cannot be used with '--matched <PATH>' / '--unmatched <PATH>'", "--filter-index"),
+        (["--fasta", "x", "-i", "a", "--report", rep, "--matched", m, "--output-format", "xml"], 1,
+         "'--report <TSV>' requires '-m/--results <RESULTS>'", "--output-format"),
+        (["--fasta", "x", "-i", "a,b", "-m", r, "--report", rep, "--matched", m], 1,
+         "'--report <TSV>' cannot be used with a list of index chunks", "'--matched <PATH>' / '--unmatched <PATH>' cannot"),
+        (["--fasta", "x", "-i", "a,b", "-m", r, "--filter-index", "f", "--matched", m], 1,
+         "'--matched <PATH>' / '--unmatched <PATH>' cannot be used with a list of index chunks", "--filter-index"),
+        (["--fasta", "x", "-i", "a", "-m", r, "--output-format", "xml", "--edit-rate", "1.5"], 1,       # usage error before panic
+         "'xml' isn't a valid value for '--output-format <OUTPUT_FORMAT>'", "panicked"),
+        (["--fasta", "x", "-i", "a", "--edit-rate", "1.5"], 101,                                          # panic before "no results path"
+         "Edit tolerance proportion must be between 0 and 1", "No results path"),
+        (["--fasta", missing, "-i", "a", "-m", str(existing), "--matched", m], 1,                         # refusal before the input is opened
+         "would resume it; '--matched' / '--unmatched' need the whole input", "cannot open"),
+        (["--fasta", missing, "-i", "a,b", "-m", str(existing), "--fold-on-gpu"], 1,
+         "would resume it; '--fold-on-gpu' does not resume", "cannot open"),
+        (["--fasta", "x", "-i", "a", "-m", r, "--output-format=xml", "--edit-rate=1.5"], 1,              # --key=value of a value flag
+         "'xml' isn't a valid value for '--output-format <OUTPUT_FORMAT>'", "panicked"),
+        (["--fasta", "x", "-i", "a", "-m", r, "--batch-reads=0", "--bogus=1"], 1,
+         "Invalid value for '--batch-reads <N>'", "--bogus"),
+        (["--fasta", "x", "-i", "a", "-m", r, "--bogus=1", "--batch-reads=0"], 1,                         # ... and of an unknown flag
+         "Found argument '--bogus=1' which wasn't expected", "--batch-reads"),
+    ]
+    for args, code, says, does_not_say in table:
+        got = run(*args)
+        text = got.stdout + got.stderr
+        assert got.returncode == code, (args, text)
+        assert says in text and does_not_say not in text, (args, text)
+    assert existing.read_bytes() == b"r0:1=0\nr1:2=3\n"
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["existing.results"]  # no results, --matched or report file was made
+
+
 def _golden_inputs(tmp_path):
     reads = [l.rstrip("\n") for l in open(os.path.join(GOLD, "e2e_reads.txt"), encoding="latin-1")]
     fa, fq = tmp_path / "reads.fasta", tmp_path / "reads.fastq"
