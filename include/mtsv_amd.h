@@ -714,6 +714,51 @@ int mtsv_fold_lca(mtsv_fold *f, const mtsv_taxonomy *tx, uint32_t edit_slack, mt
 int mtsv_format_clade_report(const mtsv_clade_stats *rows, uint64_t n_rows, uint64_t total_reads, const mtsv_taxonomy *tx,
                              char **out, uint64_t *out_len);
 
+/* ---- paired-end reads: the mates' assignments joined (pair.hip, k_pair.hip) ------------------------------------------------
+ * The two mates of a fragment come from one organism, and from one reference sequence a few hundred bases apart.  A fold whose
+ * reads are numbered so that reads 2p and 2p + 1 are the mates of pair p (mate 0 and mate 1) is joined into a fold of PAIRS:
+ * records (p, tax_id, edit) in key order, in `out`.
+ *
+ * mtsv_fold_pair: f's n_reads is 2P (an odd n_reads is MTSV_E_ARG); any grain; f is not changed.  out: another fold of the
+ *   same device at MTSV_GRAIN_TAXID.  It becomes a fold as after mtsv_fold_reset(out, P) that holds the records below; its
+ *   TaxID union is f's.  Everything a fold offers then works on it -- mtsv_fold_download, _format_text (n_reads = P, the pairs'
+ *   IDs), _taxa_report, _match_flags, _lca -- counting pairs where it counted reads.
+ *   All fields compare as unsigned.  m_k(t) is the smallest edit among mate k's records with TaxID t.
+ *     MTSV_PAIR_BOTH    t is kept for pair p when both mates have a record with t; its edit is m_0(t) + m_1(t).
+ *     MTSV_PAIR_EITHER  the union of the mates' taxa: a taxon both mates hit carries the sum, a taxon one mate hit carries that
+ *                       mate's m_k(t) + unpaired_edits, the caller's price for a mate that did not align (ignored in the other
+ *                       modes; 2^31 or more is MTSV_E_ARG, so that no sum wraps).
+ *     MTSV_PAIR_PROPER  f must be at MTSV_GRAIN_LONG (any other grain is MTSV_E_ARG).  t is kept when a record a of mate 0 and
+ *                       a record b of mate 1 exist with equal (tax_id, gi) and |a.offset - b.offset| <= max_insert; its edit is
+ *                       the smallest a.edit + b.edit over all such couples -- which need not hold the best record of either
+ *                       mate.  The window [a.offset - max_insert, a.offset + max_insert] is clamped to [0, 2^32 - 1] and never
+ *                       wraps.  Offsets are forward-strand window starts whichever strand hit (mtsv_hit.offset), so the
+ *                       distance needs no strand; the mates' ORIENTATION (forward-reverse) is NOT checked: the records carry
+ *                       no strand.  max_insert is ignored in the other two modes.
+ *   stats (may be NULL), counted on the device: pairs = P; both_mates_hit / one_mate_hit: the pairs of which both mates /
+ *   exactly one mate have a record in f; joined: the pairs with a record in out; records: the records of out.
+ *   device_ms (may be NULL): device time of all kernels of the call.
+ * On the device (k_pair.hip): the first record of every read by a lower bound; a lane per record of f that finds its window in
+ *   the other mate's stretch by binary searches and walks a window of up to MTSV_PAIR_LANE_MAX records (default 16, 0..1024;
+ *   0 sends every window that is not empty on) -- a longer window goes to a work list that a wavefront per entry strides; then
+ *   the heads of the (read, tax_id) runs, a segmented minimum, a scan and a compaction in tiles of MTSV_PAIR_TILE records (a
+ *   power of two, 64..1024); in MTSV_PAIR_EITHER the taxa only mate 1 hit form a second list that the fold's merge (k_fold.hip)
+ *   joins with the first.  Both knobs are read by mtsv_fold_create (tests); results depend on neither.  MTSV_PAIR_TIMING=1
+ *   prints the steps' times to stderr.  With no call made nothing is allocated or launched.  The call's arrays, kept by f, take
+ *   up to 36 bytes per record of f, 4 per read, and in MTSV_PAIR_EITHER 16 per output record.
+ * Refusals, all with out as it was.  MTSV_E_ARG: a null f or out; out == f; out on another device; out of a wide grain; a bad
+ *   mode; an odd n_reads; MTSV_PAIR_PROPER on a narrow grain; a record of f with edit >= 2^31 (counted on the device before
+ *   anything is written; no fold the library makes holds one, and it keeps the sums and the "none" sentinel apart).
+ *   MTSV_E_LIMIT: 2^32 or more output records; an f of 2^32 reads or more. */
+#define MTSV_PAIR_BOTH 0
+#define MTSV_PAIR_EITHER 1
+#define MTSV_PAIR_PROPER 2
+typedef struct {
+    uint64_t pairs, both_mates_hit, one_mate_hit, joined, records;
+} mtsv_pair_stats; /* 40 bytes */
+int mtsv_fold_pair(mtsv_fold *f, int mode, uint32_t max_insert, uint32_t unpaired_edits, mtsv_fold *out, mtsv_pair_stats *stats,
+                   float *device_ms);
+
 /* ---- result lines (host) ---------------------------------------------------------------- */
 /* write_assignments for a whole batch: hits ordered by read; ids = NUL-separated read ids,
  * id_off[n_reads+1].  Lines are appended to a malloc'd buffer (*out, *out_len), one per read with

@@ -42,6 +42,10 @@ from ._lib import (  # noqa: F401
     Fold,
     MGIndex,
     MtsvError,
+    PAIR_BOTH,
+    PAIR_EITHER,
+    PAIR_PROPER,
+    PairStats,
     Params,
     bin_batch_chunks,
     bin_batch_multi,

@@ -90,10 +90,19 @@ CLADE_STATS_DTYPE = np.dtype({"names": ["tax_id", "parent_tax_id", "rank", "dept
                               "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8"], "offsets": [0, 4, 8, 12, 16, 24], "itemsize": 32})
 RANK_UNKNOWN = 0xffffffff  # MTSV_RANK_UNKNOWN
 SLACK_ALL = 0xffffffff  # edit_slack of mtsv_fold_lca: every TaxID of a read enters
+PAIR_BOTH, PAIR_EITHER, PAIR_PROPER = 0, 1, 2  # MTSV_PAIR_*
 
 
 class TaxonomyInfo(C.Structure):  # mtsv_taxonomy_info_t
     _fields_ = [("n_nodes", C.c_uint64), ("n_implied_roots", C.c_uint64), ("n_ranks", C.c_uint32), ("max_depth", C.c_uint32)]
+
+
+class PairStats(C.Structure):  # mtsv_pair_stats
+    _fields_ = [("pairs", C.c_uint64), ("both_mates_hit", C.c_uint64), ("one_mate_hit", C.c_uint64), ("joined", C.c_uint64),
+                ("records", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 EXPORTS = [
@@ -120,6 +129,7 @@ EXPORTS = [
     "mtsv_taxonomy_load", "mtsv_taxonomy_free", "mtsv_taxonomy_info", "mtsv_taxonomy_parent", "mtsv_taxonomy_rank_name",
     "mtsv_fold_lca", "mtsv_format_clade_report",
     "mtsv_dupmap_create", "mtsv_dupmap_free", "mtsv_batch_take_unique", "mtsv_dupmap_download", "mtsv_fold_expand",
+    "mtsv_fold_pair",
 ]
 
 _lib = None
@@ -227,6 +237,7 @@ def lib():
         L.mtsv_batch_take_unique.argtypes = [vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_dupmap_download.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.mtsv_fold_expand.argtypes = [vp, vp, vp, C.POINTER(C.c_float)]
+        L.mtsv_fold_pair.argtypes = [vp, i32, u32, u32, vp, C.POINTER(PairStats), C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -751,6 +762,15 @@ class Fold:
         _check(lib().mtsv_fold_lca(self.h, tx.h, int(slack), out.h if out is not None else None, C.byref(ptr) if rows else None,
                                    C.byref(n), C.byref(total), C.byref(ms)))
         return (_records_from(ptr, n.value, CLADE_STATS_DTYPE) if rows else None), total.value, ms.value
+
+    def pair(self, mode, max_insert=0, unpaired_edits=0, out=None):
+        """mtsv_fold_pair: reads 2p and 2p + 1 of this fold are the mates of pair p; the Fold out (this device, GRAIN_TAXID)
+        becomes the fold of the pairs: one record (p, TaxID, edit) per TaxID that PAIR_BOTH, PAIR_EITHER or PAIR_PROPER keeps.
+        Returns (stats as a dict, device ms)"""
+        st, ms = PairStats(), C.c_float()
+        _check(lib().mtsv_fold_pair(self.h, int(mode), int(max_insert), int(unpaired_edits), out.h if out is not None else None,
+                                    C.byref(st), C.byref(ms)))
+        return st.as_dict(), ms.value
 
     def expand(self, src, dupmap):
         """mtsv_fold_expand: this fold := for every read of dupmap's last take the records the Fold src holds for the read's

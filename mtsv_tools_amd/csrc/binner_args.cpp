@@ -87,7 +87,27 @@ void print_help() {
            "at a time, at most two in host memory; the files are the same),\n"
            "--dedup (only with --fold-on-gpu: reads of a batch that are identical base for base after normalisation are binned\n"
            "once, on the GPU, and the records of the one that ran are copied to the others on the GPU before results, --report\n"
-           "and --matched / --unmatched are derived; every read keeps its own ID and every file is the same)\n");
+           "and --matched / --unmatched are derived; every read keeps its own ID and every file is the same),\n"
+           "--interleaved [--pair-mode both|either|proper] [--max-insert N] [--unpaired-penalty N] (only with --fold-on-gpu:\n"
+           "paired-end reads.  The input is one FASTA/FASTQ file whose records alternate mate 1 and mate 2; the reads are binned\n"
+           "and folded as always, and after the last chunk the two mates' records are joined on the GPU into one line per pair,\n"
+           "PAIR_ID:TAXID=EDIT,..., PAIR_ID the mates' common ID or their common stem when the IDs end in /1 and /2.  proper (the\n"
+           "default): a TaxID is kept when both mates hit the same GI of it within --max-insert bases (default 1000) of each\n"
+           "other, with the smallest sum of the two edits; the mates' orientation is not checked.  both: when both mates hit the\n"
+           "TaxID, the sum of their smallest edits.  either: every TaxID either mate hit; one that only one mate hit carries that\n"
+           "mate's edit plus --unpaired-penalty, which must be given.  --report counts pairs.  An odd number of records, or mates\n"
+           "whose IDs do not agree, is an input error.  Not with --output-format long, --matched / --unmatched or an odd\n"
+           "--read-offset; a run that would resume an existing results file is refused)\n");
+}
+
+// a number in 0 .. 2^32 - 1, or the usage error of `flag`
+uint32_t parse_u32_flag(const std::string& v, const char* flag) {
+    char* e = nullptr;
+    errno = 0;
+    const unsigned long long n = strtoull(v.c_str(), &e, 10);
+    if (v.empty() || v[0] == '-' || *e || errno || n > 0xffffffffull)
+        usage_error(std::string("Invalid value for '") + flag + " <N>': a number between 0 and 4294967295 is expected");
+    return (uint32_t)n;
 }
 
 // --merge-on-gpu and --fold-on-gpu alike: a list of chunks, one device, and not --parse-only
@@ -164,6 +184,20 @@ void check_combinations(const Args& a) {
     }
     if (a.fold_prefetch && !a.fold_gpu) usage_error("The argument '--fold-prefetch' requires '--fold-on-gpu'");
     if (a.dedup && !a.fold_gpu) usage_error("The argument '--dedup' requires '--fold-on-gpu'");
+    if (!a.interleaved) {
+        if (!a.pair_mode.empty()) usage_error("The argument '--pair-mode <MODE>' requires '--interleaved'");
+        if (!a.max_insert.empty()) usage_error("The argument '--max-insert <N>' requires '--interleaved'");
+        if (!a.unpaired_penalty.empty()) usage_error("The argument '--unpaired-penalty <N>' requires '--interleaved'");
+    } else {
+        if (!a.fold_gpu) usage_error("The argument '--interleaved' requires '--fold-on-gpu'");
+        if (a.output_format == "long") usage_error("The argument '--interleaved' cannot be used with '--output-format long': a pair's line is PAIR_ID:TAXID=EDIT,...");
+        if (partition) usage_error("The argument '--interleaved' cannot be used with '--matched <PATH>' / '--unmatched <PATH>'");
+        if (filtered) usage_error("The argument '--interleaved' cannot be used with '--filter-index <INDEX>'");
+        if (!a.pair_mode.empty() && a.pair_mode != "both" && a.pair_mode != "either" && a.pair_mode != "proper")
+            usage_error("'" + a.pair_mode + "' isn't a valid value for '--pair-mode <MODE>' [possible values: both, either, proper]");
+        if (a.pair_mode == "either" && a.unpaired_penalty.empty())
+            usage_error("The argument '--pair-mode either' requires '--unpaired-penalty <N>': what a mate that did not align costs cannot be derived from the records");
+    }
     if (a.merge_gpu) require_chunks_on_one_device(a, "--merge-on-gpu", "every chunk is made resident on that device");
     if (a.fold_gpu) {
         if (a.merge_gpu) usage_error("The argument '--merge-on-gpu' cannot be used with '--fold-on-gpu'");
@@ -230,6 +264,9 @@ void resolve_results(const Args& a, Run& run) {
     uint64_t resume = 0;
     if (a.force) {
         logmsg("INFO", "Forcing overwrite of " + a.results);
+    } else if (exists && run.interleaved) {
+        // (the resume scan looks for read IDs in the results file, and this one holds pair IDs)
+        refuse("results file " + a.results + " exists and the run would resume it; '--interleaved' does not resume (its lines carry pair IDs, not read IDs): give --force-overwrite or another results path");
     } else if (exists && run.partition) {
         // a resumed run sees only the reads after the last one in the results file: the partition files would be incomplete
         refuse("results file " + a.results + " exists and the run would resume it; '--matched' / '--unmatched' need the whole input: give --force-overwrite or another results path");
@@ -300,6 +337,10 @@ Args parse_args(int argc, char** argv) {
         else if (key == "--text-on-gpu") a.text_gpu = true;
         else if (key == "--fold-prefetch") a.fold_prefetch = true;
         else if (key == "--dedup") a.dedup = true;
+        else if (key == "--interleaved") a.interleaved = true;
+        else if (key == "--pair-mode") a.pair_mode = val();
+        else if (key == "--max-insert") a.max_insert = val();
+        else if (key == "--unpaired-penalty") a.unpaired_penalty = val();
         else if (key == "--fold-reads") a.fold_reads = parse_reads(val(), "--fold-reads", 0xffffffffull);
         else if (key == "-h" || key == "--help") {
             print_help();
@@ -336,7 +377,16 @@ Run resolve(const Args& a) {
     run.batch_reads = a.batch_reads;
     run.fold_reads = a.fold_reads;
     run.long_fmt = a.output_format == "long";
+    run.interleaved = a.interleaved;
+    if (a.interleaved) {
+        run.pair_mode = a.pair_mode == "both" ? MTSV_PAIR_BOTH : a.pair_mode == "either" ? MTSV_PAIR_EITHER : MTSV_PAIR_PROPER;
+        if (!a.max_insert.empty()) run.max_insert = parse_u32_flag(a.max_insert, "--max-insert");
+        if (!a.unpaired_penalty.empty()) run.unpaired_penalty = parse_u32_flag(a.unpaired_penalty, "--unpaired-penalty");
+        if (run.pair_mode == MTSV_PAIR_EITHER && run.unpaired_penalty >= 0x80000000u)
+            usage_error("Invalid value for '--unpaired-penalty <N>': a number below 2147483648 is expected");
+    }
     resolve_params(a, run);
+    if (run.interleaved && (run.read_offset & 1)) refuse("'--interleaved' needs an even '--read-offset': the reads are skipped pair by pair");
     resolve_results(a, run);
     return run;
 }

@@ -13,6 +13,8 @@ struct Args {
     std::string threads = "4", edit = "0.13", seed_size = "18", seed_interval = "15", min_seed = "0.015",
                 max_hits = "2000", tune_max_hits = "200", max_assign, max_cand, read_offset = "0";
     bool verbose = false, force = false, parse_only = false, merge_gpu = false, fold_gpu = false, text_gpu = false, fold_prefetch = false, dedup = false;
+    bool interleaved = false;                             // --interleaved: the input's records alternate mate 1 and mate 2
+    std::string pair_mode, max_insert, unpaired_penalty;  // --pair-mode, --max-insert, --unpaired-penalty: "" when not given
     uint64_t fold_reads = 16ull << 20;  // --fold-reads: reads per super-batch of --fold-on-gpu (every chunk is loaded once per super-batch)
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
@@ -42,6 +44,10 @@ struct Run {
     Mode mode = Mode::single;
     bool partition = false, filtered = false, parse_only = false;
     bool text_gpu = false, fold_prefetch = false, dedup = false;
+    bool interleaved = false;              // reads 2p and 2p + 1 of the input are the mates of pair p
+    int pair_mode = MTSV_PAIR_PROPER;      // --pair-mode
+    uint32_t max_insert = 1000;            // --max-insert
+    uint32_t unpaired_penalty = 0;         // --unpaired-penalty (--pair-mode either)
     uint64_t batch_reads = 0, fold_reads = 0;
 
     bool have_results() const { return !results.empty(); }

@@ -15,10 +15,16 @@
 // records out into the piece's fold proper, which everything else is derived from as without the flag.  The map is
 // computed again for every chunk, into the piece's mtsv_dupmap, with the same content every time: hashing the piece
 // once per chunk is the price of keeping no reads resident between chunks (a chunk's index may need that room).
+// --interleaved: reads 2p and 2p + 1 of the input are the mates of pair p, so a piece holds an even number of reads: where a
+// block of the parser ends on a mate 1, that read waits for the next block.  The reads are binned and folded as without the
+// flag (at MTSV_GRAIN_LONG for --pair-mode proper, which needs the mates' GIs and offsets); after the last chunk, and after
+// the expansion of --dedup, mtsv_fold_pair joins a piece's fold into its fold of PAIRS, which the result lines (one per
+// pair, under the mates' common ID) and the report are derived from.
 #include <unistd.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <thread>
 
 #include "binner_run.hpp"
@@ -57,19 +63,28 @@ struct JoinLoader {  // (no loader thread outlives flush())
 class FoldedRun {
    public:
     FoldedRun(const Run& run, Producer& producer, Outputs& outputs)
-        : run_(run), producer_(producer), out_(outputs), dev_(run.devices[0]), grain_(run.long_fmt ? MTSV_GRAIN_LONG : MTSV_GRAIN_TAXID),
-          piece_reads_(block_reads_max(run.batch_reads)), piece_bases_(workspace_bases(piece_reads_, producer.warm_len(), 1 << 22)) {
+        : run_(run), producer_(producer), out_(outputs), dev_(run.devices[0]),
+          grain_(run.long_fmt || (run.interleaved && run.pair_mode == MTSV_PAIR_PROPER) ? MTSV_GRAIN_LONG : MTSV_GRAIN_TAXID),
+          // (--interleaved: a piece may begin with the read the block before it ended on)
+          piece_reads_(block_reads_max(run.batch_reads) + (run.interleaved ? 1 : 0)),
+          piece_bases_(workspace_bases(piece_reads_, producer.warm_len(), 1 << 22)),
+          // (... and a super-batch holds whole pairs)
+          fold_reads_(run.interleaved ? std::max<uint64_t>(run.fold_reads & ~1ull, 2) : run.fold_reads) {
         pre_.chunk = run.index_paths.size();
     }
     int run();
 
    private:
+    bool take_block(std::unique_ptr<ReadBlock> rb);
+    bool take_pairs(std::unique_ptr<ReadBlock> rb);
     bool take_piece(std::unique_ptr<ReadBlock> rb);
     bool flush(bool more);  // the super-batch collected so far, through every chunk; more: another one follows
     bool make_folds();
     bool run_chunk(size_t c, bool more);
     bool write_piece(size_t k);
-    bool write_results(const ReadBlock& rb, mtsv_fold* f);
+    bool write_results(const std::string& ids, const std::vector<uint64_t>& id_off, mtsv_fold* f);
+    bool pair_piece(size_t k, const ReadBlock& rb, mtsv_fold* f);
+    bool input_error(const std::string& what);
     bool write_sides(const ReadBlock& rb, mtsv_fold* f);
     void print_timing() const;
     int leave(int c);
@@ -78,13 +93,20 @@ class FoldedRun {
     Producer& producer_;
     Outputs& out_;
     const int dev_, grain_;
-    const uint64_t piece_reads_, piece_bases_;
+    const uint64_t piece_reads_, piece_bases_, fold_reads_;
     ExitCode code_;
     Prefetch pre_;
     std::vector<std::unique_ptr<ReadBlock>> pieces_;
     std::vector<FoldPtr> folds_;  // one per piece of a super-batch, kept from super-batch to super-batch
     std::vector<FoldPtr> rep_folds_;  // --dedup: the folds of representatives, and the pieces' maps
     std::vector<DupmapPtr> dupmaps_;
+    std::vector<FoldPtr> pair_folds_;    // --interleaved: the folds of pairs
+    std::unique_ptr<ReadBlock> carry_;   // ... and a mate 1 whose mate 2 is the next block's first read
+    std::string pair_ids_;               // the IDs of a piece's pairs, as a block holds its reads'
+    std::vector<uint64_t> pair_id_off_;
+    mtsv_pair_stats pair_stats_ = {0, 0, 0, 0, 0};
+    uint64_t pairs_done_ = 0, reads_taken_ = 0;
+    float pair_device_ms_ = 0;
     TaxaSum taxa_;
     uint64_t dedup_reads_ = 0, dedup_distinct_ = 0;
     uint64_t super_reads_ = 0, n_super_ = 0, reads_done_ = 0, reads_matched_ = 0;
@@ -105,6 +127,11 @@ bool FoldedRun::make_folds() {
         rep_folds_.push_back(std::move(f));
         if (mtsv_dupmap_create(dev_, out(m)) != MTSV_OK) return code_.lib_error();
         dupmaps_.push_back(std::move(m));
+    }
+    while (run_.interleaved && pair_folds_.size() < pieces_.size()) {
+        FoldPtr f;
+        if (mtsv_fold_create(dev_, MTSV_GRAIN_TAXID, out(f)) != MTSV_OK) return code_.lib_error();
+        pair_folds_.push_back(std::move(f));
     }
     for (size_t k = 0; k < pieces_.size(); k++)
         if (mtsv_fold_reset((run_.dedup ? rep_folds_[k] : folds_[k]).get(), pieces_[k]->n()) != MTSV_OK) return code_.lib_error();
@@ -174,24 +201,64 @@ bool FoldedRun::run_chunk(size_t c, bool more) {
     return true;
 }
 
-bool FoldedRun::write_results(const ReadBlock& rb, mtsv_fold* f) {
+// the input is not what the flags say it is: the exit code and the wording of a record the parser refuses (binner.rs:81-84)
+bool FoldedRun::input_error(const std::string& what) {
+    logmsg("ERROR", "Unable to read from input file: " + what);
+    code_.set(12);
+    return false;
+}
+
+// --interleaved: the piece's fold joined into its fold of pairs, and the pairs' IDs
+bool FoldedRun::pair_piece(size_t k, const ReadBlock& rb, mtsv_fold* f) {
+    pair_ids_.clear();
+    pair_id_off_.assign(1, 0);
+    for (uint64_t p = 0; 2 * p + 1 < rb.n(); p++) {
+        const char *a = rb.ids.data() + rb.id_off[2 * p], *b = rb.ids.data() + rb.id_off[2 * p + 1];
+        const size_t la = strlen(a), lb = strlen(b);
+        size_t keep = la;
+        if (la != lb || memcmp(a, b, la) != 0) {
+            const bool stems = la == lb && la >= 2 && memcmp(a, b, la - 2) == 0 && a[la - 2] == '/' && a[la - 1] == '1' && b[la - 2] == '/' && b[la - 1] == '2';
+            if (!stems)
+                return input_error("the mates of pair " + std::to_string(run_.read_offset / 2 + pairs_done_ + p) + " of an interleaved input are named '" + a +
+                                   "' and '" + b + "': neither one ID nor a stem with /1 and /2");
+            keep = la - 2;
+        }
+        pair_ids_.append(a, keep);
+        pair_ids_.push_back('\0');
+        pair_id_off_.push_back(pair_ids_.size());
+    }
+    mtsv_pair_stats st;
+    float ms = 0;
+    if (mtsv_fold_pair(f, run_.pair_mode, run_.max_insert, run_.unpaired_penalty, pair_folds_[k].get(), &st, &ms) != MTSV_OK) return code_.lib_error();
+    pair_device_ms_ += ms;
+    pair_stats_.pairs += st.pairs;
+    pair_stats_.both_mates_hit += st.both_mates_hit;
+    pair_stats_.one_mate_hit += st.one_mate_hit;
+    pair_stats_.joined += st.joined;
+    pair_stats_.records += st.records;
+    pairs_done_ += st.pairs;
+    return true;
+}
+
+bool FoldedRun::write_results(const std::string& ids, const std::vector<uint64_t>& id_off, mtsv_fold* f) {
     ArrayPtr<char> text;
     uint64_t len = 0;
+    const uint64_t n_ids = id_off.size() - 1;
     int rc;
     if (run_.text_gpu) {  // (--text-on-gpu: the lines are written where the records are)
         float ms = 0;
-        rc = mtsv_fold_format_text(f, rb.ids.data(), rb.id_off.data(), rb.n(), out(text), &len, &ms);
+        rc = mtsv_fold_format_text(f, ids.data(), id_off.data(), n_ids, out(text), &len, &ms);
         text_device_ms_ += ms;
     } else if (run_.long_fmt) {
         ArrayPtr<mtsv_assignment_gi> recs;
         uint64_t n_recs = 0;
         rc = mtsv_fold_download_gi(f, out(recs), &n_recs);
-        if (rc == MTSV_OK) rc = mtsv_format_assignments_gi(recs.get(), n_recs, rb.ids.data(), rb.id_off.data(), rb.n(), out(text), &len);
+        if (rc == MTSV_OK) rc = mtsv_format_assignments_gi(recs.get(), n_recs, ids.data(), id_off.data(), n_ids, out(text), &len);
     } else {
         ArrayPtr<mtsv_assignment> recs;
         uint64_t n_recs = 0;
         rc = mtsv_fold_download(f, out(recs), &n_recs);
-        if (rc == MTSV_OK) rc = mtsv_format_assignments(recs.get(), n_recs, rb.ids.data(), rb.id_off.data(), rb.n(), out(text), &len);
+        if (rc == MTSV_OK) rc = mtsv_format_assignments(recs.get(), n_recs, ids.data(), id_off.data(), n_ids, out(text), &len);
     }
     if (rc != MTSV_OK) return code_.lib_error();
     if (!write_all(out_.out_fd, text.get(), len)) {
@@ -232,7 +299,11 @@ bool FoldedRun::write_piece(size_t k) {
         if (mtsv_fold_expand(f, rep_folds_[k].get(), dupmaps_[k].get(), &ms) != MTSV_OK) return code_.lib_error();
         expand_device_ms_ += ms;
     }
-    if (out_.out_fd >= 0 && !write_results(rb, f)) return false;
+    if (run_.interleaved) {  // (from here on the piece is its pairs)
+        if (!pair_piece(k, rb, f)) return false;
+        f = pair_folds_[k].get();
+    }
+    if (out_.out_fd >= 0 && !(run_.interleaved ? write_results(pair_ids_, pair_id_off_, f) : write_results(rb.ids, rb.id_off, f))) return false;
     if (run_.have_report()) {
         ArrayPtr<mtsv_taxon_stats> rows;
         uint64_t n_rows = 0, reads = 0;
@@ -266,10 +337,43 @@ bool FoldedRun::take_piece(std::unique_ptr<ReadBlock> rb) {
     if (rb->n() > piece_reads_ || rb->bases.size() > piece_bases_)
         return code_.lib_error("a batch of reads holds more than " + std::to_string(piece_reads_) + " reads or " + std::to_string(piece_bases_) +
                                " bases, which the chunks' workspaces are sized for: give a smaller --batch-reads");
-    if (!pieces_.empty() && super_reads_ + rb->n() > run_.fold_reads && !flush(true)) return false;
+    if (!pieces_.empty() && super_reads_ + rb->n() > fold_reads_ && !flush(true)) return false;
     super_reads_ += rb->n();
+    reads_taken_ += rb->n();
     pieces_.push_back(std::move(rb));
     return true;
+}
+
+// a block of the parser, cut where it holds more than a super-batch
+bool FoldedRun::take_block(std::unique_ptr<ReadBlock> rb) {
+    // (the parser hands out blocks of up to one and a half batches: a super-batch holds at most --fold-reads reads)
+    if (rb->n() <= fold_reads_) return take_piece(std::move(rb));
+    for (uint64_t from = 0; from < rb->n(); from += fold_reads_) {
+        auto part = producer_.pool.get();
+        part->append(*rb, from, std::min<uint64_t>(from + fold_reads_, rb->n()));
+        if (!take_piece(std::move(part))) return false;
+    }
+    producer_.pool.put(std::move(rb));
+    return true;
+}
+
+// --interleaved: the read a block ended on goes in front of the next block, and a block that ends on a mate 1 gives it up
+bool FoldedRun::take_pairs(std::unique_ptr<ReadBlock> rb) {
+    const bool carried = carry_ && carry_->n();
+    if (!carried && !(rb->n() & 1)) return take_block(std::move(rb));
+    auto part = producer_.pool.get();
+    if (carried) part->append(*carry_);
+    const uint64_t whole = rb->n() - ((part->n() + rb->n()) & 1);
+    part->append(*rb, 0, whole);
+    if (!carry_) carry_.reset(new ReadBlock);
+    carry_->clear();
+    carry_->append(*rb, whole);
+    producer_.pool.put(std::move(rb));
+    if (!part->n()) {
+        producer_.pool.put(std::move(part));
+        return true;
+    }
+    return take_block(std::move(part));
 }
 
 // MTSV_CLI_TIMING=1: where a folded run spends its time (seconds; tools/fold_ab.py reads this line)
@@ -285,6 +389,7 @@ void FoldedRun::print_timing() const {
             prefetch_note);
     if (run_.text_gpu) fprintf(stderr, "[cli text timing] text_on_gpu device %.3f ms\n", text_device_ms_);
     if (run_.dedup) fprintf(stderr, "[cli dedup timing] take_unique device %.3f ms, expand device %.3f ms\n", dedup_device_ms_, expand_device_ms_);
+    if (run_.interleaved) fprintf(stderr, "[cli pair timing] pair device %.3f ms\n", pair_device_ms_);
 }
 
 // every way out of the folded run ends alike: the process leaves at once, or (MTSV_CLI_CLEAN_EXIT=1) frees what it holds --
@@ -303,21 +408,16 @@ int FoldedRun::run() {
     if (!getenv("MTSV_VERIFY")) mtsv_set_default_verify_mode(MTSV_VERIFY_EDIT_FIRST);
     logmsg("INFO", "Beginning queries.");
     const double t_begin = now_s();
-    const bool parsed = producer_.produce(std::min<uint64_t>(run_.batch_reads, run_.fold_reads), [&](std::unique_ptr<ReadBlock> rb) {
-        // (the parser hands out blocks of up to one and a half batches: a super-batch holds at most --fold-reads reads)
-        if (rb->n() <= run_.fold_reads) return take_piece(std::move(rb));
-        for (uint64_t from = 0; from < rb->n(); from += run_.fold_reads) {
-            auto part = producer_.pool.get();
-            part->append(*rb, from, std::min<uint64_t>(from + run_.fold_reads, rb->n()));
-            if (!take_piece(std::move(part))) return false;
-        }
-        producer_.pool.put(std::move(rb));
-        return true;
+    const bool parsed = producer_.produce(std::min<uint64_t>(run_.batch_reads, fold_reads_), [&](std::unique_ptr<ReadBlock> rb) {
+        return run_.interleaved ? take_pairs(std::move(rb)) : take_block(std::move(rb));
     });
     if (!parsed && !code_.failed()) {
         logmsg("ERROR", "Unable to read from input file: " + producer_.error());
         code_.set(12);  // binner.rs:81-84
     }
+    if (!code_.failed() && carry_ && carry_->n())
+        input_error("an interleaved input of an odd number of records: record " + std::to_string(run_.read_offset + reads_taken_) + " ('" +
+                    carry_->ids.c_str() + "') has no mate");
     if (!code_.failed()) flush(false);
     if (code_.failed()) return leave(code_.get());
     RunEnd end;
@@ -326,6 +426,9 @@ int FoldedRun::run() {
     end.reads_matched = reads_matched_;
     end.info = [&] {
         if (run_.dedup) logmsg("INFO", "Collapsed " + std::to_string(dedup_reads_) + " reads to " + std::to_string(dedup_distinct_) + " distinct sequences.");
+        if (run_.interleaved)
+            logmsg("INFO", "Joined " + std::to_string(pair_stats_.pairs) + " pairs: both mates hit " + std::to_string(pair_stats_.both_mates_hit) + ", one mate hit " +
+                               std::to_string(pair_stats_.one_mate_hit) + ", joined " + std::to_string(pair_stats_.joined) + ".");
     };
     end.taxa = &taxa_;
     if (const int c = finish(run_, out_, end)) return leave(c);

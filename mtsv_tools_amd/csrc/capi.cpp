@@ -693,6 +693,13 @@ int mtsv_fold_lca(mtsv_fold* f, const mtsv_taxonomy* tx, uint32_t edit_slack, mt
     })
 }
 
+// ---- read pairs: the mates' records joined (pair.hip, k_pair.hip) ----
+static_assert(sizeof(mtsv_pair_stats) == 40, "the pair stats");
+int mtsv_fold_pair(mtsv_fold* f, int mode, uint32_t max_insert, uint32_t unpaired_edits, mtsv_fold* out, mtsv_pair_stats* stats, float* device_ms) {
+    if (!f || !out) return fail_arg("null argument");
+    GUARD(f->impl.pair(mode, max_insert, unpaired_edits, &out->impl, stats, device_ms))
+}
+
 int mtsv_format_clade_report(const mtsv_clade_stats* rows, uint64_t n_rows, uint64_t total_reads, const mtsv_taxonomy* tx, char** out,
                              uint64_t* out_len) {
     if ((!rows && n_rows) || !out || !out_len) return fail_arg("null argument");

@@ -32,6 +32,8 @@ Fold::Fold(int device_, int grain_) : device(device_), grain(grain_) {
     text_tile = tile_from_env("MTSV_TEXT_TILE", kTextTile, 2, kTextTileMax);
     parse_tile = tile_from_env("MTSV_PARSE_TILE", kParseTile, 64, kParseTileMax);
     lca_tile = tile_from_env("MTSV_LCA_TILE", kLcaTile, 64, kLcaTileMax);
+    pair_tile = tile_from_env("MTSV_PAIR_TILE", kPairTile, 64, kPairTileMax);
+    if (const char* e = getenv("MTSV_PAIR_LANE_MAX")) pair_lane_max = (uint32_t)std::min<uint64_t>(strtoull(e, nullptr, 10), kPairLaneMaxMax);
     trace = getenv("MTSV_TRACE") != nullptr;
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -44,6 +46,7 @@ Fold::~Fold() {
     text.reset();
     parser.reset();
     lca_state.reset();
+    pair_state.reset();
     if (stream) (void)hipStreamDestroy(stream);
 }
 

@@ -6,6 +6,7 @@
 #include "../../include/mtsv_amd.h"
 #include "batch.hpp"
 #include "lca.hpp"
+#include "pair.hpp"
 #include "parse.hpp"
 #include "text.hpp"
 
@@ -40,6 +41,9 @@ struct Fold {
     std::unique_ptr<TextParser> parser;   // created by the first add_text
     uint32_t lca_tile = kLcaTile;         // MTSV_LCA_TILE, read at creation (tests)
     std::unique_ptr<LcaState> lca_state;  // created by the first lca
+    uint32_t pair_tile = kPairTile;          // MTSV_PAIR_TILE, read at creation (tests)
+    uint32_t pair_lane_max = kPairLaneMax;   // MTSV_PAIR_LANE_MAX, read at creation (tests): 0 sends every window to the wavefront tier
+    std::unique_ptr<PairState> pair_state;   // created by the first pair
 
     Fold(int device, int grain);
     ~Fold();
@@ -63,8 +67,12 @@ struct Fold {
     // one), which becomes as after reset(n_reads) with those records; the clade rows in preorder (rows may be null); this
     // fold is not changed
     void lca(const Taxonomy& tx, uint32_t edit_slack, Fold* out, std::vector<mtsv_clade_stats>* rows, uint64_t* total_reads, float* device_ms);
+    // reads 2p and 2p + 1 are the mates of pair p: one record (p, TaxID, edit) per TaxID the mode keeps for the pair (pair.hip,
+    // k_pair.hip) into `out` (a fold of this device at MTSV_GRAIN_TAXID, not this one), which becomes as after reset(n_reads / 2)
+    // with those records and this fold's TaxID union; stats may be null; this fold is not changed
+    void pair(int mode, uint32_t max_insert, uint32_t unpaired_edits, Fold* out, mtsv_pair_stats* stats, float* device_ms);
 
-    // A write of a whole new record list (fold_in, lca, DupMap::expand) is staged: dst is the array that is not current, or,
+    // A write of a whole new record list (fold_in, lca, pair, DupMap::expand) is staged: dst is the array that is not current, or,
     // when that is too small, the first of a new pair, which the fold takes only with commit.  A Staged that is not
     // committed frees its pair; one that is frees the pair the fold had.
     struct Staged {

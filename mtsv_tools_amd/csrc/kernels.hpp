@@ -408,5 +408,41 @@ void launch_fan_count(hipStream_t s, int grain, uint32_t n_entries, const uint32
                       uint32_t* first, uint32_t* cnt, uint64_t* ctr);
 void launch_fan_write(hipStream_t s, int grain, uint32_t n_entries, const uint32_t* read, const uint32_t* first, const uint32_t* off, const void* rec,
                       uint32_t tile, uint32_t total, void* out);
+// k_pair.hip: the mates of read pairs joined (mode: the values of MTSV_PAIR_*).  rec: n records of the grain ordered by its key,
+// reads 2p and 2p + 1 the mates of pair p, n_reads = 2P of them (below 2^32); PROPER needs kCollapseGrainLong.  A RUN is the
+// records of one (read, tax_id), numbered by its head (its slot); there are at most n.  ctr: kPairCounters u64, zeroed by the
+// caller.  NONE is all ones.
+//   bounds: off[r] = the first record with read >= r, r in 0 .. n_reads
+//   join:   val[i], and add[i] at heads (n u32 each), as the head of k_pair.hip defines them; records whose window in the other
+//           mate's stretch is longer than lane_max go to list (n u32; ctr[kPairCtrList] of them); ctr[kPairCtrBadEdit] += the
+//           records with edit >= 2^31, ctr[kPairCtrBeyond] += those with read >= n_reads (they join nothing)
+//   wave:   the listed records' windows, a wavefront each; after join on the same stream
+//   heads:  tile_cnt[t] = the heads of tile t (a power of two, 64 .. kPairTileMax; pair_tiles(n, tile) tiles)
+//   (launch_scan over tile_cnt: tile_off[0 .. tiles], tile_off[tiles] = n_slots)
+//   min:    m[slot] = the smallest val of the run (m: n_slots_cap u32, set to all ones by the caller), slot_rec[slot] = (read as
+//           two words, tax_id, add) (n_slots_cap uint4)
+//   flags:  m[slot] = the run's value m + add, or NONE when either is; flag_a[slot] = it has a value and is mate 0's,
+//           flag_b[slot] (may be null) = it has one and is mate 1's; both zero from *n_slots to n_slots_cap
+//   (launch_scan over flag_a and flag_b: pos_a, pos_b, n_slots_cap + 1 entries each)
+//   write:  (read >> 1, tax_id, value) of the flagged slots to out_a[pos_a] / out_b[pos_b] (16-byte records; pos_b, out_b may
+//           be null); nothing is written at or behind n_a / n_b
+//   stats:  ctr[kPairCtrBoth] / [kPairCtrOne] += the pairs both / exactly one of whose mates have a record;
+//           ctr[kPairCtrJoined] += the distinct reads of out[0 .. n_out) (16-byte records ordered by read)
+constexpr int kPairBoth = 0, kPairEither = 1, kPairProper = 2;
+constexpr uint32_t kPairTileMax = 1024, kPairTile = 1024, kPairLaneMax = 16, kPairLaneMaxMax = 1024;
+constexpr uint32_t kPairCtrList = 0, kPairCtrBadEdit = 1, kPairCtrBeyond = 2, kPairCtrBoth = 3, kPairCtrOne = 4, kPairCtrJoined = 5, kPairCounters = 6;
+uint32_t pair_tiles(uint64_t n, uint32_t tile);
+void launch_pair_bounds(hipStream_t s, int grain, const void* rec, uint32_t n, uint64_t n_reads, uint32_t* off);
+void launch_pair_join(hipStream_t s, int grain, int mode, const void* rec, uint32_t n, uint64_t n_reads, const uint32_t* off, uint32_t max_insert,
+                      uint32_t unpaired, uint32_t lane_max, uint32_t* val, uint32_t* add, uint32_t* list, uint64_t* ctr);
+void launch_pair_wave(hipStream_t s, int grain, int mode, const void* rec, uint32_t n, uint64_t n_reads, const uint32_t* off, uint32_t max_insert,
+                      const uint32_t* list, const uint64_t* ctr, uint32_t* val, uint32_t* add);
+void launch_pair_heads(hipStream_t s, int grain, const void* rec, uint32_t n, uint32_t tile, uint32_t* tile_cnt);
+void launch_pair_min(hipStream_t s, int grain, const void* rec, uint32_t n, uint32_t tile, const uint32_t* tile_off, const uint32_t* val,
+                     const uint32_t* add, uint32_t n_slots_cap, uint32_t* m, void* slot_rec);
+void launch_pair_flags(hipStream_t s, const uint64_t* n_slots, uint32_t n_slots_cap, const void* slot_rec, uint32_t* m, uint32_t* flag_a, uint32_t* flag_b);
+void launch_pair_write(hipStream_t s, const uint64_t* n_slots, uint32_t n_slots_cap, const void* slot_rec, const uint32_t* m, const uint32_t* pos_a,
+                       const uint32_t* pos_b, uint32_t n_a, uint32_t n_b, void* out_a, void* out_b);
+void launch_pair_stats(hipStream_t s, const uint32_t* off, uint64_t n_pairs, const void* out, uint32_t n_out, uint64_t* ctr);
 
 }  // namespace mtsv
