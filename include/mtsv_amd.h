@@ -306,6 +306,8 @@ typedef struct {
  * device (the index's distinct TaxIDs, four counters each) is created when it is first switched on; the environment
  * variable MTSV_REPORT_DENSE_MAX, read then, moves the number of taxa up to which the workgroups count in one LDS
  * counter per (TaxID, category) instead of an LDS hash table (tests; at most 4095); MTSV_REPORT_HASH_SLOTS shrinks that table (tests). */
+/* Switching the report off keeps what it has counted: runs while it is off add nothing, and switching it on again goes on
+ * from those counts (only reset != 0 of mtsv_batch_taxa_report zeroes them). */
 int mtsv_batch_set_taxa_report(mtsv_batch *b, int on);
 /* Rows for every TaxID with a non-zero counter, ascending tax_id; the caller frees *rows with mtsv_free.  device_ms
  * (may be NULL): device time of the report's kernels since the last reset.  reset != 0 zeroes the accumulation after
@@ -347,6 +349,20 @@ int mtsv_batch_set_match_flags(mtsv_batch *b, int mode);
  * mtsv_batch_run_host_parts in order); bits at and above *n_reads are 0; *words holds (*n_reads + 63) / 64 words (at
  * least one) and is malloc'd (mtsv_free); *n_matched is the number of set bits, counted on the device.  No run since the
  * flags were switched on: *n_reads is 0.  MTSV_E_ARG when the mode is MTSV_MATCH_OFF. */
+/* "Switched on" is the step from MTSV_MATCH_OFF to either other mode, and for the assignments from MTSV_ASSIGN_OFF: a change
+ * between the two modes that are on keeps what the last run left.
+ * What the observers of a workspace's LAST RUN return -- mtsv_batch_download, _stats_get, _match_flags, _download_assignments*,
+ * _format_text -- is defined from the moment a run (or a merge into the workspace) completes until the workspace is given
+ * other reads (mtsv_batch_upload, _take_reads, _copy_reads, _take_unique as dst) or a run on it fails; in between it is not
+ * defined, and callers look again after the next run.  A run that returns an error (MTSV_E_LIMIT for a read above 32767
+ * bases, MTSV_E_ARG for bad parameters) leaves the resident batch and its read map as they were; the taxa report has taken
+ * the passes that completed.  The hits of a host batch (mtsv_batch_run_host*) are handed out once: a second
+ * mtsv_batch_download after the same call is not defined (the assignments may be downloaded again, below).  The hits that a
+ * resident run (mtsv_batch_run) or a merge gathered stay in HBM until the next run, merge or change of the reads, and a change
+ * of the flags' or the assignments' mode does not touch them: mtsv_batch_download copies them out again, as often as it is
+ * called (zero hits while the mode is MTSV_ASSIGN_ONLY, and after a run in MTSV_MATCH_ONLY, which gathered none).  After a
+ * host batch a change of mode leaves mtsv_batch_download undefined until the next run; the one case that is refused is named
+ * at mtsv_batch_download_assignments. */
 int mtsv_batch_match_flags(mtsv_batch *b, uint64_t **words, uint64_t *n_reads, uint64_t *n_matched);
 
 /* ---- chaining workspaces: the unmatched (matched) reads of one run as the input of another, on the device ----------
@@ -637,6 +653,8 @@ int mtsv_batch_format_text(mtsv_batch *b, const char *ids, const uint64_t *id_of
  *   that differs from src's is MTSV_E_ARG before anything is written.  Also MTSV_E_ARG, with dst as it was: dst == src,
  *   different grains or devices, an m that holds no take.  2^32 expanded records or more: MTSV_E_LIMIT.  device_ms (may be
  *   NULL): count, scan and write. */
+/* A map whose last take was of a batch of zero reads holds a take of no entries: an empty src expands to an empty dst, any
+ * other src is MTSV_E_ARG (its records belong to no representative). */
 typedef struct mtsv_dupmap mtsv_dupmap;
 int mtsv_dupmap_create(int hip_device, mtsv_dupmap **out);
 void mtsv_dupmap_free(mtsv_dupmap *m);

@@ -2038,7 +2038,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                         for (uint64_t i = i0 + 1; i <= i1; i++) {
                             if (poff[i] < poff[i - 1]) bad.store(true);
                             const uint32_t v = (uint32_t)(b0 + (poff[i] - poff[0]) - seg_first_base);
-                            m = std::max(m, (uint32_t)(poff[i] - poff[i - 1]));
+                            m = std::max(m, (uint32_t)std::min<uint64_t>(poff[i] - poff[i - 1], UINT32_MAX));  // (a length of 2^32 must not read as 0)
                             ho[i] = v;
                         }
                         uint32_t cur = ml_all.load();
@@ -2049,6 +2049,10 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                     if (bad.load()) throw std::runtime_error("arg: read_off is not ascending");
                     ml = ml_all.load();
                 }
+                // before anything is staged: the cut takes at least one read, so one long read makes nb larger than h_stage
+                if (ml > kMaxReadLen)
+                    throw std::runtime_error("limit: read of " + std::to_string(ml) + " bases; this build verifies reads up to " +
+                                             std::to_string(kMaxReadLen));
                 const double t0 = now_s();
                 hipEvent_t ev = event_for(k);
                 if (nb) {

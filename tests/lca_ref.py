@@ -28,6 +28,7 @@ def number(s):
 class Taxonomy:
     def __init__(self, text):
         self.parent, self.rank, listed_on = {}, {}, {}
+        self._chains = None  # (chain() remembers its answers once the tree stands)
         raw = {}
         for no, line in enumerate(text.split("\n"), 1):
             if not line.strip(" \t\r"):
@@ -61,6 +62,7 @@ class Taxonomy:
                     raise Format(listed_on[a], f"TaxID {a} is its own ancestor")
                 seen.add(a)
                 a = self.parent[a]
+        self._chains = {}
         self.max_depth = max((self.depth(t) for t in self.parent), default=0)
 
     def parent_of(self, t):
@@ -73,10 +75,14 @@ class Taxonomy:
         return self.rank.get(t, UNKNOWN)
 
     def chain(self, t):
-        """t, its parent, ... , 0"""
+        """t, its parent, ... , 0 (the callers do not change the list)"""
+        if self._chains is not None and t in self._chains:
+            return self._chains[t]
         out = [t]
         while out[-1]:
             out.append(self.parent_of(out[-1]))
+        if self._chains is not None:
+            self._chains[t] = out
         return out
 
     def depth(self, t):

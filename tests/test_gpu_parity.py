@@ -247,6 +247,39 @@ def test_run_host_errors_surface_from_the_uploader(small_db):
     b.close()
 
 
+@pytest.mark.parametrize("plain", [True, False], ids=["h2d_plain", "h2d_default"])
+@pytest.mark.parametrize("call", ["run_host", "run_host_parts"])
+def test_one_read_larger_than_a_staging_chunk_is_refused_before_it_is_staged(small_db, call, plain, monkeypatch):
+    # one read of 34 Mi bases in ordinary (pageable) numpy memory: the chunk cut takes at least one read, so the chunk is
+    # larger than a page-locked staging buffer (32 MiB + 64).  The length is checked before the copy into that buffer.
+    if plain:
+        monkeypatch.setenv("MTSV_H2D_PLAIN", "1")
+    else:
+        monkeypatch.delenv("MTSV_H2D_PLAIN", raising=False)
+    ix, orc = small_db
+    ix.to_device(0)
+    b = M.Batch(ix, 0, 64, 1 << 16)
+    n = 34 << 20
+    bases = np.full(n, ord("A"), dtype=np.uint8)
+    off = np.array([0, n], dtype=np.uint64)
+    with pytest.raises(M.MtsvError) as e:
+        if call == "run_host":
+            b.run_host(bases, off)
+        else:
+            b.run_host_parts([helpers.reads_to_batch([b"ACGT" * 30] * 10), (bases, off)])
+    assert e.value.code == _lib.E_LIMIT and f"read of {n} bases" in str(e.value)
+    # and the same workspace then bins 300 ordinary reads as the oracle does
+    good, goff = M.synth_reads(ix, seed=77, n_reads=300, read_len=100)
+    if call == "run_host":
+        b.run_host(good, goff)
+    else:
+        b.run_host_parts([(good[:int(goff[120])], goff[:121]), (good[int(goff[120]):], goff[120:] - goff[120])])
+    want, _ = orc.bin_batch(good, goff, O.default_params(), threads=8)
+    assert len(want) > 100
+    assert_same_hits(b.download(), want)
+    b.close()
+
+
 def test_limits_and_argument_errors(small_db):
     ix, _ = small_db
     ix.to_device(0)
