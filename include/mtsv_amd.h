@@ -777,6 +777,81 @@ typedef struct {
 int mtsv_fold_pair(mtsv_fold *f, int mode, uint32_t max_insert, uint32_t unpaired_edits, mtsv_fold *out, mtsv_pair_stats *stats,
                    float *device_ms);
 
+/* ---- coverage per reference sequence: breadth and depth (cover.hip, k_cover.hip) ---------------------------------------------
+ * Everything above is counted per read.  An mtsv_coverage counts per reference POSITION: of every reference sequence how many
+ * reads and alignments it took, how many bases they span and how many of its positions at least one of them covers -- what
+ * tells a genome that is present (alignments all over it) from a conserved or contaminated stretch (a pile on 300 bases).
+ *
+ * A REFERENCE is a (tax_id, gi) with a length L, the end - start of its bin in an index.  The accumulator holds the table of
+ * references, ascending by (tax_id, gi) as unsigned; the same (tax_id, gi) given twice, in one index or in two chunks, is one
+ * reference with the larger L.  It is fed from folds at MTSV_GRAIN_LONG, which hold one (read, tax_id, gi, offset, edit) per
+ * alignment.  For a fold f, with read_len[n_reads] the reads' lengths in the caller's numbering (as at mtsv_fold_reset):
+ *   m is a read's smallest edit over all its records in f; a record COUNTS when edit <= m + edit_slack, the sum saturating as
+ *   in mtsv_fold_lca (0: the best alignments only; 0xffffffff: all).  A counted record (r, t, g, o, e) covers the interval
+ *   [o, min(o + read_len[r], L(t, g))) of reference (t, g).  Per reference, over every add_fold since the last reset:
+ *     alignments     the counted records
+ *     reads          the (read, tax_id, gi) runs of f that hold at least one counted record.  The reads of different calls are
+ *                    different reads: that is the caller's contract, as with reports of several folds
+ *     aligned_bases  the sum of the intervals' lengths
+ *     covered_bases  the positions of the reference that lie in at least one interval, of any call
+ *   All are 64-bit and exact; f is never changed.
+ *   `offset` is the forward-strand start of the accepted WINDOW, not of the match (mtsv_hit.offset): the match's start less up to
+ *   floor(edit_rate * read length) bases, cut at the bin's start.  An interval is therefore the read's footprint shifted left by
+ *   at most that much.  Over a genome the shift is immaterial for breadth; it is documented, not corrected.
+ *
+ * mtsv_coverage_create: an accumulator bound to a device, with an empty table; MTSV_COVER_TILE, MTSV_COVER_LANE_MAX, MTSV_TRACE
+ *   and MTSV_COVER_TIMING are read here.  Nothing but a stream is made on the device.
+ * mtsv_coverage_add_index: the bins' (tax_id, gi, end - start) of a loaded index join the table.  Host only: the index need
+ *   not be resident, and may be freed afterwards.  mtsv_coverage_add_refs: the same from arrays.
+ *   References are fixed once alignments exist: they may be added until the first add_fold after a create or reset that
+ *   is not refused (a fold without records counts; a refused call leaves the accumulator as it was, the open table
+ *   included).  After that, a call that brings a NEW reference or a LONGER length is MTSV_E_ARG and
+ *   changes nothing; one that brings only what the table holds (equal or shorter lengths) is accepted and does nothing --
+ *   mtsv-binner adds every chunk once per super-batch.
+ * mtsv_coverage_reset: counters and bitmap zero, the table stays and may grow again.
+ * mtsv_coverage_add_fold: as above.  device_ms (may be NULL): device time of the kernels.  A fold without records returns at
+ *   once: nothing is launched, *device_ms is 0.
+ * mtsv_coverage_rows: EVERY reference of the table, hit or not, ascending by (tax_id, gi): malloc'd, mtsv_free.  Before the
+ *   first add_fold nothing is launched.  The accumulator is not changed and goes on accumulating.
+ * mtsv_format_coverage_report (host only, needs no device): the TSV
+ *     taxid gi length reads alignments aligned_bases depth covered_bases breadth_pct
+ *   one line per reference with alignments > 0, in the rows' order; depth = aligned_bases / length, breadth_pct =
+ *   covered_bases / length * 100, both %.2f of doubles; a length of 0 prints 0.00 for both.  After the references of a TaxID
+ *   that has any such line, one ROLLUP line: gi is `*`, length sums ALL the taxon's references, hit or not (which is why rows
+ *   returns them all), the counters are summed, depth and breadth_pct are taken of the sums.  A taxon without a hit prints
+ *   nothing.
+ * On the device (k_cover.hip), on a stream of the accumulator's own.  The bitmap gives every reference a whole number of 64-bit
+ *   words, so that no word belongs to two references; it is laid out, with the table, by the first add_fold.  add_fold: the
+ *   first record of every read by a lower bound; the reads' smallest edits, a lane per read and the wavefront for a read of
+ *   more than 32 records; a lane per record that decides whether it counts, finds its reference by binary search and flags the
+ *   heads of the runs -- here the host reads the counters and refuses; then a lane per counted record ORs its interval into
+ *   the bitmap when it spans up to MTSV_COVER_LANE_MAX words (default 8, 0..1024; 0 sends every interval that is not empty on),
+ *   a longer one goes to a work list that a wavefront per entry strides; a word that holds the mask already is not written
+ *   again; the counters are combined per wavefront and reference before they are added.  rows: the bitmap is popcounted in
+ *   tiles of MTSV_COVER_TILE words (a power of two, 64..1024).  Every atomic is an integer OR or add: results are exact and do
+ *   not depend on either knob or on the order of execution.  Memory: 8 bytes per 64 bases of the table and 48 per reference,
+ *   and per call 24 bytes per record and 12 per read, kept.
+ * Refusals of add_fold, each leaving the accumulator byte for byte as it was.  MTSV_E_ARG: a null handle or read_len; f not at
+ *   MTSV_GRAIN_LONG; f on another device; n_reads not the fold's; a record whose (tax_id, gi) the table does not hold; a record
+ *   whose offset is L or more -- these two are counted on the device in a pass of its own before anything is marked or added,
+ *   and mtsv_last_error gives the counts and names the first such record.  MTSV_E_LIMIT: a fold of 2^32 reads or more.
+ *   MTSV_E_LIMIT of add_index / add_refs, the table as it was: a length of 2^32 or more; a table whose bitmap would take 2^32
+ *   words or more. */
+typedef struct mtsv_coverage mtsv_coverage;
+typedef struct {
+    uint32_t tax_id, gi;
+    uint64_t length, reads, alignments, aligned_bases, covered_bases;
+} mtsv_ref_coverage; /* 48 bytes */
+int mtsv_coverage_create(int hip_device, mtsv_coverage **out);
+void mtsv_coverage_free(mtsv_coverage *c);
+int mtsv_coverage_add_index(mtsv_coverage *c, const mtsv_index *ix);
+int mtsv_coverage_add_refs(mtsv_coverage *c, const uint32_t *tax_id, const uint32_t *gi, const uint64_t *length, uint64_t n);
+int mtsv_coverage_reset(mtsv_coverage *c);
+int mtsv_coverage_add_fold(mtsv_coverage *c, mtsv_fold *f, const uint32_t *read_len, uint64_t n_reads, uint32_t edit_slack,
+                           float *device_ms);
+int mtsv_coverage_rows(mtsv_coverage *c, mtsv_ref_coverage **rows, uint64_t *n_rows, float *device_ms);
+int mtsv_format_coverage_report(const mtsv_ref_coverage *rows, uint64_t n_rows, char **out, uint64_t *out_len);
+
 /* ---- result lines (host) ---------------------------------------------------------------- */
 /* write_assignments for a whole batch: hits ordered by read; ids = NUL-separated read ids,
  * id_off[n_reads+1].  Lines are appended to a malloc'd buffer (*out, *out_len), one per read with

@@ -13,6 +13,7 @@ from ._lib import (  # noqa: F401
     ASSIGN_ONLY,
     ASSIGN_WITH_HITS,
     CLADE_STATS_DTYPE,
+    Coverage,
     DEVPART_BIN_END,
     DEVPART_BIN_LUT,
     DEVPART_BINS,
@@ -31,6 +32,7 @@ from ._lib import (  # noqa: F401
     MATCH_ONLY,
     MATCH_WITH_HITS,
     RANK_UNKNOWN,
+    REF_COVERAGE_DTYPE,
     SLACK_ALL,
     TAXON_STATS_DTYPE,
     Taxonomy,
@@ -55,6 +57,7 @@ from ._lib import (  # noqa: F401
     format_assignments,
     format_assignments_gi,
     format_clade_report,
+    format_coverage_report,
     format_results,
     format_taxa_report,
     merge_taxa_reports,

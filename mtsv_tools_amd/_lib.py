@@ -92,6 +92,10 @@ RANK_UNKNOWN = 0xffffffff  # MTSV_RANK_UNKNOWN
 SLACK_ALL = 0xffffffff  # edit_slack of mtsv_fold_lca: every TaxID of a read enters
 PAIR_BOTH, PAIR_EITHER, PAIR_PROPER = 0, 1, 2  # MTSV_PAIR_*
 
+# mtsv_ref_coverage: 4 + 4 + 5 * 8 = 48 bytes
+REF_COVERAGE_DTYPE = np.dtype({"names": ["tax_id", "gi", "length", "reads", "alignments", "aligned_bases", "covered_bases"],
+                               "formats": ["<u4", "<u4", "<u8", "<u8", "<u8", "<u8", "<u8"], "offsets": [0, 4, 8, 16, 24, 32, 40], "itemsize": 48})
+
 
 class TaxonomyInfo(C.Structure):  # mtsv_taxonomy_info_t
     _fields_ = [("n_nodes", C.c_uint64), ("n_implied_roots", C.c_uint64), ("n_ranks", C.c_uint32), ("max_depth", C.c_uint32)]
@@ -130,6 +134,8 @@ EXPORTS = [
     "mtsv_fold_lca", "mtsv_format_clade_report",
     "mtsv_dupmap_create", "mtsv_dupmap_free", "mtsv_batch_take_unique", "mtsv_dupmap_download", "mtsv_fold_expand",
     "mtsv_fold_pair",
+    "mtsv_coverage_create", "mtsv_coverage_free", "mtsv_coverage_add_index", "mtsv_coverage_add_refs", "mtsv_coverage_reset",
+    "mtsv_coverage_add_fold", "mtsv_coverage_rows", "mtsv_format_coverage_report",
 ]
 
 _lib = None
@@ -238,6 +244,15 @@ def lib():
         L.mtsv_dupmap_download.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.mtsv_fold_expand.argtypes = [vp, vp, vp, C.POINTER(C.c_float)]
         L.mtsv_fold_pair.argtypes = [vp, i32, u32, u32, vp, C.POINTER(PairStats), C.POINTER(C.c_float)]
+        L.mtsv_coverage_create.argtypes = [i32, C.POINTER(vp)]
+        L.mtsv_coverage_free.argtypes = [vp]
+        L.mtsv_coverage_free.restype = None
+        L.mtsv_coverage_add_index.argtypes = [vp, vp]
+        L.mtsv_coverage_add_refs.argtypes = [vp, vp, vp, vp, u64]
+        L.mtsv_coverage_reset.argtypes = [vp]
+        L.mtsv_coverage_add_fold.argtypes = [vp, vp, vp, u64, u32, C.POINTER(C.c_float)]
+        L.mtsv_coverage_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_format_coverage_report.argtypes = [vp, u64, C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -823,6 +838,71 @@ class DupMap:
             self.close()
         except Exception:
             pass
+
+
+class Coverage:
+    """Owning handle of an mtsv_coverage: per reference sequence (tax_id, gi) the reads, alignments, aligned bases and covered
+    bases of the GRAIN_LONG folds it is given.  Bound to a device.  MTSV_COVER_TILE, MTSV_COVER_LANE_MAX, MTSV_TRACE and
+    MTSV_COVER_TIMING are read when it is created."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _check(lib().mtsv_coverage_create(device, C.byref(self.h)))
+
+    def add_index(self, index):
+        """mtsv_coverage_add_index: the bins of an MGIndex join the table (host only)"""
+        _check(lib().mtsv_coverage_add_index(self.h, index.h))
+
+    def add_refs(self, tax_id, gi, length):
+        """mtsv_coverage_add_refs: references from three arrays of equal length"""
+        tax_id = np.ascontiguousarray(tax_id, dtype=np.uint32)
+        gi = np.ascontiguousarray(gi, dtype=np.uint32)
+        length = np.ascontiguousarray(length, dtype=np.uint64)
+        if not len(tax_id) == len(gi) == len(length):
+            raise ValueError("tax_id, gi and length must be of one length")
+        _check(lib().mtsv_coverage_add_refs(self.h, tax_id.ctypes.data, gi.ctypes.data, length.ctypes.data, len(tax_id)))
+
+    def reset(self):
+        """mtsv_coverage_reset: counters and bitmap zero; the table stays"""
+        _check(lib().mtsv_coverage_reset(self.h))
+
+    def add_fold(self, fold, read_len, slack=0):
+        """mtsv_coverage_add_fold: the records of the Fold (GRAIN_LONG) within `slack` edits of their read's smallest edit
+        (SLACK_ALL: all of them) are added; read_len: the lengths of the fold's n_reads reads; returns the device ms"""
+        read_len = np.ascontiguousarray(read_len, dtype=np.uint32)
+        ms = C.c_float()
+        _check(lib().mtsv_coverage_add_fold(self.h, fold.h, read_len.ctypes.data, len(read_len), int(slack), C.byref(ms)))
+        return ms.value
+
+    def rows(self):
+        """(every reference of the table as a REF_COVERAGE_DTYPE array ascending by (tax_id, gi), device ms)"""
+        out, n, ms = C.c_void_p(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_coverage_rows(self.h, C.byref(out), C.byref(n), C.byref(ms)))
+        return _records_from(out, n.value, REF_COVERAGE_DTYPE), ms.value
+
+    def close(self):
+        if self.h is not None and _lib is not None:
+            _lib.mtsv_coverage_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def format_coverage_report(rows):
+    """mtsv_format_coverage_report: the TSV of mtsv-binner --coverage, as bytes"""
+    out_rows = np.zeros(len(rows), dtype=REF_COVERAGE_DTYPE)
+    for f in REF_COVERAGE_DTYPE.names:
+        out_rows[f] = rows[f]
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_coverage_report(out_rows.ctypes.data, len(out_rows), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value)
+    finally:
+        lib().mtsv_free(out)
 
 
 class Taxonomy:

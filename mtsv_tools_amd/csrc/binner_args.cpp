@@ -97,7 +97,15 @@ void print_help() {
            "TaxID, the sum of their smallest edits.  either: every TaxID either mate hit; one that only one mate hit carries that\n"
            "mate's edit plus --unpaired-penalty, which must be given.  --report counts pairs.  An odd number of records, or mates\n"
            "whose IDs do not agree, is an input error.  Not with --output-format long, --matched / --unmatched or an odd\n"
-           "--read-offset; a run that would resume an existing results file is refused)\n");
+           "--read-offset; a run that would resume an existing results file is refused),\n"
+           "--coverage TSV [--coverage-slack N|all] (only with --fold-on-gpu, and with records that carry GI and offset:\n"
+           "--output-format long, or --interleaved --pair-mode proper.  Per reference sequence (TaxID, GI) the reads and alignments\n"
+           "it took, the bases they span and the bases at least one of them covers, counted on the GPU from the accumulated\n"
+           "records in a bitmap of one bit per reference base: columns taxid, gi, length, reads, alignments, aligned_bases, depth,\n"
+           "covered_bases, breadth_pct, one line per reference with an alignment and one per TaxID (gi *) over all its\n"
+           "references.  An alignment counts when its edit distance is within --coverage-slack (default 0) of its read's\n"
+           "smallest; all: every alignment.  It spans the read's length from the start of its accepted window, which lies up\n"
+           "to the edit tolerance before the match.  With --dedup every copy of a read counts)\n");
 }
 
 // a number in 0 .. 2^32 - 1, or the usage error of `flag`
@@ -197,6 +205,14 @@ void check_combinations(const Args& a) {
             usage_error("'" + a.pair_mode + "' isn't a valid value for '--pair-mode <MODE>' [possible values: both, either, proper]");
         if (a.pair_mode == "either" && a.unpaired_penalty.empty())
             usage_error("The argument '--pair-mode either' requires '--unpaired-penalty <N>': what a mate that did not align costs cannot be derived from the records");
+    }
+    if (a.coverage.empty()) {
+        if (!a.coverage_slack.empty()) usage_error("The argument '--coverage-slack <N|all>' requires '--coverage <TSV>'");
+    } else {
+        if (!a.fold_gpu) usage_error("The argument '--coverage <TSV>' requires '--fold-on-gpu'");
+        const bool proper = a.interleaved && (a.pair_mode.empty() || a.pair_mode == "proper");
+        if (a.output_format != "long" && !proper)
+            usage_error("The argument '--coverage <TSV>' needs records with GI and offset: give '--output-format long', or '--interleaved --pair-mode proper'");
     }
     if (a.merge_gpu) require_chunks_on_one_device(a, "--merge-on-gpu", "every chunk is made resident on that device");
     if (a.fold_gpu) {
@@ -341,6 +357,8 @@ Args parse_args(int argc, char** argv) {
         else if (key == "--pair-mode") a.pair_mode = val();
         else if (key == "--max-insert") a.max_insert = val();
         else if (key == "--unpaired-penalty") a.unpaired_penalty = val();
+        else if (key == "--coverage") a.coverage = val();
+        else if (key == "--coverage-slack") a.coverage_slack = val();
         else if (key == "--fold-reads") a.fold_reads = parse_reads(val(), "--fold-reads", 0xffffffffull);
         else if (key == "-h" || key == "--help") {
             print_help();
@@ -385,6 +403,8 @@ Run resolve(const Args& a) {
         if (run.pair_mode == MTSV_PAIR_EITHER && run.unpaired_penalty >= 0x80000000u)
             usage_error("Invalid value for '--unpaired-penalty <N>': a number below 2147483648 is expected");
     }
+    run.coverage = a.coverage;
+    if (!a.coverage_slack.empty()) run.coverage_slack = a.coverage_slack == "all" ? 0xffffffffu : parse_u32_flag(a.coverage_slack, "--coverage-slack");
     resolve_params(a, run);
     if (run.interleaved && (run.read_offset & 1)) refuse("'--interleaved' needs an even '--read-offset': the reads are skipped pair by pair");
     resolve_results(a, run);

@@ -20,6 +20,10 @@
 // flag (at MTSV_GRAIN_LONG for --pair-mode proper, which needs the mates' GIs and offsets); after the last chunk, and after
 // the expansion of --dedup, mtsv_fold_pair joins a piece's fold into its fold of PAIRS, which the result lines (one per
 // pair, under the mates' common ID) and the report are derived from.
+// --coverage: one mtsv_coverage for the whole run.  Every chunk that is loaded adds its bins to the table (from the second
+// super-batch on that brings nothing new, which the library accepts); after the last chunk, and after the expansion of --dedup
+// but before the pair join, a piece's fold of READS is added, the reads' lengths taken from the block's offsets.  The rows are
+// asked for and written once, by finish().
 #include <unistd.h>
 
 #include <cstdio>
@@ -84,6 +88,7 @@ class FoldedRun {
     bool write_piece(size_t k);
     bool write_results(const std::string& ids, const std::vector<uint64_t>& id_off, mtsv_fold* f);
     bool pair_piece(size_t k, const ReadBlock& rb, mtsv_fold* f);
+    bool cover_piece(const ReadBlock& rb, mtsv_fold* f);
     bool input_error(const std::string& what);
     bool write_sides(const ReadBlock& rb, mtsv_fold* f);
     void print_timing() const;
@@ -107,6 +112,9 @@ class FoldedRun {
     mtsv_pair_stats pair_stats_ = {0, 0, 0, 0, 0};
     uint64_t pairs_done_ = 0, reads_taken_ = 0;
     float pair_device_ms_ = 0;
+    CoveragePtr coverage_;               // --coverage
+    std::vector<uint32_t> read_len_;
+    float coverage_device_ms_ = 0;
     TaxaSum taxa_;
     uint64_t dedup_reads_ = 0, dedup_distinct_ = 0;
     uint64_t super_reads_ = 0, n_super_ = 0, reads_done_ = 0, reads_matched_ = 0;
@@ -156,6 +164,7 @@ bool FoldedRun::run_chunk(size_t c, bool more) {
         rc = mtsv_index_load(paths[c].c_str(), out(ix));
     }
     t_load_ += now_s() - t0;
+    if (rc == MTSV_OK && coverage_) rc = mtsv_coverage_add_index(coverage_.get(), ix.get());
     if (run_.fold_prefetch && rc == MTSV_OK) {
         if (c + 1 < paths.size())
             pre_.start(c + 1, paths[c + 1]);
@@ -240,6 +249,16 @@ bool FoldedRun::pair_piece(size_t k, const ReadBlock& rb, mtsv_fold* f) {
     return true;
 }
 
+// --coverage: the piece's fold of reads into the run's accumulator
+bool FoldedRun::cover_piece(const ReadBlock& rb, mtsv_fold* f) {
+    read_len_.resize(rb.n());
+    for (uint64_t i = 0; i < rb.n(); i++) read_len_[i] = (uint32_t)(rb.off[i + 1] - rb.off[i]);
+    float ms = 0;
+    if (mtsv_coverage_add_fold(coverage_.get(), f, read_len_.data(), rb.n(), run_.coverage_slack, &ms) != MTSV_OK) return code_.lib_error();
+    coverage_device_ms_ += ms;
+    return true;
+}
+
 bool FoldedRun::write_results(const std::string& ids, const std::vector<uint64_t>& id_off, mtsv_fold* f) {
     ArrayPtr<char> text;
     uint64_t len = 0;
@@ -299,6 +318,7 @@ bool FoldedRun::write_piece(size_t k) {
         if (mtsv_fold_expand(f, rep_folds_[k].get(), dupmaps_[k].get(), &ms) != MTSV_OK) return code_.lib_error();
         expand_device_ms_ += ms;
     }
+    if (coverage_ && !cover_piece(rb, f)) return false;
     if (run_.interleaved) {  // (from here on the piece is its pairs)
         if (!pair_piece(k, rb, f)) return false;
         f = pair_folds_[k].get();
@@ -390,6 +410,7 @@ void FoldedRun::print_timing() const {
     if (run_.text_gpu) fprintf(stderr, "[cli text timing] text_on_gpu device %.3f ms\n", text_device_ms_);
     if (run_.dedup) fprintf(stderr, "[cli dedup timing] take_unique device %.3f ms, expand device %.3f ms\n", dedup_device_ms_, expand_device_ms_);
     if (run_.interleaved) fprintf(stderr, "[cli pair timing] pair device %.3f ms\n", pair_device_ms_);
+    if (run_.have_coverage()) fprintf(stderr, "[cli coverage timing] coverage device %.3f ms\n", coverage_device_ms_);
 }
 
 // every way out of the folded run ends alike: the process leaves at once, or (MTSV_CLI_CLEAN_EXIT=1) frees what it holds --
@@ -408,6 +429,10 @@ int FoldedRun::run() {
     if (!getenv("MTSV_VERIFY")) mtsv_set_default_verify_mode(MTSV_VERIFY_EDIT_FIRST);
     logmsg("INFO", "Beginning queries.");
     const double t_begin = now_s();
+    if (run_.have_coverage() && mtsv_coverage_create(dev_, out(coverage_)) != MTSV_OK) {
+        code_.lib_error();
+        return leave(code_.get());
+    }
     const bool parsed = producer_.produce(std::min<uint64_t>(run_.batch_reads, fold_reads_), [&](std::unique_ptr<ReadBlock> rb) {
         return run_.interleaved ? take_pairs(std::move(rb)) : take_block(std::move(rb));
     });
@@ -431,6 +456,7 @@ int FoldedRun::run() {
                                std::to_string(pair_stats_.one_mate_hit) + ", joined " + std::to_string(pair_stats_.joined) + ".");
     };
     end.taxa = &taxa_;
+    end.coverage = coverage_.get();
     if (const int c = finish(run_, out_, end)) return leave(c);
     print_timing();
     return leave(0);

@@ -26,6 +26,9 @@ struct FoldFree {
 struct DupmapFree {
     void operator()(mtsv_dupmap* q) const { mtsv_dupmap_free(q); }
 };
+struct CoverageFree {
+    void operator()(mtsv_coverage* q) const { mtsv_coverage_free(q); }
+};
 struct ArrayFree {
     void operator()(void* q) const { mtsv_free(q); }
 };
@@ -33,6 +36,7 @@ using IndexPtr = std::unique_ptr<mtsv_index, IndexFree>;
 using BatchPtr = std::unique_ptr<mtsv_batch, BatchFree>;
 using FoldPtr = std::unique_ptr<mtsv_fold, FoldFree>;
 using DupmapPtr = std::unique_ptr<mtsv_dupmap, DupmapFree>;
+using CoveragePtr = std::unique_ptr<mtsv_coverage, CoverageFree>;
 template <class T>
 using ArrayPtr = std::unique_ptr<T, ArrayFree>;  // what the library hands out for mtsv_free
 

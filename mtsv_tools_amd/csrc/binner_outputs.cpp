@@ -73,6 +73,24 @@ int finish(const Run& run, Outputs& outputs, const RunEnd& end) {
         }
         mark("taxa report written");
     }
+    if (run.have_coverage()) {
+        ArrayPtr<mtsv_ref_coverage> rows;
+        ArrayPtr<char> text;
+        uint64_t n_rows = 0, text_len = 0;
+        int rc = end.coverage ? mtsv_coverage_rows(end.coverage, out(rows), &n_rows, nullptr) : MTSV_E_ARG;
+        if (rc == MTSV_OK) rc = mtsv_format_coverage_report(rows.get(), n_rows, out(text), &text_len);
+        if (rc != MTSV_OK) {
+            logmsg("ERROR", std::string("Error running query: ") + (end.coverage ? mtsv_last_error() : "no coverage was counted"));
+            return 2;
+        }
+        FILE* cf = fopen(run.coverage.c_str(), "wb");
+        const bool written = cf && fwrite(text.get(), 1, text_len, cf) == text_len;
+        if ((cf && fclose(cf) != 0) || !written) {
+            logmsg("ERROR", "Error writing to coverage report file");
+            return 11;
+        }
+        mark("coverage report written");
+    }
     char msg[160];
     snprintf(msg, sizeof msg, "All worker and result consumer threads terminated. Took %.3f seconds.", now_s() - end.t_begin);
     logmsg("INFO", msg);

@@ -36,10 +36,12 @@ struct RunEnd {
     std::function<void()> info;               // the run's own INFO lines, after that one
     TaxaSum* taxa = nullptr;                  // --report: the counts ...
     std::function<bool(TaxaSum&)> gather;     // ... or what still has to be added to them (false: a library error)
+    mtsv_coverage* coverage = nullptr;        // --coverage: the run's accumulator
     std::function<void(const char*)> mark;    // MTSV_CLI_TIMING: a phase has ended
 };
 // The end of a run whose reads are all through: closes the results file and the partition files, logs the "Partitioned"
-// line and the run's own, writes the taxa report, logs "Took ... seconds.".  0, or the exit code (logged).
+// line and the run's own, writes the taxa report and the coverage report, logs "Took ... seconds.".  0, or the exit code
+// (logged).
 int finish(const Run& run, Outputs& outputs, const RunEnd& end);
 
 }  // namespace mtsv_cli

@@ -11,6 +11,7 @@
 
 #include "../../include/mtsv_amd.h"
 #include "batch.hpp"
+#include "cover.hpp"
 #include "dedup.hpp"
 #include "dev_index.hpp"
 #include "fold.hpp"
@@ -698,6 +699,93 @@ static_assert(sizeof(mtsv_pair_stats) == 40, "the pair stats");
 int mtsv_fold_pair(mtsv_fold* f, int mode, uint32_t max_insert, uint32_t unpaired_edits, mtsv_fold* out, mtsv_pair_stats* stats, float* device_ms) {
     if (!f || !out) return fail_arg("null argument");
     GUARD(f->impl.pair(mode, max_insert, unpaired_edits, &out->impl, stats, device_ms))
+}
+
+// ---- coverage per reference sequence (cover.hip, k_cover.hip, cover_refs.hpp) ----
+static_assert(sizeof(mtsv_ref_coverage) == 48, "the coverage row");
+int mtsv_coverage_create(int hip_device, mtsv_coverage** out) {
+    if (!out) return fail_arg("null argument");
+    GUARD(*out = new mtsv_coverage(hip_device))
+}
+
+void mtsv_coverage_free(mtsv_coverage* c) { delete c; }
+
+int mtsv_coverage_add_refs(mtsv_coverage* c, const uint32_t* tax_id, const uint32_t* gi, const uint64_t* length, uint64_t n) {
+    if (!c || (n && (!tax_id || !gi || !length))) return fail_arg("null argument");
+    GUARD(c->impl.add_refs(CoverRefs::normalise(tax_id, gi, length, n)))
+}
+
+int mtsv_coverage_add_index(mtsv_coverage* c, const mtsv_index* ix) {
+    if (!c || !ix) return fail_arg("null argument");
+    GUARD({
+        const std::vector<Bin>& bins = ix->host.bins;
+        std::vector<uint32_t> tax(bins.size()), gi(bins.size());
+        std::vector<uint64_t> len(bins.size());
+        for (size_t k = 0; k < bins.size(); k++) {
+            tax[k] = bins[k].tax_id;
+            gi[k] = bins[k].gi;
+            len[k] = bins[k].end >= bins[k].start ? bins[k].end - bins[k].start : 0;
+        }
+        c->impl.add_refs(CoverRefs::normalise(tax.data(), gi.data(), len.data(), bins.size()));
+    })
+}
+
+int mtsv_coverage_reset(mtsv_coverage* c) {
+    if (!c) return fail_arg("null argument");
+    GUARD(c->impl.reset())
+}
+
+int mtsv_coverage_add_fold(mtsv_coverage* c, mtsv_fold* f, const uint32_t* read_len, uint64_t n_reads, uint32_t edit_slack, float* device_ms) {
+    if (!c || !f || !read_len) return fail_arg("null argument");
+    GUARD(c->impl.add_fold(f->impl, read_len, n_reads, edit_slack, device_ms))
+}
+
+int mtsv_coverage_rows(mtsv_coverage* c, mtsv_ref_coverage** rows, uint64_t* n_rows, float* device_ms) {
+    if (!c || !rows || !n_rows) return fail_arg("null argument");
+    GUARD({
+        std::vector<mtsv_ref_coverage> r;
+        c->impl.rows(r, device_ms);
+        auto* mem = (mtsv_ref_coverage*)malloc(std::max<size_t>(r.size(), 1) * sizeof(mtsv_ref_coverage));
+        if (!mem) throw std::bad_alloc();
+        if (!r.empty()) memcpy(mem, r.data(), r.size() * sizeof(mtsv_ref_coverage));
+        *rows = mem;
+        *n_rows = r.size();
+    })
+}
+
+int mtsv_format_coverage_report(const mtsv_ref_coverage* rows, uint64_t n_rows, char** out, uint64_t* out_len) {
+    if ((!rows && n_rows) || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        std::string text = "taxid\tgi\tlength\treads\talignments\taligned_bases\tdepth\tcovered_bases\tbreadth_pct\n";
+        char line[320];
+        auto put = [&](uint32_t tax_id, const char* gi, uint64_t length, uint64_t reads, uint64_t alignments, uint64_t bases, uint64_t covered) {
+            const double depth = length ? (double)bases / (double)length : 0.0, breadth = length ? (double)covered / (double)length * 100.0 : 0.0;
+            snprintf(line, sizeof line, "%u\t%s\t%llu\t%llu\t%llu\t%llu\t%.2f\t%llu\t%.2f\n", tax_id, gi, (unsigned long long)length, (unsigned long long)reads,
+                     (unsigned long long)alignments, (unsigned long long)bases, depth, (unsigned long long)covered, breadth);
+            text += line;
+        };
+        for (uint64_t i = 0; i < n_rows;) {
+            uint64_t j = i, sum[5] = {0, 0, 0, 0, 0};
+            bool any = false;
+            for (; j < n_rows && rows[j].tax_id == rows[i].tax_id; j++) {
+                const mtsv_ref_coverage& s = rows[j];
+                const uint64_t v[5] = {s.length, s.reads, s.alignments, s.aligned_bases, s.covered_bases};
+                for (int k = 0; k < 5; k++) sum[k] += v[k];
+                if (!s.alignments) continue;
+                any = true;
+                char gi[16];
+                snprintf(gi, sizeof gi, "%u", s.gi);
+                put(s.tax_id, gi, s.length, s.reads, s.alignments, s.aligned_bases, s.covered_bases);
+            }
+            if (any) put(rows[i].tax_id, "*", sum[0], sum[1], sum[2], sum[3], sum[4]);
+            i = j;
+        }
+        char* p = (char*)malloc(text.size() + 1);
+        if (!p) throw std::bad_alloc();
+        memcpy(p, text.c_str(), text.size() + 1);
+        *out = p;
+        *out_len = text.size();
+    })
 }
 
 int mtsv_format_clade_report(const mtsv_clade_stats* rows, uint64_t n_rows, uint64_t total_reads, const mtsv_taxonomy* tx, char** out,

@@ -444,5 +444,40 @@ void launch_pair_flags(hipStream_t s, const uint64_t* n_slots, uint32_t n_slots_
 void launch_pair_write(hipStream_t s, const uint64_t* n_slots, uint32_t n_slots_cap, const void* slot_rec, const uint32_t* m, const uint32_t* pos_a,
                        const uint32_t* pos_b, uint32_t n_a, uint32_t n_b, void* out_a, void* out_b);
 void launch_pair_stats(hipStream_t s, const uint32_t* off, uint64_t n_pairs, const void* out, uint32_t n_out, uint64_t* ctr);
+// k_cover.hip: coverage per reference sequence from a list at kCollapseGrainLong (n records of 6 words ordered by (read, tax_id,
+// gi, offset), n_reads below 2^32).  The table: n_refs references ascending by key = tax_id << 32 | gi, ref_len[r] bases
+// each, reference r owning the words [word_off[r], word_off[r + 1]) of the bitmap (ceil(ref_len[r] / 64) of them).  A record
+// COUNTS when its edit is at most m[read] + slack (saturating); a counted record (r, t, g, o, e) covers [o, min(o + read_len[r],
+// L)).  A RUN is the records of one (read, tax_id, gi), numbered by its head.  NONE is all ones.  off[] comes from
+// launch_pair_bounds.  ctr: kCoverCounters u64, set by the caller to 0 except [kCoverCtrFirstBad] (all ones).
+//   min:    m[r] = the smallest edit of read r's records (NONE for a read without one): a lane per read walks a stretch of up
+//           to kCoverMinLane records, a longer one is strided by the lanes of its wavefront
+//   map:    ref[i] = the reference of record i when it counts, else NONE; head[i] = it begins a run; nothing else is written
+//           but ctr: [kCoverCtrUnknown] += records whose key the table does not hold, [kCoverCtrRange] += those whose offset is
+//           at or beyond their reference's length, [kCoverCtrBeyond] += those with read >= n_reads, [kCoverCtrFirstBad] = the
+//           smallest i among all of these, [kCoverCtrCounted] += the records that count
+//   (launch_scan over head: run[0 .. n], run[n] = the runs; record i belongs to run run[i + 1] - 1)
+//   mark:   only after a map that left the first three counters at zero.  Per counted record: its interval OR-ed into the
+//           bitmap by its lane when it spans up to lane_max words, else the record goes to list (n u32, ctr[kCoverCtrList] of
+//           them); run_hit[its run] = 1 (zeroed by the caller), run_ref[its run] = its reference; cnt[n_refs + r] += 1 and
+//           cnt[2 n_refs + r] += the interval's bases, the lanes of a wavefront that share r combined first
+//   wave:   the listed records' intervals, a wavefront each; after mark on the same stream
+//   reads:  cnt[r] += the runs of reference r with run_hit set (*n_runs of them, at most n)
+//   pop:    cov[r] (n_refs u64, zeroed by the caller) += the bits set in reference r's words.  A workgroup owns `tile` words (a
+//           power of two, 64 .. kCoverTileMax) and adds one value per reference that has words in its tile
+constexpr uint32_t kCoverTileMax = 1024, kCoverTile = 1024, kCoverLaneMax = 8, kCoverLaneMaxMax = 1024, kCoverMinLane = 32;
+constexpr uint32_t kCoverCtrUnknown = 0, kCoverCtrRange = 1, kCoverCtrBeyond = 2, kCoverCtrFirstBad = 3, kCoverCtrCounted = 4, kCoverCtrList = 5,
+                   kCoverCounters = 6;
+void launch_cover_min(hipStream_t s, const void* rec, uint32_t n, uint64_t n_reads, const uint32_t* off, uint32_t* m);
+void launch_cover_map(hipStream_t s, const void* rec, uint32_t n, uint64_t n_reads, const uint32_t* m, uint32_t slack, const uint64_t* ref_key,
+                      const uint32_t* ref_len, uint32_t n_refs, uint32_t* ref, uint32_t* head, uint64_t* ctr);
+void launch_cover_mark(hipStream_t s, const void* rec, uint32_t n, const uint32_t* read_len, const uint32_t* ref, const uint32_t* run,
+                       const uint32_t* ref_len, const uint32_t* word_off, uint32_t n_refs, uint32_t lane_max, uint64_t* bitmap, uint64_t* cnt,
+                       uint32_t* run_hit, uint32_t* run_ref, uint32_t* list, uint64_t* ctr);
+void launch_cover_wave(hipStream_t s, const void* rec, uint32_t n, const uint32_t* read_len, const uint32_t* ref, const uint32_t* ref_len,
+                       const uint32_t* word_off, uint32_t n_refs, const uint32_t* list, const uint64_t* ctr, uint64_t* bitmap);
+void launch_cover_reads(hipStream_t s, const uint64_t* n_runs, uint32_t n, const uint32_t* run_hit, const uint32_t* run_ref, uint32_t n_refs,
+                        uint64_t* cnt);
+void launch_cover_pop(hipStream_t s, const uint64_t* bitmap, uint32_t n_words, const uint32_t* word_off, uint32_t n_refs, uint32_t tile, uint64_t* cov);
 
 }  // namespace mtsv
