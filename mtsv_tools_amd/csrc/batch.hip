@@ -1,4 +1,4 @@
-// batch.hip -- device workspace for one batch of reads and the stage-by-stage driver of the hot
+// batch.hip -- device workspace for one batch of reads; batch_pass.hip is the stage-by-stage driver of the hot
 // path.  Replaces the producer -> workers -> joiner queue of vendor/cue/src/lib.rs:45-105 with
 // large HBM-resident batches: reads stay on the device between stages, every stage is one launch
 // over the whole batch, and the only host round-trips are two 8-byte totals per pass.
@@ -15,9 +15,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "../../include/mtsv_amd.h"
-#include "batch.hpp"
-#include "kernels.hpp"
+#include "batch_internal.hpp"
 
 namespace mtsv {
 
@@ -42,13 +40,6 @@ void parallel_ranges(uint64_t n, F f) {
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 void parallel_copy(uint8_t* dst, const uint8_t* src, uint64_t n) {
     parallel_ranges(n, [=](uint64_t a, uint64_t b) { memcpy(dst + a, src + a, b - a); });
-}
-
-template <class T>
-void dev_alloc(T** p, uint64_t count, uint64_t* bytes) {
-    uint64_t b = std::max<uint64_t>(count, 1) * sizeof(T);
-    HIP_CHECK(hipMalloc((void**)p, b));
-    *bytes += b;
 }
 }  // namespace
 
@@ -89,11 +80,9 @@ bool host_pinned_unregister(void* p) {
     return false;
 }
 
-
 int g_default_verify_mode = MTSV_VERIFY_REFERENCE;
 
 constexpr uint32_t kMyersWgsPerCuLanes = 3;  // k_edit_myers workgroups per CU on a workspace of several lanes (4: 0.44 ms per step slower, profiles/README.md r10)
-constexpr uint64_t kLaneMinReads = 32768;  // a lane below this many reads does not fill the device
 constexpr uint64_t kChunkMaxReads = 4ull << 20;  // lanes take a range in chunks of at most this many reads (smaller chunks measured slower: per-pass launches and host round trips)
 
 Batch::Batch(mtsv_index* ix_, DeviceIndex* di_, uint64_t max_reads_, uint64_t max_bases_, uint64_t hit_cap_, Batch* parent_, int lanes_)
@@ -305,8 +294,6 @@ void Batch::upload(const uint8_t* bases, const uint64_t* read_off, uint64_t n) {
     codes_resident = mapped = false;
 }
 
-// counters in d_counters: [0] scan total (u64), [1] wl_count (u32), [2] lf_steps, [3] n_cand,
-// [4] n_verified, [5] window_bytes, [6] second scan total
 void Batch::reset_lane() {
     HIP_CHECK(hipSetDevice(di->device));
     memset(&stats, 0, sizeof stats);
@@ -317,32 +304,32 @@ void Batch::reset_lane() {
     n_hits_total = 0;
     n_assign_total = 0;
     HIP_CHECK(hipMemsetAsync(d_counters, 0, kCounters * sizeof(uint64_t), stream));
-    ctr22_zero = true;
-    HIP_CHECK(hipEventRecord(ev[8], stream));
+    listed_zero = true;
+    HIP_CHECK(hipEventRecord(ev[kEvRunBegin], stream));
 }
 
 void Batch::finish_lane() {
-    HIP_CHECK(hipEventRecord(ev[9], stream));
+    HIP_CHECK(hipEventRecord(ev[kEvRunEnd], stream));
     launch_publish(stream, d_counters, h_counters, kCounters);
     HIP_CHECK(hipStreamSynchronize(stream));
-    HIP_CHECK(hipEventElapsedTime(&stage_acc[7], ev[8], ev[9]));
+    HIP_CHECK(hipEventElapsedTime(&stage_acc[7], ev[kEvRunBegin], ev[kEvRunEnd]));
     if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] last pass: %llu strands of 13..64 seed hits (or more than 4 candidates) to k_coalesce_mid, %llu heavier ones\n",
-                                      (unsigned long long)(h_counters[15] & 0xffffffffull), (unsigned long long)(h_counters[1] >> 32));
+                                      (unsigned long long)(h_counters[kCtrMidStrands] & 0xffffffffull), (unsigned long long)(h_counters[kCtrWorklist] >> 32));
     if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] k_coalesce_heavy: %llu strands walked by runs, %llu by the wavefront walk (a run too long)\n",
                                       (unsigned long long)(h_counters[kCtrHeavyWalk] & 0xffffffffull), (unsigned long long)(h_counters[kCtrHeavyWalk] >> 32));
-    stats.sw_cell_pairs = h_counters[14];
+    stats.sw_cell_pairs = h_counters[kCtrSwCellPairs];
     stats.sw_prefilter_ms = sw_ms_acc;
     stats.sw_sweep_ms = sweep_ms_acc;
     stats.sw_diag_ms = diag_ms_acc;
     stats.sw_bound_ms = bound_ms_acc;
     stats.edit_ms = edit_ms_acc;
-    stats.myers_columns = h_counters[19];
-    stats.n_sw_bound_refuted = h_counters[20];
-    stats.n_sw_passed = sw_passed_acc + h_counters[21];  // (+ the successors k_edit_myers' list mode passed by its own bound)
-    stats.lf_steps = h_counters[2];
-    stats.n_candidates = h_counters[3];
-    stats.n_verified = h_counters[4];
-    stats.window_bytes = h_counters[5];
+    stats.myers_columns = h_counters[kCtrMyersColumns];
+    stats.n_sw_bound_refuted = h_counters[kCtrBoundRefuted];
+    stats.n_sw_passed = sw_passed_acc + h_counters[kCtrListPassed];  // (+ the successors k_edit_myers' list mode passed by its own bound)
+    stats.lf_steps = h_counters[kCtrLfSteps];
+    stats.n_candidates = h_counters[kCtrCandidates];
+    stats.n_verified = h_counters[kCtrVerified];
+    stats.window_bytes = h_counters[kCtrWindowBytes];
 }
 
 void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
@@ -384,8 +371,7 @@ void Batch::match_begin(uint64_t n, uint64_t read_base) {
         (void)hipFree(match.d_words);
         match.d_words = nullptr;
         match.cap_words = 0;
-        uint64_t b = 0;
-        dev_alloc(&match.d_words, need + need / 16 + 1, &b);
+        dev_alloc(&match.d_words, need + need / 16 + 1);
         match.cap_words = need + need / 16;
     }
     match.n_reads = n;
@@ -467,9 +453,8 @@ void Batch::set_taxa_report(bool on) {
             fprintf(stderr, "[report] %u taxa: %s tier (dense up to %u taxa, hash table of %u slots)\n", report.n_taxa,
                     report.dense ? "dense" : "hashed", dense_max, report.hash_slots);
         HIP_CHECK(hipSetDevice(di->device));
-        uint64_t b = 0;
-        dev_alloc(&report.d_taxa, report.n_taxa, &b);
-        dev_alloc(&report.d_counts, 4ull * report.n_taxa + 2, &b);
+        dev_alloc(&report.d_taxa, report.n_taxa);
+        dev_alloc(&report.d_counts, 4ull * report.n_taxa + 2);
         if (report.n_taxa) HIP_CHECK(hipMemcpyAsync(report.d_taxa, t.data(), t.size() * 4, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipMemsetAsync(report.d_counts, 0, (4ull * report.n_taxa + 2) * 8, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -595,11 +580,10 @@ void Batch::collapse_trace(const char* what) {
 
 void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
     CollapseScratch& c = collapse;
-    const Assignments& as = (parent ? parent : this)->assign;
+    const Assignments& as = root()->assign;
     const uint64_t rec = as.rec_bytes(), key_bytes = as.key_bytes();
-    uint64_t dummy = 0;
     if (n_hits >= (1ull << 32)) throw std::runtime_error("limit: 2^32 hits or more in one pass of the collapse");
-    if (!c.d_ctr) dev_alloc(&c.d_ctr, kCollapseCounters, &dummy);
+    if (!c.d_ctr) dev_alloc(&c.d_ctr, kCollapseCounters);
     if (!c.h_ctr) HIP_CHECK(hipHostMalloc((void**)&c.h_ctr, kCollapseCounters * sizeof(uint64_t), hipHostMallocMapped));
     for (auto& e : c.ev)
         if (!e) HIP_CHECK(hipEventCreate(&e));
@@ -610,11 +594,11 @@ void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
         c.flags = c.place = nullptr;
         c.cap_hits = 0;
         const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(n_hits + n_hits / 8, 1ull << 16), 0xffffffffull);
-        dev_alloc(&c.keys, cap * (key_bytes / 8), &dummy);
+        dev_alloc(&c.keys, cap * (key_bytes / 8));
         c.key_bytes = key_bytes;
-        dev_alloc(&c.flags, cap + 1, &dummy);
-        dev_alloc(&c.place, cap + 1, &dummy);
-        dev_alloc(&c.tiles, (uint64_t)scan_tiles((uint32_t)cap) + 1, &dummy);
+        dev_alloc(&c.flags, cap + 1);
+        dev_alloc(&c.place, cap + 1);
+        dev_alloc(&c.tiles, (uint64_t)scan_tiles((uint32_t)cap) + 1);
         c.cap_hits = cap;
     }
     if (n_pass_reads > c.cap_reads || !c.list) {
@@ -623,22 +607,21 @@ void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
         c.list = nullptr;
         c.cap_reads = 0;
         const uint64_t cap = std::max<uint64_t>(n_pass_reads + n_pass_reads / 16, 1024);
-        dev_alloc(&c.list, cap, &dummy);
+        dev_alloc(&c.list, cap);
         c.cap_reads = cap;
     }
     if ((n_assign_total + n_hits) * rec > assign_cap_bytes || !d_assign) {
         // grow the result array, keeping what earlier passes produced
         const uint64_t ncap = std::max<uint64_t>(std::max(assign_cap_bytes * 2, (n_assign_total + n_hits) * rec), (1ull << 16) * rec);
         uint8_t* na = nullptr;
-        dev_alloc(&na, ncap, &dummy);
+        dev_alloc(&na, ncap);
         if (n_assign_total) HIP_CHECK(hipMemcpyAsync(na, d_assign, n_assign_total * rec, hipMemcpyDeviceToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         // run_host may be copying an earlier range's assignments out of the old array on the owner's copy stream (and another
         // lane's thread may be issuing such a copy right now: the commit mutex covers the pointer swap), as with d_hits
-        Batch* root = parent ? parent : this;
         std::unique_lock<std::mutex> commit_lk;
-        if (root->commit_mu) commit_lk = std::unique_lock<std::mutex>(*root->commit_mu);
-        if (root->commit_mu && root->copy_stream2) HIP_CHECK(hipStreamSynchronize(root->copy_stream2));
+        if (root()->commit_mu) commit_lk = std::unique_lock<std::mutex>(*root()->commit_mu);
+        if (root()->commit_mu && root()->copy_stream2) HIP_CHECK(hipStreamSynchronize(root()->copy_stream2));
         (void)hipFree(d_assign);
         d_assign = na;
         assign_cap_bytes = ncap;
@@ -646,7 +629,7 @@ void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
 }
 
 void Batch::collapse_enqueue(uint32_t n_pass_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits, uint64_t n_hits) {
-    const Assignments& as = (parent ? parent : this)->assign;
+    const Assignments& as = root()->assign;
     collapse_room(n_pass_reads, n_hits);
     CollapseScratch& c = collapse;
     c.pending_hits = n_hits;
@@ -659,7 +642,7 @@ void Batch::collapse_enqueue(uint32_t n_pass_reads, const uint32_t* strand_nout,
 }
 
 uint64_t Batch::collapse_commit() {
-    Assignments& as = (parent ? parent : this)->assign;
+    Assignments& as = root()->assign;
     CollapseScratch& c = collapse;
     const uint64_t cnt = c.h_ctr[kCollapseCtrTotal];
     if (cnt > c.pending_hits) throw std::runtime_error("internal: the collapse wrote " + std::to_string(cnt) + " assignments from " + std::to_string(c.pending_hits) + " hits");
@@ -725,13 +708,11 @@ void Batch::compact_room(uint64_t tiles) {
         (void)hipFree(d_compact);
         d_compact = nullptr;
         compact_cap = 0;
-        uint64_t b = 0;
-        dev_alloc(&d_compact, 3 + 2 * (tiles + tiles / 16), &b);
+        dev_alloc(&d_compact, 3 + 2 * (tiles + tiles / 16));
         compact_cap = tiles + tiles / 16;
     }
     if (!d_read_map) {
-        uint64_t b = 0;
-        dev_alloc(&d_read_map, max_reads, &b);
+        dev_alloc(&d_read_map, max_reads);
     }
 }
 
@@ -828,8 +809,7 @@ void Batch::copy_reads(Batch& src, float* device_ms) {
     const uint32_t* s_off = host_batch ? src.arena[0].d_off : src.d_read_off;
     HIP_CHECK(hipSetDevice(di->device));
     if (with_map && !d_read_map) {
-        uint64_t b = 0;
-        dev_alloc(&d_read_map, max_reads, &b);
+        dev_alloc(&d_read_map, max_reads);
     }
     if (!compact_ev[0])
         for (auto& e : compact_ev) HIP_CHECK(hipEventCreate(&e));
@@ -895,9 +875,8 @@ void Batch::report_extend(Batch* const* srcs, int n_srcs) {
     c_new[n_new - 1] = c_old[n_old - 1];
     uint32_t* nt = nullptr;
     uint64_t* nc = nullptr;
-    uint64_t b = 0;
-    dev_alloc(&nt, u.size(), &b);
-    dev_alloc(&nc, n_new, &b);
+    dev_alloc(&nt, u.size());
+    dev_alloc(&nc, n_new);
     HIP_CHECK(hipMemcpyAsync(nt, u.data(), u.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(nc, c_new.data(), n_new * 8, hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -961,17 +940,16 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
     MergeState& m = merge;
     if (!m.ev[0])
         for (auto& e : m.ev) HIP_CHECK(hipEventCreate(&e));
-    uint64_t dummy = 0;
     if (n > m.cap_reads || !m.d_nout) {
         for (void* p : {(void*)m.d_nout, (void*)m.d_off, (void*)m.d_tiles}) (void)hipFree(p);
         m.d_nout = m.d_off = nullptr;
         m.d_tiles = nullptr;
         m.cap_reads = 0;
         const uint64_t cap = std::min<uint64_t>(n + n / 16, 0x7fffffffull);  // (a workspace's limit)
-        dev_alloc(&m.d_nout, 2 * cap + 1, &dummy);
-        dev_alloc(&m.d_off, 2 * cap + 1, &dummy);
+        dev_alloc(&m.d_nout, 2 * cap + 1);
+        dev_alloc(&m.d_off, 2 * cap + 1);
         m.cap_tiles = (uint64_t)scan_tiles((uint32_t)(2 * cap)) + 1;
-        dev_alloc(&m.d_tiles, m.cap_tiles + 2, &dummy);
+        dev_alloc(&m.d_tiles, m.cap_tiles + 2);
         m.cap_reads = cap;
     }
     if ((uint64_t)n_srcs * n > m.cap_sn || !m.d_lo) {
@@ -980,8 +958,8 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
         m.d_lo = m.d_base = nullptr;
         m.cap_sn = 0;
         const uint64_t cap = (uint64_t)n_srcs * (n + n / 16);
-        dev_alloc(&m.d_lo, cap, &dummy);
-        dev_alloc(&m.d_base, cap, &dummy);
+        dev_alloc(&m.d_lo, cap);
+        dev_alloc(&m.d_base, cap);
         m.cap_sn = cap;
     }
     if (parts.size() > m.cap_parts || !m.d_parts) {
@@ -989,7 +967,7 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
         m.d_parts = nullptr;
         m.cap_parts = 0;
         const uint64_t cap = std::max<uint64_t>(parts.size() * 2, 64);
-        dev_alloc(&m.d_parts, cap, &dummy);
+        dev_alloc(&m.d_parts, cap);
         m.cap_parts = cap;
     }
     // (before the result array grows, so that it cannot fail once the result is being replaced; if that allocation then
@@ -998,7 +976,7 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
     // (the collapse's scratch and the room behind the assignments so far: the last ones stay readable until then)
     if (assign.mode != MTSV_ASSIGN_OFF && n) collapse_room(n, total);
     DevHit* grown = nullptr;  // (the last result stays in the old array until nothing can refuse the merge any more)
-    if (total > hits_cap) dev_alloc(&grown, total + total / 16, &dummy);
+    if (total > hits_cap) dev_alloc(&grown, total + total / 16);
     // ---- from here on the destination's result is being replaced ----
     if (grown) {
         (void)hipFree(d_hits);
@@ -1105,539 +1083,6 @@ void Batch::download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& r
     if (nb) HIP_CHECK(hipMemcpyAsync(codes.data(), d_codes, nb, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     read_off.assign(h_read_off.begin(), h_read_off.begin() + n_reads + 1);
-}
-
-// A resident range of reads, split over the lanes; the hits stay in the lanes, `segments` records them in
-// read order.  raw != nullptr: the range is still ASCII in `raw` and each chunk normalises its bytes into
-// `sb` first (h_off = host copy of the range's n + 1 offsets); raw == nullptr: `sb` already holds codes.
-void Batch::run_range(const mtsv_params& p, const uint8_t* raw, uint8_t* sb, const uint32_t* so, const uint32_t* h_off, uint64_t n,
-                      uint32_t range_max_len, uint64_t read_base) {
-    std::vector<Batch*> ls{this};
-    for (auto& l : extra) ls.push_back(l.get());
-    // Chunks of at most ws_reads reads, handed to the lanes from a shared counter.  The lanes must not march in
-    // step (three index lookups at once, then three prefilters at once overlap nothing): every lane gets several
-    // chunks, and the first chunk of lane i is (i + 1) / lanes of a full one, so the lanes stay a fraction of a
-    // chunk apart and one lane's index lookups (gather-bound) run under another lane's prefilter (VALU-bound).
-    uint64_t k = n >= ls.size() * kLaneMinReads ? ls.size() : 1;
-    uint64_t per_lane = 2;  // measured on config2: 1: 52.2 ms, 2: 51.9, 3: 53.0, 4: 54.7, 6: 57.0 per 10 M reads
-    if (const char* e = getenv("MTSV_CHUNKS_PER_LANE")) per_lane = std::max(1, atoi(e));
-    uint64_t n_chunks = std::max<uint64_t>(k, (n + ws_reads - 1) / ws_reads);
-    if (k > 1 && n >= k * per_lane * kLaneMinReads) n_chunks = std::max(n_chunks, k * per_lane);
-    std::vector<uint64_t> bound(n_chunks + 1, n);
-    bound[0] = 0;
-    // (the short first chunks make the full ones longer: more chunks until a full one fits the workspace)
-    while (k > 1 && n_chunks >= 2 * k && (double)n / ((double)n_chunks - (double)(k - 1) / 2.0) > (double)ws_reads) n_chunks++;
-    bound.assign(n_chunks + 1, n);
-    bound[0] = 0;
-    if (k > 1 && n_chunks >= 2 * k) {
-        // sizes: per * 1/k, per * 2/k, .., per, then equal chunks of the rest
-        const double per0 = (double)n / ((double)n_chunks - (double)(k - 1) / 2.0);  // full chunk size with the short ones counted
-        uint64_t at = 0;
-        for (uint64_t c = 0; c < k; c++) {
-            at += (uint64_t)(per0 * (double)(c + 1) / (double)k);
-            bound[c + 1] = std::min(at, n);
-        }
-        const uint64_t rest = n - bound[k], m = n_chunks - k;
-        for (uint64_t c = 0; c < m; c++) bound[k + c + 1] = bound[k] + rest * (c + 1) / m;
-    } else {
-        for (uint64_t c = 0; c < n_chunks; c++) bound[c + 1] = n * (c + 1) / n_chunks;
-    }
-    for (uint64_t c = 0; c < n_chunks; c++)
-        if (bound[c + 1] - bound[c] > ws_reads) throw std::runtime_error("arg: range holds more reads than the workspace was created for");
-    k = std::min(k, n_chunks);
-    lanes_used = std::max<uint64_t>(lanes_used, k);
-    std::vector<Segment> segs(n_chunks);
-    std::atomic<uint64_t> next{0};
-    auto work = [&](Batch* lane) {
-        for (;;) {
-            const uint64_t c = next.fetch_add(1);
-            if (c >= n_chunks) return;
-            const uint64_t a = bound[c], b = bound[c + 1];
-            const uint64_t before = lane->n_hits_total, a_before = lane->n_assign_total;
-            // base normalisation (binner.rs:88-100) of this chunk's bytes: raw -> codes, on the lane's stream
-            if (raw) launch_normalise(lane->stream, raw, sb, h_off[a], h_off[b]);
-            lane->run_slice(p, sb, so + a, h_off ? h_off + a : nullptr, b - a, range_max_len, read_base + a);
-            segs[c] = Segment{lane, before, lane->n_hits_total - before, a, b - a, a_before, lane->n_assign_total - a_before};
-        }
-    };
-    if (k == 1) {
-        work(this);
-    } else {
-        std::vector<std::exception_ptr> errs(k);
-        std::vector<std::thread> th;
-        for (uint64_t i = 1; i < k; i++)
-            th.emplace_back([&, i] {
-                try {
-                    HIP_CHECK(hipSetDevice(di->device));
-                    work(ls[i]);
-                } catch (...) {
-                    errs[i] = std::current_exception();
-                    next.store(n_chunks);  // stop the others
-                }
-            });
-        try {
-            work(this);
-        } catch (...) {
-            errs[0] = std::current_exception();
-            next.store(n_chunks);
-        }
-        for (auto& t : th) t.join();
-        for (auto& e : errs)
-            if (e) std::rethrow_exception(e);
-    }
-    for (auto& sg : segs) segments.push_back(sg);
-}
-
-// One slice of reads already in HBM (bases `sb`, offsets `so`, `n_slice` reads whose first read is
-// number `read_base` of the caller's batch): passes over the slice, hits appended to d_hits.
-// h_off: host copy of the slice's n_slice + 1 offsets (needed only when the slice holds reads beyond
-// kMaxRegisterReadLen bases).
-void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* so, const uint32_t* h_off, uint64_t n_slice,
-                      uint32_t slice_max_len, uint64_t read_base) {
-    if (slice_max_len > kMaxReadLen)
-        throw std::runtime_error("limit: read of " + std::to_string(slice_max_len) + " bases; this build verifies reads up to " +
-                                 std::to_string(kMaxReadLen));
-    const DevIndexView& v = di->view;
-    const uint32_t K = p.seed_size, G = p.seed_interval;
-    const bool only_flags = flags_only();
-    float* stage_ms = stage_acc;
-    // Long reads (beyond the register-resident kernels) run in passes of their own, through the tiled kernel:
-    // a pass is a contiguous range of reads, so cutting the slice at them keeps the hits in read order, and
-    // the dense per-strand seed slots of the other passes stay sized for ordinary reads.
-    const bool mixed = slice_max_len > kMaxRegisterReadLen;
-    if (mixed && !h_off) throw std::runtime_error("internal: a slice with long reads needs its host offsets");
-    constexpr uint64_t kLongPassSlots = 16ull << 20;  // seed slots of one long-read pass, at most
-
-    uint64_t pass_reads = n_slice;
-    uint64_t r0 = 0;
-    while (r0 < n_slice) {
-        uint32_t nr = (uint32_t)std::min<uint64_t>(pass_reads, n_slice - r0);
-        uint32_t pass_max_len = slice_max_len;
-        bool tiled = false;
-        if (mixed) {
-            auto len_of = [&](uint64_t i) { return h_off[i + 1] - h_off[i]; };
-            tiled = len_of(r0) > kMaxRegisterReadLen;
-            uint32_t cnt = 0, ml = 0;
-            while (cnt < nr && (len_of(r0 + cnt) > kMaxRegisterReadLen) == tiled) {
-                const uint32_t ml2 = std::max(ml, len_of(r0 + cnt));
-                if (tiled && cnt && 2ull * (cnt + 1) * (ml2 >= K ? (ml2 - K) / G + 1 : 0) > kLongPassSlots) break;
-                ml = ml2;
-                cnt++;
-            }
-            nr = cnt;
-            pass_max_len = ml;
-        }
-        const uint32_t max_ns = pass_max_len >= K ? (pass_max_len - K) / G + 1 : 0;
-        const uint32_t nstr = nr * 2;
-        const uint64_t slots = (uint64_t)nstr * max_ns;
-        if (slots > seed_cap) {
-            (void)hipFree(d_seed_lo);
-            (void)hipFree(d_seed_cnt);
-            (void)hipFree(d_seed_pre);
-            d_seed_lo = d_seed_cnt = d_seed_pre = nullptr;
-            // room for a full workspace of reads like these, not just this pass: slices of a host batch grow
-            // towards the workspace size, and every hipFree / hipMalloc stalls the whole device
-            const uint64_t want = tiled ? slots : std::max<uint64_t>(slots, 2 * ws_reads * (uint64_t)max_ns);
-            uint64_t dummy = 0;
-            if (getenv("MTSV_TRACE")) fprintf(stderr, "[workspace] seed slot arrays grow %llu -> %llu entries\n", (unsigned long long)seed_cap, (unsigned long long)want);
-            dev_alloc(&d_seed_lo, want, &dummy);
-            dev_alloc(&d_seed_cnt, want, &dummy);
-            dev_alloc(&d_seed_pre, want, &dummy);
-            seed_cap = want;
-        }
-        // the reads' bit planes (EvalArgs::planes) for the passes k_edit_myers verifies: k_thin writes them, sized like
-        // the seed slot arrays for a full workspace of reads like these
-        // the verify path of the pass, decided once: edit-first order, or the reference order in rounds (k_sw_pairs +
-        // k_edit_myers; bit 31 of a work item is a flag, so hit_cap < 2^31) -- both through k_edit_myers, reads up to 253 bases
-        const bool edit_first_path = !tiled && verify_mode == 1 && pass_max_len <= 253;
-        const bool rounds_path = !tiled && !edit_first_path && sw_pairs && pass_max_len <= 253 && hit_cap < 0x80000000ull;
-        const bool myers_pass = edit_first_path || rounds_path;
-        const uint32_t plane_words = myers_pass ? myers_words(pass_max_len) : 0;
-        if ((uint64_t)nr * 3 * plane_words > plane_cap) {
-            (void)hipFree(d_planes);
-            d_planes = nullptr;
-            const uint64_t want = std::max<uint64_t>(nr, ws_reads) * 3 * plane_words;
-            uint64_t dummy = 0;
-            dev_alloc(&d_planes, want, &dummy);
-            plane_cap = want;
-        }
-        // ---- seeds ----
-        HIP_CHECK(hipEventRecord(ev[0], stream));
-        // (d_seed_pre is k_thin's output: until then it holds the list of the slots that take the general code -- an N in
-        //  the seed's table part; counter slot 22.  The second kernel's grid covers the share of such slots the passes before
-        //  had, half as much again: the count is checked at the pass's first round trip below.)
-        const uint32_t listed_cap = (uint32_t)std::min<uint64_t>(slots, std::max<uint64_t>(4096, (uint64_t)((double)slots * listed_share)));
-        launch_search(stream, v, sb, so, (uint32_t)r0, nr, max_ns, K, G, d_seed_lo, d_seed_cnt, d_seed_pre, (uint32_t*)(d_counters + 22), listed_cap, di->d_kmer_levels,
-                      fused_clear && ctr22_zero);
-        ctr22_zero = false;
-        HIP_CHECK(hipEventRecord(ev[1], stream));
-        // the seed stage by tiles when the pass fits them (kernels.hpp); k_thin and k_expand with seed_pre between them otherwise
-        const bool tile_pass = seed_tiles && max_ns && seed_tile_fits(max_ns, pass_max_len, slots);
-        if (tile_pass)
-            launch_thin_tiled(stream, sb, so, (uint32_t)r0, nr, p.edit_rate, p.min_seed, max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,
-                              d_strand_hits, d_strand_nseeds, myers_pass ? d_planes : nullptr, plane_words);
-        else if (max_ns)
-            launch_thin(stream, sb, so, (uint32_t)r0, nr, p.edit_rate, p.min_seed, max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,
-                        d_seed_pre, d_strand_hits, d_strand_nseeds, myers_pass ? d_planes : nullptr, plane_words);
-        else {
-            HIP_CHECK(hipMemsetAsync(d_strand_hits, 0, (uint64_t)nstr * 4, stream));
-            HIP_CHECK(hipMemsetAsync(d_strand_nseeds, 0, (uint64_t)nstr * 4, stream));
-        }
-        launch_scan(stream, d_strand_hits, nstr, d_tile_sums, d_counters + 0, d_strand_off);
-        launch_publish(stream, d_counters, h_counters, 1);
-        launch_publish(stream, d_counters + 22, h_counters + 22, 1);
-        HIP_CHECK(hipEventRecord(ev[2], stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        {
-            const uint64_t n_listed = h_counters[22] & 0xffffffffull;
-            const double share = slots ? (double)n_listed / (double)slots : 0.0;
-            if (n_listed > listed_cap) {  // more slots on the list than the grid covered: the pass again, with a grid for them
-                listed_share = std::min(1.0, share * 1.25 + 0.01);
-                if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] %llu listed seed slots, grid for %u: pass again\n", (unsigned long long)n_listed, listed_cap);
-                continue;
-            }
-            listed_share = std::min(1.0, std::max(0.02, share * 1.5 + 0.005));
-        }
-        const uint64_t total_hits = h_counters[0];
-        if (total_hits > hit_cap) {
-            if (nr > 1) {
-                pass_reads = std::max<uint64_t>(1, nr / 2);
-                continue;  // redo this pass with fewer reads
-            }
-            // one read with more seed hits than the workspace (a long read in a repeat): grow the workspace
-            if (total_hits > 0xfffffff0ull)
-                throw std::runtime_error("device: one read has " + std::to_string(total_hits) + " seed hits, more than 2^32");
-            grow_hit_workspace(total_hits);
-        }
-        stats.n_passes++;
-        stats.n_seed_tile_passes += tile_pass;
-        if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] pass of %u reads, max_ns %u, longest read %u: seed stage %s\n", nr, max_ns, pass_max_len, tile_pass ? "by tiles" : "legacy");
-        stats.n_seed_slots += slots;
-        stats.n_seed_hits += total_hits;
-        // ---- locate ----
-        if (tile_pass)
-            launch_expand_tiled(stream, v, nstr, max_ns, G, d_seed_lo, d_seed_cnt, d_strand_off, d_hit_row, d_hit_ref, d_hit_q);
-        else
-            launch_expand(stream, v, nstr, max_ns, G, d_seed_lo, d_seed_cnt, d_seed_pre, d_strand_off, d_hit_row, d_hit_ref,
-                          d_hit_q);
-        HIP_CHECK(hipEventRecord(ev[3], stream));
-        if (!v.sa_full)
-            launch_locate(stream, v, (uint32_t)total_hits, d_strand_off + nstr, d_hit_row, d_hit_ref,
-                          (unsigned long long*)(d_counters + 2));
-        HIP_CHECK(hipEventRecord(ev[4], stream));
-        // ---- candidates ----
-        // counters: [1] lo = round-0 worklist count, [7] lo/hi = ping-pong counts of later rounds
-        // [15] lo = strands for k_coalesce_mid, hi = strands of 13..16 seed hits
-        // One launch zeroes these, k_coalesce_heavy's ticket, the counters round 0 of the verify rounds starts from ([8..11],
-        // [17..18]; no coalescing kernel touches them) and k_search's list count of the next pass ([22]: the host has read it).
-        if (fused_clear) {
-            uint64_t mask = 1ull << 1 | 1ull << 7 | 1ull << 15 | 1ull << kCtrHeavyTicket | 1ull << 22;
-            if (rounds_path) mask |= 1ull << 8 | 1ull << 9 | 1ull << 10 | 1ull << 11 | 1ull << 17 | 1ull << 18;
-            launch_clear_counters(stream, d_counters, mask);
-            ctr22_zero = true;
-        } else {
-            HIP_CHECK(hipMemsetAsync(d_counters + 1, 0, 8, stream));
-            HIP_CHECK(hipMemsetAsync(d_counters + 7, 0, 8, stream));
-            HIP_CHECK(hipMemsetAsync(d_counters + 15, 0, 8, stream));
-        }
-        launch_coalesce(stream, v, so, (uint32_t)r0, nstr, p.max_candidates, d_strand_off,
-                        d_strand_nseeds, d_hit_ref, d_hit_q, d_hit_key, d_cand_tmp, d_cand, d_cand_next,
-                        d_cand_status, d_strand_ncand, d_worklist, d_heavy_list, d_counters, fused_clear);
-        HIP_CHECK(hipEventRecord(ev[5], stream));
-        // ---- verify: rounds over the same-TaxId chains ----
-        // One lane of the workspace at a time (the turn): this lane's coalescing kernels are enqueued and run while it waits,
-        // beside the verify kernels of the lane that has it.  It goes back after the pass's last verify round trip, or with
-        // whatever leaves this pass early.  (A pass without seed hits does not take it; its kernels are still launched, at
-        // their smallest grids, and find nothing.)
-        Batch* const root = parent ? parent : this;
-        VerifyTurn::Guard turn;
-        if (total_hits) turn.take(root->verify_turn, read_base + r0, this);
-        const uint32_t R = root->myers_wgs_per_cu;
-        {
-            EvalArgs a;
-            a.bases = sb;
-            a.read_off = so;
-            a.r0 = (uint32_t)r0;
-            a.edit_rate = p.edit_rate;
-            a.max_candidates = p.max_candidates;
-            a.strand_off = d_strand_off;
-            a.cand = d_cand;
-            a.cand_next = d_cand_next;
-            a.cand_status = d_cand_status;
-            a.planes = myers_pass ? d_planes : nullptr;
-            a.plane_words = plane_words;
-            a.out = d_out;
-            a.n_verified = (unsigned long long*)(d_counters + 4);
-            a.window_bytes = (unsigned long long*)(d_counters + 5);
-            a.sw_columns = (unsigned long long*)(d_counters + 14);
-            // one launch: a group whose candidate fails walks on to the next candidate of the same TaxId
-            a.worklist = d_worklist;
-            a.wl_count = (const uint32_t*)(d_counters + 1);
-            a.wl_cursor = (uint32_t*)(d_counters + 7);
-            stats.n_rounds = 1;
-            if (tiled) {
-                // strips sized from the longest window of the pass (one small round trip; long reads are rare)
-                HIP_CHECK(hipMemsetAsync(d_counters + 13, 0, sizeof(uint64_t), stream));
-                launch_max_window(stream, nstr, d_strand_off, d_strand_ncand, d_cand, (unsigned long long*)(d_counters + 13));
-                launch_publish(stream, d_counters + 13, h_counters + 13, 1);
-                HIP_CHECK(hipStreamSynchronize(stream));
-                const uint32_t strip_len = (uint32_t)std::max<uint64_t>(h_counters[13], 1);
-                const uint64_t need = (uint64_t)tiled_groups(total_hits, strip_len) * strip_len;
-                if (need > strip_cap) {
-                    (void)hipFree(d_strip);
-                    d_strip = nullptr;
-                    uint64_t dummy = 0;
-                    dev_alloc(&d_strip, need, &dummy);
-                    strip_cap = need;
-                }
-                a.strip = d_strip;
-                a.strip_len = strip_len;
-                launch_evaluate_tiled(stream, v, a, total_hits);
-            } else if (edit_first_path) {
-                root->verify_turn.note_grid(launch_edit_myers(stream, v, a, total_hits, pass_max_len, 0, R));
-            } else if (rounds_path) {
-                // Reference order, split by predicate: k_sw_pairs runs the prefilter of index.rs:406 two
-                // candidates per group, k_edit_myers the edit distance of :407-410 on those that passed.
-                // A candidate that passes the first and fails the second sends its TaxId's next
-                // candidate to another round (rare); rounds end when nothing is left.
-                // counters: [8] SW cursor, [9] pass count, [10] Myers cursor, [11]/[12] next-round counts, [16] sweep list
-                // Round 0 is one pass of k_edit_myers in fused mode over the whole worklist: the unit-cost distance under the SW
-                // matrix's matches decides the prefilter from both sides and, wherever read or window holds no N, is the edit
-                // distance itself.  k_sw_pairs sweeps what lies between its thresholds, list mode finishes what the sweep passed.
-                // MTSV_SW_FUSED=0 (and MTSV_SW_BOUND=0) start with k_sw_diag instead: the lower bounds on the seed diagonal, a
-                // lane per work item; what they decide goes straight to pass_list, the rest to sweep_list for k_sw_pairs.
-                const bool fused = sw_bound && sw_fused;
-                uint32_t* pass_list = (uint32_t*)d_hit_key;                       // coalesce scratch is free now
-                uint32_t* sweep_list = (uint32_t*)d_hit_key + hit_cap;            // (8 bytes per seed hit)
-                uint32_t* next_lists[2] = {(uint32_t*)d_cand_tmp, (uint32_t*)d_cand_tmp + hit_cap};
-                const uint32_t* wl = d_worklist;
-                const uint32_t* wl_count = (const uint32_t*)(d_counters + 1);
-                uint64_t items = total_hits;
-                for (uint32_t round = 0;; round++) {
-                    uint64_t* next_slot = d_counters + 11 + (round & 1);
-                    if (!fused_clear) {
-                        HIP_CHECK(hipMemsetAsync(d_counters + 8, 0, 3 * sizeof(uint64_t), stream));
-                        HIP_CHECK(hipMemsetAsync(next_slot, 0, sizeof(uint64_t), stream));
-                    } else if (round) {  // (round 0: zeroed with the coalescing kernels' counters)
-                        launch_clear_counters(stream, d_counters, 1ull << 8 | 1ull << 9 | 1ull << 10 | 1ull << (11 + (round & 1)));
-                    }
-                    // The tail of a round -- k_sw_pairs and list-mode k_edit_myers -- is sized from its own list: later rounds
-                    // have its length on the host (n_next); round 0 asks for what the fused pass left undecided, one more round
-                    // trip in place of two persistent grids sized from the pass's seed hits.  An empty list launches nothing.
-                    uint64_t tail_items = items;
-                    bool tail_listed = tail_from_list && round > 0;
-                    EvalArgs sw = a;
-                    sw.worklist = wl;
-                    sw.wl_count = wl_count;
-                    sw.wl_cursor = (uint32_t*)(d_counters + 8);
-                    sw.wl_reverse = round == 0;
-                    sw.counters = d_counters;
-                    sw.wl_count_slot = round == 0 ? 1u : 11u + ((round - 1) & 1u);
-                    sw.pass_list = pass_list;
-                    sw.pass_count = (uint32_t*)(d_counters + 9);
-#ifdef MTSV_SW_HIST
-                    if (!d_strip) { uint64_t dummy = 0; dev_alloc(&d_strip, 4096, &dummy); strip_cap = 4096; }
-                    HIP_CHECK(hipMemsetAsync(d_strip, 0, 768 * 4, stream));
-                    sw.strip = d_strip;
-#endif
-                    if (round == 0) HIP_CHECK(hipEventRecord(ev[10], stream));
-                    if (round == 0 && sw_diag && sw_prepass && !fused) {
-                        HIP_CHECK(hipMemsetAsync(d_counters + 16, 0, sizeof(uint64_t), stream));
-                        launch_sw_diag(stream, v, sw, items, pass_max_len, sweep_list, 16);
-                        HIP_CHECK(hipEventRecord(ev[12], stream));
-                        sw.worklist = sweep_list;
-                        sw.wl_count_slot = 16;
-                        sw.wl_reverse = 0;  // k_sw_diag read the worklist from its end
-                    }
-                    if (round == 0 && sw_bound) {
-                        // What the lower bounds leave are mostly chance seed hits.  The unit-cost edit distance under the SW
-                        // matrix's matches bounds the score from both sides (k_edit_myers in bound mode) at a third of a
-                        // sweep's instructions: it refutes those, passes most of the rest, and only what lies between its
-                        // two thresholds ([17] counts it; the seed-hit rows of k_expand are free by now) is swept below.
-                        if (!fused_clear) HIP_CHECK(hipMemsetAsync(d_counters + 17, 0, 2 * sizeof(uint64_t), stream));  // [18]: its claim cursor
-                        EvalArgs bd = sw;
-                        bd.wl_count = (const uint32_t*)(d_counters + sw.wl_count_slot);
-                        bd.wl_cursor = (uint32_t*)(d_counters + 18);
-                        bd.und_list = (uint32_t*)d_hit_row;
-                        bd.und_slot = 17;
-                        bd.myers_ctr = (unsigned long long*)(d_counters + 19);
-                        // (fused: from the worklist's end, and accepted candidates go straight to `out`)
-                        root->verify_turn.note_grid(launch_edit_myers(stream, v, bd, items, pass_max_len, fused ? 3 : 2, R));
-                        HIP_CHECK(hipEventRecord(ev[13], stream));
-                        sw.worklist = bd.und_list;
-                        sw.wl_count_slot = 17;
-                        sw.wl_reverse = 0;
-                        if (fused && tail_from_list) {  // (fused: the pass list holds only what k_sw_pairs passes of these)
-                            launch_publish(stream, d_counters + 17, h_counters + 17, 1);
-                            HIP_CHECK(hipStreamSynchronize(stream));
-                            tail_items = h_counters[17] & 0xffffffffull;
-                            tail_listed = true;
-                        }
-                    } else if (round == 0 && sw_diag && sw_prepass && sw_top) {
-                        // (MTSV_SW_BOUND=0) most of these are refuted on the top half of the read rows; the full-height launch
-                        // below takes what is left ([17] counts it)
-                        HIP_CHECK(hipMemsetAsync(d_counters + 17, 0, sizeof(uint64_t), stream));
-                        sw.und_list = (uint32_t*)d_hit_row;
-                        sw.und_slot = 17;
-                        launch_sw_pairs(stream, v, sw, items, pass_max_len, false, true);
-                        HIP_CHECK(hipMemsetAsync(d_counters + 8, 0, sizeof(uint64_t), stream));  // the claim cursor
-                        sw.worklist = sw.und_list;
-                        sw.wl_count_slot = 17;
-                    }
-                    const bool tail_empty = tail_listed && tail_items == 0;
-                    if (!tail_empty) launch_sw_pairs(stream, v, sw, tail_items, pass_max_len, sw_diag, false, round == 0 && sw_bound && !tail_listed);
-#ifdef MTSV_SW_HIST
-                    {
-                        static uint32_t hh[768];
-                        HIP_CHECK(hipMemcpyAsync(hh, d_strip, sizeof hh, hipMemcpyDeviceToHost, stream));
-                        HIP_CHECK(hipStreamSynchronize(stream));
-                        fprintf(stderr, "SWHIST round %u steps/4:", round);
-                        for (int i = 0; i < 128; i++) if (hh[i]) fprintf(stderr, " %d:%u", i * 4, hh[i]);
-                        fprintf(stderr, "\nSWHIST halves sweeping 0/1/2: %u %u %u\nSWHIST fail best:", hh[128], hh[129], hh[130]);
-                        for (int i = 0; i < 256; i++) if (hh[256 + i]) fprintf(stderr, " %d:%u", i, hh[256 + i]);
-                        fprintf(stderr, "\nSWHIST pass best:");
-                        for (int i = 0; i < 256; i++) if (hh[512 + i]) fprintf(stderr, " %d:%u", i, hh[512 + i]);
-                        fprintf(stderr, "\n");
-                    }
-#endif
-                    if (round == 0) HIP_CHECK(hipEventRecord(ev[11], stream));
-                    EvalArgs my = a;
-                    my.worklist = pass_list;
-                    my.wl_count = (const uint32_t*)(d_counters + 9);
-                    my.wl_cursor = (uint32_t*)(d_counters + 10);
-                    my.next_list = next_lists[round & 1];
-                    my.next_count = (uint32_t*)next_slot;
-                    my.myers_ctr = (unsigned long long*)(d_counters + 19);
-                    if (!tail_empty) root->verify_turn.note_grid(launch_edit_myers(stream, v, my, tail_items, pass_max_len, 1, R, tail_listed));
-                    if (round == 0) HIP_CHECK(hipEventRecord(ev[14], stream));
-                    if (tail_empty) {
-                        h_counters[9] = h_counters[11] = 0;  // nothing passed, nothing for another round
-                        if (round == 0) HIP_CHECK(hipEventSynchronize(ev[14]));
-                    } else {
-                        launch_publish(stream, next_slot, h_counters + 11, 1);
-                        launch_publish(stream, d_counters + 9, h_counters + 9, 1);
-                        HIP_CHECK(hipStreamSynchronize(stream));
-                    }
-                    sw_passed_acc += h_counters[9] & 0xffffffffull;
-                    if (round == 0) {
-                        float ms = 0;
-                        HIP_CHECK(hipEventElapsedTime(&ms, ev[10], ev[11]));
-                        sw_ms_acc += ms;
-                        int from = 10;  // the sweeps start after whichever bound kernels ran
-                        if (sw_diag && sw_prepass && !fused) {
-                            HIP_CHECK(hipEventElapsedTime(&ms, ev[10], ev[12]));
-                            diag_ms_acc += ms;
-                            from = 12;
-                        }
-                        if (sw_bound) {
-                            HIP_CHECK(hipEventElapsedTime(&ms, ev[from], ev[13]));
-                            bound_ms_acc += ms;
-                            from = 13;
-                        }
-                        HIP_CHECK(hipEventElapsedTime(&ms, ev[from], ev[11]));
-                        sweep_ms_acc += ms;
-                        HIP_CHECK(hipEventElapsedTime(&ms, ev[11], ev[14]));
-                        edit_ms_acc += ms;
-                    }
-                    const uint64_t n_next = h_counters[11] & 0xffffffffull;
-                    if (n_next == 0) break;
-                    stats.n_rounds++;
-                    wl = next_lists[round & 1];
-                    wl_count = (const uint32_t*)next_slot;
-                    items = n_next;
-                }
-                turn.release();
-            } else {
-                launch_evaluate(stream, v, a, total_hits, pass_max_len);
-            }
-            // (flags only: whether a strand has a hit does not depend on max_assignments -- the loop of index.rs:384-428
-            //  pushes its first accepted candidate before it looks at the limit -- so the selection stops at the first)
-            launch_resolve(stream, nstr, p.max_candidates, only_flags ? 1 : p.max_assignments, d_strand_off, d_strand_ncand, d_cand_status,
-                           d_out, d_strand_nout);
-        }
-        HIP_CHECK(hipEventRecord(ev[6], stream));
-        // ---- gather ----
-        // (flags only: no scan of the hit counts, no result array, no gather -- the pass ends with k_match below)
-        uint64_t total_out = 0;
-        if (!only_flags) {
-            launch_scan(stream, d_strand_nout, nstr, d_tile_sums, d_counters + 6, d_out_off);
-            launch_publish(stream, d_counters, h_counters, 8);
-            HIP_CHECK(hipStreamSynchronize(stream));
-            total_out = h_counters[6];
-            turn.release();  // (the paths without rounds: their verify kernels are through)
-        }
-        if (n_hits_total + total_out > hits_cap) {
-            // grow the result array, keeping what earlier passes produced
-            uint64_t ncap = std::max(hits_cap * 2, n_hits_total + total_out);
-            DevHit* nh = nullptr;
-            uint64_t dummy = 0;
-            dev_alloc(&nh, ncap, &dummy);
-            if (n_hits_total) HIP_CHECK(hipMemcpyAsync(nh, d_hits, n_hits_total * sizeof(DevHit), hipMemcpyDeviceToDevice, stream));
-            HIP_CHECK(hipStreamSynchronize(stream));
-            // run_host may be copying an earlier slice's hits out of the old array on the owner's copy stream (and
-            // another lane's thread may be issuing such a copy right now: the commit mutex covers the pointer swap)
-            Batch* root = parent ? parent : this;
-            std::unique_lock<std::mutex> commit_lk;
-            if (root->commit_mu) commit_lk = std::unique_lock<std::mutex>(*root->commit_mu);
-            if (root->copy_stream2) HIP_CHECK(hipStreamSynchronize(root->copy_stream2));
-            (void)hipFree(d_hits);
-            d_hits = nh;
-            hits_cap = ncap;
-        }
-        if (!only_flags) launch_gather(stream, nstr, read_base + r0, d_strand_off, d_strand_nout, d_out_off, d_out, d_hits, n_hits_total);
-        // (a compacted batch: the hits carry the caller's read numbers; the report and the flags below are per resident read)
-        if (!only_flags && root->mapped) launch_remap_reads(stream, d_hits + n_hits_total, total_out, root->d_read_map);
-        HIP_CHECK(hipEventRecord(ev[7], stream));
-        // the pass is committed from here on (a pass that is run again has not come this far): its reads join the taxa report
-        TaxaReport& rep = (parent ? parent : this)->report;
-        if (rep.on) {
-            if (!report_ev[0])
-                for (auto& e : report_ev) HIP_CHECK(hipEventCreate(&e));
-            HIP_CHECK(hipEventRecord(report_ev[0], stream));
-            launch_report(stream, nr, d_strand_nout, d_out_off, d_hits + n_hits_total, rep.d_taxa, rep.n_taxa, rep.dense, rep.hash_slots, rep.d_counts,
-                          rep.d_counts + 4ull * rep.n_taxa, rep.trace ? rep.d_counts + 4ull * rep.n_taxa + 1 : nullptr);
-            HIP_CHECK(hipEventRecord(report_ev[1], stream));
-        }
-        // ... and they get their match flags
-        MatchFlags& mf = (parent ? parent : this)->match;
-        if (mf.mode != MTSV_MATCH_OFF) {
-            const uint64_t first_bit = read_base + r0 - mf.call_base;
-            if (first_bit + nr > mf.n_reads) throw std::runtime_error("internal: match flags of a pass beyond the run's reads");
-            if (!match_ev[0])
-                for (auto& e : match_ev) HIP_CHECK(hipEventCreate(&e));
-            HIP_CHECK(hipEventRecord(match_ev[0], stream));
-            launch_match(stream, nr, d_strand_nout, first_bit, mf.d_words, mf.d_words + mf.cap_words);
-            HIP_CHECK(hipEventRecord(match_ev[1], stream));
-        }
-        // ... and their hits are reduced to assignments
-        const bool collapse_on = !only_flags && root->assign.mode != MTSV_ASSIGN_OFF;
-        if (collapse_on) collapse_enqueue(nr, d_strand_nout, d_out_off, d_hits + n_hits_total, total_out);
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipGetLastError());
-        turn.release();
-        if (collapse_on) collapse_commit();
-        if (mf.mode != MTSV_MATCH_OFF) {
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, match_ev[0], match_ev[1]));
-            std::lock_guard<std::mutex> lk(mf.mu);
-            mf.ms += ms;
-            mf.launches++;
-        }
-        if (rep.on) {
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, report_ev[0], report_ev[1]));
-            std::lock_guard<std::mutex> lk(rep.mu);
-            rep.ms += ms;
-            rep.launches++;
-        }
-        n_hits_total += total_out;
-        for (int s = 0; s < 7; s++) {
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, ev[s], ev[s + 1]));
-            stage_ms[s] += ms;
-        }
-        r0 += nr;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2157,18 +1602,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                         while (seg_begin[sg] > next_read) sg--;
                         const uint64_t seg_end = sg + 1 < seg_begin.size() ? seg_begin[sg + 1] : n;
                         const uint64_t avail = std::min(arrived, seg_end) > next_read ? std::min(arrived, seg_end) - next_read : 0;
-                        // the ramp: grows with the reads already taken, falls with the reads left
-                        uint64_t want = ws_reads;
-                        if (n > 2 * ws_reads) {
-                            const uint64_t floor_reads = std::min<uint64_t>(ws_reads, ramp_floor);
-                            const uint64_t up = floor_reads + next_read / n_lanes_used;
-                            const uint64_t down = std::max(floor_reads, (n - next_read) / (n_lanes_used + 1));
-                            want = std::min(ws_reads, std::min(up, down));
-                        }
-                        uint64_t take = 0;
-                        if (avail >= want) take = want;
-                        else if (avail && (all_arrived || arrived >= seg_end)) take = avail;            // nothing more will come for it
-                        else if (busy_lanes == 0 && avail >= std::min(idle_take, want)) take = avail;  // do not leave the device idle
+                        const uint64_t take = range_take(n, next_read, ws_reads, ramp_floor, idle_take, n_lanes_used, avail, all_arrived || arrived >= seg_end, busy_lanes);
                         if (take) {
                             rb = next_read;
                             re = next_read + take;

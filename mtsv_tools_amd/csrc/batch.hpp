@@ -1,4 +1,4 @@
-// batch.hpp -- device workspace of one read batch (see batch.hip).
+// batch.hpp -- device workspace of one read batch (see batch.hip; the pass driver: batch_pass.hip).
 #pragma once
 #include <condition_variable>
 #include <memory>
@@ -44,6 +44,8 @@ struct Batch {
     // HBM-latency-bound stages of one part overlap the VALU-bound verification of another.  The owner
     // is lane 0 and holds the input buffers; the other lanes borrow them.  MTSV_LANES=1 disables it.
     Batch* parent = nullptr;
+    Batch* root() { return parent ? parent : this; }  // the owner: turn, report, flags, assignments and lane policies are its
+    const Batch* root() const { return parent ? parent : this; }
     std::vector<std::unique_ptr<Batch>> extra;
     int n_lanes = 1;
     uint64_t ws_reads = 0;  // reads one lane's workspace is sized for
@@ -77,14 +79,23 @@ struct Batch {
     uint32_t* d_planes = nullptr;  // bit planes of a pass's reads (EvalArgs::planes): k_thin writes them, k_edit_myers sets up from them
     uint64_t plane_cap = 0;        // ... in words; allocated when a pass first needs them, for a full workspace of such reads
     uint64_t* h_counters = nullptr;  // pinned
-    hipEvent_t ev[15];  // [0..7] stage boundaries of a pass, [8..9] the lane's run, [10..11] around the prefilter kernels, [12] after k_sw_diag,
-                        // [13] after the edit-distance bound, [14] after the first round's edit distances
+    enum Ev {
+        // a pass: stage s (MTSV_N_STAGES' first seven) lies between events s and s + 1
+        kEvPassBegin = 0, kEvSearched, kEvSeeded, kEvExpanded, kEvLocated, kEvCoalesced, kEvVerified, kEvGathered,
+        kEvRunBegin, kEvRunEnd,  // the lane's run
+        kEvSwBegin, kEvSwEnd,    // round 0: around the prefilter kernels
+        kEvDiagEnd,              // ... after k_sw_diag
+        kEvBoundEnd,             // ... after the edit-distance bound
+        kEvEditEnd,              // ... after its edit distances
+        kEvCount
+    };
+    hipEvent_t ev[kEvCount];
     float sw_ms_acc = 0, sweep_ms_acc = 0, diag_ms_acc = 0, bound_ms_acc = 0, edit_ms_acc = 0;
     uint64_t sw_passed_acc = 0;   // candidates k_sw_pairs sent on to the edit distance (all rounds and passes of the run)
 
     std::vector<uint32_t> h_read_off;
     uint32_t max_len = 0;
-    static constexpr int kCounters = 25;
+    static constexpr int kCounters = kCtrCount;  // (the slots: kernels.hpp)
     double listed_share = 0.125;  // seed slots that took the general search code in the last pass, with a margin (k_search_listed's grid)
     bool sw_diag = true;   // k_sw_pairs tries the ungapped diagonal as a lower bound first (MTSV_SW_DIAG=0: off)
     bool sw_top = true;      // ... and what they leave is swept on the top half of the read rows first (MTSV_SW_TOP=0: off)
@@ -100,7 +111,7 @@ struct Batch {
     bool fused_clear = true;     // the counters of a stage are zeroed by one launch_clear_counters (MTSV_FUSED_CLEAR=0: a memset each)
     bool seed_tiles = true;      // the seed stage by tiles, k_thin_tiled + k_expand_tiled, for the passes that fit them (MTSV_SEED_STAGE=legacy:
                                  // k_thin writing seed_pre and k_expand reading it, for every pass)
-    bool ctr22_zero = false;     // ... slot 22 (k_search's list count) is known to be zero on the stream
+    bool listed_zero = false;    // ... kCtrListedSlots (k_search's list count) is known to be zero on the stream
     // The verify turn: one lane of a workspace at a time has the verify kernels of a pass in flight (two VALU-bound launches beside
     // each other gain nothing, and the second takes the LDS the first frees from the memory-bound kernels that could use it).  The
     // owner holds it; lanes waiting for it are served in the order of their passes' first reads (MTSV_VERIFY_TURN=0: off; never
@@ -201,7 +212,7 @@ struct Batch {
     };
     MatchFlags match;
     hipEvent_t match_ev[2] = {nullptr, nullptr};  // around a lane's k_match; created with the lane's first one
-    bool flags_only() const { return (parent ? parent : this)->match.mode == MTSV_MATCH_ONLY; }
+    bool flags_only() const { return root()->match.mode == MTSV_MATCH_ONLY; }
     void set_match_flags(int mode);
     // the flags of the last run as ceil(n_reads / 64) words (at least one), bits at and above n_reads zero
     void match_flags(std::vector<uint64_t>& words, uint64_t* n_reads, uint64_t* n_matched);
@@ -279,7 +290,7 @@ struct Batch {
         hipEvent_t ev[2] = {nullptr, nullptr};
     };
     CollapseScratch collapse;
-    bool assign_only() const { return (parent ? parent : this)->assign.mode == MTSV_ASSIGN_ONLY; }
+    bool assign_only() const { return root()->assign.mode == MTSV_ASSIGN_ONLY; }
     void set_assignments(int mode);
     void set_assignment_grain(int grain);
     // the assignments of the last run, in read order, in a pinned array of the pool (*n may be 0: *a is still to be freed)
@@ -318,6 +329,27 @@ struct Batch {
     void run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* so, const uint32_t* h_off, uint64_t n_slice,
                    uint32_t slice_max_len, uint64_t read_base);
     void end_run();
+    // A pass of run_slice and its stages (batch_pass.hip; DESIGN.md, "How a pass is laid out")
+    struct Pass;
+    struct Round;
+    enum class Seeded { kGoOn, kSameReads, kHalfReads };  // what the seed stage found: go on, or the pass again
+    void room_seed_slots(const PassPlan& pl);
+    void room_planes(const PassPlan& pl);
+    void room_strip(uint64_t need);
+    void room_hits(uint64_t total_out);
+    Seeded stage_seeds(Pass& ps);
+    void stage_locate(Pass& ps);
+    void stage_candidates(Pass& ps);
+    void stage_verify(Pass& ps);
+    void verify_tiled(Pass& ps, EvalArgs& a);
+    void verify_rounds(Pass& ps, const EvalArgs& a);
+    void round0_diag(Pass& ps, Round& r);
+    void round0_bound(Pass& ps, Round& r);
+    void round0_top(Pass& ps, Round& r);
+    void round_tail(Pass& ps, Round& r, const EvalArgs& a);
+    void round0_times();
+    void stage_gather(Pass& ps);
+    void stage_commit(Pass& ps);
 };
 
 extern int g_default_verify_mode;  // mtsv_set_default_verify_mode

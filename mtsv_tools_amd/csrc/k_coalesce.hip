@@ -504,12 +504,12 @@ struct CoalesceArgs {
     uint32_t* heavy_list;   // n_strands entries: 17..64-hit strands from the front, longer ones from the back
     uint64_t* counters;     // the lane's counter block: one pointer instead of four (this kernel sits at the SGPR limit)
 };
-// slots of the counter block (batch.hip's d_counters) the coalescing kernels use
-__device__ inline uint32_t* co_wl_count(const CoalesceArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + 1); }
-__device__ inline uint32_t* co_heavy_count(const CoalesceArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + 1) + 1; }
-__device__ inline uint32_t* co_lane16_count(const CoalesceArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + 15) + 1; }
-__device__ inline uint32_t* co_mid_count(const CoalesceArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + 15); }
-__device__ inline unsigned long long* co_n_cand(const CoalesceArgs& a) { return reinterpret_cast<unsigned long long*>(a.counters + 3); }
+// slots of the counter block (kernels.hpp: CtrSlot) the coalescing kernels use
+__device__ inline uint32_t* co_wl_count(const CoalesceArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + kCtrWorklist); }
+__device__ inline uint32_t* co_heavy_count(const CoalesceArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + kCtrWorklist) + 1; }
+__device__ inline uint32_t* co_lane16_count(const CoalesceArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + kCtrMidStrands) + 1; }
+__device__ inline uint32_t* co_mid_count(const CoalesceArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + kCtrMidStrands); }
+__device__ inline unsigned long long* co_n_cand(const CoalesceArgs& a) { return reinterpret_cast<unsigned long long*>(a.counters + kCtrCandidates); }
 
 // A strand per LANE.  Most strands hold no seed hit at all (the other strand of a read, reads without an origin), a
 // chance hit or two, or the seven to ten hits of the read's own origin -- and the walk of index.rs:445-485 is sequential,
@@ -937,9 +937,9 @@ void launch_coalesce(hipStream_t s, const DevIndexView& ix, const uint32_t* read
                      uint64_t* cand_tmp, uint4* cand, uint32_t* cand_next, uint32_t* cand_status,
                      uint32_t* strand_ncand, uint32_t* worklist, uint32_t* heavy_list, uint64_t* counters,
                      bool ticket_is_zero) {
-    uint32_t* wl_count = reinterpret_cast<uint32_t*>(counters + 1);
+    uint32_t* wl_count = reinterpret_cast<uint32_t*>(counters + kCtrWorklist);
     uint32_t* heavy_count = wl_count + 1;
-    unsigned long long* n_cand_total = reinterpret_cast<unsigned long long*>(counters + 3);
+    unsigned long long* n_cand_total = reinterpret_cast<unsigned long long*>(counters + kCtrCandidates);
     // Grids follow the work on passes of a few hundred thousand reads: a workgroup costs ~0.1 us to dispatch whether it
     // finds work or not, and the kernels of the other lanes wait for the same dispatcher (a host batch of 10 M reads in
     // ranges of 0.3 - 1 M: 39.7 -> 38.8 ms).  Every kernel here strides over its list; a wavefront takes 64 strands per

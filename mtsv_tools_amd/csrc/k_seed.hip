@@ -439,7 +439,7 @@ __global__ __launch_bounds__(256) void k_search_fast(DevIndexView ix, const uint
 
 // the listed slots through the general code, every lane of a wavefront busy.  One entry per thread, no loop (a grid that
 // strides over the device-side count keeps every field of the index view live across the loop: scalar-register spills):
-// the host sizes the grid from the share of such slots in the passes before (batch.hip: it runs the pass again when the
+// the host sizes the grid from the share of such slots in the passes before (batch_pass.hip: it runs the pass again when the
 // list turned out longer than the grid).
 __global__ __launch_bounds__(256) void k_search_listed(DevIndexView ix, const uint8_t* __restrict__ bases,
                                                        const uint32_t* __restrict__ read_off, uint32_t r0, uint32_t max_ns, uint32_t K,

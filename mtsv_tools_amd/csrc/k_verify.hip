@@ -484,7 +484,7 @@ __device__ inline void wave_lds_handoff() {
 
 // DIAG: try the lower bounds on the seed diagonal before a sweep (default; MTSV_SW_DIAG=0 launches the
 // instantiation without them, which tests use to check that bounds and sweeps decide alike).
-// k_sw_pairs reaches its counters through one base pointer (slots of batch.hip's d_counters): six separate
+// k_sw_pairs reaches its counters through one base pointer (kernels.hpp: CtrSlot): six separate
 // pointers cost twelve scalar registers of a kernel that sits at the SGPR file's limit.
 __device__ inline uint32_t* sw_cursor(const EvalArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + kCtrSwCursor); }
 __device__ inline uint32_t* sw_pass_count(const EvalArgs& a) { return reinterpret_cast<uint32_t*>(a.counters + kCtrPassCount); }

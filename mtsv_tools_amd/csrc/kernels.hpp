@@ -34,6 +34,7 @@
 #include <algorithm>
 
 #include "dev_layout.hpp"
+#include "pass_plan.hpp"
 
 namespace mtsv {
 
@@ -48,11 +49,56 @@ struct DevHit {  // byte-identical to mtsv_hit (include/mtsv_amd.h)
 };
 static_assert(sizeof(DevHit) == 32, "DevHit must match mtsv_hit");
 
-// slots of a lane's counter block (batch.hip: d_counters) that kernels address by number
-constexpr uint32_t kCtrVerified = 4, kCtrWindowBytes = 5, kCtrSwCursor = 8, kCtrPassCount = 9, kCtrSwCellPairs = 14;
-// k_coalesce_heavy: [kCtrHeavyWalk] lo = strands of the lane's passes walked by runs, hi = by the wavefront walk because a run
-// was too long; [kCtrHeavyTicket] lo = the next strand of the list to claim (zeroed by launch_coalesce)
-constexpr uint32_t kCtrHeavyWalk = 23, kCtrHeavyTicket = 24;
+// The slots of a lane's counter block (Batch::d_counters, u64 each; published to Batch::h_counters).  Per slot: width;
+// writer; reader; who zeroes it.  "run" = Batch::reset_lane zeroes the whole block when a run begins and nothing else does;
+// "pass" = the clear of the candidates stage (kCtrClearPass, with the rounds path kCtrClearRound0 too; MTSV_FUSED_CLEAR=0: a
+// memset each); "round" = ctr_clear_round() before every verify round after the first.
+enum CtrSlot : uint32_t {
+    kCtrSeedHits = 0,      // u64; launch_scan over the strands' seed hits (stored, not added); host: the pass's seed hits; run
+    kCtrWorklist = 1,      // lo: round-0 work list length; k_coalesce*; the verify kernels, k_sw_*.  hi: heavy strands listed;
+                           //   k_coalesce; k_coalesce_heavy, host trace.  pass
+    kCtrLfSteps = 2,       // u64; k_locate adds; host statistic at the run's end; run
+    kCtrCandidates = 3,    // u64; k_coalesce* add; host statistic at the run's end; run
+    kCtrVerified = 4,      // u64; k_coalesce*, verify kernels add; host statistic at the run's end; run
+    kCtrWindowBytes = 5,   // u64; k_coalesce*, verify kernels add; host statistic at the run's end; run
+    kCtrOutTotal = 6,      // u64; launch_scan over the strands' hits (stored); host: the pass's hits; run
+    kCtrWlCursor = 7,      // lo: claim cursor of the one-launch paths (k_evaluate, tiled, edit-first k_edit_myers); the same; pass
+    kCtrSwCursor = 8,      // lo: claim cursor of k_sw_pairs and k_sw_diag; the same; pass (round 0), round, and after the top-half sweep
+    kCtrPassCount = 9,     // lo: pass list length; k_sw_pairs, k_sw_diag, bound-mode k_edit_myers; list-mode k_edit_myers, host; pass, round
+    kCtrMyersCursor = 10,  // lo: claim cursor of list-mode k_edit_myers; the same; pass, round
+    kCtrNext0 = 11,        // lo: work list length of the next round, written by even rounds; list-mode k_edit_myers; the next
+    kCtrNext1 = 12,        //   round's kernels, host.  kCtrNext1: by odd rounds.  The slot a round writes: pass (kCtrNext0), round
+    kCtrMaxWindow = 13,    // u64; k_max_window (max); host: strip length of a tiled pass; a memset before that launch
+    kCtrSwCellPairs = 14,  // u64; k_sw_pairs adds; host statistic at the run's end; run
+    kCtrMidStrands = 15,   // lo: strands listed for k_coalesce_mid.  hi: strands of 13..16 seed hits.  k_coalesce; the later
+                           //   coalescing kernels, host trace; pass
+    kCtrSweepCount = 16,   // lo: sweep list length; k_sw_diag; k_sw_pairs, bound-mode k_edit_myers; a memset before k_sw_diag
+    kCtrUndecided = 17,    // lo: undecided list length; bound/fused k_edit_myers, top-half k_sw_pairs; k_sw_pairs, host
+                           //   (MTSV_TAIL_FROM_LIST); pass (rounds path), else a memset before its writer
+    kCtrBoundCursor = 18,  // lo: claim cursor of bound/fused k_edit_myers; the same; pass (rounds path), else with kCtrUndecided
+    kCtrMyersColumns = 19, // u64 each, EvalArgs::myers_ctr[0..2]: columns advanced, candidates the bound refuted, successors the
+    kCtrBoundRefuted = 20, //   list mode's bound passed; k_edit_myers adds; host statistics at the run's end; run
+    kCtrListPassed = 21,
+    kCtrListedSlots = 22,  // lo: seed slots listed for the general search; k_search; k_search_listed, host; pass (after the host
+                           //   has read it: Batch::listed_zero), else a memset in launch_search
+    kCtrHeavyWalk = 23,    // lo: strands k_coalesce_heavy walked by runs, hi: by the wavefront walk (a run too long); host trace; run
+    kCtrHeavyTicket = 24,  // lo: next strand of the heavy list to claim; k_coalesce_heavy; the same; pass, else a memset in launch_coalesce
+    kCtrCount
+};
+constexpr uint64_t ctr_bit(uint32_t slot) { return 1ull << slot; }
+// what launch_clear_counters zeroes before the coalescing kernels of a pass; on the rounds path also what round 0 starts from
+// (no coalescing kernel touches those); before round > 0
+constexpr uint64_t kCtrClearPass = ctr_bit(kCtrWorklist) | ctr_bit(kCtrWlCursor) | ctr_bit(kCtrMidStrands) | ctr_bit(kCtrHeavyTicket) | ctr_bit(kCtrListedSlots);
+constexpr uint64_t ctr_clear_round(uint32_t round) {
+    return ctr_bit(kCtrSwCursor) | ctr_bit(kCtrPassCount) | ctr_bit(kCtrMyersCursor) | ctr_bit(kCtrNext0 + (round & 1));
+}
+constexpr uint64_t kCtrClearRound0 = ctr_clear_round(0) | ctr_bit(kCtrUndecided) | ctr_bit(kCtrBoundCursor);
+static_assert(kCtrCount <= 64, "launch_clear_counters takes a mask of 64 slots");
+static_assert(kCtrNext1 == kCtrNext0 + 1, "the rounds ping-pong between two adjacent slots");
+static_assert(kCtrPassCount == kCtrSwCursor + 1 && kCtrMyersCursor == kCtrSwCursor + 2, "one memset zeroes the three of a round");
+static_assert(kCtrBoundCursor == kCtrUndecided + 1, "one memset zeroes the bound pass's two");
+static_assert(kCtrBoundRefuted == kCtrMyersColumns + 1 && kCtrListPassed == kCtrMyersColumns + 2, "EvalArgs::myers_ctr is an array of three");
+static_assert(kCtrVerified == kCtrCandidates + 1 && kCtrWindowBytes == kCtrCandidates + 2, "k_coalesce adds to the three side by side");
 
 struct EvalArgs {
     const uint8_t* bases;
@@ -101,11 +147,7 @@ struct EvalArgs {
     uint32_t claim_shift = 0;     // k_sw_pairs: work items per claim = clamp(n_work >> claim_shift, 4, 32)
 };
 
-// 32-bit words per column k_edit_myers<W> runs a pass whose longest read has max_len bases with (reads up to 253 bases)
-inline uint32_t myers_words(uint32_t max_len) { return std::min(std::max((max_len + 31) / 32, 2u), 8u); }
-
-constexpr uint32_t kMaxRegisterReadLen = 256;  // 16 lanes x 16 read rows per lane: k_evaluate with the whole matrix band in registers
-constexpr uint32_t kMaxReadLen = 32767;        // the tiled kernel's packed 16-bit cells (edit distance <= read length)
+// (myers_words(), kMaxRegisterReadLen and kMaxReadLen: pass_plan.hpp)
 
 // n <= 64 counters from HBM into mapped page-locked host memory, by a kernel on stream s (no copy engine involved)
 void launch_publish(hipStream_t s, const uint64_t* src, uint64_t* dst_host, uint32_t n);
