@@ -15,7 +15,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "batch_internal.hpp"
+#include "batch.hpp"
 
 namespace mtsv {
 
@@ -105,30 +105,32 @@ Batch::Batch(mtsv_index* ix_, DeviceIndex* di_, uint64_t max_reads_, uint64_t ma
     }
     if (hit_cap == 0) hit_cap = std::max<uint64_t>(1ull << 20, 32 * ws_reads);
     if (hit_cap > 0xfffffff0ull) hit_cap = 0xfffffff0ull;
-    hits_cap = std::max<uint64_t>(1ull << 20, 16 * ws_reads);
+    uint64_t hits_cap = std::max<uint64_t>(1ull << 20, 16 * ws_reads);
     if (const char* e = getenv("MTSV_HITS_CAP")) hits_cap = std::max<uint64_t>(1024, strtoull(e, nullptr, 10));  // (tests: initial size)
+    // the device before the first member allocates: whatever throws from here on frees what exists, on that device
     HIP_CHECK(hipSetDevice(di->device));
-    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    stream.create(hipStreamNonBlocking);
     const uint64_t ns = 2 * ws_reads;
     if (!parent) {
-        dev_alloc(&d_bases, max_bases + 64, &bytes);  // k_search reads up to 36 bytes past a seed start with dword loads
-        dev_alloc(&d_read_off, max_reads + 1, &bytes);
-        dev_alloc(&d_codes, max_bases + 64, &bytes);  // normalised copy of d_bases, rewritten by every run()
+        d_bases.alloc(max_bases + 64, "the resident bases");  // k_search reads up to 36 bytes past a seed start with dword loads
+        d_read_off.alloc(max_reads + 1, "the resident read offsets");
+        d_codes.alloc(max_bases + 64, "the resident codes");  // normalised copy of d_bases, rewritten by every run()
     }
-    dev_alloc(&d_strand_hits, ns + 1, &bytes);
-    dev_alloc(&d_strand_nseeds, ns, &bytes);
-    dev_alloc(&d_strand_off, ns + 1, &bytes);
-    dev_alloc(&d_strand_ncand, ns, &bytes);
-    dev_alloc(&d_strand_nout, ns + 1, &bytes);
-    dev_alloc(&d_heavy_list, 2 * ns, &bytes);  // [0, ns): the two strand lists of the coalescing kernels (front / back), [ns, 2 ns): the 13..16-hit strands
-    dev_alloc(&d_out_off, ns + 1, &bytes);
-    dev_alloc(&d_tile_sums, (uint64_t)scan_tiles((uint32_t)ns) + 1, &bytes);
-    dev_alloc(&d_counters, kCounters, &bytes);
-    alloc_hit_workspace();
-    dev_alloc(&d_hits, hits_cap, &bytes);
+    d_strand_hits.alloc(ns + 1, "strands: seed hits");
+    d_strand_nseeds.alloc(ns, "strands: seeds kept");
+    d_strand_off.alloc(ns + 1, "strands: seed-hit offsets");
+    d_strand_ncand.alloc(ns, "strands: candidates");
+    d_strand_nout.alloc(ns + 1, "strands: hits");
+    d_heavy_list.alloc(2 * ns, "strands: lists");  // [0, ns): the two strand lists of the coalescing kernels (front / back), [ns, 2 ns): the 13..16-hit strands
+    d_out_off.alloc(ns + 1, "strands: hit offsets");
+    d_tile_sums.alloc((uint64_t)scan_tiles((uint32_t)ns) + 1, "the scans' tile sums");
+    d_counters.alloc(kCounters, "the pass counters");
+    hit_cap_first = hit_cap;
+    size_hit_workspace(hit_cap_first);
+    d_hits.alloc(hits_cap, "the result array");
     // page-locked and mapped: kernels store the counters the host waits for straight into it (launch_publish) -- a
     // hipMemcpyAsync of 8 bytes can queue on a copy engine behind tens of milliseconds of the reads' own transfer
-    HIP_CHECK(hipHostMalloc((void**)&h_counters, kCounters * sizeof(uint64_t), hipHostMallocMapped));
+    h_counters.renew(kCounters, hipHostMallocMapped);
     if (const char* e = getenv("MTSV_SW")) sw_pairs = strcmp(e, "packed") != 0;
     if (const char* e = getenv("MTSV_SW_DIAG")) sw_diag = atoi(e) != 0;
     if (const char* e = getenv("MTSV_SW_PREPASS")) sw_prepass = atoi(e) != 0;
@@ -152,93 +154,41 @@ Batch::Batch(mtsv_index* ix_, DeviceIndex* di_, uint64_t max_reads_, uint64_t ma
         fused_clear = parent->fused_clear;
         seed_tiles = parent->seed_tiles;
     }
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    for (int k = 1; k < n_lanes; k++) {
-        extra.emplace_back(new Batch(ix, di, ws_reads, 0, hit_cap_user, this));
-        bytes += extra.back()->bytes;
-    }
+    ev.create();
+    for (int k = 1; k < n_lanes; k++) extra.emplace_back(new Batch(ix, di, ws_reads, 0, hit_cap_user, this));
 }
 
+// The lanes first: they borrow the owner's inputs.  The members free themselves after this body, on the device it sets.
 Batch::~Batch() {
     extra.clear();
     (void)hipSetDevice(di->device);
-    (void)hipStreamSynchronize(stream);
-    for (void* p : {(void*)d_bases, (void*)d_read_off, (void*)d_seed_lo, (void*)d_seed_cnt, (void*)d_seed_pre, (void*)d_strand_hits,
-                    (void*)d_strand_nseeds, (void*)d_strand_off, (void*)d_strand_ncand, (void*)d_worklist,
-                    (void*)d_strand_nout, (void*)d_out_off, (void*)d_tile_sums, (void*)d_counters, (void*)d_hit_row,
-                    (void*)d_hit_ref, (void*)d_hit_q, (void*)d_hit_key, (void*)d_cand_tmp, (void*)d_cand, (void*)d_out,
-                    (void*)d_hits, (void*)d_cand_next, (void*)d_cand_status, (void*)d_heavy_list})
-        (void)hipFree(p);
-    (void)hipFree(d_codes);
-    (void)hipFree(d_strip);
-    (void)hipFree(d_planes);
-    (void)hipFree(report.d_taxa);
-    (void)hipFree(report.d_counts);
-    for (auto& e : report_ev)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipFree(match.d_words);
-    for (auto& e : match_ev)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipFree(d_read_map);
-    (void)hipFree(d_compact);
-    for (auto& e : compact_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (void* p : {(void*)merge.d_nout, (void*)merge.d_off, (void*)merge.d_tiles, (void*)merge.d_lo, (void*)merge.d_base, (void*)merge.d_parts})
-        (void)hipFree(p);
-    for (auto& e : merge.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (void* p : {(void*)d_assign, (void*)collapse.keys, (void*)collapse.flags, (void*)collapse.place, (void*)collapse.tiles, (void*)collapse.list,
-                    (void*)collapse.d_ctr})
-        (void)hipFree(p);
-    if (collapse.h_ctr) (void)hipHostFree(collapse.h_ctr);
-    for (auto& e : collapse.ev)
-        if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : {stream.s, copy_stream.s, copy_stream2.s})
+        if (s) (void)hipStreamSynchronize(s);
     if (h_hits_stage) pinned_hits_release(h_hits_stage);
     if (h_assign_stage) pinned_hits_release(h_assign_stage);
-    if (copy_stream2) (void)hipStreamDestroy(copy_stream2);
-    if (copy_stream) {
-        (void)hipStreamSynchronize(copy_stream);
-        (void)hipStreamDestroy(copy_stream);
-    }
-    for (auto& ar : arena) {
-        (void)hipFree(ar.d_bases);
-        (void)hipFree(ar.d_packed);
-        (void)hipFree(ar.d_off);
-    }
-    if (h_off_all) (void)hipHostFree(h_off_all);
-    for (auto& hs : h_stage)
-        if (hs) (void)hipHostFree(hs);
-    for (auto& e : chunk_ev) (void)hipEventDestroy(e);
-    (void)hipHostFree(h_counters);
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(stream);
 }
 
 // the arrays indexed by seed hit / candidate; nothing of a pass lives in them before its locate stage
-void Batch::alloc_hit_workspace() {
-    dev_alloc(&d_hit_row, hit_cap, &bytes);
-    dev_alloc(&d_hit_ref, hit_cap, &bytes);
-    dev_alloc(&d_hit_q, hit_cap, &bytes);
-    dev_alloc(&d_hit_key, hit_cap, &bytes);
-    dev_alloc(&d_cand_tmp, 2 * hit_cap, &bytes);
-    dev_alloc(&d_cand, hit_cap, &bytes);
-    dev_alloc(&d_out, hit_cap, &bytes);
-    dev_alloc(&d_cand_next, hit_cap, &bytes);
-    dev_alloc(&d_cand_status, hit_cap, &bytes);
-    dev_alloc(&d_worklist, hit_cap, &bytes);
+void Batch::size_hit_workspace(uint64_t cap) {
+    hit_cap = 0;
+    release_all(d_hit_row, d_hit_ref, d_hit_q, d_hit_key, d_cand_tmp, d_cand, d_out, d_cand_next, d_cand_status, d_worklist);
+    d_hit_row.alloc(cap, "hit workspace: rows");
+    d_hit_ref.alloc(cap, "hit workspace: references");
+    d_hit_q.alloc(cap, "hit workspace: read positions");
+    d_hit_key.alloc(cap, "hit workspace: keys");
+    d_cand_tmp.alloc(2 * cap, "hit workspace: candidate scratch");
+    d_cand.alloc(cap, "hit workspace: candidates");
+    d_out.alloc(cap, "hit workspace: verified candidates");
+    d_cand_next.alloc(cap, "hit workspace: successors");
+    d_cand_status.alloc(cap, "hit workspace: status");
+    d_worklist.alloc(cap, "hit workspace: work list");
+    hit_cap = cap;
 }
 
 void Batch::grow_hit_workspace(uint64_t need) {
     if (getenv("MTSV_TRACE")) fprintf(stderr, "[workspace] seed-hit arrays grow %llu -> %llu entries\n", (unsigned long long)hit_cap, (unsigned long long)need);
     HIP_CHECK(hipStreamSynchronize(stream));
-    for (void* p : {(void*)d_hit_row, (void*)d_hit_ref, (void*)d_hit_q, (void*)d_hit_key, (void*)d_cand_tmp, (void*)d_cand,
-                    (void*)d_out, (void*)d_cand_next, (void*)d_cand_status, (void*)d_worklist})
-        (void)hipFree(p);
-    d_hit_row = d_hit_ref = d_hit_q = d_cand_next = d_cand_status = d_worklist = nullptr;
-    d_hit_key = d_cand_tmp = nullptr;
-    d_cand = d_out = nullptr;
-    hit_cap = need;
-    alloc_hit_workspace();
+    size_hit_workspace(need);
 }
 
 void Batch::VerifyTurn::enter(uint64_t first_read, const Batch* lane) {
@@ -282,8 +232,8 @@ void Batch::upload(const uint8_t* bases, const uint64_t* read_off, uint64_t n) {
     }
     if (n == 0) h_read_off[0] = 0;
     HIP_CHECK(hipSetDevice(di->device));
-    if (nb) HIP_CHECK(hipMemcpyAsync(d_bases, bases + first, nb, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(d_read_off, h_read_off.data(), (n + 1) * 4, hipMemcpyHostToDevice, stream));
+    if (nb) HIP_CHECK(hipMemcpyAsync(d_bases.p, bases + first, nb, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(d_read_off.p, h_read_off.data(), (n + 1) * 4, hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     n_reads = n;
     n_hits_total = 0;
@@ -303,33 +253,34 @@ void Batch::reset_lane() {
     sw_passed_acc = 0;
     n_hits_total = 0;
     n_assign_total = 0;
-    HIP_CHECK(hipMemsetAsync(d_counters, 0, kCounters * sizeof(uint64_t), stream));
+    if (!hit_cap) size_hit_workspace(hit_cap_first);  // (a growth failed in the run before)
+    HIP_CHECK(hipMemsetAsync(d_counters.p, 0, kCounters * sizeof(uint64_t), stream));
     listed_zero = true;
     HIP_CHECK(hipEventRecord(ev[kEvRunBegin], stream));
 }
 
 void Batch::finish_lane() {
     HIP_CHECK(hipEventRecord(ev[kEvRunEnd], stream));
-    launch_publish(stream, d_counters, h_counters, kCounters);
+    launch_publish(stream, d_counters.p, h_counters.p, kCounters);
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipEventElapsedTime(&stage_acc[7], ev[kEvRunBegin], ev[kEvRunEnd]));
     if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] last pass: %llu strands of 13..64 seed hits (or more than 4 candidates) to k_coalesce_mid, %llu heavier ones\n",
-                                      (unsigned long long)(h_counters[kCtrMidStrands] & 0xffffffffull), (unsigned long long)(h_counters[kCtrWorklist] >> 32));
+                                      (unsigned long long)(h_counters.p[kCtrMidStrands] & 0xffffffffull), (unsigned long long)(h_counters.p[kCtrWorklist] >> 32));
     if (getenv("MTSV_TRACE")) fprintf(stderr, "[lane] k_coalesce_heavy: %llu strands walked by runs, %llu by the wavefront walk (a run too long)\n",
-                                      (unsigned long long)(h_counters[kCtrHeavyWalk] & 0xffffffffull), (unsigned long long)(h_counters[kCtrHeavyWalk] >> 32));
-    stats.sw_cell_pairs = h_counters[kCtrSwCellPairs];
+                                      (unsigned long long)(h_counters.p[kCtrHeavyWalk] & 0xffffffffull), (unsigned long long)(h_counters.p[kCtrHeavyWalk] >> 32));
+    stats.sw_cell_pairs = h_counters.p[kCtrSwCellPairs];
     stats.sw_prefilter_ms = sw_ms_acc;
     stats.sw_sweep_ms = sweep_ms_acc;
     stats.sw_diag_ms = diag_ms_acc;
     stats.sw_bound_ms = bound_ms_acc;
     stats.edit_ms = edit_ms_acc;
-    stats.myers_columns = h_counters[kCtrMyersColumns];
-    stats.n_sw_bound_refuted = h_counters[kCtrBoundRefuted];
-    stats.n_sw_passed = sw_passed_acc + h_counters[kCtrListPassed];  // (+ the successors k_edit_myers' list mode passed by its own bound)
-    stats.lf_steps = h_counters[kCtrLfSteps];
-    stats.n_candidates = h_counters[kCtrCandidates];
-    stats.n_verified = h_counters[kCtrVerified];
-    stats.window_bytes = h_counters[kCtrWindowBytes];
+    stats.myers_columns = h_counters.p[kCtrMyersColumns];
+    stats.n_sw_bound_refuted = h_counters.p[kCtrBoundRefuted];
+    stats.n_sw_passed = sw_passed_acc + h_counters.p[kCtrListPassed];  // (+ the successors k_edit_myers' list mode passed by its own bound)
+    stats.lf_steps = h_counters.p[kCtrLfSteps];
+    stats.n_candidates = h_counters.p[kCtrCandidates];
+    stats.n_verified = h_counters.p[kCtrVerified];
+    stats.window_bytes = h_counters.p[kCtrWindowBytes];
 }
 
 void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
@@ -367,19 +318,13 @@ void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
 // this run's flags: all zero before any lane's first pass (the lanes' streams do not wait for this one by themselves)
 void Batch::match_begin(uint64_t n, uint64_t read_base) {
     const uint64_t need = (n + 63) / 64;
-    if (need > match.cap_words || !match.d_words) {
-        (void)hipFree(match.d_words);
-        match.d_words = nullptr;
-        match.cap_words = 0;
-        dev_alloc(&match.d_words, need + need / 16 + 1);
-        match.cap_words = need + need / 16;
-    }
+    if (need > match.cap_words() || !match.d_words.p) match.d_words.renew(need + need / 16 + 1, "the match flags");
     match.n_reads = n;
     match.call_base = read_base;
     match.ms = 0;
     match.launches = 0;
     // (the counter sits behind the last word the allocation holds, wherever this run's flags end)
-    HIP_CHECK(hipMemsetAsync(match.d_words, 0, (match.cap_words + 1) * sizeof(uint64_t), stream));
+    HIP_CHECK(hipMemsetAsync(match.d_words.p, 0, (match.cap_words() + 1) * sizeof(uint64_t), stream));
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
@@ -432,7 +377,7 @@ void Batch::set_taxa_report(bool on) {
     if (parent) throw std::runtime_error("internal: the taxa report belongs to the workspace's owner");
     if (on && match.mode == MTSV_MATCH_ONLY)
         throw std::runtime_error("arg: the taxa report reads gathered hits and MTSV_MATCH_ONLY gathers none (mtsv_batch_set_match_flags)");
-    if (on && !report.d_counts) {
+    if (on && !report.d_counts.p) {
         std::vector<uint32_t>& t = report.h_taxa;
         t.clear();
         for (const Bin& b : ix->host.bins) t.push_back(b.tax_id);
@@ -453,10 +398,10 @@ void Batch::set_taxa_report(bool on) {
             fprintf(stderr, "[report] %u taxa: %s tier (dense up to %u taxa, hash table of %u slots)\n", report.n_taxa,
                     report.dense ? "dense" : "hashed", dense_max, report.hash_slots);
         HIP_CHECK(hipSetDevice(di->device));
-        dev_alloc(&report.d_taxa, report.n_taxa);
-        dev_alloc(&report.d_counts, 4ull * report.n_taxa + 2);
-        if (report.n_taxa) HIP_CHECK(hipMemcpyAsync(report.d_taxa, t.data(), t.size() * 4, hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipMemsetAsync(report.d_counts, 0, (4ull * report.n_taxa + 2) * 8, stream));
+        report.d_taxa.alloc(report.n_taxa, "the report's TaxIDs");
+        report.d_counts.alloc(4ull * report.n_taxa + 2, "the report's counters");
+        if (report.n_taxa) HIP_CHECK(hipMemcpyAsync(report.d_taxa.p, t.data(), t.size() * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemsetAsync(report.d_counts.p, 0, (4ull * report.n_taxa + 2) * 8, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     }
     report.on = on;
@@ -468,8 +413,8 @@ void Batch::taxa_report(std::vector<mtsv_taxon_stats>& rows, uint64_t* total_rea
     const uint64_t n = 4ull * report.n_taxa + 2;
     std::vector<uint64_t> c(n);
     // (every run is synchronous: no lane has a pass in flight)
-    HIP_CHECK(hipMemcpyAsync(c.data(), report.d_counts, n * 8, hipMemcpyDeviceToHost, stream));
-    if (reset) HIP_CHECK(hipMemsetAsync(report.d_counts, 0, n * 8, stream));
+    HIP_CHECK(hipMemcpyAsync(c.data(), report.d_counts.p, n * 8, hipMemcpyDeviceToHost, stream));
+    if (reset) HIP_CHECK(hipMemsetAsync(report.d_counts.p, 0, n * 8, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     rows.clear();
     for (uint32_t k = 0; k < report.n_taxa; k++) {
@@ -506,8 +451,8 @@ void Batch::match_flags(std::vector<uint64_t>& words, uint64_t* n_reads_out, uin
     if (!match.n_reads) return;
     HIP_CHECK(hipSetDevice(di->device));
     // (every run is synchronous: no lane has a pass in flight)
-    HIP_CHECK(hipMemcpyAsync(words.data(), match.d_words, nw * 8, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync(n_matched, match.d_words + match.cap_words, 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(words.data(), match.d_words.p, nw * 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(n_matched, match.d_words.p + match.cap_words(), 8, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     std::lock_guard<std::mutex> lk(match.mu);
     if (match.trace)
@@ -583,49 +528,42 @@ void Batch::collapse_room(uint64_t n_pass_reads, uint64_t n_hits) {
     const Assignments& as = root()->assign;
     const uint64_t rec = as.rec_bytes(), key_bytes = as.key_bytes();
     if (n_hits >= (1ull << 32)) throw std::runtime_error("limit: 2^32 hits or more in one pass of the collapse");
-    if (!c.d_ctr) dev_alloc(&c.d_ctr, kCollapseCounters);
-    if (!c.h_ctr) HIP_CHECK(hipHostMalloc((void**)&c.h_ctr, kCollapseCounters * sizeof(uint64_t), hipHostMallocMapped));
-    for (auto& e : c.ev)
-        if (!e) HIP_CHECK(hipEventCreate(&e));
-    if (n_hits > c.cap_hits || !c.keys || c.key_bytes != key_bytes) {
+    if (!c.d_ctr.p) c.d_ctr.alloc(kCollapseCounters, "the collapse counters");
+    if (!c.h_ctr.p) c.h_ctr.renew(kCollapseCounters, hipHostMallocMapped);
+    c.ev.create();
+    if (n_hits > c.cap_hits || !c.cap_hits || c.key_bytes != key_bytes) {
         HIP_CHECK(hipStreamSynchronize(stream));
-        for (void* p : {(void*)c.keys, (void*)c.flags, (void*)c.place, (void*)c.tiles}) (void)hipFree(p);
-        c.keys = c.tiles = nullptr;
-        c.flags = c.place = nullptr;
-        c.cap_hits = 0;
-        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(n_hits + n_hits / 8, 1ull << 16), 0xffffffffull);
-        dev_alloc(&c.keys, cap * (key_bytes / 8));
-        c.key_bytes = key_bytes;
-        dev_alloc(&c.flags, cap + 1);
-        dev_alloc(&c.place, cap + 1);
-        dev_alloc(&c.tiles, (uint64_t)scan_tiles((uint32_t)cap) + 1);
-        c.cap_hits = cap;
+        c.resize(std::min<uint64_t>(std::max<uint64_t>(n_hits + n_hits / 8, 1ull << 16), 0xffffffffull), key_bytes);
     }
-    if (n_pass_reads > c.cap_reads || !c.list) {
+    if (n_pass_reads > c.list.cap || !c.list.p) {
         HIP_CHECK(hipStreamSynchronize(stream));
-        (void)hipFree(c.list);
-        c.list = nullptr;
-        c.cap_reads = 0;
-        const uint64_t cap = std::max<uint64_t>(n_pass_reads + n_pass_reads / 16, 1024);
-        dev_alloc(&c.list, cap);
-        c.cap_reads = cap;
+        c.list.renew(std::max<uint64_t>(n_pass_reads + n_pass_reads / 16, 1024), "collapse scratch: read list");
     }
-    if ((n_assign_total + n_hits) * rec > assign_cap_bytes || !d_assign) {
-        // grow the result array, keeping what earlier passes produced
-        const uint64_t ncap = std::max<uint64_t>(std::max(assign_cap_bytes * 2, (n_assign_total + n_hits) * rec), (1ull << 16) * rec);
-        uint8_t* na = nullptr;
-        dev_alloc(&na, ncap);
-        if (n_assign_total) HIP_CHECK(hipMemcpyAsync(na, d_assign, n_assign_total * rec, hipMemcpyDeviceToDevice, stream));
+    if ((n_assign_total + n_hits) * rec > d_assign.cap || !d_assign.p) {
+        // grow the result array, keeping what earlier passes produced (a failure leaves the lane as it was; the old array
+        // leaves with this one)
+        DevBuf<uint8_t> grown;
+        grown.alloc(std::max<uint64_t>(std::max(d_assign.cap * 2, (n_assign_total + n_hits) * rec), (1ull << 16) * rec), "the assignments");
+        if (n_assign_total) HIP_CHECK(hipMemcpyAsync(grown.p, d_assign.p, n_assign_total * rec, hipMemcpyDeviceToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         // run_host may be copying an earlier range's assignments out of the old array on the owner's copy stream (and another
         // lane's thread may be issuing such a copy right now: the commit mutex covers the pointer swap), as with d_hits
         std::unique_lock<std::mutex> commit_lk;
         if (root()->commit_mu) commit_lk = std::unique_lock<std::mutex>(*root()->commit_mu);
         if (root()->commit_mu && root()->copy_stream2) HIP_CHECK(hipStreamSynchronize(root()->copy_stream2));
-        (void)hipFree(d_assign);
-        d_assign = na;
-        assign_cap_bytes = ncap;
+        d_assign.swap(grown);
     }
+}
+
+void Batch::CollapseScratch::resize(uint64_t hits, uint64_t kb) {
+    cap_hits = 0;
+    release_all(keys, flags, place, tiles);
+    keys.alloc(hits * (kb / 8), "collapse scratch: keys");
+    key_bytes = kb;
+    flags.alloc(hits + 1, "collapse scratch: flags");
+    place.alloc(hits + 1, "collapse scratch: places");
+    tiles.alloc((uint64_t)scan_tiles((uint32_t)hits) + 1, "collapse scratch: tile sums");
+    cap_hits = hits;
 }
 
 void Batch::collapse_enqueue(uint32_t n_pass_reads, const uint32_t* strand_nout, const uint32_t* out_off, const DevHit* hits, uint64_t n_hits) {
@@ -634,17 +572,17 @@ void Batch::collapse_enqueue(uint32_t n_pass_reads, const uint32_t* strand_nout,
     CollapseScratch& c = collapse;
     c.pending_hits = n_hits;
     HIP_CHECK(hipEventRecord(c.ev[0], stream));
-    launch_collapse(stream, as.grain, n_pass_reads, strand_nout, out_off, hits, (uint32_t)n_hits, as.lane_max, as.wave_max, as.lds_max, c.keys, c.flags,
-                    c.place, c.tiles, c.list, c.d_ctr, d_assign + n_assign_total * as.rec_bytes());
+    launch_collapse(stream, as.grain, n_pass_reads, strand_nout, out_off, hits, (uint32_t)n_hits, as.lane_max, as.wave_max, as.lds_max, c.keys.p, c.flags.p,
+                    c.place.p, c.tiles.p, c.list.p, c.d_ctr.p, d_assign.p + n_assign_total * as.rec_bytes());
     HIP_CHECK(hipEventRecord(c.ev[1], stream));
     // the pass's record count reaches the host with the synchronise the pass ends with anyway
-    launch_publish(stream, c.d_ctr, c.h_ctr, kCollapseCounters);
+    launch_publish(stream, c.d_ctr.p, c.h_ctr.p, kCollapseCounters);
 }
 
 uint64_t Batch::collapse_commit() {
     Assignments& as = root()->assign;
     CollapseScratch& c = collapse;
-    const uint64_t cnt = c.h_ctr[kCollapseCtrTotal];
+    const uint64_t cnt = c.h_ctr.p[kCollapseCtrTotal];
     if (cnt > c.pending_hits) throw std::runtime_error("internal: the collapse wrote " + std::to_string(cnt) + " assignments from " + std::to_string(c.pending_hits) + " hits");
     float ms = 0;
     HIP_CHECK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
@@ -652,7 +590,7 @@ uint64_t Batch::collapse_commit() {
     std::lock_guard<std::mutex> lk(as.mu);
     as.ms += ms;
     as.launches++;
-    for (int t = 0; t < 5; t++) as.tiers[t] += c.h_ctr[kCollapseCtrLane + t];
+    for (int t = 0; t < 5; t++) as.tiers[t] += c.h_ctr.p[kCollapseCtrLane + t];
     return cnt;
 }
 
@@ -680,7 +618,7 @@ void Batch::download_assignments(void** a, uint64_t* n, float* device_ms, bool w
         // (every run is synchronous: no lane has a pass in flight)
         for (auto& sg : segments) {
             if (!sg.a_count) continue;
-            const hipError_t e = hipMemcpy(out + at * rec, sg.lane->d_assign + sg.a_offset * rec, sg.a_count * rec, hipMemcpyDeviceToHost);
+            const hipError_t e = hipMemcpy(out + at * rec, sg.lane->d_assign.p + sg.a_offset * rec, sg.a_count * rec, hipMemcpyDeviceToHost);
             if (e != hipSuccess) {
                 pinned_hits_release(out);
                 throw_hip(e, "hipMemcpy(assignments)", __FILE__, __LINE__);
@@ -697,23 +635,15 @@ void Batch::download_assignments(void** a, uint64_t* n, float* device_ms, bool w
 void Batch::run(const mtsv_params& p) {
     begin_run(p);
     // (a batch take_reads left is codes already: fast_code would turn every one of them into N)
-    run_range(p, codes_resident ? nullptr : d_bases, d_codes, d_read_off, h_read_off.data(), n_reads, max_len, 0);
+    run_range(p, codes_resident ? nullptr : d_bases.p, d_codes.p, d_read_off.p, h_read_off.data(), n_reads, max_len, 0);
     end_run();
     last_run = kRunResident;
 }
 
 // d_compact for `tiles` tiles of the compaction kernels, and d_read_map (take_reads, and DupMap::take_unique of dedup.hip)
 void Batch::compact_room(uint64_t tiles) {
-    if (!d_compact || compact_cap < tiles) {
-        (void)hipFree(d_compact);
-        d_compact = nullptr;
-        compact_cap = 0;
-        dev_alloc(&d_compact, 3 + 2 * (tiles + tiles / 16));
-        compact_cap = tiles + tiles / 16;
-    }
-    if (!d_read_map) {
-        dev_alloc(&d_read_map, max_reads);
-    }
+    if (!d_compact.p || compact_cap() < tiles) d_compact.renew(3 + 2 * (tiles + tiles / 16), "the compaction's tile sums");
+    if (!d_read_map.p) d_read_map.alloc(max_reads, "the read map");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -736,18 +666,17 @@ void Batch::take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_k
     const bool trace = getenv("MTSV_TRACE") != nullptr;
     const uint64_t n = src.n_reads;
     const bool host_batch = src.last_run == kRunHostOneSegment;
-    const uint8_t* s_codes = host_batch ? src.arena[0].d_bases : src.d_codes;
-    const uint32_t* s_off = host_batch ? src.arena[0].d_off : src.d_read_off;
-    const uint32_t* s_map = src.mapped ? src.d_read_map : nullptr;
+    const uint8_t* s_codes = host_batch ? src.arena[0].d_bases.p : src.d_codes.p;
+    const uint32_t* s_off = host_batch ? src.arena[0].d_off.p : src.d_read_off.p;
+    const uint32_t* s_map = src.mapped ? src.d_read_map.p : nullptr;
     HIP_CHECK(hipSetDevice(di->device));
     compact_room(compact_tiles(n));
-    if (!compact_ev[0])
-        for (auto& e : compact_ev) HIP_CHECK(hipEventCreate(&e));
-    uint64_t* result = d_compact;
-    uint64_t *tile_cnt = d_compact + 3, *tile_bases = d_compact + 3 + compact_cap;
+    if (!compact_ev.created()) compact_ev.create();
+    uint64_t* result = d_compact.p;
+    uint64_t *tile_cnt = d_compact.p + 3, *tile_bases = d_compact.p + 3 + compact_cap();
     HIP_CHECK(hipMemsetAsync(result, 0, 3 * sizeof(uint64_t), stream));
     HIP_CHECK(hipEventRecord(compact_ev[0], stream));
-    launch_compact_scan(stream, (uint32_t)n, src.match.d_words, s_off, keep, tile_cnt, tile_bases, result);
+    launch_compact_scan(stream, (uint32_t)n, src.match.d_words.p, s_off, keep, tile_cnt, tile_bases, result);
     HIP_CHECK(hipEventRecord(compact_ev[1], stream));
     uint64_t h_result[3] = {0, 0, 0};
     HIP_CHECK(hipMemcpyAsync(h_result, result, sizeof h_result, hipMemcpyDeviceToHost, stream));
@@ -760,10 +689,10 @@ void Batch::take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_k
     resident = false;
     last_run = kRunNone;
     HIP_CHECK(hipEventRecord(compact_ev[2], stream));
-    launch_compact_copy(stream, (uint32_t)n, src.match.d_words, s_off, s_codes, keep, s_map, tile_cnt, tile_bases, result, d_codes, d_read_off, d_read_map);
+    launch_compact_copy(stream, (uint32_t)n, src.match.d_words.p, s_off, s_codes, keep, s_map, tile_cnt, tile_bases, result, d_codes.p, d_read_off.p, d_read_map.p);
     HIP_CHECK(hipEventRecord(compact_ev[3], stream));
     h_read_off.resize(m + 1);
-    HIP_CHECK(hipMemcpyAsync(h_read_off.data(), d_read_off, (m + 1) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(h_read_off.data(), d_read_off.p, (m + 1) * 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     if (h_read_off[0] != 0 || h_read_off[m] != nb) throw std::runtime_error("internal: offsets of the compacted batch do not close on its bases");
@@ -798,29 +727,26 @@ void Batch::copy_reads(Batch& src, float* device_ms) {
     if (!src.resident && !host_batch)
         throw std::runtime_error("arg: the source workspace holds no resident batch (mtsv_batch_upload, mtsv_batch_take_reads, mtsv_batch_copy_reads, or a host batch of one input segment)");
     const uint64_t n = src.n_reads;
-    const uint32_t* ho = host_batch ? src.h_off_all : src.h_read_off.data();
+    const uint32_t* ho = host_batch ? src.h_off_all.p : src.h_read_off.data();
     const uint64_t nb = n ? ho[n] : 0;
     if (n > max_reads || nb > max_bases)
         throw std::runtime_error("arg: the source holds " + std::to_string(n) + " reads of " + std::to_string(nb) + " bases, the destination workspace was created for " +
                                  std::to_string(max_reads) + " reads of " + std::to_string(max_bases) + " bases");
     const bool codes = host_batch || src.codes_resident;
     const bool with_map = !host_batch && src.mapped;
-    const uint8_t* s_bytes = host_batch ? src.arena[0].d_bases : codes ? src.d_codes : src.d_bases;
-    const uint32_t* s_off = host_batch ? src.arena[0].d_off : src.d_read_off;
+    const uint8_t* s_bytes = host_batch ? src.arena[0].d_bases.p : codes ? src.d_codes.p : src.d_bases.p;
+    const uint32_t* s_off = host_batch ? src.arena[0].d_off.p : src.d_read_off.p;
     HIP_CHECK(hipSetDevice(di->device));
-    if (with_map && !d_read_map) {
-        dev_alloc(&d_read_map, max_reads);
-    }
-    if (!compact_ev[0])
-        for (auto& e : compact_ev) HIP_CHECK(hipEventCreate(&e));
+    if (with_map && !d_read_map.p) d_read_map.alloc(max_reads, "the read map");
+    if (!compact_ev.created()) compact_ev.create();
     // from here on the destination's resident batch is being replaced
     resident = false;
     last_run = kRunNone;
     HIP_CHECK(hipEventRecord(compact_ev[0], stream));
-    if (nb) HIP_CHECK(hipMemcpyDtoDAsync(codes ? d_codes : d_bases, const_cast<uint8_t*>(s_bytes), nb, stream));
-    if (n) HIP_CHECK(hipMemcpyDtoDAsync(d_read_off, const_cast<uint32_t*>(s_off), (n + 1) * 4, stream));
-    else HIP_CHECK(hipMemsetAsync(d_read_off, 0, 4, stream));
-    if (with_map && n) HIP_CHECK(hipMemcpyDtoDAsync(d_read_map, src.d_read_map, n * 4, stream));
+    if (nb) HIP_CHECK(hipMemcpyDtoDAsync(codes ? d_codes.p : d_bases.p, const_cast<uint8_t*>(s_bytes), nb, stream));
+    if (n) HIP_CHECK(hipMemcpyDtoDAsync(d_read_off.p, const_cast<uint32_t*>(s_off), (n + 1) * 4, stream));
+    else HIP_CHECK(hipMemsetAsync(d_read_off.p, 0, 4, stream));
+    if (with_map && n) HIP_CHECK(hipMemcpyDtoDAsync(d_read_map.p, src.d_read_map.p, n * 4, stream));
     HIP_CHECK(hipEventRecord(compact_ev[1], stream));
     if (n) h_read_off.assign(ho, ho + n + 1);
     else h_read_off.assign(1, 0u);
@@ -865,7 +791,7 @@ void Batch::report_extend(Batch* const* srcs, int n_srcs) {
     // new TaxIDs: the list and the counters so far, rebuilt (host work; a database's chunks bring theirs once)
     const uint64_t n_old = 4ull * report.n_taxa + 2, n_new = 4ull * u.size() + 2;
     std::vector<uint64_t> c_old(n_old), c_new(n_new, 0);
-    HIP_CHECK(hipMemcpyAsync(c_old.data(), report.d_counts, n_old * 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(c_old.data(), report.d_counts.p, n_old * 8, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     for (uint32_t k = 0; k < report.n_taxa; k++) {
         const uint64_t at = (uint64_t)(std::lower_bound(u.begin(), u.end(), report.h_taxa[k]) - u.begin());
@@ -873,17 +799,15 @@ void Batch::report_extend(Batch* const* srcs, int n_srcs) {
     }
     c_new[n_new - 2] = c_old[n_old - 2];
     c_new[n_new - 1] = c_old[n_old - 1];
-    uint32_t* nt = nullptr;
-    uint64_t* nc = nullptr;
-    dev_alloc(&nt, u.size());
-    dev_alloc(&nc, n_new);
-    HIP_CHECK(hipMemcpyAsync(nt, u.data(), u.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(nc, c_new.data(), n_new * 8, hipMemcpyHostToDevice, stream));
+    DevBuf<uint32_t> nt;  // (the old arrays leave with these)
+    DevBuf<uint64_t> nc;
+    nt.alloc(u.size(), "the report's TaxIDs");
+    nc.alloc(n_new, "the report's counters");
+    HIP_CHECK(hipMemcpyAsync(nt.p, u.data(), u.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(nc.p, c_new.data(), n_new * 8, hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    (void)hipFree(report.d_taxa);
-    (void)hipFree(report.d_counts);
-    report.d_taxa = nt;
-    report.d_counts = nc;
+    report.d_taxa.swap(nt);
+    report.d_counts.swap(nc);
     report.h_taxa.swap(u);
     report.n_taxa = (uint32_t)report.h_taxa.size();
     uint32_t dense_max = kReportDenseTaxa;
@@ -926,7 +850,7 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
             next += sg.n_reads;
             if (sg.count >= (1ull << 32)) throw std::runtime_error("limit: 2^32 hits or more in one stretch of a source");
             if (!sg.n_reads) continue;
-            parts.push_back(MergePart{sg.lane->d_hits + sg.offset, (uint32_t)sg.count, (uint32_t)sg.first_read, (uint32_t)sg.n_reads, (uint32_t)k, 0});
+            parts.push_back(MergePart{sg.lane->d_hits.p + sg.offset, (uint32_t)sg.count, (uint32_t)sg.first_read, (uint32_t)sg.n_reads, (uint32_t)k, 0});
             max_part_reads = std::max(max_part_reads, sg.n_reads);
             max_part_hits = std::max(max_part_hits, sg.count);
         }
@@ -934,54 +858,40 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
     }
     if (total >= (1ull << 32)) throw std::runtime_error("limit: the merge holds " + std::to_string(total) + " hits, 2^32 or more");
     if (parts.size() > 65535) throw std::runtime_error("limit: more than 65535 stretches of hits in the sources of one merge");
-    const uint32_t* map = s0.mapped ? s0.d_read_map : nullptr;
+    const uint32_t* map = s0.mapped ? s0.d_read_map.p : nullptr;
     HIP_CHECK(hipSetDevice(di->device));
     // ---- room (created by the first merge; whatever fails here leaves the last result where it was) ----
     MergeState& m = merge;
-    if (!m.ev[0])
-        for (auto& e : m.ev) HIP_CHECK(hipEventCreate(&e));
-    if (n > m.cap_reads || !m.d_nout) {
-        for (void* p : {(void*)m.d_nout, (void*)m.d_off, (void*)m.d_tiles}) (void)hipFree(p);
-        m.d_nout = m.d_off = nullptr;
-        m.d_tiles = nullptr;
+    if (!m.ev.created()) m.ev.create();
+    if (n > m.cap_reads || !m.d_nout.p) {
         m.cap_reads = 0;
+        release_all(m.d_nout, m.d_off, m.d_tiles);
         const uint64_t cap = std::min<uint64_t>(n + n / 16, 0x7fffffffull);  // (a workspace's limit)
-        dev_alloc(&m.d_nout, 2 * cap + 1);
-        dev_alloc(&m.d_off, 2 * cap + 1);
-        m.cap_tiles = (uint64_t)scan_tiles((uint32_t)(2 * cap)) + 1;
-        dev_alloc(&m.d_tiles, m.cap_tiles + 2);
+        m.d_nout.alloc(2 * cap + 1, "merge: hit counts");
+        m.d_off.alloc(2 * cap + 1, "merge: hit offsets");
+        m.d_tiles.alloc((uint64_t)scan_tiles((uint32_t)(2 * cap)) + 1 + 2, "merge: tile sums");
         m.cap_reads = cap;
     }
-    if ((uint64_t)n_srcs * n > m.cap_sn || !m.d_lo) {
-        (void)hipFree(m.d_lo);
-        (void)hipFree(m.d_base);
-        m.d_lo = m.d_base = nullptr;
+    if ((uint64_t)n_srcs * n > m.cap_sn || !m.d_lo.p) {
         m.cap_sn = 0;
+        release_all(m.d_lo, m.d_base);
         const uint64_t cap = (uint64_t)n_srcs * (n + n / 16);
-        dev_alloc(&m.d_lo, cap);
-        dev_alloc(&m.d_base, cap);
+        m.d_lo.alloc(cap, "merge: lower bounds");
+        m.d_base.alloc(cap, "merge: hit bases");
         m.cap_sn = cap;
     }
-    if (parts.size() > m.cap_parts || !m.d_parts) {
-        (void)hipFree(m.d_parts);
-        m.d_parts = nullptr;
-        m.cap_parts = 0;
-        const uint64_t cap = std::max<uint64_t>(parts.size() * 2, 64);
-        dev_alloc(&m.d_parts, cap);
-        m.cap_parts = cap;
-    }
+    if (parts.size() > m.d_parts.cap || !m.d_parts.p) m.d_parts.renew(std::max<uint64_t>(parts.size() * 2, 64), "merge: stretches");
     // (before the result array grows, so that it cannot fail once the result is being replaced; if that allocation then
     //  fails, the list has grown already, with the counts so far kept and the new rows 0: the header says so)
     if (report.on) report_extend(srcs, n_srcs);
     // (the collapse's scratch and the room behind the assignments so far: the last ones stay readable until then)
     if (assign.mode != MTSV_ASSIGN_OFF && n) collapse_room(n, total);
-    DevHit* grown = nullptr;  // (the last result stays in the old array until nothing can refuse the merge any more)
-    if (total > hits_cap) dev_alloc(&grown, total + total / 16);
+    DevBuf<DevHit> grown;  // (the last result stays in the old array until nothing can refuse the merge any more)
+    if (total > d_hits.cap) grown.alloc(total + total / 16, "the result array");
     // ---- from here on the destination's result is being replaced ----
-    if (grown) {
-        (void)hipFree(d_hits);
-        d_hits = grown;
-        hits_cap = total + total / 16;
+    if (grown.p) {
+        d_hits.swap(grown);
+        grown.release();
     }
     segments.clear();
     total_hits = 0;
@@ -999,32 +909,30 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
     uint64_t h_total[2] = {0, 0};  // the scan's total, the hits the copy could not place
     float ms = 0, ms_report = 0, ms_match = 0;
     if (n) {
-        HIP_CHECK(hipMemcpyAsync(m.d_parts, parts.data(), parts.size() * sizeof(MergePart), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipMemsetAsync(m.d_tiles + m.cap_tiles, 0, 2 * sizeof(uint64_t), stream));
+        HIP_CHECK(hipMemcpyAsync(m.d_parts.p, parts.data(), parts.size() * sizeof(MergePart), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemsetAsync(m.d_tiles.p + m.cap_tiles(), 0, 2 * sizeof(uint64_t), stream));
         HIP_CHECK(hipEventRecord(m.ev[0], stream));
-        launch_merge_bounds(stream, m.d_parts, (uint32_t)parts.size(), (uint32_t)max_part_reads, (uint32_t)n, map, m.d_lo, m.d_base);
-        launch_merge_sum(stream, (uint32_t)n, (uint32_t)n_srcs, m.d_lo, m.d_base, m.d_nout);
-        launch_scan(stream, m.d_nout, (uint32_t)(2 * n), m.d_tiles, m.d_tiles + m.cap_tiles, m.d_off);
-        launch_merge_copy(stream, m.d_parts, (uint32_t)parts.size(), (uint32_t)max_part_hits, (uint32_t)n, map, m.d_base, m.d_off, d_hits, (uint32_t)total, m.d_tiles + m.cap_tiles + 1);
+        launch_merge_bounds(stream, m.d_parts.p, (uint32_t)parts.size(), (uint32_t)max_part_reads, (uint32_t)n, map, m.d_lo.p, m.d_base.p);
+        launch_merge_sum(stream, (uint32_t)n, (uint32_t)n_srcs, m.d_lo.p, m.d_base.p, m.d_nout.p);
+        launch_scan(stream, m.d_nout.p, (uint32_t)(2 * n), m.d_tiles.p, m.d_tiles.p + m.cap_tiles(), m.d_off.p);
+        launch_merge_copy(stream, m.d_parts.p, (uint32_t)parts.size(), (uint32_t)max_part_hits, (uint32_t)n, map, m.d_base.p, m.d_off.p, d_hits.p, (uint32_t)total, m.d_tiles.p + m.cap_tiles() + 1);
         HIP_CHECK(hipEventRecord(m.ev[1], stream));
-        HIP_CHECK(hipMemcpyAsync(h_total, m.d_tiles + m.cap_tiles, sizeof h_total, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(h_total, m.d_tiles.p + m.cap_tiles(), sizeof h_total, hipMemcpyDeviceToHost, stream));
         if (report.on) {
-            if (!report_ev[0])
-                for (auto& e : report_ev) HIP_CHECK(hipEventCreate(&e));
+            if (!report_ev.created()) report_ev.create();
             HIP_CHECK(hipEventRecord(report_ev[0], stream));
-            launch_report(stream, (uint32_t)n, m.d_nout, m.d_off, d_hits, report.d_taxa, report.n_taxa, report.dense, report.hash_slots, report.d_counts,
-                          report.d_counts + 4ull * report.n_taxa, report.trace ? report.d_counts + 4ull * report.n_taxa + 1 : nullptr);
+            launch_report(stream, (uint32_t)n, m.d_nout.p, m.d_off.p, d_hits.p, report.d_taxa.p, report.n_taxa, report.dense, report.hash_slots, report.d_counts.p,
+                          report.d_counts.p + 4ull * report.n_taxa, report.trace ? report.d_counts.p + 4ull * report.n_taxa + 1 : nullptr);
             HIP_CHECK(hipEventRecord(report_ev[1], stream));
         }
         if (match.mode != MTSV_MATCH_OFF) {
-            if (!match_ev[0])
-                for (auto& e : match_ev) HIP_CHECK(hipEventCreate(&e));
+            if (!match_ev.created()) match_ev.create();
             HIP_CHECK(hipEventRecord(match_ev[0], stream));
-            launch_match(stream, (uint32_t)n, m.d_nout, 0, match.d_words, match.d_words + match.cap_words);
+            launch_match(stream, (uint32_t)n, m.d_nout.p, 0, match.d_words.p, match.d_words.p + match.cap_words());
             HIP_CHECK(hipEventRecord(match_ev[1], stream));
         }
         // the collector is laid out as one pass: its assignments are those of the merged reads, all sources together
-        if (collapse_on) collapse_enqueue((uint32_t)n, m.d_nout, m.d_off, d_hits, total);
+        if (collapse_on) collapse_enqueue((uint32_t)n, m.d_nout.p, m.d_off.p, d_hits.p, total);
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipGetLastError());
         if (collapse_on) n_assign = collapse_commit();
@@ -1068,7 +976,7 @@ void Batch::read_map(std::vector<uint64_t>& map) {
     }
     std::vector<uint32_t> m32(n_reads);
     HIP_CHECK(hipSetDevice(di->device));
-    if (n_reads) HIP_CHECK(hipMemcpyAsync(m32.data(), d_read_map, n_reads * 4, hipMemcpyDeviceToHost, stream));
+    if (n_reads) HIP_CHECK(hipMemcpyAsync(m32.data(), d_read_map.p, n_reads * 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     for (uint64_t i = 0; i < n_reads; i++) map[i] = m32[i];
 }
@@ -1078,9 +986,9 @@ void Batch::download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& r
     HIP_CHECK(hipSetDevice(di->device));
     const uint64_t nb = h_read_off[n_reads];
     // (an uploaded batch is normalised into d_codes as run() would do it)
-    if (!codes_resident && nb) launch_normalise(stream, d_bases, d_codes, 0, nb);
+    if (!codes_resident && nb) launch_normalise(stream, d_bases.p, d_codes.p, 0, nb);
     codes.resize(nb);
-    if (nb) HIP_CHECK(hipMemcpyAsync(codes.data(), d_codes, nb, hipMemcpyDeviceToHost, stream));
+    if (nb) HIP_CHECK(hipMemcpyAsync(codes.data(), d_codes.p, nb, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     read_off.assign(h_read_off.begin(), h_read_off.begin() + n_reads + 1);
 }
@@ -1186,8 +1094,8 @@ void Batch::host_room(uint64_t n, uint64_t total_bases, bool trace) {
         // that shared one with the reads' transfer did not get a kernel in for 20 ms at a time.
         int prio_low = 0, prio_high = 0;
         HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-        HIP_CHECK(hipStreamCreateWithPriority(&copy_stream, hipStreamNonBlocking, prio_high));
-        HIP_CHECK(hipStreamCreateWithPriority(&copy_stream2, hipStreamNonBlocking, prio_high));
+        copy_stream.create(hipStreamNonBlocking, prio_high);
+        copy_stream2.create(hipStreamNonBlocking, prio_high);
     }
     uint64_t arena_bases = kArenaBases, arena_reads = kArenaReads;
     if (const char* e = getenv("MTSV_ARENA_BASES")) arena_bases = std::max<uint64_t>(1 << 16, strtoull(e, nullptr, 10));  // (tests)
@@ -1198,31 +1106,26 @@ void Batch::host_room(uint64_t n, uint64_t total_bases, bool trace) {
             Arena& ar = arena[k];
             if (ar.cap_bases < want_b || ar.cap_reads < want_r) {
                 if (trace) fprintf(stderr, "[run_host] arena %d: %.1f MB of bases, %llu reads\n", k, want_b / 1e6, (unsigned long long)want_r);
-                (void)hipFree(ar.d_bases);
-                (void)hipFree(ar.d_packed);
-                (void)hipFree(ar.d_off);
-                ar.d_bases = nullptr;
-                ar.d_packed = nullptr;
-                ar.d_off = nullptr;
-                ar.cap_bases = ar.cap_reads = 0;
                 const uint64_t cb = want_b + want_b / 16, cr = want_r + want_r / 16;  // a little room: the next batch is rarely the same size
-                dev_alloc(&ar.d_bases, std::min(cb, arena_bases) + 64, &bytes);  // k_search reads up to 36 bytes past a seed start
-                dev_alloc(&ar.d_packed, std::min(cb, arena_bases) / 2 + 64, &bytes);
-                dev_alloc(&ar.d_off, std::min(cr, arena_reads) + 1, &bytes);
-                ar.cap_bases = std::min(cb, arena_bases);
-                ar.cap_reads = std::min(cr, arena_reads);
+                ar.resize(k, std::min(cb, arena_bases), std::min(cr, arena_reads));
             }
         }
     }
     // the whole batch's narrowed offsets, every segment with a closing entry of its own (a segment is closed when the next
     // read does not fit: it is more than half full); run_slice looks at read lengths on the host when a range holds long reads
     const uint64_t off_need = n + 2 + (one_segment ? 0 : 2 * (total_bases / arena_bases + n / arena_reads) + 8);
-    if (h_off_cap < off_need) {
-        if (h_off_all) (void)hipHostFree(h_off_all);
-        h_off_all = nullptr;
-        h_off_cap = off_need + n / 16;
-        HIP_CHECK(hipHostMalloc((void**)&h_off_all, h_off_cap * sizeof(uint32_t)));
-    }
+    if (h_off_all.cap < off_need) h_off_all.renew(off_need + n / 16);
+}
+
+void Batch::Arena::resize(int k, uint64_t bases, uint64_t reads) {
+    cap_bases = cap_reads = 0;
+    release_all(d_bases, d_packed, d_off);
+    const std::string name = "arena " + std::to_string(k);
+    d_bases.alloc(bases + 64, (name + ": bases").c_str());  // k_search reads up to 36 bytes past a seed start
+    d_packed.alloc(bases / 2 + 64, (name + ": packed bases").c_str());
+    d_off.alloc(reads + 1, (name + ": offsets").c_str());
+    cap_bases = bases;
+    cap_reads = reads;
 }
 
 void Batch::reserve_host(uint64_t n, uint64_t n_bases) {
@@ -1295,8 +1198,9 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
         ~HostRun() { c--; }
     } host_run{host_runs};
     const bool packed = !getenv("MTSV_H2D_PLAIN") && pack_threads() >= kPackWorthwhile && host_run.mine == 1;
-    if ((packed || !direct) && !h_stage[0])
-        for (auto& hs : h_stage) HIP_CHECK(hipHostMalloc((void**)&hs, kChunkMax + 64));
+    if ((packed || !direct) && !h_stage[kStage - 1].p)
+        for (auto& hs : h_stage)
+            if (!hs.p) hs.renew(kChunkMax + 64);
 
     struct Chunk {
         uint64_t begin = 0, end = 0;  // reads
@@ -1330,14 +1234,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
         abort = true;
         cv.notify_all();
     };
-    auto event_for = [&](size_t k) {
-        while (chunk_ev.size() <= k) {
-            hipEvent_t e;
-            HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            chunk_ev.push_back(e);
-        }
-        return chunk_ev[k];
-    };
+    auto event_for = [&](size_t k) { return chunk_ev.at(k, hipEventDisableTiming); };
 
     n_reads = n;
     max_len = 0;
@@ -1469,8 +1366,8 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                 const uint64_t dst_b = b0 - seg_first_base, dst_r = r - seg_first_read;
                 // offsets relative to the segment's first base; h_off_all[seg ... ] holds them at index (read + seg) so that
                 // every segment has its own closing entry
-                uint32_t* ho = h_off_all + r + seg;
-                if (r + seg + cnt + 1 > h_off_cap) throw std::runtime_error("internal: more input segments than the offset array was sized for");
+                uint32_t* ho = h_off_all.p + r + seg;
+                if (r + seg + cnt + 1 > h_off_all.cap) throw std::runtime_error("internal: more input segments than the offset array was sized for");
                 uint32_t ml = 0;
                 if (r == seg_first_read) ho[0] = 0;  // (else the previous chunk wrote this entry; a lane may be reading it)
                 {
@@ -1503,7 +1400,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                 if (nb) {
                     const uint8_t* src = src_part.bases + poff[0];
                     if (packed || !src_part.pinned) {
-                        uint8_t* hs = h_stage[k % kStage];
+                        uint8_t* hs = h_stage[k % kStage].p;
                         if (k >= kStage) {  // its last copy must have left (polled, like the watcher)
                             for (;;) {
                                 const hipError_t q = hipEventQuery(chunk_ev[k - kStage]);
@@ -1521,11 +1418,11 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                         src = hs;
                     }
                     if (packed)
-                        HIP_CHECK(hipMemcpyAsync(ar->d_packed + (dst_b >> 1), src, ((dst_b + nb + 1) >> 1) - (dst_b >> 1), hipMemcpyHostToDevice, copy_stream));
+                        HIP_CHECK(hipMemcpyAsync(ar->d_packed.p + (dst_b >> 1), src, ((dst_b + nb + 1) >> 1) - (dst_b >> 1), hipMemcpyHostToDevice, copy_stream));
                     else
-                        HIP_CHECK(hipMemcpyAsync(ar->d_bases + dst_b, src, nb, hipMemcpyHostToDevice, copy_stream));
+                        HIP_CHECK(hipMemcpyAsync(ar->d_bases.p + dst_b, src, nb, hipMemcpyHostToDevice, copy_stream));
                 }
-                HIP_CHECK(hipMemcpyAsync(ar->d_off + dst_r, ho, (cnt + 1) * 4, hipMemcpyHostToDevice, copy_stream));
+                HIP_CHECK(hipMemcpyAsync(ar->d_off.p + dst_r, ho, (cnt + 1) * 4, hipMemcpyHostToDevice, copy_stream));
                 HIP_CHECK(hipEventRecord(ev, copy_stream));
                 if (trace) fprintf(stderr, "[run_host] chunk %zu: reads %llu..%llu (%.1f MB, segment %llu) issued at %.2f ms (host side %.2f ms)\n", k, (unsigned long long)r, (unsigned long long)e, nb / 1e6, (unsigned long long)seg, (now_s() - run_t0) * 1e3, (now_s() - t0) * 1e3);
                 {
@@ -1555,13 +1452,13 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
             Range& rg = ranges[next_commit];
             if (rg.hit_cnt && stage_hits) {
                 stage_reserve(staged_hits + rg.hit_cnt);
-                HIP_CHECK(hipMemcpyAsync(h_hits_stage + staged_hits, rg.lane->d_hits + rg.hit_off, rg.hit_cnt * sizeof(mtsv_hit),
+                HIP_CHECK(hipMemcpyAsync(h_hits_stage + staged_hits, rg.lane->d_hits.p + rg.hit_off, rg.hit_cnt * sizeof(mtsv_hit),
                                          hipMemcpyDeviceToHost, copy_stream2));
                 staged_hits += rg.hit_cnt;
             }
             if (rg.a_cnt && stage_assign) {
                 assign_stage_reserve(staged_assign + rg.a_cnt);
-                HIP_CHECK(hipMemcpyAsync(h_assign_stage + staged_assign * a_rec, rg.lane->d_assign + rg.a_off * a_rec, rg.a_cnt * a_rec,
+                HIP_CHECK(hipMemcpyAsync(h_assign_stage + staged_assign * a_rec, rg.lane->d_assign.p + rg.a_off * a_rec, rg.a_cnt * a_rec,
                                          hipMemcpyDeviceToHost, copy_stream2));
                 staged_assign += rg.a_cnt;
             }
@@ -1589,7 +1486,7 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                     // The lane's result array only has to hold hits until they have left for the host: once it is half
                     // full and everything in it has been committed, start again at its beginning (a 100 M-read host
                     // batch would otherwise pile a third of its hits up on the device).
-                    if (!keep_on_device && lane->n_hits_total > lane->hits_cap / 2 && (last_done == ~0ull || last_done < next_commit)) {
+                    if (!keep_on_device && lane->n_hits_total > lane->d_hits.cap / 2 && (last_done == ~0ull || last_done < next_commit)) {
                         HIP_CHECK(hipStreamSynchronize(copy_stream2));
                         lane->n_hits_total = 0;
                     }
@@ -1623,15 +1520,15 @@ void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params
                 }
                 cv.notify_all();
                 const Arena& ar = arena[seg & 1];
-                const uint32_t* ho = h_off_all + rb + seg;  // offsets of reads rb .. re inside segment seg
-                const uint32_t* dso = ar.d_off + (rb - seg_first);
+                const uint32_t* ho = h_off_all.p + rb + seg;  // offsets of reads rb .. re inside segment seg
+                const uint32_t* dso = ar.d_off.p + (rb - seg_first);
                 const uint64_t before = lane->n_hits_total, a_before = lane->n_assign_total;
                 const double t0 = now_s();
                 // base normalisation (binner.rs:88-100) in place, on the lane's own stream: a kernel on the copy
                 // stream would queue behind the persistent verification kernels of the other lanes
-                if (packed) launch_unpack(lane->stream, ar.d_packed, ar.d_bases, ho[0], ho[re - rb]);
-                else launch_normalise(lane->stream, ar.d_bases, ar.d_bases, ho[0], ho[re - rb]);
-                lane->run_slice(p, ar.d_bases, dso, ho, re - rb, ml, read_base + rb);
+                if (packed) launch_unpack(lane->stream, ar.d_packed.p, ar.d_bases.p, ho[0], ho[re - rb]);
+                else launch_normalise(lane->stream, ar.d_bases.p, ar.d_bases.p, ho[0], ho[re - rb]);
+                lane->run_slice(p, ar.d_bases.p, dso, ho, re - rb, ml, read_base + rb);
                 if (trace) fprintf(stderr, "[run_host] range %llu (reads %llu..%llu): kernels %.1f ms, done at %.1f ms\n", (unsigned long long)k, (unsigned long long)rb, (unsigned long long)re, (now_s() - t0) * 1e3, (now_s() - run_t0) * 1e3);
                 {
                     std::lock_guard<std::mutex> lk(mu);
@@ -1734,7 +1631,7 @@ void Batch::download(mtsv_hit** hits, uint64_t* n) {
     uint64_t at = 0;
     for (auto& sg : segments) {
         if (!sg.count) continue;
-        hipError_t e = hipMemcpy(h + at, sg.lane->d_hits + sg.offset, sg.count * sizeof(mtsv_hit), hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(h + at, sg.lane->d_hits.p + sg.offset, sg.count * sizeof(mtsv_hit), hipMemcpyDeviceToHost);
         if (e != hipSuccess) {
             pinned_hits_release(h);
             throw_hip(e, "hipMemcpy(hits)", __FILE__, __LINE__);
@@ -1749,11 +1646,11 @@ void Batch::download_into(mtsv_hit* dst, uint64_t n) {
     HIP_CHECK(hipSetDevice(di->device));
     if (n != total_hits) throw std::runtime_error("internal: download_into of " + std::to_string(n) + " hits, the run produced " + std::to_string(total_hits));
     last_total_hits = total_hits;
-    hipStream_t cs = copy_stream2 ? copy_stream2 : stream;
+    hipStream_t cs = copy_stream2 ? copy_stream2.s : stream.s;
     uint64_t at = 0;
     for (auto& sg : segments) {
         if (!sg.count) continue;
-        HIP_CHECK(hipMemcpyAsync(dst + at, sg.lane->d_hits + sg.offset, sg.count * sizeof(mtsv_hit), hipMemcpyDeviceToHost, cs));
+        HIP_CHECK(hipMemcpyAsync(dst + at, sg.lane->d_hits.p + sg.offset, sg.count * sizeof(mtsv_hit), hipMemcpyDeviceToHost, cs));
         at += sg.count;
     }
     HIP_CHECK(hipStreamSynchronize(cs));

@@ -8,6 +8,7 @@
 #include "../../include/mtsv_amd.h"
 #include "host_pack.hpp"
 #include "dev_index.hpp"
+#include "dev_mem.hpp"
 #include "kernels.hpp"
 
 namespace mtsv {
@@ -15,30 +16,34 @@ namespace mtsv {
 struct Batch {
     mtsv_index* ix;
     DeviceIndex* di;
-    hipStream_t stream = nullptr, copy_stream2 = nullptr;
+    // Every resource is a member that frees itself (dev_mem.hpp; DESIGN.md, "The host side of the stages behind the binner"),
+    // the streams first, so that they are destroyed after the arrays.  copy_stream (the reads' transfer) and copy_stream2
+    // (results to the host) are created by the first host batch, at high priority (host_room).
+    DevStream stream, copy_stream, copy_stream2;
     mtsv_hit* h_hits_stage = nullptr;  // pinned (pool): run_host copies every slice's hits here while later slices run
     uint64_t h_hits_cap = 0, staged_hits = 0, last_total_hits = 0;
     bool staged_valid = false;
     // run_host: the input arenas in HBM (the whole host batch, or segments of it taking turns), filled in read order by one
     // feeder thread on copy_stream; page-locked staging chunks for bases that lie in ordinary memory
     struct Arena {
-        uint8_t* d_bases = nullptr;
-        uint8_t* d_packed = nullptr;  // the same bases as they arrive: 4-bit codes, two per byte (host_pack.hpp)
-        uint32_t* d_off = nullptr;
-        uint64_t cap_bases = 0, cap_reads = 0;
+        DevBuf<uint8_t> d_bases;
+        DevBuf<uint8_t> d_packed;  // the same bases as they arrive: 4-bit codes, two per byte (host_pack.hpp)
+        DevBuf<uint32_t> d_off;
+        uint64_t cap_bases = 0, cap_reads = 0;  // above zero: the three arrays exist at these sizes
+        void resize(int k, uint64_t bases, uint64_t reads);  // contents not kept
     };
     static constexpr uint64_t kArenaBases = 3ull << 30;   // offsets inside a segment are u32
     static constexpr uint64_t kArenaReads = 1ull << 30;
     Arena arena[2];
-    uint32_t* h_off_all = nullptr;  // pinned: the batch's offsets, narrowed to segment-relative u32
-    uint64_t h_off_cap = 0;
+    HostBuf<uint32_t> h_off_all;  // pinned: the batch's offsets, narrowed to segment-relative u32
     static constexpr int kStage = 4;
-    uint8_t* h_stage[kStage] = {};
-    hipStream_t copy_stream = nullptr;
-    std::vector<hipEvent_t> chunk_ev;  // one per copy chunk, kept between runs
+    HostBuf<uint8_t> h_stage[kStage];
+    DevEventList chunk_ev;  // one per copy chunk (hipEventDisableTiming), kept between runs
     std::mutex* commit_mu = nullptr;  // set while run_host's threads may touch the lanes' result arrays
-    uint64_t max_reads, max_bases, hit_cap, hits_cap = 0;
-    uint64_t bytes = 0;
+    uint64_t max_reads, max_bases;
+    // entries of each of the ten seed-hit arrays (d_hit_row .. d_worklist).  Above zero: all ten exist at that size, on every
+    // path; zero after a growth that failed, and then the next run begins with the first size again (hit_cap_first)
+    uint64_t hit_cap, hit_cap_first = 0;
     // Lanes: the workspace is cut into n_lanes equal parts, each with its own stream; a resident range of
     // reads is split across them and the parts run concurrently (one host thread each), so that the
     // HBM-latency-bound stages of one part overlap the VALU-bound verification of another.  The owner
@@ -60,25 +65,24 @@ struct Batch {
     double run_t0 = 0;
     uint64_t lanes_used = 1;
 
-    uint8_t* d_codes = nullptr;  // run(): normalised copy of d_bases
-    uint8_t* d_bases = nullptr;  // resident batch of upload() / run()
-    uint32_t* d_read_off = nullptr;
-    uint32_t *d_seed_lo = nullptr, *d_seed_cnt = nullptr, *d_seed_pre = nullptr;
-    uint64_t seed_cap = 0;
-    uint32_t *d_strand_hits = nullptr, *d_strand_nseeds = nullptr, *d_strand_off = nullptr, *d_strand_ncand = nullptr,
-             *d_worklist = nullptr, *d_strand_nout = nullptr, *d_out_off = nullptr;
-    uint64_t* d_tile_sums = nullptr;
-    uint64_t* d_counters = nullptr;
-    uint32_t *d_hit_row = nullptr, *d_hit_ref = nullptr, *d_hit_q = nullptr;
-    uint64_t *d_hit_key = nullptr, *d_cand_tmp = nullptr;
-    uint4 *d_cand = nullptr, *d_out = nullptr;
-    uint32_t *d_cand_next = nullptr, *d_cand_status = nullptr, *d_heavy_list = nullptr;
-    DevHit* d_hits = nullptr;
-    uint2* d_strip = nullptr;  // tiled long-read kernel: band hand-over strips, allocated when a pass first needs them
-    uint64_t strip_cap = 0;
-    uint32_t* d_planes = nullptr;  // bit planes of a pass's reads (EvalArgs::planes): k_thin writes them, k_edit_myers sets up from them
-    uint64_t plane_cap = 0;        // ... in words; allocated when a pass first needs them, for a full workspace of such reads
-    uint64_t* h_counters = nullptr;  // pinned
+    // (the owner's; empty in the other lanes, which borrow them)
+    DevBuf<uint8_t> d_codes;  // run(): normalised copy of d_bases
+    DevBuf<uint8_t> d_bases;  // resident batch of upload() / run()
+    DevBuf<uint32_t> d_read_off;
+    DevBuf<uint32_t> d_seed_lo, d_seed_cnt, d_seed_pre;
+    uint64_t seed_cap = 0;  // above zero: the three seed slot arrays exist at that size
+    DevBuf<uint32_t> d_strand_hits, d_strand_nseeds, d_strand_off, d_strand_ncand, d_worklist, d_strand_nout, d_out_off;
+    DevBuf<uint64_t> d_tile_sums;
+    DevBuf<uint64_t> d_counters;
+    DevBuf<uint32_t> d_hit_row, d_hit_ref, d_hit_q;
+    DevBuf<uint64_t> d_hit_key, d_cand_tmp;
+    DevBuf<uint4> d_cand, d_out;
+    DevBuf<uint32_t> d_cand_next, d_cand_status, d_heavy_list;
+    DevBuf<DevHit> d_hits;    // grows keeping its contents (room_hits)
+    DevBuf<uint2> d_strip;    // tiled long-read kernel: band hand-over strips, allocated when a pass first needs them
+    DevBuf<uint32_t> d_planes;  // bit planes of a pass's reads (EvalArgs::planes): k_thin writes them, k_edit_myers sets up from them;
+                                // in words, allocated when a pass first needs them, for a full workspace of such reads
+    HostBuf<uint64_t> h_counters;  // pinned, mapped
     enum Ev {
         // a pass: stage s (MTSV_N_STAGES' first seven) lies between events s and s + 1
         kEvPassBegin = 0, kEvSearched, kEvSeeded, kEvExpanded, kEvLocated, kEvCoalesced, kEvVerified, kEvGathered,
@@ -89,7 +93,7 @@ struct Batch {
         kEvEditEnd,              // ... after its edit distances
         kEvCount
     };
-    hipEvent_t ev[kEvCount];
+    DevEvents<kEvCount> ev;
     float sw_ms_acc = 0, sweep_ms_acc = 0, diag_ms_acc = 0, bound_ms_acc = 0, edit_ms_acc = 0;
     uint64_t sw_passed_acc = 0;   // candidates k_sw_pairs sent on to the edit distance (all rounds and passes of the run)
 
@@ -185,8 +189,8 @@ struct Batch {
         bool dense = true;
         uint32_t hash_slots = kReportHashSlots;  // of the hashed tier's LDS table (MTSV_REPORT_HASH_SLOTS: fewer, tests)
         uint32_t n_taxa = 0;
-        uint32_t* d_taxa = nullptr;    // the index's distinct TaxIDs, ascending
-        uint64_t* d_counts = nullptr;  // 4 per taxon (only_hit, only_best, tied_best, not_best), then the reads with a hit,
+        DevBuf<uint32_t> d_taxa;    // the index's distinct TaxIDs, ascending
+        DevBuf<uint64_t> d_counts;  // 4 per taxon (only_hit, only_best, tied_best, not_best), then the reads with a hit,
                                        // then (trace) the atomic adds the kernels made on all of these
         bool trace = false;            // MTSV_TRACE was set when the report was switched on
         uint64_t launches = 0;         // (under mu) report kernels since the last reset
@@ -195,14 +199,14 @@ struct Batch {
         float ms = 0;                  // device time of the report kernels since the last reset
     };
     TaxaReport report;
-    hipEvent_t report_ev[2] = {nullptr, nullptr};  // around a lane's report kernel; created with the lane's first one
+    DevEvents<2> report_ev;  // around a lane's report kernel; created with the lane's first one
     void set_taxa_report(bool on);
     // Match flags (k_match.hip): one bit per read of the last run, "the run returned a hit for it".  Like the report they
     // belong to the owner; unlike it they describe one run: zeroed when a run begins, sized with it.
     struct MatchFlags {
         int mode = MTSV_MATCH_OFF;
-        uint64_t* d_words = nullptr;  // cap_words words of flags, then the matched-reads counter
-        uint64_t cap_words = 0;
+        DevBuf<uint64_t> d_words;  // cap_words() words of flags, then the matched-reads counter
+        uint64_t cap_words() const { return d_words.p ? d_words.cap - 1 : 0; }
         uint64_t n_reads = 0;         // of the last run with the flags on
         uint64_t call_base = 0;       // read_base of that run: bit 0 is its first read
         bool trace = false;
@@ -211,7 +215,7 @@ struct Batch {
         uint64_t launches = 0;
     };
     MatchFlags match;
-    hipEvent_t match_ev[2] = {nullptr, nullptr};  // around a lane's k_match; created with the lane's first one
+    DevEvents<2> match_ev;  // around a lane's k_match; created with the lane's first one
     bool flags_only() const { return root()->match.mode == MTSV_MATCH_ONLY; }
     void set_match_flags(int mode);
     // the flags of the last run as ceil(n_reads / 64) words (at least one), bits at and above n_reads zero
@@ -224,10 +228,10 @@ struct Batch {
     bool resident = false;         // upload() or take_reads() filled the resident batch, no host batch has run since
     bool codes_resident = false;   // ... take_reads did: d_codes holds it (d_bases does not), run() must not normalise
     bool mapped = false;           // ... and d_read_map translates its read numbers in every gathered hit
-    uint32_t* d_read_map = nullptr;   // max_reads entries
-    uint64_t* d_compact = nullptr;    // the result block (3 words), then two arrays of tile sums
-    uint64_t compact_cap = 0;         // ... entries each
-    hipEvent_t compact_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the scan and around the copy
+    DevBuf<uint32_t> d_read_map;   // max_reads entries
+    DevBuf<uint64_t> d_compact;    // the result block (3 words), then two arrays of tile sums
+    uint64_t compact_cap() const { return d_compact.p ? (d_compact.cap - 3) / 2 : 0; }  // ... entries each
+    DevEvents<4> compact_ev;  // around the scan and around the copy
     void compact_room(uint64_t tiles);  // d_compact for that many tiles, and d_read_map; on the workspace's device
     void take_reads(Batch& src, int keep, uint64_t* n_kept, uint64_t* bases_kept, float* device_ms);
     // this workspace's resident batch := a copy of src's (codes or bases, offsets, longest read, read map), HBM to HBM
@@ -236,14 +240,14 @@ struct Batch {
     // workspace's result array, laid out as one pass; the report and the flags, where on, take the merged reads.  All of
     // it belongs to the owner and is created by the first merge_runs.
     struct MergeState {
-        uint32_t *d_nout = nullptr, *d_off = nullptr;  // 2 n + 1 entries each
-        uint64_t* d_tiles = nullptr;                   // the scan's tile sums, then its total, then the copy's dropped hits
-        uint64_t cap_reads = 0, cap_tiles = 0;
-        uint32_t *d_lo = nullptr, *d_base = nullptr;   // per (source, read)
-        uint64_t cap_sn = 0;
-        MergePart* d_parts = nullptr;
-        uint64_t cap_parts = 0;
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        DevBuf<uint32_t> d_nout, d_off;  // 2 n + 1 entries each
+        DevBuf<uint64_t> d_tiles;        // the scan's cap_tiles() tile sums, then its total, then the copy's dropped hits
+        uint64_t cap_reads = 0;          // above zero: d_nout, d_off and d_tiles exist for that many reads
+        uint64_t cap_tiles() const { return d_tiles.cap - 2; }
+        DevBuf<uint32_t> d_lo, d_base;   // per (source, read)
+        uint64_t cap_sn = 0;             // above zero: both exist at that size
+        DevBuf<MergePart> d_parts;
+        DevEvents<2> ev;
     };
     MergeState merge;
     // Assignments (k_collapse.hip): per read of the last run one (read, tax_id, smallest edit) record per distinct TaxID,
@@ -275,19 +279,21 @@ struct Batch {
     bool assign_staged_valid = false;
     bool host_hits_dropped = false;  // the last run was a host batch in MTSV_ASSIGN_ONLY: its hits were never staged and the lanes' arrays were recycled
     void assign_stage_reserve(uint64_t n_needed);
-    uint8_t* d_assign = nullptr;  // the lane's assignments (records of the grain), those of a pass behind those of the passes before
-    uint64_t assign_cap_bytes = 0, n_assign_total = 0;
+    DevBuf<uint8_t> d_assign;  // the lane's assignments (records of the grain), those of a pass behind those of the passes before;
+                               // grows keeping its contents (collapse_room)
+    uint64_t n_assign_total = 0;
     struct CollapseScratch {
-        uint64_t* keys = nullptr;   // cap_hits sort keys of key_bytes each, mirroring a pass's hits
+        DevBuf<uint64_t> keys;   // cap_hits sort keys of key_bytes each, mirroring a pass's hits
         uint64_t key_bytes = 0;
-        uint32_t *flags = nullptr, *place = nullptr;  // cap_hits + 1 each
-        uint64_t* tiles = nullptr;  // the scan's tile sums
-        uint32_t* list = nullptr;   // cap_reads: the reads left to k_collapse_heavy
-        uint64_t cap_hits = 0, cap_reads = 0;
+        DevBuf<uint32_t> flags, place;  // cap_hits + 1 each
+        DevBuf<uint64_t> tiles;  // the scan's tile sums
+        uint64_t cap_hits = 0;   // above zero: keys, flags, place and tiles exist for that many hits
+        void resize(uint64_t hits, uint64_t key_bytes);  // contents not kept
+        DevBuf<uint32_t> list;   // the reads left to k_collapse_heavy
         uint64_t pending_hits = 0;  // the hits of the pass whose collapse is on the stream
-        uint64_t* d_ctr = nullptr;  // kCollapseCounters
-        uint64_t* h_ctr = nullptr;  // pinned, mapped: the pass's counters (launch_publish)
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        DevBuf<uint64_t> d_ctr;  // kCollapseCounters
+        HostBuf<uint64_t> h_ctr;  // pinned, mapped: the pass's counters (launch_publish)
+        DevEvents<2> ev;
     };
     CollapseScratch collapse;
     bool assign_only() const { return root()->assign.mode == MTSV_ASSIGN_ONLY; }
@@ -322,7 +328,7 @@ struct Batch {
     void stage_reserve(uint64_t n_hits_needed);
     void host_room(uint64_t n, uint64_t total_bases, bool trace);
     void finish_lane();
-    void alloc_hit_workspace();
+    void size_hit_workspace(uint64_t cap);  // the ten seed-hit arrays at `cap` entries, contents not kept
     void grow_hit_workspace(uint64_t need);
     void run_range(const mtsv_params& p, const uint8_t* raw, uint8_t* sb, const uint32_t* so, const uint32_t* h_off, uint64_t n,
                    uint32_t range_max_len, uint64_t read_base);

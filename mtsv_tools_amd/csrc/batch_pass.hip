@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <thread>
 
-#include "batch_internal.hpp"
+#include "batch.hpp"
 
 namespace mtsv {
 
@@ -119,55 +119,44 @@ void Batch::run_slice(const mtsv_params& p, const uint8_t* sb, const uint32_t* s
 
 void Batch::room_seed_slots(const PassPlan& pl) {
     if (pl.slots <= seed_cap) return;
-    (void)hipFree(d_seed_lo);
-    (void)hipFree(d_seed_cnt);
-    (void)hipFree(d_seed_pre);
-    d_seed_lo = d_seed_cnt = d_seed_pre = nullptr;
+    const uint64_t had = seed_cap;
+    seed_cap = 0;
+    release_all(d_seed_lo, d_seed_cnt, d_seed_pre);
     // room for a full workspace of reads like these, not just this pass: slices of a host batch grow
     // towards the workspace size, and every hipFree / hipMalloc stalls the whole device
     const uint64_t want = pl.tiled() ? pl.slots : std::max<uint64_t>(pl.slots, 2 * ws_reads * (uint64_t)pl.max_ns);
-    if (getenv("MTSV_TRACE")) fprintf(stderr, "[workspace] seed slot arrays grow %llu -> %llu entries\n", (unsigned long long)seed_cap, (unsigned long long)want);
-    dev_alloc(&d_seed_lo, want);
-    dev_alloc(&d_seed_cnt, want);
-    dev_alloc(&d_seed_pre, want);
+    if (getenv("MTSV_TRACE")) fprintf(stderr, "[workspace] seed slot arrays grow %llu -> %llu entries\n", (unsigned long long)had, (unsigned long long)want);
+    d_seed_lo.alloc(want, "seed slots: ranges");
+    d_seed_cnt.alloc(want, "seed slots: counts");
+    d_seed_pre.alloc(want, "seed slots: prefix sums");
     seed_cap = want;
 }
 
 // the reads' bit planes (EvalArgs::planes) for the passes k_edit_myers verifies: k_thin writes them, sized like
 // the seed slot arrays for a full workspace of reads like these
 void Batch::room_planes(const PassPlan& pl) {
-    if ((uint64_t)pl.nr * 3 * pl.plane_words <= plane_cap) return;
-    (void)hipFree(d_planes);
-    d_planes = nullptr;
-    const uint64_t want = std::max<uint64_t>(pl.nr, ws_reads) * 3 * pl.plane_words;
-    dev_alloc(&d_planes, want);
-    plane_cap = want;
+    if ((uint64_t)pl.nr * 3 * pl.plane_words <= d_planes.cap) return;
+    d_planes.renew(std::max<uint64_t>(pl.nr, ws_reads) * 3 * pl.plane_words, "the reads' bit planes");
 }
 
 void Batch::room_strip(uint64_t need) {
-    if (need <= strip_cap) return;
-    (void)hipFree(d_strip);
-    d_strip = nullptr;
-    dev_alloc(&d_strip, need);
-    strip_cap = need;
+    if (need <= d_strip.cap) return;
+    d_strip.renew(need, "the band strips");
 }
 
 // the result array grows, keeping what earlier passes produced
 void Batch::room_hits(uint64_t total_out) {
-    if (n_hits_total + total_out <= hits_cap) return;
-    uint64_t ncap = std::max(hits_cap * 2, n_hits_total + total_out);
-    DevHit* nh = nullptr;
-    dev_alloc(&nh, ncap);
-    if (n_hits_total) HIP_CHECK(hipMemcpyAsync(nh, d_hits, n_hits_total * sizeof(DevHit), hipMemcpyDeviceToDevice, stream));
+    if (n_hits_total + total_out <= d_hits.cap) return;
+    DevBuf<DevHit> grown;  // (a failure leaves the lane as it was; the old array leaves with this one)
+    grown.alloc(std::max(d_hits.cap * 2, n_hits_total + total_out), "the result array");
+    if (n_hits_total) HIP_CHECK(hipMemcpyAsync(grown.p, d_hits.p, n_hits_total * sizeof(DevHit), hipMemcpyDeviceToDevice, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     // run_host may be copying an earlier slice's hits out of the old array on the owner's copy stream (and
     // another lane's thread may be issuing such a copy right now: the commit mutex covers the pointer swap)
     std::unique_lock<std::mutex> commit_lk;
     if (root()->commit_mu) commit_lk = std::unique_lock<std::mutex>(*root()->commit_mu);
     if (root()->copy_stream2) HIP_CHECK(hipStreamSynchronize(root()->copy_stream2));
-    (void)hipFree(d_hits);
-    d_hits = nh;
-    hits_cap = ncap;
+    d_hits.swap(grown);
 }
 
 // ---- seeds: search, thin, scan; the pass's first round trip.  Nothing here touches the statistics.
@@ -175,34 +164,34 @@ Batch::Seeded Batch::stage_seeds(Pass& ps) {
     const PassPlan& pl = ps.plan;
     const mtsv_params& p = ps.p;
     const uint32_t K = p.seed_size, G = p.seed_interval, r0 = (uint32_t)ps.r0;
-    uint32_t* planes = pl.myers() ? d_planes : nullptr;
+    uint32_t* planes = pl.myers() ? d_planes.p : nullptr;
     HIP_CHECK(hipEventRecord(ev[kEvPassBegin], stream));
     // (d_seed_pre is k_thin's output: until then it holds the list of the slots that take the general code -- an N in
     //  the seed's table part; counter kCtrListedSlots.  The second kernel's grid covers the share of such slots the passes
     //  before had, half as much again: the count is checked at the round trip below.)
     const uint32_t listed_cap = (uint32_t)std::min<uint64_t>(pl.slots, std::max<uint64_t>(4096, (uint64_t)((double)pl.slots * listed_share)));
-    launch_search(stream, di->view, ps.sb, ps.so, r0, pl.nr, pl.max_ns, K, G, d_seed_lo, d_seed_cnt, d_seed_pre, (uint32_t*)(d_counters + kCtrListedSlots),
+    launch_search(stream, di->view, ps.sb, ps.so, r0, pl.nr, pl.max_ns, K, G, d_seed_lo.p, d_seed_cnt.p, d_seed_pre.p, (uint32_t*)(d_counters.p + kCtrListedSlots),
                   listed_cap, di->d_kmer_levels, fused_clear && listed_zero);
     listed_zero = false;
     HIP_CHECK(hipEventRecord(ev[kEvSearched], stream));
     // the seed stage by tiles when the pass fits them (kernels.hpp); k_thin and k_expand with seed_pre between them otherwise
     ps.tile_pass = seed_tiles && pl.max_ns && seed_tile_fits(pl.max_ns, pl.pass_max_len, pl.slots);
     if (ps.tile_pass)
-        launch_thin_tiled(stream, ps.sb, ps.so, r0, pl.nr, p.edit_rate, p.min_seed, pl.max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,
-                          d_strand_hits, d_strand_nseeds, planes, pl.plane_words);
+        launch_thin_tiled(stream, ps.sb, ps.so, r0, pl.nr, p.edit_rate, p.min_seed, pl.max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt.p,
+                          d_strand_hits.p, d_strand_nseeds.p, planes, pl.plane_words);
     else if (pl.max_ns)
-        launch_thin(stream, ps.sb, ps.so, r0, pl.nr, p.edit_rate, p.min_seed, pl.max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt,
-                    d_seed_pre, d_strand_hits, d_strand_nseeds, planes, pl.plane_words);
+        launch_thin(stream, ps.sb, ps.so, r0, pl.nr, p.edit_rate, p.min_seed, pl.max_ns, K, G, p.max_hits, p.tune_max_hits, d_seed_cnt.p,
+                    d_seed_pre.p, d_strand_hits.p, d_strand_nseeds.p, planes, pl.plane_words);
     else {
-        HIP_CHECK(hipMemsetAsync(d_strand_hits, 0, (uint64_t)ps.nstr * 4, stream));
-        HIP_CHECK(hipMemsetAsync(d_strand_nseeds, 0, (uint64_t)ps.nstr * 4, stream));
+        HIP_CHECK(hipMemsetAsync(d_strand_hits.p, 0, (uint64_t)ps.nstr * 4, stream));
+        HIP_CHECK(hipMemsetAsync(d_strand_nseeds.p, 0, (uint64_t)ps.nstr * 4, stream));
     }
-    launch_scan(stream, d_strand_hits, ps.nstr, d_tile_sums, d_counters + kCtrSeedHits, d_strand_off);
-    launch_publish(stream, d_counters + kCtrSeedHits, h_counters + kCtrSeedHits, 1);
-    launch_publish(stream, d_counters + kCtrListedSlots, h_counters + kCtrListedSlots, 1);
+    launch_scan(stream, d_strand_hits.p, ps.nstr, d_tile_sums.p, d_counters.p + kCtrSeedHits, d_strand_off.p);
+    launch_publish(stream, d_counters.p + kCtrSeedHits, h_counters.p + kCtrSeedHits, 1);
+    launch_publish(stream, d_counters.p + kCtrListedSlots, h_counters.p + kCtrListedSlots, 1);
     HIP_CHECK(hipEventRecord(ev[kEvSeeded], stream));
     HIP_CHECK(hipStreamSynchronize(stream));
-    const uint64_t n_listed = h_counters[kCtrListedSlots] & 0xffffffffull;
+    const uint64_t n_listed = h_counters.p[kCtrListedSlots] & 0xffffffffull;
     const double share = pl.slots ? (double)n_listed / (double)pl.slots : 0.0;
     if (n_listed > listed_cap) {  // more slots on the list than the grid covered: the pass again, with a grid for them
         listed_share = std::min(1.0, share * 1.25 + 0.01);
@@ -210,7 +199,7 @@ Batch::Seeded Batch::stage_seeds(Pass& ps) {
         return Seeded::kSameReads;
     }
     listed_share = std::min(1.0, std::max(0.02, share * 1.5 + 0.005));
-    ps.total_hits = h_counters[kCtrSeedHits];
+    ps.total_hits = h_counters.p[kCtrSeedHits];
     if (ps.total_hits > hit_cap) {
         if (pl.nr > 1) return Seeded::kHalfReads;  // redo this pass with fewer reads
         // one read with more seed hits than the workspace (a long read in a repeat): grow the workspace
@@ -225,14 +214,14 @@ Batch::Seeded Batch::stage_seeds(Pass& ps) {
 void Batch::stage_locate(Pass& ps) {
     const DevIndexView& v = di->view;
     if (ps.tile_pass)
-        launch_expand_tiled(stream, v, ps.nstr, ps.plan.max_ns, ps.p.seed_interval, d_seed_lo, d_seed_cnt, d_strand_off, d_hit_row, d_hit_ref, d_hit_q);
+        launch_expand_tiled(stream, v, ps.nstr, ps.plan.max_ns, ps.p.seed_interval, d_seed_lo.p, d_seed_cnt.p, d_strand_off.p, d_hit_row.p, d_hit_ref.p, d_hit_q.p);
     else
-        launch_expand(stream, v, ps.nstr, ps.plan.max_ns, ps.p.seed_interval, d_seed_lo, d_seed_cnt, d_seed_pre, d_strand_off, d_hit_row, d_hit_ref,
-                      d_hit_q);
+        launch_expand(stream, v, ps.nstr, ps.plan.max_ns, ps.p.seed_interval, d_seed_lo.p, d_seed_cnt.p, d_seed_pre.p, d_strand_off.p, d_hit_row.p, d_hit_ref.p,
+                      d_hit_q.p);
     HIP_CHECK(hipEventRecord(ev[kEvExpanded], stream));
     if (!v.sa_full)
-        launch_locate(stream, v, (uint32_t)ps.total_hits, d_strand_off + ps.nstr, d_hit_row, d_hit_ref,
-                      (unsigned long long*)(d_counters + kCtrLfSteps));
+        launch_locate(stream, v, (uint32_t)ps.total_hits, d_strand_off.p + ps.nstr, d_hit_row.p, d_hit_ref.p,
+                      (unsigned long long*)(d_counters.p + kCtrLfSteps));
     HIP_CHECK(hipEventRecord(ev[kEvLocated], stream));
 }
 
@@ -241,16 +230,16 @@ void Batch::stage_candidates(Pass& ps) {
     // One launch zeroes the counters these kernels start from, k_coalesce_heavy's ticket, the counters round 0 of the verify
     // rounds starts from (no coalescing kernel touches them) and k_search's list count of the next pass (the host has read it).
     if (fused_clear) {
-        launch_clear_counters(stream, d_counters, kCtrClearPass | (ps.plan.path == VerifyPath::kRounds ? kCtrClearRound0 : 0));
+        launch_clear_counters(stream, d_counters.p, kCtrClearPass | (ps.plan.path == VerifyPath::kRounds ? kCtrClearRound0 : 0));
         listed_zero = true;
     } else {
-        HIP_CHECK(hipMemsetAsync(d_counters + kCtrWorklist, 0, 8, stream));
-        HIP_CHECK(hipMemsetAsync(d_counters + kCtrWlCursor, 0, 8, stream));
-        HIP_CHECK(hipMemsetAsync(d_counters + kCtrMidStrands, 0, 8, stream));
+        HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrWorklist, 0, 8, stream));
+        HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrWlCursor, 0, 8, stream));
+        HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrMidStrands, 0, 8, stream));
     }
-    launch_coalesce(stream, di->view, ps.so, (uint32_t)ps.r0, ps.nstr, ps.p.max_candidates, d_strand_off,
-                    d_strand_nseeds, d_hit_ref, d_hit_q, d_hit_key, d_cand_tmp, d_cand, d_cand_next,
-                    d_cand_status, d_strand_ncand, d_worklist, d_heavy_list, d_counters, fused_clear);
+    launch_coalesce(stream, di->view, ps.so, (uint32_t)ps.r0, ps.nstr, ps.p.max_candidates, d_strand_off.p,
+                    d_strand_nseeds.p, d_hit_ref.p, d_hit_q.p, d_hit_key.p, d_cand_tmp.p, d_cand.p, d_cand_next.p,
+                    d_cand_status.p, d_strand_ncand.p, d_worklist.p, d_heavy_list.p, d_counters.p, fused_clear);
     HIP_CHECK(hipEventRecord(ev[kEvCoalesced], stream));
 }
 
@@ -269,20 +258,20 @@ void Batch::stage_verify(Pass& ps) {
     a.r0 = (uint32_t)ps.r0;
     a.edit_rate = ps.p.edit_rate;
     a.max_candidates = ps.p.max_candidates;
-    a.strand_off = d_strand_off;
-    a.cand = d_cand;
-    a.cand_next = d_cand_next;
-    a.cand_status = d_cand_status;
-    a.planes = pl.myers() ? d_planes : nullptr;
+    a.strand_off = d_strand_off.p;
+    a.cand = d_cand.p;
+    a.cand_next = d_cand_next.p;
+    a.cand_status = d_cand_status.p;
+    a.planes = pl.myers() ? d_planes.p : nullptr;
     a.plane_words = pl.plane_words;
-    a.out = d_out;
-    a.n_verified = (unsigned long long*)(d_counters + kCtrVerified);
-    a.window_bytes = (unsigned long long*)(d_counters + kCtrWindowBytes);
-    a.sw_columns = (unsigned long long*)(d_counters + kCtrSwCellPairs);
+    a.out = d_out.p;
+    a.n_verified = (unsigned long long*)(d_counters.p + kCtrVerified);
+    a.window_bytes = (unsigned long long*)(d_counters.p + kCtrWindowBytes);
+    a.sw_columns = (unsigned long long*)(d_counters.p + kCtrSwCellPairs);
     // one launch: a group whose candidate fails walks on to the next candidate of the same TaxId
-    a.worklist = d_worklist;
-    a.wl_count = (const uint32_t*)(d_counters + kCtrWorklist);
-    a.wl_cursor = (uint32_t*)(d_counters + kCtrWlCursor);
+    a.worklist = d_worklist.p;
+    a.wl_count = (const uint32_t*)(d_counters.p + kCtrWorklist);
+    a.wl_cursor = (uint32_t*)(d_counters.p + kCtrWlCursor);
     stats.n_rounds = 1;
     switch (pl.path) {
         case VerifyPath::kTiled: verify_tiled(ps, a); break;
@@ -292,20 +281,20 @@ void Batch::stage_verify(Pass& ps) {
     }
     // (flags only: whether a strand has a hit does not depend on max_assignments -- the loop of index.rs:384-428
     //  pushes its first accepted candidate before it looks at the limit -- so the selection stops at the first)
-    launch_resolve(stream, ps.nstr, ps.p.max_candidates, flags_only() ? 1 : ps.p.max_assignments, d_strand_off, d_strand_ncand, d_cand_status,
-                   d_out, d_strand_nout);
+    launch_resolve(stream, ps.nstr, ps.p.max_candidates, flags_only() ? 1 : ps.p.max_assignments, d_strand_off.p, d_strand_ncand.p, d_cand_status.p,
+                   d_out.p, d_strand_nout.p);
     HIP_CHECK(hipEventRecord(ev[kEvVerified], stream));
 }
 
 // strips sized from the longest window of the pass (one small round trip; long reads are rare)
 void Batch::verify_tiled(Pass& ps, EvalArgs& a) {
-    HIP_CHECK(hipMemsetAsync(d_counters + kCtrMaxWindow, 0, sizeof(uint64_t), stream));
-    launch_max_window(stream, ps.nstr, d_strand_off, d_strand_ncand, d_cand, (unsigned long long*)(d_counters + kCtrMaxWindow));
-    launch_publish(stream, d_counters + kCtrMaxWindow, h_counters + kCtrMaxWindow, 1);
+    HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrMaxWindow, 0, sizeof(uint64_t), stream));
+    launch_max_window(stream, ps.nstr, d_strand_off.p, d_strand_ncand.p, d_cand.p, (unsigned long long*)(d_counters.p + kCtrMaxWindow));
+    launch_publish(stream, d_counters.p + kCtrMaxWindow, h_counters.p + kCtrMaxWindow, 1);
     HIP_CHECK(hipStreamSynchronize(stream));
-    const uint32_t strip_len = (uint32_t)std::max<uint64_t>(h_counters[kCtrMaxWindow], 1);
+    const uint32_t strip_len = (uint32_t)std::max<uint64_t>(h_counters.p[kCtrMaxWindow], 1);
     room_strip((uint64_t)tiled_groups(ps.total_hits, strip_len) * strip_len);
-    a.strip = d_strip;
+    a.strip = d_strip.p;
     a.strip_len = strip_len;
     launch_evaluate_tiled(stream, di->view, a, ps.total_hits);
 }
@@ -333,20 +322,20 @@ struct Batch::Round {
 void Batch::verify_rounds(Pass& ps, const EvalArgs& a) {
     Round r;
     r.fused = sw_bound && sw_fused;
-    r.pass_list = (uint32_t*)d_hit_key;              // coalesce scratch is free now
-    r.sweep_list = (uint32_t*)d_hit_key + hit_cap;   // (8 bytes per seed hit)
-    uint32_t* next_lists[2] = {(uint32_t*)d_cand_tmp, (uint32_t*)d_cand_tmp + hit_cap};
-    const uint32_t* wl = d_worklist;
+    r.pass_list = (uint32_t*)d_hit_key.p;              // coalesce scratch is free now
+    r.sweep_list = (uint32_t*)d_hit_key.p + hit_cap;   // (8 bytes per seed hit)
+    uint32_t* next_lists[2] = {(uint32_t*)d_cand_tmp.p, (uint32_t*)d_cand_tmp.p + hit_cap};
+    const uint32_t* wl = d_worklist.p;
     uint32_t wl_slot = kCtrWorklist;  // the slot whose low word is wl's length
     r.items = ps.total_hits;
     for (;; r.round++) {
-        r.next_slot = d_counters + kCtrNext0 + (r.round & 1);
+        r.next_slot = d_counters.p + kCtrNext0 + (r.round & 1);
         r.next_list = next_lists[r.round & 1];
         if (!fused_clear) {
-            HIP_CHECK(hipMemsetAsync(d_counters + kCtrSwCursor, 0, 3 * sizeof(uint64_t), stream));
+            HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrSwCursor, 0, 3 * sizeof(uint64_t), stream));
             HIP_CHECK(hipMemsetAsync(r.next_slot, 0, sizeof(uint64_t), stream));
         } else if (r.round) {  // (round 0: zeroed with the coalescing kernels' counters)
-            launch_clear_counters(stream, d_counters, ctr_clear_round(r.round));
+            launch_clear_counters(stream, d_counters.p, ctr_clear_round(r.round));
         }
         // The tail of a round -- k_sw_pairs and list-mode k_edit_myers -- is sized from its own list: later rounds
         // have its length on the host (n_next); round 0 asks for what the fused pass left undecided, one more round
@@ -355,17 +344,17 @@ void Batch::verify_rounds(Pass& ps, const EvalArgs& a) {
         r.tail_listed = tail_from_list && r.round > 0;
         r.sw = a;
         r.sw.worklist = wl;
-        r.sw.wl_count = (const uint32_t*)(d_counters + wl_slot);
-        r.sw.wl_cursor = (uint32_t*)(d_counters + kCtrSwCursor);
+        r.sw.wl_count = (const uint32_t*)(d_counters.p + wl_slot);
+        r.sw.wl_cursor = (uint32_t*)(d_counters.p + kCtrSwCursor);
         r.sw.wl_reverse = r.round == 0;
-        r.sw.counters = d_counters;
+        r.sw.counters = d_counters.p;
         r.sw.wl_count_slot = wl_slot;
         r.sw.pass_list = r.pass_list;
-        r.sw.pass_count = (uint32_t*)(d_counters + kCtrPassCount);
+        r.sw.pass_count = (uint32_t*)(d_counters.p + kCtrPassCount);
 #ifdef MTSV_SW_HIST
-        if (!d_strip) room_strip(4096);
-        HIP_CHECK(hipMemsetAsync(d_strip, 0, 768 * 4, stream));
-        r.sw.strip = d_strip;
+        if (!d_strip.p) room_strip(4096);
+        HIP_CHECK(hipMemsetAsync(d_strip.p, 0, 768 * 4, stream));
+        r.sw.strip = d_strip.p;
 #endif
         if (r.round == 0) {
             HIP_CHECK(hipEventRecord(ev[kEvSwBegin], stream));
@@ -375,7 +364,7 @@ void Batch::verify_rounds(Pass& ps, const EvalArgs& a) {
         }
         round_tail(ps, r, a);
         if (r.round == 0) round0_times();
-        const uint64_t n_next = h_counters[kCtrNext0] & 0xffffffffull;  // (either slot is published there)
+        const uint64_t n_next = h_counters.p[kCtrNext0] & 0xffffffffull;  // (either slot is published there)
         if (n_next == 0) break;
         stats.n_rounds++;
         wl = r.next_list;
@@ -387,7 +376,7 @@ void Batch::verify_rounds(Pass& ps, const EvalArgs& a) {
 
 // round 0 without the fused pass: the lower bounds on the seed diagonal first
 void Batch::round0_diag(Pass& ps, Round& r) {
-    HIP_CHECK(hipMemsetAsync(d_counters + kCtrSweepCount, 0, sizeof(uint64_t), stream));
+    HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrSweepCount, 0, sizeof(uint64_t), stream));
     launch_sw_diag(stream, di->view, r.sw, r.items, ps.plan.pass_max_len, r.sweep_list, kCtrSweepCount);
     HIP_CHECK(hipEventRecord(ev[kEvDiagEnd], stream));
     r.sw.worklist = r.sweep_list;
@@ -400,13 +389,13 @@ void Batch::round0_diag(Pass& ps, Round& r) {
 // of the rest, and only what lies between its two thresholds (kCtrUndecided counts it; the seed-hit rows of k_expand are free
 // by now) is swept by the tail.
 void Batch::round0_bound(Pass& ps, Round& r) {
-    if (!fused_clear) HIP_CHECK(hipMemsetAsync(d_counters + kCtrUndecided, 0, 2 * sizeof(uint64_t), stream));  // and kCtrBoundCursor
+    if (!fused_clear) HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrUndecided, 0, 2 * sizeof(uint64_t), stream));  // and kCtrBoundCursor
     EvalArgs bd = r.sw;
-    bd.wl_count = (const uint32_t*)(d_counters + r.sw.wl_count_slot);
-    bd.wl_cursor = (uint32_t*)(d_counters + kCtrBoundCursor);
-    bd.und_list = (uint32_t*)d_hit_row;
+    bd.wl_count = (const uint32_t*)(d_counters.p + r.sw.wl_count_slot);
+    bd.wl_cursor = (uint32_t*)(d_counters.p + kCtrBoundCursor);
+    bd.und_list = (uint32_t*)d_hit_row.p;
     bd.und_slot = kCtrUndecided;
-    bd.myers_ctr = (unsigned long long*)(d_counters + kCtrMyersColumns);
+    bd.myers_ctr = (unsigned long long*)(d_counters.p + kCtrMyersColumns);
     // (fused: from the worklist's end, and accepted candidates go straight to `out`)
     root()->verify_turn.note_grid(launch_edit_myers(stream, di->view, bd, r.items, ps.plan.pass_max_len, r.fused ? 3 : 2, root()->myers_wgs_per_cu));
     HIP_CHECK(hipEventRecord(ev[kEvBoundEnd], stream));
@@ -414,9 +403,9 @@ void Batch::round0_bound(Pass& ps, Round& r) {
     r.sw.wl_count_slot = kCtrUndecided;
     r.sw.wl_reverse = 0;
     if (r.fused && tail_from_list) {  // (fused: the pass list holds only what k_sw_pairs passes of these)
-        launch_publish(stream, d_counters + kCtrUndecided, h_counters + kCtrUndecided, 1);
+        launch_publish(stream, d_counters.p + kCtrUndecided, h_counters.p + kCtrUndecided, 1);
         HIP_CHECK(hipStreamSynchronize(stream));
-        r.tail_items = h_counters[kCtrUndecided] & 0xffffffffull;
+        r.tail_items = h_counters.p[kCtrUndecided] & 0xffffffffull;
         r.tail_listed = true;
     }
 }
@@ -424,11 +413,11 @@ void Batch::round0_bound(Pass& ps, Round& r) {
 // (MTSV_SW_BOUND=0) most of these are refuted on the top half of the read rows; the full-height launch of the tail takes
 // what is left (kCtrUndecided counts it)
 void Batch::round0_top(Pass& ps, Round& r) {
-    HIP_CHECK(hipMemsetAsync(d_counters + kCtrUndecided, 0, sizeof(uint64_t), stream));
-    r.sw.und_list = (uint32_t*)d_hit_row;
+    HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrUndecided, 0, sizeof(uint64_t), stream));
+    r.sw.und_list = (uint32_t*)d_hit_row.p;
     r.sw.und_slot = kCtrUndecided;
     launch_sw_pairs(stream, di->view, r.sw, r.items, ps.plan.pass_max_len, false, true);
-    HIP_CHECK(hipMemsetAsync(d_counters + kCtrSwCursor, 0, sizeof(uint64_t), stream));  // the claim cursor
+    HIP_CHECK(hipMemsetAsync(d_counters.p + kCtrSwCursor, 0, sizeof(uint64_t), stream));  // the claim cursor
     r.sw.worklist = r.sw.und_list;
     r.sw.wl_count_slot = kCtrUndecided;
 }
@@ -442,7 +431,7 @@ void Batch::round_tail(Pass& ps, Round& r, const EvalArgs& a) {
 #ifdef MTSV_SW_HIST
     {
         static uint32_t hh[768];
-        HIP_CHECK(hipMemcpyAsync(hh, d_strip, sizeof hh, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(hh, d_strip.p, sizeof hh, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
         fprintf(stderr, "SWHIST round %u steps/4:", r.round);
         for (int i = 0; i < 128; i++) if (hh[i]) fprintf(stderr, " %d:%u", i * 4, hh[i]);
@@ -456,22 +445,22 @@ void Batch::round_tail(Pass& ps, Round& r, const EvalArgs& a) {
     if (first) HIP_CHECK(hipEventRecord(ev[kEvSwEnd], stream));
     EvalArgs my = a;
     my.worklist = r.pass_list;
-    my.wl_count = (const uint32_t*)(d_counters + kCtrPassCount);
-    my.wl_cursor = (uint32_t*)(d_counters + kCtrMyersCursor);
+    my.wl_count = (const uint32_t*)(d_counters.p + kCtrPassCount);
+    my.wl_cursor = (uint32_t*)(d_counters.p + kCtrMyersCursor);
     my.next_list = r.next_list;
     my.next_count = (uint32_t*)r.next_slot;
-    my.myers_ctr = (unsigned long long*)(d_counters + kCtrMyersColumns);
+    my.myers_ctr = (unsigned long long*)(d_counters.p + kCtrMyersColumns);
     if (!tail_empty) root()->verify_turn.note_grid(launch_edit_myers(stream, v, my, r.tail_items, max_len, 1, root()->myers_wgs_per_cu, r.tail_listed));
     if (first) HIP_CHECK(hipEventRecord(ev[kEvEditEnd], stream));
     if (tail_empty) {
-        h_counters[kCtrPassCount] = h_counters[kCtrNext0] = 0;  // nothing passed, nothing for another round
+        h_counters.p[kCtrPassCount] = h_counters.p[kCtrNext0] = 0;  // nothing passed, nothing for another round
         if (first) HIP_CHECK(hipEventSynchronize(ev[kEvEditEnd]));
     } else {
-        launch_publish(stream, r.next_slot, h_counters + kCtrNext0, 1);
-        launch_publish(stream, d_counters + kCtrPassCount, h_counters + kCtrPassCount, 1);
+        launch_publish(stream, r.next_slot, h_counters.p + kCtrNext0, 1);
+        launch_publish(stream, d_counters.p + kCtrPassCount, h_counters.p + kCtrPassCount, 1);
         HIP_CHECK(hipStreamSynchronize(stream));
     }
-    sw_passed_acc += h_counters[kCtrPassCount] & 0xffffffffull;
+    sw_passed_acc += h_counters.p[kCtrPassCount] & 0xffffffffull;
 }
 
 // round 0's device times by kernel family, from the events its kernels were bracketed with
@@ -501,16 +490,16 @@ void Batch::round0_times() {
 void Batch::stage_gather(Pass& ps) {
     const bool only_flags = flags_only();
     if (!only_flags) {
-        launch_scan(stream, d_strand_nout, ps.nstr, d_tile_sums, d_counters + kCtrOutTotal, d_out_off);
-        launch_publish(stream, d_counters, h_counters, kCtrWlCursor + 1);
+        launch_scan(stream, d_strand_nout.p, ps.nstr, d_tile_sums.p, d_counters.p + kCtrOutTotal, d_out_off.p);
+        launch_publish(stream, d_counters.p, h_counters.p, kCtrWlCursor + 1);
         HIP_CHECK(hipStreamSynchronize(stream));
-        ps.total_out = h_counters[kCtrOutTotal];
+        ps.total_out = h_counters.p[kCtrOutTotal];
         ps.turn.release();  // (the paths without rounds: their verify kernels are through)
     }
     room_hits(ps.total_out);
-    if (!only_flags) launch_gather(stream, ps.nstr, ps.read_base + ps.r0, d_strand_off, d_strand_nout, d_out_off, d_out, d_hits, n_hits_total);
+    if (!only_flags) launch_gather(stream, ps.nstr, ps.read_base + ps.r0, d_strand_off.p, d_strand_nout.p, d_out_off.p, d_out.p, d_hits.p, n_hits_total);
     // (a compacted batch: the hits carry the caller's read numbers; the report and the flags are per resident read)
-    if (!only_flags && root()->mapped) launch_remap_reads(stream, d_hits + n_hits_total, ps.total_out, root()->d_read_map);
+    if (!only_flags && root()->mapped) launch_remap_reads(stream, d_hits.p + n_hits_total, ps.total_out, root()->d_read_map.p);
     HIP_CHECK(hipEventRecord(ev[kEvGathered], stream));
 }
 
@@ -520,25 +509,23 @@ void Batch::stage_commit(Pass& ps) {
     const uint32_t nr = ps.plan.nr;
     TaxaReport& rep = root()->report;
     if (rep.on) {
-        if (!report_ev[0])
-            for (auto& e : report_ev) HIP_CHECK(hipEventCreate(&e));
+        if (!report_ev.created()) report_ev.create();
         HIP_CHECK(hipEventRecord(report_ev[0], stream));
-        launch_report(stream, nr, d_strand_nout, d_out_off, d_hits + n_hits_total, rep.d_taxa, rep.n_taxa, rep.dense, rep.hash_slots, rep.d_counts,
-                      rep.d_counts + 4ull * rep.n_taxa, rep.trace ? rep.d_counts + 4ull * rep.n_taxa + 1 : nullptr);
+        launch_report(stream, nr, d_strand_nout.p, d_out_off.p, d_hits.p + n_hits_total, rep.d_taxa.p, rep.n_taxa, rep.dense, rep.hash_slots, rep.d_counts.p,
+                      rep.d_counts.p + 4ull * rep.n_taxa, rep.trace ? rep.d_counts.p + 4ull * rep.n_taxa + 1 : nullptr);
         HIP_CHECK(hipEventRecord(report_ev[1], stream));
     }
     MatchFlags& mf = root()->match;
     if (mf.mode != MTSV_MATCH_OFF) {
         const uint64_t first_bit = ps.read_base + ps.r0 - mf.call_base;
         if (first_bit + nr > mf.n_reads) throw std::runtime_error("internal: match flags of a pass beyond the run's reads");
-        if (!match_ev[0])
-            for (auto& e : match_ev) HIP_CHECK(hipEventCreate(&e));
+        if (!match_ev.created()) match_ev.create();
         HIP_CHECK(hipEventRecord(match_ev[0], stream));
-        launch_match(stream, nr, d_strand_nout, first_bit, mf.d_words, mf.d_words + mf.cap_words);
+        launch_match(stream, nr, d_strand_nout.p, first_bit, mf.d_words.p, mf.d_words.p + mf.cap_words());
         HIP_CHECK(hipEventRecord(match_ev[1], stream));
     }
     const bool collapse_on = !flags_only() && root()->assign.mode != MTSV_ASSIGN_OFF;
-    if (collapse_on) collapse_enqueue(nr, d_strand_nout, d_out_off, d_hits + n_hits_total, ps.total_out);
+    if (collapse_on) collapse_enqueue(nr, d_strand_nout.p, d_out_off.p, d_hits.p + n_hits_total, ps.total_out);
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     ps.turn.release();

@@ -42,12 +42,12 @@ void DupMap::take_unique(Batch& dst, Batch& src, uint64_t* n_unique_out, uint64_
         throw std::runtime_error("arg: the source workspace holds no resident batch (mtsv_batch_upload, mtsv_batch_take_reads, mtsv_batch_copy_reads, or a host batch of one input segment)");
     const uint64_t n_src = src.n_reads;
     if (n_src > (1ull << 30)) throw std::runtime_error("limit: more than 2^30 reads in one take_unique (the table's slots are numbered in 32 bits)");
-    const uint32_t* ho = host_batch ? src.h_off_all : src.h_read_off.data();
+    const uint32_t* ho = host_batch ? src.h_off_all.p : src.h_read_off.data();
     const uint64_t nb_src = n_src ? ho[n_src] : 0;
     const bool codes = host_batch || src.codes_resident;
-    const uint8_t* s_codes = host_batch ? src.arena[0].d_bases : src.d_codes;
-    const uint32_t* s_off = host_batch ? src.arena[0].d_off : src.d_read_off;
-    const uint32_t* s_map = !host_batch && src.mapped ? src.d_read_map : nullptr;
+    const uint8_t* s_codes = host_batch ? src.arena[0].d_bases.p : src.d_codes.p;
+    const uint32_t* s_off = host_batch ? src.arena[0].d_off.p : src.d_read_off.p;
+    const uint32_t* s_map = !host_batch && src.mapped ? src.d_read_map.p : nullptr;
     HIP_CHECK(hipSetDevice(device));
     hipStream_t stream = dst.stream;
     // ---- room: the map's (a refusal from here on leaves both the map and dst as they were) ----
@@ -75,12 +75,12 @@ void DupMap::take_unique(Batch& dst, Batch& src, uint64_t* n_unique_out, uint64_
     d_ctr.room(stream, 2, "the counters");
     // ---- room: dst's, as take_reads makes it ----
     dst.compact_room(compact_tiles(n_src));
-    uint64_t* result = dst.d_compact;
-    uint64_t *tile_cnt = dst.d_compact + 3, *tile_bases = dst.d_compact + 3 + dst.compact_cap;
+    uint64_t* result = dst.d_compact.p;
+    uint64_t *tile_cnt = dst.d_compact.p + 3, *tile_bases = dst.d_compact.p + 3 + dst.compact_cap();
     uint32_t *new_read = d_read[cur ^ 1].p, *new_rep = d_rep[cur ^ 1].p;
     // ---- which reads are identical ----
     // (a batch as uploaded is normalised into the source's d_codes first, as run() would do it)
-    if (!codes && nb_src) launch_normalise(stream, src.d_bases, src.d_codes, 0, nb_src);
+    if (!codes && nb_src) launch_normalise(stream, src.d_bases.p, src.d_codes.p, 0, nb_src);
     HIP_CHECK(hipMemsetAsync(result, 0, 3 * sizeof(uint64_t), stream));
     HIP_CHECK(hipMemsetAsync(d_ctr.p, 0, 2 * sizeof(uint64_t), stream));
     HIP_CHECK(hipMemsetAsync(d_words.p, 0, std::max<uint64_t>((n_src + 63) / 64, 1) * sizeof(uint64_t), stream));
@@ -111,11 +111,11 @@ void DupMap::take_unique(Batch& dst, Batch& src, uint64_t* n_unique_out, uint64_
     dst.resident = false;
     dst.last_run = Batch::kRunNone;
     HIP_CHECK(hipEventRecord(ev[5], stream));
-    launch_compact_copy(stream, (uint32_t)n_src, d_words.p, s_off, s_codes, MTSV_KEEP_MATCHED, s_map, tile_cnt, tile_bases, result, dst.d_codes, dst.d_read_off,
-                        dst.d_read_map);
+    launch_compact_copy(stream, (uint32_t)n_src, d_words.p, s_off, s_codes, MTSV_KEEP_MATCHED, s_map, tile_cnt, tile_bases, result, dst.d_codes.p, dst.d_read_off.p,
+                        dst.d_read_map.p);
     HIP_CHECK(hipEventRecord(ev[6], stream));
     dst.h_read_off.resize(m + 1);
-    HIP_CHECK(hipMemcpyAsync(dst.h_read_off.data(), dst.d_read_off, (m + 1) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(dst.h_read_off.data(), dst.d_read_off.p, (m + 1) * 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     HIP_CHECK(hipGetLastError());
     if (dst.h_read_off[0] != 0 || dst.h_read_off[m] != nb) throw std::runtime_error("internal: offsets of the distinct reads do not close on their bases");

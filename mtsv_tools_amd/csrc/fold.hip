@@ -155,7 +155,7 @@ void Fold::add_run(Batch& src, float* device_ms) {
         uint64_t at = 0;
         for (const auto& sg : src.segments) {
             if (!sg.a_count) continue;
-            HIP_CHECK(hipMemcpyAsync(d_in.p + at * rec, sg.lane->d_assign + sg.a_offset * rec, sg.a_count * rec, hipMemcpyDeviceToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(d_in.p + at * rec, sg.lane->d_assign.p + sg.a_offset * rec, sg.a_count * rec, hipMemcpyDeviceToDevice, stream));
             at += sg.a_count;
         }
         if (from_records) {  // (a collector is the rare source: its gathered records come to the host once, for the word behind the 8-byte read)

@@ -154,7 +154,7 @@ void Batch::format_text(const char* ids, const uint64_t* id_off, uint64_t n_read
     std::vector<TextFormatter::Stretch> src;
     // (the run has returned: nothing of the workspace is in flight)
     for (const auto& sg : segments)
-        if (sg.a_count) src.push_back(TextFormatter::Stretch{sg.lane->d_assign + sg.a_offset * rec, sg.a_count});
+        if (sg.a_count) src.push_back(TextFormatter::Stretch{sg.lane->d_assign.p + sg.a_offset * rec, sg.a_count});
     text->format(assign.grain, src, ids, id_off, n_reads_, text_out, len, device_ms);
 }
 
