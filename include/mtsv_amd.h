@@ -184,6 +184,7 @@ int mtsv_index_to_device(mtsv_index *ix, int hip_device, uint32_t flags);
 #define MTSV_DEVPART_BINS 4     /* n_bins x {start, end, tax_id, gi} u32 */
 #define MTSV_DEVPART_BIN_END 5
 #define MTSV_DEVPART_BIN_LUT 6
+#define MTSV_DEVPART_TEXT_SECTORS 7 /* the text's whole array: (n + 63) / 64 * 64 + 64 codes, 7 behind n */
 typedef struct {
     uint32_t n, n_blocks;
     uint32_t C[5];             /* less[] of A, C, G, T, N */

@@ -21,6 +21,7 @@ from ._lib import (  # noqa: F401
     DEVPART_HEADER,
     DEVPART_SA_SAMPLE,
     DEVPART_TEXT,
+    DEVPART_TEXT_SECTORS,
     DeviceHeader,
     GRAIN_LONG,
     GRAIN_TAXID,

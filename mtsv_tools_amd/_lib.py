@@ -24,7 +24,7 @@ ASSIGN_OFF, ASSIGN_WITH_HITS, ASSIGN_ONLY = 0, 1, 2  # MTSV_ASSIGN_*
 GRAIN_TAXID, GRAIN_TAXID_GI, GRAIN_LONG = 0, 1, 2  # MTSV_GRAIN_*
 KEEP_UNMATCHED, KEEP_MATCHED = 0, 1  # MTSV_KEEP_*
 # MTSV_DEVPART_*
-DEVPART_HEADER, DEVPART_BLOCKS, DEVPART_TEXT, DEVPART_SA_SAMPLE, DEVPART_BINS, DEVPART_BIN_END, DEVPART_BIN_LUT = range(7)
+DEVPART_HEADER, DEVPART_BLOCKS, DEVPART_TEXT, DEVPART_SA_SAMPLE, DEVPART_BINS, DEVPART_BIN_END, DEVPART_BIN_LUT, DEVPART_TEXT_SECTORS = range(8)
 
 
 class Params(C.Structure):  # mtsv_params

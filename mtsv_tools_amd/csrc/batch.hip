@@ -148,11 +148,13 @@ Batch::Batch(mtsv_index* ix_, DeviceIndex* di_, uint64_t max_reads_, uint64_t ma
         if (const char* e = getenv("MTSV_TAIL_FROM_LIST")) tail_from_list = atoi(e) != 0;
         if (const char* e = getenv("MTSV_FUSED_CLEAR")) fused_clear = atoi(e) != 0;
         if (const char* e = getenv("MTSV_SEED_STAGE")) seed_tiles = strcmp(e, "legacy") != 0;
+        if (const char* e = getenv("MTSV_MYERS_FETCH")) myers_fetch_legacy = strcmp(e, "legacy") == 0;
     } else {
         myers_wgs_per_cu = parent->myers_wgs_per_cu;
         tail_from_list = parent->tail_from_list;
         fused_clear = parent->fused_clear;
         seed_tiles = parent->seed_tiles;
+        myers_fetch_legacy = parent->myers_fetch_legacy;
     }
     ev.create();
     for (int k = 1; k < n_lanes; k++) extra.emplace_back(new Batch(ix, di, ws_reads, 0, hit_cap_user, this));

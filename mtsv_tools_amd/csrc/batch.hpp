@@ -115,6 +115,8 @@ struct Batch {
     bool fused_clear = true;     // the counters of a stage are zeroed by one launch_clear_counters (MTSV_FUSED_CLEAR=0: a memset each)
     bool seed_tiles = true;      // the seed stage by tiles, k_thin_tiled + k_expand_tiled, for the passes that fit them (MTSV_SEED_STAGE=legacy:
                                  // k_thin writing seed_pre and k_expand reading it, for every pass)
+    bool myers_fetch_legacy = false;  // k_edit_myers fetches its windows lane by lane, 16 columns at a time, and not by quads and whole
+                                      // sectors (MTSV_MYERS_FETCH=legacy)
     bool listed_zero = false;    // ... kCtrListedSlots (k_search's list count) is known to be zero on the stream
     // The verify turn: one lane of a workspace at a time has the verify kernels of a pass in flight (two VALU-bound launches beside
     // each other gain nothing, and the second takes the LDS the first frees from the memory-bound kernels that could use it).  The

@@ -275,7 +275,7 @@ void Batch::stage_verify(Pass& ps) {
     stats.n_rounds = 1;
     switch (pl.path) {
         case VerifyPath::kTiled: verify_tiled(ps, a); break;
-        case VerifyPath::kEditFirst: root()->verify_turn.note_grid(launch_edit_myers(stream, v, a, ps.total_hits, pl.pass_max_len, 0, root()->myers_wgs_per_cu)); break;
+        case VerifyPath::kEditFirst: root()->verify_turn.note_grid(launch_edit_myers(stream, v, a, ps.total_hits, pl.pass_max_len, 0, root()->myers_wgs_per_cu, false, root()->myers_fetch_legacy)); break;
         case VerifyPath::kRounds: verify_rounds(ps, a); break;
         case VerifyPath::kPacked: launch_evaluate(stream, v, a, ps.total_hits, pl.pass_max_len); break;
     }
@@ -397,7 +397,7 @@ void Batch::round0_bound(Pass& ps, Round& r) {
     bd.und_slot = kCtrUndecided;
     bd.myers_ctr = (unsigned long long*)(d_counters.p + kCtrMyersColumns);
     // (fused: from the worklist's end, and accepted candidates go straight to `out`)
-    root()->verify_turn.note_grid(launch_edit_myers(stream, di->view, bd, r.items, ps.plan.pass_max_len, r.fused ? 3 : 2, root()->myers_wgs_per_cu));
+    root()->verify_turn.note_grid(launch_edit_myers(stream, di->view, bd, r.items, ps.plan.pass_max_len, r.fused ? 3 : 2, root()->myers_wgs_per_cu, false, root()->myers_fetch_legacy));
     HIP_CHECK(hipEventRecord(ev[kEvBoundEnd], stream));
     r.sw.worklist = bd.und_list;
     r.sw.wl_count_slot = kCtrUndecided;
@@ -450,7 +450,7 @@ void Batch::round_tail(Pass& ps, Round& r, const EvalArgs& a) {
     my.next_list = r.next_list;
     my.next_count = (uint32_t*)r.next_slot;
     my.myers_ctr = (unsigned long long*)(d_counters.p + kCtrMyersColumns);
-    if (!tail_empty) root()->verify_turn.note_grid(launch_edit_myers(stream, v, my, r.tail_items, max_len, 1, root()->myers_wgs_per_cu, r.tail_listed));
+    if (!tail_empty) root()->verify_turn.note_grid(launch_edit_myers(stream, v, my, r.tail_items, max_len, 1, root()->myers_wgs_per_cu, r.tail_listed, root()->myers_fetch_legacy));
     if (first) HIP_CHECK(hipEventRecord(ev[kEvEditEnd], stream));
     if (tail_empty) {
         h_counters.p[kCtrPassCount] = h_counters.p[kCtrNext0] = 0;  // nothing passed, nothing for another round

@@ -260,6 +260,7 @@ int mtsv_index_download_device(mtsv_index* ix, int hip_device, int part, void** 
             break;
         case MTSV_DEVPART_BLOCKS: src = di->d_blocks, len = (uint64_t)v.n_blocks * sizeof(RankBlock); break;
         case MTSV_DEVPART_TEXT: src = di->d_text, len = di->text_bytes; break;
+        case MTSV_DEVPART_TEXT_SECTORS: src = di->d_text, len = di->text_alloc_bytes; break;
         case MTSV_DEVPART_SA_SAMPLE: src = di->d_sa_sample, len = di->sa_sample_bytes; break;
         case MTSV_DEVPART_BINS: src = di->d_bins, len = (uint64_t)v.n_bins * sizeof(DevBin); break;
         case MTSV_DEVPART_BIN_END: src = di->d_bin_end, len = (uint64_t)v.n_bins * 4; break;

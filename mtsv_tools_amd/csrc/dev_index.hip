@@ -223,7 +223,7 @@ static void pack_on_host(const HostIndex& hx, const uint32_t n, const uint32_t n
     if (sentinel_row == UINT64_MAX) throw std::runtime_error("format: bwt holds no sentinel");
 
     // ---- text codes ---------------------------------------------------------------------------
-    codes.assign(((uint64_t)n + 15) / 16 * 16 + 32, (uint8_t)7);  // padded for load16(): two aligned 16-byte loads from any position
+    codes.assign(text_padded_bytes(n), (uint8_t)7);  // padded for load16() and for the sectors of k_edit_myers (dev_layout.hpp)
     parallel_ranges(n, threads, [&](uint64_t lo, uint64_t hi, int) {
         for (uint64_t i = lo; i < hi; i++) codes[i] = (uint8_t)sym_code(hx.text[i]);
     });
@@ -288,14 +288,14 @@ static uint64_t pack_on_device(const HostIndex& hx, const uint32_t n, const uint
         throw std::runtime_error("format: Occ checkpoint " + std::to_string(ctr[kPackCtrOccBadFirst]) + " disagrees with the bwt");
     if (!ctr[kPackCtrSentinels]) throw std::runtime_error("format: bwt holds no sentinel");
 
-    HIP_CHECK(hipMalloc((void**)&di.d_text, di.text_bytes));
-    di.bytes += di.text_bytes;
+    HIP_CHECK(hipMalloc((void**)&di.d_text, di.text_alloc_bytes));
+    di.bytes += di.text_alloc_bytes;
     d_raw_text.alloc(raw_bytes, "the raw text");
     t0 = now_ms();
     HIP_CHECK(hipMemcpy(d_raw_text.p, hx.text.data(), n, hipMemcpyHostToDevice));
     copy_ms += now_ms() - t0;
     HIP_CHECK(hipEventRecord(ev.e[5], 0));
-    launch_pack_text(0, d_raw_text.p, n, di.d_text, di.text_bytes);
+    launch_pack_text(0, d_raw_text.p, n, di.d_text, di.text_alloc_bytes);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ev.e[6], 0));
     HIP_CHECK(hipEventSynchronize(ev.e[6]));
@@ -367,7 +367,8 @@ std::unique_ptr<DeviceIndex> upload_index(const HostIndex& hx, int device, uint3
         copy_ms += now_ms() - t0;
         di->bytes += bytes;
     };
-    di->text_bytes = ((uint64_t)n + 15) / 16 * 16 + 32;
+    di->text_bytes = ((uint64_t)n + 15) / 16 * 16 + 32;  // (what MTSV_DEVPART_TEXT shows: load16()'s padding)
+    di->text_alloc_bytes = text_padded_bytes(n);
     di->sa_sample_bytes = samp.size() * 4;
     di->bin_lut_bytes = bin_lut.size() * 4;
     di->packed_on_device = on_device;

@@ -35,6 +35,7 @@ struct DeviceIndex {
     // mtsv_index_download_device: the sizes of the arrays the view does not carry, how the upload packed, and its times --
     // pack_ms: the host pack (host clock) or the pack kernels (device events); copy_ms: the host-to-device copies (host clock)
     uint64_t text_bytes = 0, sa_sample_bytes = 0, bin_lut_bytes = 0;
+    uint64_t text_alloc_bytes = 0;  // d_text as allocated: text_padded_bytes(n), of which text_bytes are MTSV_DEVPART_TEXT
     bool packed_on_device = false;
     float pack_ms = 0.f, copy_ms = 0.f;
 

@@ -35,6 +35,11 @@ struct DevBin {  // src/index.rs:45-54 narrowed to u32 positions
     uint32_t start, end, tax_id, gi;
 };
 
+// Bytes of the text's code array on the device for a text of n symbols: padded with code 7 to whole 64-byte sectors and one
+// sector more.  load16() reads two aligned 16-byte pieces from any position below n, and k_edit_myers' window stream
+// the whole sector that such a piece lies in.
+__host__ __device__ inline uint64_t text_padded_bytes(uint64_t n) { return (n + 63) / 64 * 64 + 64; }
+
 // Passed by value to every kernel.
 struct DevIndexView {
     const RankBlock* blocks;

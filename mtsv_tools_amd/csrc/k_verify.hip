@@ -43,7 +43,7 @@ __device__ inline int row_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v,
 __device__ inline uint32_t group_ballot(bool p, uint32_t group) { return (uint32_t)(__ballot(p) >> (group * kGroup)) & 0xffffu; }
 
 // 16 window symbols starting at text[pos] (any alignment) as four little-endian dwords; bytes past the text read as 7
-// (the text allocation is padded with 7 to a 16-byte multiple plus 32: dev_index.hip).  Two aligned 16-byte loads and a
+// (the text allocation is padded with 7 to whole sectors and one more: text_padded_bytes).  Two aligned 16-byte loads and a
 // select instead of five dword loads: a lane's window lies anywhere in a multi-GB text, so every load instruction of a
 // wavefront touches 64 different lines, and it is the number of such instructions that the texture path pays for.
 __device__ inline uint4 load16(const uint8_t* __restrict__ text, uint32_t n, uint32_t pos) {
@@ -1308,6 +1308,123 @@ __device__ inline uint4 fetch_cols(const DevIndexView& ix, uint32_t start, uint3
 }
 
 // ---------------------------------------------------------------------------------------------
+// The window stream of k_edit_myers by whole sectors.  fetch_cols above asks for two aligned 16-byte pieces per lane and
+// block of 16 columns, the second of which is the first of the next block: every load instruction of a wavefront
+// touches 64 different lines, and a 64-byte sector of the text is asked for up to eight times, microseconds apart.
+// Here the four lanes of a quad fetch ONE lane's sector together, 16 bytes each, once for every lane of the quad: a
+// load instruction of the wavefront touches 16 whole sectors, and four of them bring 64 columns to all 64 lanes.  The
+// pieces then change hands inside the quad (a 4 x 4 transpose by two DPP butterflies), so that every lane holds its
+// own sector, in the order its columns are consumed: a reverse-strand lane has its sectors fetched downwards with the
+// pieces swapped, and reverses the bytes of each piece.  All of this moves data between lanes: it runs with every lane of
+// the wavefront active, outside the per-lane control flow (DPP reads nothing from a lane that is switched off).
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kSectorNone = 0xffffffffu;  // no sector to fetch (a sector code is its byte offset, | 1 on the reverse strand)
+constexpr uint32_t kSectorFill = 0x07070707u;  // what such a sector reads as: padding, like the bytes past the text
+
+template <int CTRL>  // quad_perm: lane q of every quad reads lane (CTRL >> 2q) & 3 of its quad
+__device__ inline uint32_t quad_perm(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+
+// A 64-byte sector as four 16-byte pieces (named members, never indexed: the pieces live in registers)
+struct Sector {
+    uint4 p0, p1, p2, p3;
+};
+
+// D.p<i> of lane q = piece q (3 - q on the reverse strand) of the sector that lane i of the quad asked for
+__device__ inline Sector quad_fetch(const uint8_t* __restrict__ text, uint32_t code, uint32_t q) {
+    Sector D;
+#define MTSV_QUAD_FETCH(P, CTRL)                                                                                       \
+    {                                                                                                                  \
+        const uint32_t ci = quad_perm<CTRL>(code);                                                                     \
+        uint4 v = make_uint4(kSectorFill, kSectorFill, kSectorFill, kSectorFill);                                      \
+        if (ci != kSectorNone) v = *reinterpret_cast<const uint4*>(text + (ci & ~63u) + 16u * (q ^ ((ci & 1u) * 3u)));  \
+        D.P = v;                                                                                                       \
+    }
+    MTSV_QUAD_FETCH(p0, 0x00)
+    MTSV_QUAD_FETCH(p1, 0x55)
+    MTSV_QUAD_FETCH(p2, 0xAA)
+    MTSV_QUAD_FETCH(p3, 0xFF)
+#undef MTSV_QUAD_FETCH
+    return D;
+}
+
+// in: D.p<i> of lane q = the piece lane q fetched for lane i.  out: D.p<j> = the piece lane j fetched for this lane
+__device__ inline Sector quad_transpose(Sector D, uint32_t q) {
+    const bool b0 = (q & 1u) != 0, b1 = (q & 2u) != 0;
+#define MTSV_QUAD_SWAP(A, B, f, CTRL, bit)                                         \
+    {                                                                              \
+        const uint32_t xa = quad_perm<CTRL>(D.A.f), xb = quad_perm<CTRL>(D.B.f);   \
+        const uint32_t na = bit ? xb : D.A.f, nb = bit ? D.B.f : xa;               \
+        D.A.f = na;                                                                \
+        D.B.f = nb;                                                                \
+    }
+#define MTSV_QUAD_STAGE(A, B, CTRL, bit) \
+    MTSV_QUAD_SWAP(A, B, x, CTRL, bit) MTSV_QUAD_SWAP(A, B, y, CTRL, bit) MTSV_QUAD_SWAP(A, B, z, CTRL, bit) MTSV_QUAD_SWAP(A, B, w, CTRL, bit)
+    MTSV_QUAD_STAGE(p0, p1, 0xB1, b0)  // with lane q ^ 1
+    MTSV_QUAD_STAGE(p2, p3, 0xB1, b0)
+    MTSV_QUAD_STAGE(p0, p2, 0x4E, b1)  // with lane q ^ 2
+    MTSV_QUAD_STAGE(p1, p3, 0x4E, b1)
+#undef MTSV_QUAD_STAGE
+#undef MTSV_QUAD_SWAP
+    return D;
+}
+
+// reverse strand: the bytes of every piece in reverse (the pieces themselves were fetched in reverse); forward: as they are
+__device__ inline uint4 piece_in_column_order(const uint4 t, uint32_t sel) {
+    return make_uint4(__builtin_amdgcn_perm(t.w, t.x, sel), __builtin_amdgcn_perm(t.z, t.y, sel), __builtin_amdgcn_perm(t.y, t.z, sel),
+                      __builtin_amdgcn_perm(t.x, t.w, sel));
+}
+__device__ inline Sector sector_in_column_order(const Sector T, uint32_t strand) {
+    const uint32_t sel = strand ? 0x04050607u : 0x03020100u;  // v_perm_b32: the first operand reversed, or the second as it is
+    Sector r;
+    r.p0 = piece_in_column_order(T.p0, sel);
+    r.p1 = piece_in_column_order(T.p1, sel);
+    r.p2 = piece_in_column_order(T.p2, sel);
+    r.p3 = piece_in_column_order(T.p3, sel);
+    return r;
+}
+
+// 16 columns from byte boff + 16 * M of the 128 bytes lo | hi (boff 0..63 per lane), unclamped
+template <int M>
+__device__ inline uint4 sector_cols(const Sector lo, const Sector hi, uint32_t boff) {
+    const uint32_t s4 = boff >> 4, dsel = (boff >> 2) & 3u, sh = boff & 3u;
+    auto pick = [s4](const uint4 p0, const uint4 p1, const uint4 p2, const uint4 p3) {
+        uint4 r;
+        r.x = s4 == 0 ? p0.x : s4 == 1 ? p1.x : s4 == 2 ? p2.x : p3.x;
+        r.y = s4 == 0 ? p0.y : s4 == 1 ? p1.y : s4 == 2 ? p2.y : p3.y;
+        r.z = s4 == 0 ? p0.z : s4 == 1 ? p1.z : s4 == 2 ? p2.z : p3.z;
+        r.w = s4 == 0 ? p0.w : s4 == 1 ? p1.w : s4 == 2 ? p2.w : p3.w;
+        return r;
+    };
+    uint4 a, b;  // pieces s4 + M and s4 + M + 1
+    if constexpr (M == 0) {
+        a = pick(lo.p0, lo.p1, lo.p2, lo.p3);
+        b = pick(lo.p1, lo.p2, lo.p3, hi.p0);
+    } else if constexpr (M == 1) {
+        a = pick(lo.p1, lo.p2, lo.p3, hi.p0);
+        b = pick(lo.p2, lo.p3, hi.p0, hi.p1);
+    } else if constexpr (M == 2) {
+        a = pick(lo.p2, lo.p3, hi.p0, hi.p1);
+        b = pick(lo.p3, hi.p0, hi.p1, hi.p2);
+    } else {
+        a = pick(lo.p3, hi.p0, hi.p1, hi.p2);
+        b = pick(hi.p0, hi.p1, hi.p2, hi.p3);
+    }
+    const uint32_t e0 = dsel == 0 ? a.x : dsel == 1 ? a.y : dsel == 2 ? a.z : a.w;  // (as load16 aligns its two pieces)
+    const uint32_t e1 = dsel == 0 ? a.y : dsel == 1 ? a.z : dsel == 2 ? a.w : b.x;
+    const uint32_t e2 = dsel == 0 ? a.z : dsel == 1 ? a.w : dsel == 2 ? b.x : b.y;
+    const uint32_t e3 = dsel == 0 ? a.w : dsel == 1 ? b.x : dsel == 2 ? b.y : b.z;
+    const uint32_t e4 = dsel == 0 ? b.x : dsel == 1 ? b.y : dsel == 2 ? b.z : b.w;
+    uint4 r;
+    r.x = __builtin_amdgcn_alignbyte(e1, e0, sh);
+    r.y = __builtin_amdgcn_alignbyte(e2, e1, sh);
+    r.z = __builtin_amdgcn_alignbyte(e3, e2, sh);
+    r.w = __builtin_amdgcn_alignbyte(e4, e3, sh);
+    return r;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Alternative verification order ("edit first"): acceptance is the conjunction of two pure
 // predicates, SW >= L - 2*ED and edits <= ED (index.rs:406,410), and for reads up to 253 bases the
 // SW score is the exact local score, for which edits <= ED implies SW >= L - 2*ED (an alignment with
@@ -1343,8 +1460,9 @@ __device__ inline uint4 fetch_cols(const DevIndexView& ix, uint32_t start, uint3
 // edit distance's own pass (ph = 2).  What lies between the thresholds goes to und_list for the sweep of the same round.
 // The minimum over all columns is the reported distance, so only the refuting exit leaves the columns early.
 enum : int { MY_CHAIN = 0, MY_LIST = 1, MY_BOUND = 2, MY_FUSED = 3 };
-template <int W, int MODE>  // W 32-bit words per column: reads of up to 32*W bases
-__global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a) {
+// QUAD: the window's columns come by whole sectors, fetched by quads of lanes (above); otherwise by fetch_cols, a lane for itself
+template <int W, int MODE, bool QUAD>  // W 32-bit words per column: reads of up to 32*W bases
+__global__ __launch_bounds__(256, (QUAD && W <= 5) ? 5 : 1) void k_edit_myers(DevIndexView ix, EvalArgs a) {
     // match masks of the lane's read, one row per window symbol (A C G T, other), word-major so that a
     // lane's reads are conflict-free whatever row it picks.  The read sits at the TOP of the 32*W rows
     // (its last base is bit 31 of word W-1); the rows below it are wildcard rows whose vertical deltas
@@ -1361,8 +1479,12 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
     const uint32_t n_work = *a.wl_count;
     const uint32_t maxc = a.maxc;  // max_candidates as a rank bound, clamped on the host
     const uint32_t lane = lane_id();
-    uint32_t verified = 0, wbytes = 0;  // per lane: far below 2^32 in one launch, like cols
-    uint32_t cols = 0, refuted = 0;  // columns this lane's recurrences advanced; bound and fused mode: candidates it refuted
+    uint32_t wbytes = 0;  // per lane: far below 2^32 in one launch, like cols
+    uint32_t cols = 0;    // columns this lane's recurrences advanced
+    // candidates verified; bound and fused mode: candidates refuted; list and fused mode: successors that passed the prefilter here.
+    // QUAD: the wavefront's, counted by ballot at the end of every trip -- three scalar registers, where the two sectors leave no
+    // vector registers to spare.  fetch_cols: the lane's own -- that kernel is at its limit of scalar registers instead.
+    uint32_t verified = 0, refuted = 0, extra_passed = 0;
     // wave-uniform slice of the worklist, claimed 256 items at a time; a lane whose candidate passed
     // (or whose TaxId chain ended) takes the next item, a lane whose candidate failed keeps its read
     // and moves to the next candidate of the same TaxId (index.rs:393)
@@ -1377,7 +1499,7 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
     // by the edit-distance bound (as in bound mode), 2: its edit distance once the bound has passed it (reads with N only:
     // without N, or without N in the window, the two distances are the same number).  Only a successor the bound leaves undecided
     // goes to another round.  Fused mode: every item starts at 1, and what the bound leaves undecided is swept in the same round.
-    uint32_t ph = 0, extra_passed = 0;
+    uint32_t ph = 0;
     bool read_n = false;  // the read holds an N
     for (;;) {
         unsigned long long need = __ballot(!active);
@@ -1405,7 +1527,7 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                 const uint32_t rs = a.cand[g].w;
                 const uint32_t r_ = a.r0 + (rs >> 1);
                 strand = rs & 1;
-                o = a.strand_off[rs];
+                if (!QUAD) o = a.strand_off[rs];
                 const uint32_t b0 = a.read_off[r_];
                 L = a.read_off[r_ + 1] - b0;
                 ED = (uint32_t)ceil((double)L * a.edit_rate);
@@ -1463,80 +1585,164 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
             if (exhausted) break;
             continue;
         }
+        bool verified_now = false, refuted_now = false, passed_now = false;  // QUAD: this lane, this trip
+        auto count_verified = [&]() { if (QUAD) verified_now = true; else verified++; };
+        auto count_refuted = [&]() { if (QUAD) refuted_now = true; else refuted++; };
+        auto count_passed = [&]() { if (QUAD) passed_now = true; else extra_passed++; };
         uint32_t verdict = 0, vg = 0;  // bound mode: 1 = passes the prefilter, 2 = undecided (candidate vg; fused mode: candidate g)
-        if ((FUSED ? thr_wrapped : !LIST && hopeless) && active) {  // no sweep needed: every candidate of this strand fails
+        const uint32_t* lane_tab = &eq_tab[0][0][tid];
+        // a block of the window: the recurrence over its first lim columns (cur: 16 clamped codes, a byte each)
+        auto columns16 = [&](const uint4 cur, const uint32_t lim, uint32_t (&Pv)[W], uint32_t (&Mv)[W], int& score, int& best) {
+#pragma unroll
+            for (int jj = 0; jj < 16; jj++) {
+                if ((uint32_t)jj < lim) {  // predicated, not a break: keeps the 16 columns unrolled
+                    const uint32_t word = jj < 4 ? cur.x : jj < 8 ? cur.y : jj < 12 ? cur.z : cur.w;
+                    const uint32_t tc = (word >> ((jj & 3) * 8)) & 0xffu;
+                    const uint32_t* row = lane_tab + tc * (W * 256);
+                    // One word step in 12 vector instructions: the horizontal deltas enter a word as bit 31 of the word
+                    // below (v_alignbit_b32 shifts them in), and the delta entering word 0 is 0 (first row all zeros).
+                    uint32_t ph_below = 0, mh_below = 0;
+#pragma unroll
+                    for (int k = 0; k < W; k++) {
+                        const uint32_t Eq = row[k * 256];
+                        const uint32_t pv = Pv[k], mv = Mv[k];
+                        const uint32_t Xv = Eq | mv;
+                        const uint32_t Eqh = k ? (Eq | (mh_below >> 31)) : Eq;
+                        const uint32_t Xh = __builtin_amdgcn_bitop3_b32((Eqh & pv) + pv, pv, Eqh, 0xBE);  // (sum ^ pv) | Eqh
+                        const uint32_t Ph = mv | ~(Xh | pv);
+                        const uint32_t Mh = pv & Xh;
+                        const uint32_t Phs = k ? __builtin_amdgcn_alignbit(Ph, ph_below, 31) : (Ph << 1);  // (Ph << 1) | carry
+                        const uint32_t Mhs = k ? __builtin_amdgcn_alignbit(Mh, mh_below, 31) : (Mh << 1);
+                        Pv[k] = Mhs | ~(Xv | Phs);
+                        Mv[k] = Phs & Xv;
+                        ph_below = Ph;
+                        mh_below = Mh;
+                    }
+                    const uint32_t hp = ph_below >> 31, hm = mh_below >> 31;
+                    score += (int)hp - (int)hm;  // the read's last base is bit 31 of the last word
+                    best = min(best, score);
+                }
+            }
+        };
+        // where the strand's candidates start (QUAD: from the candidate's own word, at the few places that walk on: a load there,
+        // not a register held through the sweep)
+        auto strand_base = [&](const uint4& cd) { return QUAD ? a.strand_off[cd.w] : o; };
+        const bool no_sweep = (FUSED ? thr_wrapped : !LIST && hopeless) && active;
+        const bool sweep = active && !no_sweep;
+        if (no_sweep) {  // no sweep needed: every candidate of this strand fails
             const uint4 c = a.cand[g];
             if (!BOUND || !counted) {
-                verified++;
+                count_verified();
                 wbytes += c.y - c.x;
             }
             counted = false;
             a.cand_status[g] = 1;
             const uint32_t nxt = a.cand_next[g];
             if (nxt == 0xffffffffu || nxt >= maxc) active = false;
-            else g = o + nxt;
-        } else if (active) {
-            const uint4 c = a.cand[g];
-            uint32_t Pv[W], Mv[W];
+            else g = strand_base(c) + nxt;
+        }
+        // The sweep.  With QUAD every lane of the wavefront goes through it, the ones that have no window with an empty one:
+        // its fetches are the work of whole quads.
+        uint4 c = make_uint4(0, 0, 0, 0);
+        if (sweep) c = a.cand[g];
+        uint32_t Pv[W], Mv[W];
 #pragma unroll
-            for (int k = 0; k < W; k++) {
-                Pv[k] = pv0[k];
-                Mv[k] = 0;
-            }
-            const uint32_t Wn = c.y - c.x;
-            int score = (int)L, best = (int)L;  // D[L][0] = L
-            // The window's columns arrive 16 at a time, one fetch ahead of the recurrence (three ahead measured the same and
-            // cost eight registers: a wavefront of occupancy here)
-            const bool swm = BOUND || (LIST && ph == 1);  // matches of the SW matrix, early exits of the bound
-            uint4 nxt4 = Wn ? fetch_cols(ix, c.x, c.y, strand, 0, swm) : make_uint4(0, 0, 0, 0);
-            const uint32_t* lane_tab = &eq_tab[0][0][tid];
-            uint32_t j0 = 0;
-            // list mode: bit 2 of the clamped codes that streamed by, i.e. "the window may hold an N" (the don't-care columns
-            // past the window in the last 16 may set it too: that errs to the second pass)
-            uint32_t win_n = 0;
-            for (; j0 < Wn; j0 += 16) {
-                if (swm) {  // decided already: passes, or the last row cannot come down to 2*ED any more
-                    if (BOUND && best <= (int)ED) break;  // (list mode goes on: its minimum is the edit distance of a read without N)
-                    if (best > 2 * (int)ED && score - (int)(Wn - j0) > 2 * (int)ED) break;
+        for (int k = 0; k < W; k++) {
+            // (QUAD: column 0 from the wildcard row the lane wrote for its read, not from five registers held through the sweep)
+            Pv[k] = QUAD ? ~eq_tab[4][k][tid] : pv0[k];
+            Mv[k] = 0;
+        }
+        const uint32_t Wn = c.y - c.x;
+        int score = (int)L, best = (int)L;  // D[L][0] = L
+        const bool swm = BOUND || (LIST && ph == 1);  // matches of the SW matrix, early exits of the bound
+        // list mode: bit 2 of the clamped codes that streamed by, i.e. "the window may hold an N" (the don't-care columns
+        // past the window in the last 16 may set it too: that errs to the second pass)
+        uint32_t win_n = 0;
+        uint32_t jstop = 0;  // fetch_cols: the column the lane's sweep stopped at (a multiple of 16: Wn or beyond, or an early exit)
+        if constexpr (!QUAD) {
+            if (sweep) {
+                // The window's columns arrive 16 at a time, one fetch ahead of the recurrence (three ahead measured the same and
+                // cost eight registers: a wavefront of occupancy here)
+                uint4 nxt4 = Wn ? fetch_cols(ix, c.x, c.y, strand, 0, swm) : make_uint4(0, 0, 0, 0);
+                uint32_t j0 = 0;
+                for (; j0 < Wn; j0 += 16) {
+                    if (swm) {  // decided already: passes, or the last row cannot come down to 2*ED any more
+                        if (BOUND && best <= (int)ED) break;  // (list mode goes on: its minimum is the edit distance of a read without N)
+                        if (best > 2 * (int)ED && score - (int)(Wn - j0) > 2 * (int)ED) break;
+                    }
+                    const uint4 cur = nxt4;
+                    if (LIST) win_n |= cur.x | cur.y | cur.z | cur.w;
+                    if (j0 + 16 < Wn) nxt4 = fetch_cols(ix, c.x, c.y, strand, j0 + 16, swm);  // prefetch the next 16 columns
+                    columns16(cur, min(16u, Wn - j0), Pv, Mv, score, best);
                 }
-                const uint4 cur = nxt4;
-                if (LIST) win_n |= cur.x | cur.y | cur.z | cur.w;
-                if (j0 + 16 < Wn) nxt4 = fetch_cols(ix, c.x, c.y, strand, j0 + 16, swm);  // prefetch the next 16 columns
-                const uint32_t lim = min(16u, Wn - j0);
-#pragma unroll
-                for (int jj = 0; jj < 16; jj++) {
-                    if ((uint32_t)jj < lim) {  // predicated, not a break: keeps the 16 columns unrolled
-                        const uint32_t word = jj < 4 ? cur.x : jj < 8 ? cur.y : jj < 12 ? cur.z : cur.w;
-                        const uint32_t tc = (word >> ((jj & 3) * 8)) & 0xffu;
-                        const uint32_t* row = lane_tab + tc * (W * 256);
-                        // One word step in 12 vector instructions: the horizontal deltas enter a word as bit 31 of the word
-                        // below (v_alignbit_b32 shifts them in), and the delta entering word 0 is 0 (first row all zeros).
-                        uint32_t ph_below = 0, mh_below = 0;
-#pragma unroll
-                        for (int k = 0; k < W; k++) {
-                            const uint32_t Eq = row[k * 256];
-                            const uint32_t pv = Pv[k], mv = Mv[k];
-                            const uint32_t Xv = Eq | mv;
-                            const uint32_t Eqh = k ? (Eq | (mh_below >> 31)) : Eq;
-                            const uint32_t Xh = __builtin_amdgcn_bitop3_b32((Eqh & pv) + pv, pv, Eqh, 0xBE);  // (sum ^ pv) | Eqh
-                            const uint32_t Ph = mv | ~(Xh | pv);
-                            const uint32_t Mh = pv & Xh;
-                            const uint32_t Phs = k ? __builtin_amdgcn_alignbit(Ph, ph_below, 31) : (Ph << 1);  // (Ph << 1) | carry
-                            const uint32_t Mhs = k ? __builtin_amdgcn_alignbit(Mh, mh_below, 31) : (Mh << 1);
-                            Pv[k] = Mhs | ~(Xv | Phs);
-                            Mv[k] = Phs & Xv;
-                            ph_below = Ph;
-                            mh_below = Mh;
-                        }
-                        const uint32_t hp = ph_below >> 31, hm = mh_below >> 31;
-                        score += (int)hp - (int)hm;  // the read's last base is bit 31 of the last word
-                        best = min(best, score);
+                jstop = j0;
+            }
+        } else {
+            // The lanes advance in lock step, 16 columns a trip of the loop, until the last of them has left its window; lo and hi
+            // are sectors k and k + 1 of the lane's stream (k = j0 / 64: text sectors upwards from the one of c.x, or downwards
+            // from the one of c.y - 1), of which the window's first column is byte boff.  Before the last block of 64 columns hi
+            // moves to lo and sector k + 2 is asked for: it has the time of that block to arrive, as fetch_cols' 16 columns have.
+            // hi holds the quad's pieces as they were fetched until the first block that needs the sector as the lane's own.
+            const uint32_t q = lane & 3u;
+            const uint32_t first = strand ? c.y - 1u : c.x;  // text position of column 0
+            const uint32_t boff = strand ? 63u - (first & 63u) : first & 63u;
+            const uint32_t s0 = first >> 6, nblk = (Wn + 15u) >> 4;
+            const uint32_t nsec = nblk ? ((boff + 16u * nblk - 1u) >> 6) + 1u : 0u;  // sectors that the blocks' 16 bytes reach into
+            const uint32_t sec_end = (uint32_t)(text_padded_bytes(ix.n) >> 6);
+            bool run = sweep && Wn != 0;
+            auto sector_code = [&](uint32_t k) -> uint32_t {  // (a lane that has left its window asks for nothing more)
+                if (!run || k >= nsec || (strand && k > s0)) return kSectorNone;  // (below text position 0: reads as padding)
+                const uint32_t s = strand ? s0 - k : s0 + k;
+                return s < sec_end ? (s << 6) | strand : kSectorNone;
+            };
+            Sector lo = quad_fetch(ix.text, sector_code(0), q);
+            Sector hi = quad_fetch(ix.text, sector_code(1), q);
+            lo = sector_in_column_order(quad_transpose(lo, q), strand);
+            for (uint32_t j0 = 0;; j0 += 16) {
+                if (run) {
+                    bool stop = j0 >= Wn;
+                    if (!stop && swm) {  // decided already: passes, or the last row cannot come down to 2*ED any more
+                        if (BOUND && best <= (int)ED) stop = true;  // (list mode goes on: its minimum is the edit distance of a read without N)
+                        else if (best > 2 * (int)ED && score - (int)(Wn - j0) > 2 * (int)ED) stop = true;
+                    }
+                    if (stop) {
+                        run = false;
+                        cols += min(j0, Wn);
                     }
                 }
+                if (!__any(run)) break;
+                const uint32_t m = (j0 >> 4) & 3u;
+                if (m == 0) {
+                    hi = sector_in_column_order(quad_transpose(hi, q), strand);
+                }
+                uint4 cur;  // (m is the same in every lane: four straight pieces of code, no piece is ever indexed)
+                if (m == 0) cur = sector_cols<0>(lo, hi, boff);
+                else if (m == 1) cur = sector_cols<1>(lo, hi, boff);
+                else if (m == 2) cur = sector_cols<2>(lo, hi, boff);
+                else cur = sector_cols<3>(lo, hi, boff);
+                cur.x = swm ? clamp_codes_sw(cur.x) : clamp_codes4(cur.x);
+                cur.y = swm ? clamp_codes_sw(cur.y) : clamp_codes4(cur.y);
+                cur.z = swm ? clamp_codes_sw(cur.z) : clamp_codes4(cur.z);
+                cur.w = swm ? clamp_codes_sw(cur.w) : clamp_codes4(cur.w);
+                if (m == 3) {
+                    lo = hi;
+                    hi = quad_fetch(ix.text, sector_code((j0 >> 6) + 2u), q);
+                }
+                if (run) {
+                    if (LIST) win_n |= cur.x | cur.y | cur.z | cur.w;
+                    columns16(cur, min(16u, Wn - j0), Pv, Mv, score, best);
+                }
             }
-            cols += min(j0, Wn);
+        }
+        if constexpr (QUAD) {  // the candidate again, rather than three of its words held in registers through the sweep
+            uint32_t g_again = g;
+            asm volatile("" : "+v"(g_again));
+            if (sweep) c = a.cand[g_again];
+        }
+        if (sweep) {
+            if (!QUAD) cols += min(jstop, Wn);
             if (LIST ? ph == 1 : (!BOUND || !counted)) {  // (list mode: a successor is counted where its prefilter runs)
-                verified++;
+                count_verified();
                 wbytes += Wn;
             }
             counted = false;  // a TaxId's next candidate has not been counted by anyone
@@ -1551,19 +1757,19 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                     vg = g;
                     active = false;
                 } else {  // refuted: index.rs:406 fails
-                    refuted++;
+                    count_refuted();
                     a.cand_status[g] = 1;
                     const uint32_t nxt = a.cand_next[g];
                     if (nxt == 0xffffffffu || nxt >= maxc) active = false;
-                    else g = o + nxt;
+                    else g = strand_base(c) + nxt;
                 }
             } else if (LIST && ph == 1) {  // a successor's prefilter (fused mode: every candidate's), decided by the bound
                 if (ed > 2 * ED) {  // refuted (index.rs:406)
-                    if (FUSED) refuted++;
+                    if (FUSED) count_refuted();
                     a.cand_status[g] = 1;
                     const uint32_t nxt = a.cand_next[g];
                     if (nxt == 0xffffffffu || nxt >= maxc) active = false;
-                    else g = o + nxt;
+                    else g = strand_base(c) + nxt;
                 } else if (ed > ED) {  // neither bound decides: the sweep of the next round does (counted here: flagged)
                     if (FUSED) {  // ... of this round: k_sw_pairs runs on und_list after this kernel
                         verdict = 2;
@@ -1572,7 +1778,7 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                     }
                     active = false;
                 } else {  // passes the prefilter; with no N in the read, or none in the window, this number is its edit distance too
-                    extra_passed++;
+                    count_passed();
                     if (!read_n || !(win_n & 0x04040404u)) {
                         const DevBin bin = ix.bins[c.z];
                         a.out[g] = make_uint4(bin.tax_id, bin.gi, c.x >= bin.start ? c.x - bin.start : 0, ed);
@@ -1594,7 +1800,7 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                 const uint32_t nxt = a.cand_next[g];
                 if (nxt == 0xffffffffu || nxt >= maxc) active = false;
                 else {
-                    g = o + nxt;
+                    g = strand_base(c) + nxt;
                     if (LIST) ph = 1;  // passed the prefilter, failed the edit distance (rare): the TaxId's next candidate, here
                 }
             }
@@ -1617,7 +1823,13 @@ __global__ __launch_bounds__(256) void k_edit_myers(DevIndexView ix, EvalArgs a)
                 if (verdict == 2) a.und_list[base + (uint32_t)__popcll(um & lower)] = (FUSED ? g : vg) | kSweepFlag;  // counted, bounds tried
             }
         }
+        if constexpr (QUAD) {
+            verified += (uint32_t)__popcll(__ballot(verified_now));
+            if (BOUND || FUSED) refuted += (uint32_t)__popcll(__ballot(refuted_now));
+            if (LIST) extra_passed += (uint32_t)__popcll(__ballot(passed_now));
+        }
     }
+    if (QUAD && lane) verified = refuted = extra_passed = 0;  // (the wavefront's, in every lane)
     unsigned long long v64 = verified, w64 = wbytes;
     for (int d = 32; d > 0; d >>= 1) {
         v64 += __shfl_down(v64, d);
@@ -1814,7 +2026,7 @@ void launch_sw_diag(hipStream_t s, const DevIndexView& ix, const EvalArgs& a, ui
 }
 
 uint32_t launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a_, uint64_t max_items, uint32_t max_len,
-                           int mode, uint32_t wgs_per_cu, bool listed) {
+                           int mode, uint32_t wgs_per_cu, bool listed, bool legacy_fetch) {
     EvalArgs a = a_;
     a.maxc = rank_bound(a.max_candidates);
     if (!a.planes || a.plane_words != myers_words(max_len)) throw std::runtime_error("internal: k_edit_myers needs the pass's read planes");
@@ -1828,12 +2040,17 @@ uint32_t launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs
     const uint32_t resident = 256 * std::max<uint32_t>(1, std::min<uint32_t>(wgs_per_cu, kMyersWgsPerCuMax));
     uint32_t blocks = std::max<uint32_t>(16, std::min<uint32_t>(cdiv(max_items, listed ? 256 : 4096), resident));
     const uint32_t W = myers_words(max_len);
-#define MYERS_CASE(WW)                                                                                   \
+#define MYERS_FETCH_CASE(WW, Q)                                                                              \
     do {                                                                                                 \
-        if (mode == MY_LIST) hipLaunchKernelGGL((k_edit_myers<WW, MY_LIST>), dim3(blocks), dim3(256), 0, s, ix, a);        \
-        else if (mode == MY_FUSED) hipLaunchKernelGGL((k_edit_myers<WW, MY_FUSED>), dim3(blocks), dim3(256), 0, s, ix, a); \
-        else if (mode == MY_BOUND) hipLaunchKernelGGL((k_edit_myers<WW, MY_BOUND>), dim3(blocks), dim3(256), 0, s, ix, a); \
-        else hipLaunchKernelGGL((k_edit_myers<WW, MY_CHAIN>), dim3(blocks), dim3(256), 0, s, ix, a);                      \
+        if (mode == MY_LIST) hipLaunchKernelGGL((k_edit_myers<WW, MY_LIST, Q>), dim3(blocks), dim3(256), 0, s, ix, a);        \
+        else if (mode == MY_FUSED) hipLaunchKernelGGL((k_edit_myers<WW, MY_FUSED, Q>), dim3(blocks), dim3(256), 0, s, ix, a); \
+        else if (mode == MY_BOUND) hipLaunchKernelGGL((k_edit_myers<WW, MY_BOUND, Q>), dim3(blocks), dim3(256), 0, s, ix, a); \
+        else hipLaunchKernelGGL((k_edit_myers<WW, MY_CHAIN, Q>), dim3(blocks), dim3(256), 0, s, ix, a);                      \
+    } while (0)
+#define MYERS_CASE(WW)                              \
+    do {                                            \
+        if (legacy_fetch) MYERS_FETCH_CASE(WW, false); \
+        else MYERS_FETCH_CASE(WW, true);            \
     } while (0)
     if (W == 2) MYERS_CASE(2);
     else if (W == 3) MYERS_CASE(3);
@@ -1843,6 +2060,7 @@ uint32_t launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs
     else if (W == 7) MYERS_CASE(7);
     else MYERS_CASE(8);
 #undef MYERS_CASE
+#undef MYERS_FETCH_CASE
     return blocks;
 }
 

@@ -215,11 +215,12 @@ void launch_max_window(hipStream_t s, uint32_t n_strands, const uint32_t* strand
 // distance's matches otherwise), and leaves the rest on a.und_list like mode 2; a.pass_list is not written
 // wgs_per_cu: the grid is capped at 256 * wgs_per_cu persistent workgroups of 30 KiB of LDS each (1..5; five fill a CU's
 // LDS, fewer leave room for other streams' kernels beside them).  listed: max_items counts the entries of the work list
-// itself (known on the host), not the pass's seed hits: a lane per entry
+// itself (known on the host), not the pass's seed hits: a lane per entry.  legacy_fetch: every lane fetches its own window, two
+// 16-byte pieces per 16 columns (fetch_cols), instead of the quads fetching whole sectors
 constexpr uint32_t kMyersWgsPerCuMax = 5;
 // returns the grid it launched, in workgroups
 uint32_t launch_edit_myers(hipStream_t s, const DevIndexView& ix, const EvalArgs& a, uint64_t max_items, uint32_t max_len,
-                           int mode = 0, uint32_t wgs_per_cu = kMyersWgsPerCuMax, bool listed = false);
+                           int mode = 0, uint32_t wgs_per_cu = kMyersWgsPerCuMax, bool listed = false, bool legacy_fetch = false);
 // reference order for reads <= 253 bases: SW prefilter alone, two candidates per 16-lane group
 // diag = false: without the lower bounds on the seed diagonal (every candidate that is not hopeless is swept)
 // top = true: the sweep on the top half of the read rows (k_sw_pairs<R/2, false, TOP>): refutes or passes what those rows

@@ -21,7 +21,7 @@ def norm(name):
     return re.sub(r"\(.*", "", name)
 
 
-FUSED = re.compile(r"k_edit_myers<\d+, 3>")
+FUSED = re.compile(r"k_edit_myers<\d+, 3[,>]")
 
 
 def main():
