@@ -853,6 +853,55 @@ int mtsv_coverage_add_fold(mtsv_coverage *c, mtsv_fold *f, const uint32_t *read_
 int mtsv_coverage_rows(mtsv_coverage *c, mtsv_ref_coverage **rows, uint64_t *n_rows, float *device_ms);
 int mtsv_format_coverage_report(const mtsv_ref_coverage *rows, uint64_t n_rows, char **out, uint64_t *out_len);
 
+/* ---- alignments: where a hit lies in its reference, on which strand, and its edit script (place.hip, k_place.hip) -----------
+ * A hit says which reference a read aligned to and with how many edits; its `offset` is the start of the accepted WINDOW.  A
+ * PLACEMENT adds the alignment itself.  For one hit (read, strand, tax_id, gi, offset, edit):
+ *   P is the read's codes on that strand -- forward, or reverse complement with N staying N -- and L their number; b is the bin
+ *   of (tax_id, gi); T = text[b.start + offset, b.end).  Row i matches column j iff P[i-1] == T[j-1] and the code is a base: an
+ *   N on either side never matches (align.rs after N -> '.').  D is the semi-global matrix of align.rs:28-85: D[0][j] = 0,
+ *   D[i][0] = i, unit costs.
+ *   end    the smallest j >= 0 with D[L][j] <= edit.  For a hit the binner produced that is the leftmost minimum of the
+ *          window's last row; it lies inside the accepted window and does not depend on the window's end.
+ *   path   from (L, end) while i > 0: the diagonal when j > 0 and D[i-1][j-1] + (match ? 0 : 1) == D[i][j] (op '=' or 'X');
+ *          else the step up when D[i-1][j] + 1 == D[i][j] (op 'I': a read base and no reference base); else the step left
+ *          (op 'D').  At i == 0, start = j.
+ *   ref_start = offset + start, ref_end = offset + end: forward-strand offsets inside the GI, half open.  The ops are run-length
+ *   encoded in reference order as len << 4 | op with BAM's codes I = 1, D = 2, '=' = 7, X = 8; at most 2 * edit + 1 runs.
+ *   A hit is UNPLACEABLE when no column of T reaches its edit: only a hit a caller made up.
+ * mtsv_batch_place_hits: hits == NULL places the hits of the workspace's last run where they lie in HBM -- every stretch, in the
+ *   order mtsv_batch_download returns them, in any assignment mode, MTSV_ASSIGN_ONLY included; otherwise `hits` are n_hits
+ *   caller-given hits, uploaded and placed against the resident batch.  It needs a resident batch (mtsv_batch_upload,
+ *   _take_reads, _take_unique, _copy_reads: after the last two `read` is the caller's number, found in the read map) and, for
+ *   hits == NULL, a completed mtsv_batch_run or mtsv_batch_merge_runs on it.  Placement k describes hit k; its ops are
+ *   (*ops)[ops_off .. ops_off + n_ops).  The ops array is sized before the kernel runs, 2 * min(edit, L) + 1 slots per hit, and
+ *   may hold unused slots between hits, which are zero: *n_ops_total is its length.  Both arrays: mtsv_free.  device_ms (may be NULL): the
+ *   device time of the map pass and scan, the placement kernel and the copies to the host.  Zero hits: two empty arrays,
+ *   nothing is launched.  A workspace that never calls this allocates and launches nothing for it.
+ *   Nothing of the run is changed: hits, assignments, statistics, flags and report are what they were.
+ *   MTSV_PLACE_RING (tests; read by the workspace's first call): columns of the ring the kernel keeps per hit, a power of two,
+ *   forced up to what the call needs.  MTSV_PLACE_TIMING=1: one line per call on stderr with the steps' times.
+ * Refusals, each leaving the workspace as it was; mtsv_last_error gives the counts and the first offender.  MTSV_E_ARG: null
+ *   arguments; no resident batch, or a host batch; hits == NULL without such a run; an index that holds one (tax_id, gi) in two
+ *   bins (checked on the host); a hit whose (tax_id, gi) the index does not hold, whose offset is at or beyond its bin's
+ *   length, whose read is not resident, whose strand is above 1 (all counted on the device before anything is placed), or that
+ *   is unplaceable (counted by the placement kernel, before anything is handed out).  MTSV_E_LIMIT: a resident read above 256
+ *   bases; 2^32 hits or op slots or more.
+ * mtsv_format_placements (host only, needs no device): one line per placement, in the order given,
+ *     READ_ID \t TAXID \t GI \t +|- \t START \t END \t EDIT \t CIGAR \n
+ *   CIGAR as text, e.g. 37=1X112=, `*` for a placement without ops (a read of no bases).  ids = NUL-separated read ids,
+ *   id_off[n_reads + 1].  MTSV_E_ARG: a read >= n_reads. */
+typedef struct {
+    uint64_t read;
+    uint32_t tax_id, gi, edit;
+    uint8_t strand, _pad[3];
+    uint32_t ref_start, ref_end, n_ops;
+    uint64_t ops_off; /* (8-byte aligned: four bytes of padding lie before it) */
+} mtsv_placement; /* 48 bytes */
+int mtsv_batch_place_hits(mtsv_batch *b, const mtsv_hit *hits, uint64_t n_hits, mtsv_placement **out, uint64_t *n_out,
+                          uint32_t **ops, uint64_t *n_ops_total, float *device_ms);
+int mtsv_format_placements(const mtsv_placement *pl, uint64_t n, const uint32_t *ops, const char *ids, const uint64_t *id_off,
+                           uint64_t n_reads, char **out, uint64_t *out_len);
+
 /* ---- result lines (host) ---------------------------------------------------------------- */
 /* write_assignments for a whole batch: hits ordered by read; ids = NUL-separated read ids,
  * id_off[n_reads+1].  Lines are appended to a malloc'd buffer (*out, *out_len), one per read with

@@ -96,6 +96,12 @@ PAIR_BOTH, PAIR_EITHER, PAIR_PROPER = 0, 1, 2  # MTSV_PAIR_*
 REF_COVERAGE_DTYPE = np.dtype({"names": ["tax_id", "gi", "length", "reads", "alignments", "aligned_bases", "covered_bases"],
                                "formats": ["<u4", "<u4", "<u8", "<u8", "<u8", "<u8", "<u8"], "offsets": [0, 4, 8, 16, 24, 32, 40], "itemsize": 48})
 
+# mtsv_placement: 8 + 3 * 4 + 1 + 3 pad + 3 * 4 + 4 pad + 8 = 48 bytes
+PLACEMENT_DTYPE = np.dtype({"names": ["read", "tax_id", "gi", "edit", "strand", "ref_start", "ref_end", "n_ops", "ops_off"],
+                            "formats": ["<u8", "<u4", "<u4", "<u4", "u1", "<u4", "<u4", "<u4", "<u8"],
+                            "offsets": [0, 8, 12, 16, 20, 24, 28, 32, 40], "itemsize": 48})
+CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # BAM's op codes: an op is len << 4 | code
+
 
 class TaxonomyInfo(C.Structure):  # mtsv_taxonomy_info_t
     _fields_ = [("n_nodes", C.c_uint64), ("n_implied_roots", C.c_uint64), ("n_ranks", C.c_uint32), ("max_depth", C.c_uint32)]
@@ -136,6 +142,7 @@ EXPORTS = [
     "mtsv_fold_pair",
     "mtsv_coverage_create", "mtsv_coverage_free", "mtsv_coverage_add_index", "mtsv_coverage_add_refs", "mtsv_coverage_reset",
     "mtsv_coverage_add_fold", "mtsv_coverage_rows", "mtsv_format_coverage_report",
+    "mtsv_batch_place_hits", "mtsv_format_placements",
 ]
 
 _lib = None
@@ -253,6 +260,8 @@ def lib():
         L.mtsv_coverage_add_fold.argtypes = [vp, vp, vp, u64, u32, C.POINTER(C.c_float)]
         L.mtsv_coverage_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_format_coverage_report.argtypes = [vp, u64, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_batch_place_hits.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_format_placements.argtypes = [vp, u64, vp, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -592,6 +601,27 @@ class Batch:
         ms = C.c_float()
         _check(lib().mtsv_batch_copy_reads(self.h, src.h, C.byref(ms)))
         return ms.value
+
+    def place_hits(self, hits=None):
+        """mtsv_batch_place_hits: the alignments of the last run's hits, where they lie on the device (hits None), or of the
+        given HIT_DTYPE hits against the resident batch.  Returns (placements as a PLACEMENT_DTYPE array, one per hit in the
+        hits' order; the ops as a uint32 array, len << 4 | code, placement k owning ops[ops_off : ops_off + n_ops]; device ms)"""
+        out, n, ops, n_ops, ms = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_float()
+        if hits is None:
+            ptr, cnt = None, 0
+        else:
+            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+            ptr, cnt = hits.ctypes.data, len(hits)
+        _check(lib().mtsv_batch_place_hits(self.h, ptr, cnt, C.byref(out), C.byref(n), C.byref(ops), C.byref(n_ops), C.byref(ms)))
+        try:
+            pl = np.frombuffer((C.c_ubyte * (n.value * PLACEMENT_DTYPE.itemsize)).from_address(out.value), dtype=PLACEMENT_DTYPE).copy() \
+                if n.value else np.zeros(0, dtype=PLACEMENT_DTYPE)
+            op = np.frombuffer((C.c_ubyte * (n_ops.value * 4)).from_address(ops.value), dtype="<u4").copy() \
+                if n_ops.value else np.zeros(0, dtype="<u4")
+            return pl, op, ms.value
+        finally:
+            lib().mtsv_free(out)
+            lib().mtsv_free(ops)
 
     def merge_runs(self, srcs):
         """mtsv_batch_merge_runs: the last runs of srcs (the same reads in each) merged per read into this workspace, in
@@ -976,6 +1006,21 @@ def format_assignments(a, read_ids):
     np.cumsum([len(i.encode()) + 1 for i in read_ids], out=off[1:])
     out, n = C.c_void_p(), C.c_uint64()
     _check(lib().mtsv_format_assignments(a.ctypes.data, len(a), blob, off.ctypes.data, len(read_ids), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value).decode()
+    finally:
+        lib().mtsv_free(out)
+
+
+def format_placements(placements, ops, read_ids):
+    """mtsv_format_placements: one line READ_ID TAXID GI +|- START END EDIT CIGAR (tab-separated) per placement, as one str"""
+    pl = np.ascontiguousarray(placements, dtype=PLACEMENT_DTYPE)
+    ops = np.ascontiguousarray(ops, dtype="<u4")
+    blob = b"".join(i.encode() + b"\0" for i in read_ids)
+    off = np.zeros(len(read_ids) + 1, dtype=np.uint64)
+    np.cumsum([len(i.encode()) + 1 for i in read_ids], out=off[1:])
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_placements(pl.ctypes.data, len(pl), ops.ctypes.data, blob, off.ctypes.data, len(read_ids), C.byref(out), C.byref(n)))
     try:
         return C.string_at(out.value, n.value).decode()
     finally:

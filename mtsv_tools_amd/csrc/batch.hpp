@@ -308,6 +308,10 @@ struct Batch {
     // formatter is created by the first call.  (owner only)
     std::shared_ptr<struct TextFormatter> text;
     void format_text(const char* ids, const uint64_t* id_off, uint64_t n_reads, char** text_out, uint64_t* len, float* device_ms);
+    // the alignments of hits against the resident batch (place.hip: mtsv_batch_place_hits) -- of the last run's hits where they
+    // lie in HBM (hits null), or of n_hits given ones; the placer is created by the first call.  (owner only)
+    std::shared_ptr<struct Placer> placer;
+    void place_hits(const mtsv_hit* hits, uint64_t n_hits, mtsv_placement** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops_total, float* device_ms);
     void merge_runs(Batch* const* srcs, int n_srcs, float* device_ms);
     void read_map(std::vector<uint64_t>& map);
     void download_reads(std::vector<uint8_t>& codes, std::vector<uint64_t>& read_off);

@@ -105,7 +105,13 @@ void print_help() {
            "covered_bases, breadth_pct, one line per reference with an alignment and one per TaxID (gi *) over all its\n"
            "references.  An alignment counts when its edit distance is within --coverage-slack (default 0) of its read's\n"
            "smallest; all: every alignment.  It spans the read's length from the start of its accepted window, which lies up\n"
-           "to the edit tolerance before the match.  With --dedup every copy of a read counts)\n");
+           "to the edit tolerance before the match.  With --dedup every copy of a read counts),\n"
+           "--alignments FILE (only with --fold-on-gpu, not with --dedup: after every chunk's run over a batch of reads the hits\n"
+           "it accepted are aligned on the GPU, and one line per hit is appended to FILE,\n"
+           "READ_ID<TAB>TAXID<TAB>GI<TAB>+|-<TAB>START<TAB>END<TAB>EDIT<TAB>CIGAR: the strand, the half-open interval of the\n"
+           "match inside the GI on the forward strand, and the edit script with = X I D, in reference order.  Lines come chunk\n"
+           "by chunk, batch by batch; each stands for itself, so the file may be sorted.  Reads of up to 256 bases.  Every other\n"
+           "output is what it is without the flag)\n");
 }
 
 // a number in 0 .. 2^32 - 1, or the usage error of `flag`
@@ -213,6 +219,11 @@ void check_combinations(const Args& a) {
         const bool proper = a.interleaved && (a.pair_mode.empty() || a.pair_mode == "proper");
         if (a.output_format != "long" && !proper)
             usage_error("The argument '--coverage <TSV>' needs records with GI and offset: give '--output-format long', or '--interleaved --pair-mode proper'");
+    }
+    if (!a.alignments.empty()) {
+        if (!a.fold_gpu) refuse("'--alignments <FILE>' requires '--fold-on-gpu': the hits are aligned where a chunk's run leaves them, on the device");
+        if (a.dedup) refuse("'--alignments <FILE>' cannot be used with '--dedup': only the representatives of identical reads are binned");
+        if (a.alignments == a.results) refuse("'--alignments <FILE>' and '-m/--results <RESULTS>' name the same file");
     }
     if (a.merge_gpu) require_chunks_on_one_device(a, "--merge-on-gpu", "every chunk is made resident on that device");
     if (a.fold_gpu) {
@@ -359,6 +370,7 @@ Args parse_args(int argc, char** argv) {
         else if (key == "--unpaired-penalty") a.unpaired_penalty = val();
         else if (key == "--coverage") a.coverage = val();
         else if (key == "--coverage-slack") a.coverage_slack = val();
+        else if (key == "--alignments") a.alignments = val();
         else if (key == "--fold-reads") a.fold_reads = parse_reads(val(), "--fold-reads", 0xffffffffull);
         else if (key == "-h" || key == "--help") {
             print_help();
@@ -404,6 +416,7 @@ Run resolve(const Args& a) {
             usage_error("Invalid value for '--unpaired-penalty <N>': a number below 2147483648 is expected");
     }
     run.coverage = a.coverage;
+    run.alignments = a.alignments;
     if (!a.coverage_slack.empty()) run.coverage_slack = a.coverage_slack == "all" ? 0xffffffffu : parse_u32_flag(a.coverage_slack, "--coverage-slack");
     resolve_params(a, run);
     if (run.interleaved && (run.read_offset & 1)) refuse("'--interleaved' needs an even '--read-offset': the reads are skipped pair by pair");

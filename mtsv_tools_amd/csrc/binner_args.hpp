@@ -16,6 +16,7 @@ struct Args {
     bool interleaved = false;                             // --interleaved: the input's records alternate mate 1 and mate 2
     std::string pair_mode, max_insert, unpaired_penalty;  // --pair-mode, --max-insert, --unpaired-penalty: "" when not given
     std::string coverage, coverage_slack;                 // --coverage, --coverage-slack: "" when not given
+    std::string alignments;                               // --alignments: "" when not given
     uint64_t fold_reads = 16ull << 20;  // --fold-reads: reads per super-batch of --fold-on-gpu (every chunk is loaded once per super-batch)
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
@@ -51,11 +52,13 @@ struct Run {
     uint32_t unpaired_penalty = 0;         // --unpaired-penalty (--pair-mode either)
     std::string coverage;                  // --coverage: "" : not asked for
     uint32_t coverage_slack = 0;           // --coverage-slack: 0xffffffff for `all`
+    std::string alignments;                // --alignments: "" : not asked for
     uint64_t batch_reads = 0, fold_reads = 0;
 
     bool have_results() const { return !results.empty(); }
     bool have_report() const { return !report.empty(); }
     bool have_coverage() const { return !coverage.empty(); }
+    bool have_alignments() const { return !alignments.empty(); }
     bool merged() const { return mode == Mode::merged; }
     bool folded() const { return mode == Mode::folded; }
     bool chunked() const { return index_paths.size() > 1; }

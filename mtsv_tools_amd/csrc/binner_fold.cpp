@@ -24,6 +24,10 @@
 // super-batch on that brings nothing new, which the library accepts); after the last chunk, and after the expansion of --dedup
 // but before the pair join, a piece's fold of READS is added, the reads' lengths taken from the block's offsets.  The rows are
 // asked for and written once, by finish().
+// --alignments: after every run of a chunk over a piece, the hits the run left on the device are placed
+// (mtsv_batch_place_hits with no hits given) and their lines, under the piece's read IDs, appended to the file: chunk by
+// chunk, piece by piece.  Nothing else reads the placements, so every other output is what it is without the flag.
+#include <fcntl.h>
 #include <unistd.h>
 
 #include <cstdio>
@@ -89,6 +93,7 @@ class FoldedRun {
     bool write_results(const std::string& ids, const std::vector<uint64_t>& id_off, mtsv_fold* f);
     bool pair_piece(size_t k, const ReadBlock& rb, mtsv_fold* f);
     bool cover_piece(const ReadBlock& rb, mtsv_fold* f);
+    bool align_piece(const ReadBlock& rb, mtsv_batch* ws);
     bool input_error(const std::string& what);
     bool write_sides(const ReadBlock& rb, mtsv_fold* f);
     void print_timing() const;
@@ -115,6 +120,9 @@ class FoldedRun {
     CoveragePtr coverage_;               // --coverage
     std::vector<uint32_t> read_len_;
     float coverage_device_ms_ = 0;
+    int align_fd_ = -1;                  // --alignments
+    uint64_t alignments_ = 0;
+    float place_device_ms_ = 0;
     TaxaSum taxa_;
     uint64_t dedup_reads_ = 0, dedup_distinct_ = 0;
     uint64_t super_reads_ = 0, n_super_ = 0, reads_done_ = 0, reads_matched_ = 0;
@@ -196,6 +204,7 @@ bool FoldedRun::run_chunk(size_t c, bool more) {
         }
         if (rc == MTSV_OK) rc = mtsv_batch_run(ws.get(), &run_.params);
         t_run_ += now_s() - t0;
+        if (rc == MTSV_OK && align_fd_ >= 0 && !align_piece(rb, ws.get())) return false;
         t0 = now_s();
         float ms = 0;
         if (rc == MTSV_OK) rc = mtsv_fold_add_run((run_.dedup ? rep_folds_[k] : folds_[k]).get(), ws.get(), &ms);
@@ -246,6 +255,26 @@ bool FoldedRun::pair_piece(size_t k, const ReadBlock& rb, mtsv_fold* f) {
     pair_stats_.joined += st.joined;
     pair_stats_.records += st.records;
     pairs_done_ += st.pairs;
+    return true;
+}
+
+// --alignments: the hits of the run that has just ended on ws, placed and written under the piece's read IDs
+bool FoldedRun::align_piece(const ReadBlock& rb, mtsv_batch* ws) {
+    ArrayPtr<mtsv_placement> pl;
+    ArrayPtr<uint32_t> ops;
+    ArrayPtr<char> text;
+    uint64_t n = 0, n_ops = 0, len = 0;
+    float ms = 0;
+    int rc = mtsv_batch_place_hits(ws, nullptr, 0, out(pl), &n, out(ops), &n_ops, &ms);
+    if (rc == MTSV_OK) rc = mtsv_format_placements(pl.get(), n, ops.get(), rb.ids.data(), rb.id_off.data(), rb.n(), out(text), &len);
+    if (rc != MTSV_OK) return code_.lib_error();
+    place_device_ms_ += ms;
+    alignments_ += n;
+    if (!write_all(align_fd_, text.get(), len)) {
+        logmsg("ERROR", "Error writing to alignments file");
+        code_.set(11);
+        return false;
+    }
     return true;
 }
 
@@ -411,6 +440,7 @@ void FoldedRun::print_timing() const {
     if (run_.dedup) fprintf(stderr, "[cli dedup timing] take_unique device %.3f ms, expand device %.3f ms\n", dedup_device_ms_, expand_device_ms_);
     if (run_.interleaved) fprintf(stderr, "[cli pair timing] pair device %.3f ms\n", pair_device_ms_);
     if (run_.have_coverage()) fprintf(stderr, "[cli coverage timing] coverage device %.3f ms\n", coverage_device_ms_);
+    if (run_.have_alignments()) fprintf(stderr, "[cli alignments timing] alignments %llu, place device %.3f ms\n", (unsigned long long)alignments_, place_device_ms_);
 }
 
 // every way out of the folded run ends alike: the process leaves at once, or (MTSV_CLI_CLEAN_EXIT=1) frees what it holds --
@@ -433,6 +463,13 @@ int FoldedRun::run() {
         code_.lib_error();
         return leave(code_.get());
     }
+    if (run_.have_alignments()) {
+        align_fd_ = ::open(run_.alignments.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (align_fd_ < 0) {
+            logmsg("ERROR", "Error running query: cannot open alignments file " + run_.alignments);
+            return leave(2);
+        }
+    }
     const bool parsed = producer_.produce(std::min<uint64_t>(run_.batch_reads, fold_reads_), [&](std::unique_ptr<ReadBlock> rb) {
         return run_.interleaved ? take_pairs(std::move(rb)) : take_block(std::move(rb));
     });
@@ -445,6 +482,10 @@ int FoldedRun::run() {
                     carry_->ids.c_str() + "') has no mate");
     if (!code_.failed()) flush(false);
     if (code_.failed()) return leave(code_.get());
+    if (align_fd_ >= 0 && ::close(align_fd_) != 0) {
+        logmsg("ERROR", "Error writing to alignments file");
+        return leave(11);
+    }
     RunEnd end;
     end.t_begin = t_begin;
     end.reads = reads_done_;

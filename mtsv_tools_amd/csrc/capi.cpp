@@ -422,6 +422,12 @@ int mtsv_batch_copy_reads(mtsv_batch* dst, mtsv_batch* src, float* device_ms) {
     GUARD(dst->impl.copy_reads(src->impl, device_ms))
 }
 
+int mtsv_batch_place_hits(mtsv_batch* b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placement** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops_total,
+                          float* device_ms) {
+    if (!b || !out || !n_out || !ops || !n_ops_total) return fail_arg("null argument");
+    GUARD(b->impl.place_hits(hits, n_hits, out, n_out, ops, n_ops_total, device_ms))
+}
+
 int mtsv_batch_merge_runs(mtsv_batch* dst, mtsv_batch* const* srcs, int n_srcs, float* device_ms) {
     if (!dst || (n_srcs > 0 && !srcs)) return fail_arg("null argument");
     GUARD({
@@ -1165,6 +1171,52 @@ int mtsv_format_assignments(const mtsv_assignment* a, uint64_t n, const char* id
             }
             buf.p[buf.n++] = '\n';
             i = j;
+        }
+        buf.room(1);
+        buf.p[buf.n] = 0;
+        *out = buf.p;
+        *out_len = buf.n;
+        buf.p = nullptr;  // the caller's now (mtsv_free)
+    })
+}
+
+// one line per placement: READ_ID TAXID GI +|- START END EDIT CIGAR, tab-separated
+int mtsv_format_placements(const mtsv_placement* pl, uint64_t n, const uint32_t* ops, const char* ids, const uint64_t* id_off, uint64_t n_reads, char** out,
+                           uint64_t* out_len) {
+    if ((!pl && n) || !ids || !id_off || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        Text buf;
+        static const char kOp[] = "MIDNSHP=X";  // BAM's op codes
+        for (uint64_t i = 0; i < n; i++) {
+            const mtsv_placement& q = pl[i];
+            if (q.read >= n_reads)
+                throw std::runtime_error("arg: placement " + std::to_string(i) + " refers to read " + std::to_string(q.read) + ", outside the batch of " +
+                                         std::to_string(n_reads));
+            if (q.n_ops && !ops) throw std::runtime_error("arg: null argument");
+            const uint64_t id_len = strnlen(ids + id_off[q.read], id_off[q.read + 1] - id_off[q.read]);
+            buf.room(id_len + 5 * 11 + 4 + (uint64_t)q.n_ops * 11 + 2);  // five numbers and the strand, tabs; "len op" is at most 10 + 1 characters
+            memcpy(buf.p + buf.n, ids + id_off[q.read], id_len);
+            buf.n += id_len;
+            buf.p[buf.n++] = '\t';
+            buf.put(q.tax_id);
+            buf.p[buf.n++] = '\t';
+            buf.put(q.gi);
+            buf.p[buf.n++] = '\t';
+            buf.p[buf.n++] = q.strand ? '-' : '+';
+            buf.p[buf.n++] = '\t';
+            buf.put(q.ref_start);
+            buf.p[buf.n++] = '\t';
+            buf.put(q.ref_end);
+            buf.p[buf.n++] = '\t';
+            buf.put(q.edit);
+            buf.p[buf.n++] = '\t';
+            if (!q.n_ops) buf.p[buf.n++] = '*';
+            for (uint32_t k = 0; k < q.n_ops; k++) {
+                const uint32_t op = ops[q.ops_off + k];
+                buf.put(op >> 4);
+                buf.p[buf.n++] = (op & 15u) < 9 ? kOp[op & 15u] : '?';
+            }
+            buf.p[buf.n++] = '\n';
         }
         buf.room(1);
         buf.p[buf.n] = 0;

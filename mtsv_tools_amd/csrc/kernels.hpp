@@ -522,5 +522,32 @@ void launch_cover_wave(hipStream_t s, const void* rec, uint32_t n, const uint32_
 void launch_cover_reads(hipStream_t s, const uint64_t* n_runs, uint32_t n, const uint32_t* run_hit, const uint32_t* run_ref, uint32_t n_refs,
                         uint64_t* cnt);
 void launch_cover_pop(hipStream_t s, const uint64_t* bitmap, uint32_t n_words, const uint32_t* word_off, uint32_t n_refs, uint32_t tile, uint64_t* cov);
+// k_place.hip: per hit of a list (n of them, any order) the alignment's interval in its reference and its edit script, as the
+// head of k_place.hip defines them.  The table: n_keys keys = tax_id << 32 | gi, strictly ascending, bin_of_key[k] the bin of
+// key k among `bins`.  The reads: codes and read_off[n_reads + 1] of the resident batch; read_map (null: the identity): resident
+// read -> the number its hits carry, ascending.  ctr: kPlaceCounters u64, set by the caller to 0 except the two *First* minima
+// (all ones).
+//   map:    hit_bin[i], hit_read[i] = the hit's bin and resident read (NONE for a hit that is refused), cnt[i] = the op slots it
+//           may need, 2 min(edit, L) + 1 (0 for a refused one); nothing else is written but ctr: [kPlaceCtrUnknown] += hits whose
+//           (tax_id, gi) the table does not hold, [kPlaceCtrRange] += those whose offset is at or beyond their bin's length,
+//           [kPlaceCtrAbsent] += those whose read is not resident, [kPlaceCtrStrand] += those with a strand above 1,
+//           [kPlaceCtrFirstBad] = the smallest i among all of these, [kPlaceCtrSpan] = the largest L + min(edit, L) of the others
+//   (launch_scan over cnt: off[0 .. n], off[n] = the op slots, which must be below 2^32)
+//   place:  only after a map that left the first four counters at zero.  words = myers_words(longest resident read), 2 .. 8;
+//           `blocks` workgroups of place_threads() lanes stride the hits; ring: ring_cols (a power of two >= [kPlaceCtrSpan] + 2)
+//           x 2 words x blocks x place_threads() u32 of scratch.  out[i] (48 bytes, mtsv_placement) and the hit's runs, in
+//           reference order, at the END of ops[off[i] .. off[i + 1]): out[i].ops_off is where they begin.  A hit no column of
+//           whose text reaches its edit adds to [kPlaceCtrUnplaceable] ([kPlaceCtrFirstUnplaceable]: the smallest such i) and
+//           writes nothing; [kPlaceCtrBroken] += paths that left the ring or their slots (none); [kPlaceCtrColumns] += the columns
+//           the placed hits stored into the ring
+constexpr uint32_t kPlaceCtrUnknown = 0, kPlaceCtrRange = 1, kPlaceCtrAbsent = 2, kPlaceCtrStrand = 3, kPlaceCtrFirstBad = 4, kPlaceCtrSpan = 5,
+                   kPlaceCtrUnplaceable = 6, kPlaceCtrFirstUnplaceable = 7, kPlaceCtrBroken = 8, kPlaceCtrColumns = 9, kPlaceCounters = 10;
+uint32_t place_threads();
+void launch_place_map(hipStream_t s, const DevHit* hits, uint32_t n, const uint64_t* bin_key, const uint32_t* bin_of_key, uint32_t n_keys, const DevBin* bins,
+                      const uint32_t* read_off, uint32_t n_reads, const uint32_t* read_map, uint32_t* hit_bin, uint32_t* hit_read, uint32_t* cnt,
+                      uint64_t* ctr);
+void launch_place(hipStream_t s, uint32_t words, uint32_t blocks, const DevHit* hits, uint32_t n, const uint32_t* hit_bin, const uint32_t* hit_read,
+                  const DevBin* bins, uint32_t n_bins, const uint8_t* text, const uint8_t* codes, const uint32_t* read_off, const uint32_t* off,
+                  uint32_t* ring, uint32_t ring_cols, uint32_t* ops, void* out, uint64_t* ctr);
 
 }  // namespace mtsv
