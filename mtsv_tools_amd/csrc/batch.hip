@@ -1,14 +1,10 @@
 // batch.hip -- device workspace for one batch of reads; batch_pass.hip is the stage-by-stage driver of the hot
-// path.  Replaces the producer -> workers -> joiner queue of vendor/cue/src/lib.rs:45-105 with
-// large HBM-resident batches: reads stay on the device between stages, every stage is one launch
-// over the whole batch, and the only host round-trips are two 8-byte totals per pass.
-#include <atomic>
-#include <chrono>
+// path, batch_host.hip the run of a batch that lies in host memory.  Replaces the producer -> workers -> joiner
+// queue of vendor/cue/src/lib.rs:45-105 with large HBM-resident batches: reads stay on the device between stages,
+// every stage is one launch over the whole batch, and the only host round-trips are two 8-byte totals per pass.
 #include <cmath>
 #include <condition_variable>
-#include <exception>
 #include <mutex>
-#include <thread>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,30 +14,6 @@
 #include "batch.hpp"
 
 namespace mtsv {
-
-namespace {
-// memcpy / first-touch split over a few threads for large host buffers
-template <class F>
-void parallel_ranges(uint64_t n, F f) {
-    static const int max_nt = [] {
-        const char* e = getenv("MTSV_COPY_THREADS");
-        return e ? std::max(1, std::min(16, atoi(e))) : 4;
-    }();
-    const int nt = std::min(max_nt, n >= (32ull << 20) ? 4 : n >= (4ull << 20) ? 2 : 1);
-    if (nt == 1) return f(0, n);
-    std::vector<std::thread> th;
-    const uint64_t chunk = ((n + nt - 1) / nt + 4095) & ~4095ull;
-    for (int k = 0; k < nt; k++) {
-        uint64_t a = std::min(n, chunk * k), b = std::min(n, chunk * (k + 1));
-        if (a < b) th.emplace_back([=] { f(a, b); });
-    }
-    for (auto& t : th) t.join();
-}
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-void parallel_copy(uint8_t* dst, const uint8_t* src, uint64_t n) {
-    parallel_ranges(n, [=](uint64_t a, uint64_t b) { memcpy(dst + a, src + a, b - a); });
-}
-}  // namespace
 
 // true when [p, p + bytes) is page-locked host memory the runtime knows (hipHostMalloc / hipHostRegister)
 bool host_pinned(const void* p, uint64_t bytes) {
@@ -160,14 +132,13 @@ Batch::Batch(mtsv_index* ix_, DeviceIndex* di_, uint64_t max_reads_, uint64_t ma
     for (int k = 1; k < n_lanes; k++) extra.emplace_back(new Batch(ix, di, ws_reads, 0, hit_cap_user, this));
 }
 
-// The lanes first: they borrow the owner's inputs.  The members free themselves after this body, on the device it sets.
+// The lanes first: they borrow the owner's inputs.  The members free themselves after this body, on the device it sets; the
+// two pinned stages return their arrays to the pool then, after the streams that filled them have been waited for here.
 Batch::~Batch() {
     extra.clear();
     (void)hipSetDevice(di->device);
     for (hipStream_t s : {stream.s, copy_stream.s, copy_stream2.s})
         if (s) (void)hipStreamSynchronize(s);
-    if (h_hits_stage) pinned_hits_release(h_hits_stage);
-    if (h_assign_stage) pinned_hits_release(h_assign_stage);
 }
 
 // the arrays indexed by seed hit / candidate; nothing of a pass lives in them before its locate stage
@@ -292,9 +263,9 @@ void Batch::begin_run(const mtsv_params& p, uint64_t read_base) {
     segments.clear();
     total_hits = 0;
     lanes_used = 1;
-    staged_valid = false;
-    assign_staged_valid = false;
-    staged_assign = 0;
+    hits_stage.valid = false;
+    assign_stage.valid = false;
+    assign_stage.staged = 0;
     host_hits_dropped = false;
     last_run = kRunNone;  // until this one completes
     run_t0 = now_s();
@@ -501,10 +472,9 @@ void Batch::set_assignment_grain(int grain) {
     if (grain == assign.grain) return;
     assign.grain = grain;
     // the pinned array a host batch left was sized in the old records
-    if (h_assign_stage) pinned_hits_release(h_assign_stage);
-    h_assign_stage = nullptr;
-    h_assign_cap = staged_assign = last_total_assign = 0;
-    assign_staged_valid = false;
+    assign_stage.drop();
+    assign_stage.rec = assign.rec_bytes();
+    assign_stage.last_total = 0;
 }
 
 void Batch::collapse_begin() {
@@ -606,13 +576,10 @@ void Batch::download_assignments(void** a, uint64_t* n, float* device_ms, bool w
     HIP_CHECK(hipSetDevice(di->device));
     uint64_t total = 0;
     for (auto& sg : segments) total += sg.a_count;
-    last_total_assign = total;
+    assign_stage.last_total = total;
     uint8_t* out = nullptr;
-    if (assign_staged_valid && h_assign_stage && staged_assign == total) {  // run_host already brought them over
-        out = h_assign_stage;
-        h_assign_stage = nullptr;
-        h_assign_cap = 0;
-        assign_staged_valid = false;
+    if (assign_stage.valid && assign_stage.p && assign_stage.staged == total) {  // run_host already brought them over
+        out = (uint8_t*)assign_stage.hand_out();
     } else {
         uint64_t cap = 0;
         out = (uint8_t*)pinned_hits_alloc((total * rec + 31) / 32, &cap);  // (the pool counts in 32-byte hits)
@@ -898,8 +865,8 @@ void Batch::merge_runs(Batch* const* srcs, int n_srcs, float* device_ms) {
     segments.clear();
     total_hits = 0;
     n_hits_total = 0;
-    staged_valid = false;
-    assign_staged_valid = false;
+    hits_stage.valid = false;
+    assign_stage.valid = false;
     host_hits_dropped = false;
     last_run = kRunNone;
     memset(&stats, 0, sizeof stats);
@@ -1064,554 +1031,45 @@ mtsv_hit* pinned_hits_alloc(uint64_t n_hits, uint64_t* cap_hits) {
 }
 bool pinned_hits_release(void* p) { return p && pool().put(p); }
 
-// Host buffers in, hits in pinned host memory out.
-//
-// The PCIe rate of the reads (~50 GB/s = 330 k reads of 150 bases per ms) and the rate of the kernels are about
-// equal, so the copy must run flat out from the first microsecond and the kernels must follow right behind it:
-//   * one FEEDER thread copies the batch, strictly in read order, in chunks of a few MB (growing to 32 MB) on one
-//     copy stream into an ARENA in HBM that holds the whole batch (or 3 GiB segments of it, two arenas taking
-//     turns), an event after every chunk.  Bases in page-locked memory are copied from where they lie, others are
-//     staged through a few page-locked chunk buffers; the u64 offsets are narrowed to arena-relative u32 on the way;
-//   * the LANES -- a host thread and a stream each -- take the reads that HAVE ARRIVED and nobody has taken yet:
-//     a pass is a range of reads of the arena, as large as the ramp allows and the copy has delivered, never
-//     tied to how the copy was cut.  An idle device takes what is there; while other lanes keep it busy a lane
-//     waits for a worthwhile range (the ramp grows with the reads already taken and falls towards the end, so
-//     the lanes finish together);
-//   * a finished range's hits leave for the pinned result array at once, in read order, on a third stream.
-// ---------------------------------------------------------------------------------------------
-void Batch::run_host(const uint8_t* bases, const uint64_t* read_off, uint64_t n, const mtsv_params& p, uint64_t read_base) {
-    const HostPart one{bases, read_off, n};
-    run_host_parts(&one, 1, p, read_base);
+// (a fresh page-locked array costs ~60 us per MB to create and is slow on its first copy: ask for little more than the
+//  last batch needed, so that the array that batch returned to the pool fits again)
+void PinnedStage::begin(uint64_t expected_first) {
+    if (p) return;
+    uint64_t units = 0;
+    p = (uint8_t*)pinned_hits_alloc(((last_total ? last_total + last_total / 64 : expected_first) * rec + 31) / 32, &units);
+    cap = units * 32 / rec;
 }
 
-// The same for a batch that lies in several pieces (mtsv_batch_run_host_parts: a host that parses its input in blocks hands
-// several blocks to one call -- larger passes on the device -- without putting them together first).  The reads are
-// numbered through the parts in order.
-// What run_host sizes by its batch: the copy streams, the device arenas, the page-locked offset table.
-void Batch::host_room(uint64_t n, uint64_t total_bases, bool trace) {
-    if (!copy_stream) {
-        // The copy streams get a priority of their own.  The runtime maps streams onto a few hardware queues (four by
-        // default, GPU_MAX_HW_QUEUES) round robin, per priority; an asynchronous copy holds its queue with a barrier
-        // packet until the copy engine is done, and with it every kernel of any stream that shares the queue -- a lane
-        // that shared one with the reads' transfer did not get a kernel in for 20 ms at a time.
-        int prio_low = 0, prio_high = 0;
-        HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-        copy_stream.create(hipStreamNonBlocking, prio_high);
-        copy_stream2.create(hipStreamNonBlocking, prio_high);
-    }
-    uint64_t arena_bases = kArenaBases, arena_reads = kArenaReads;
-    if (const char* e = getenv("MTSV_ARENA_BASES")) arena_bases = std::max<uint64_t>(1 << 16, strtoull(e, nullptr, 10));  // (tests)
-    const bool one_segment = total_bases <= arena_bases && n <= arena_reads;
-    {
-        const uint64_t want_b = one_segment ? total_bases : arena_bases, want_r = one_segment ? n : std::min(n, arena_reads);
-        for (int k = 0; k < (one_segment ? 1 : 2); k++) {
-            Arena& ar = arena[k];
-            if (ar.cap_bases < want_b || ar.cap_reads < want_r) {
-                if (trace) fprintf(stderr, "[run_host] arena %d: %.1f MB of bases, %llu reads\n", k, want_b / 1e6, (unsigned long long)want_r);
-                const uint64_t cb = want_b + want_b / 16, cr = want_r + want_r / 16;  // a little room: the next batch is rarely the same size
-                ar.resize(k, std::min(cb, arena_bases), std::min(cr, arena_reads));
-            }
-        }
-    }
-    // the whole batch's narrowed offsets, every segment with a closing entry of its own (a segment is closed when the next
-    // read does not fit: it is more than half full); run_slice looks at read lengths on the host when a range holds long reads
-    const uint64_t off_need = n + 2 + (one_segment ? 0 : 2 * (total_bases / arena_bases + n / arena_reads) + 8);
-    if (h_off_all.cap < off_need) h_off_all.renew(off_need + n / 16);
+// grown geometrically through the pool (mu of the host run held)
+void PinnedStage::reserve(uint64_t need, hipStream_t stream) {
+    if (need <= cap) return;
+    if (getenv("MTSV_TRACE")) fprintf(stderr, "[run_host] %s array grows %llu -> %llu %s\n", name, (unsigned long long)cap, (unsigned long long)need, unit);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    uint64_t units = 0;
+    auto* q = (uint8_t*)pinned_hits_alloc((std::max<uint64_t>(2 * cap, need) * rec + 31) / 32, &units);
+    if (staged) memcpy(q, p, staged * rec);
+    pinned_hits_release(p);
+    p = q;
+    cap = units * 32 / rec;
 }
 
-void Batch::Arena::resize(int k, uint64_t bases, uint64_t reads) {
-    cap_bases = cap_reads = 0;
-    release_all(d_bases, d_packed, d_off);
-    const std::string name = "arena " + std::to_string(k);
-    d_bases.alloc(bases + 64, (name + ": bases").c_str());  // k_search reads up to 36 bytes past a seed start
-    d_packed.alloc(bases / 2 + 64, (name + ": packed bases").c_str());
-    d_off.alloc(reads + 1, (name + ": offsets").c_str());
-    cap_bases = bases;
-    cap_reads = reads;
+void* PinnedStage::hand_out() {
+    void* out = p;
+    p = nullptr;
+    cap = 0;
+    valid = false;
+    return out;
 }
 
-void Batch::reserve_host(uint64_t n, uint64_t n_bases) {
-    HIP_CHECK(hipSetDevice(di->device));
-    host_room(n, n_bases, getenv("MTSV_TRACE") != nullptr);
-    if (!keep_on_device) {  // a result array of the size the first call will ask for, parked in the pool
-        uint64_t cap = 0;
-        mtsv_hit* h = pinned_hits_alloc(n + n / 8, &cap);
-        pinned_hits_release(h);
-    }
-}
-
-void Batch::run_host_parts(const HostPart* parts, int n_parts, const mtsv_params& p, uint64_t read_base) {
-    const double t_entry = now_s();
-    HIP_CHECK(hipSetDevice(di->device));
-    std::vector<Batch*> ls{this};
-    for (auto& l : extra) ls.push_back(l.get());
-    const bool trace = getenv("MTSV_TRACE") != nullptr;
-    // the parts as one batch: reads numbered through them, a virtual byte offset that ascends through them
-    struct PartView {
-        const uint8_t* bases;
-        const uint64_t* off;
-        uint64_t n, first, virt;
-        bool pinned;
-    };
-    std::vector<PartView> pv;
-    uint64_t n = 0, total_bases = 0;
-    for (int k = 0; k < n_parts; k++) {
-        const HostPart& hp = parts[k];
-        if (!hp.n) continue;
-        if (!hp.read_off || hp.read_off[hp.n] < hp.read_off[0]) throw std::runtime_error("arg: read_off is not ascending");
-        const uint64_t nb = hp.read_off[hp.n] - hp.read_off[0];
-        if (nb && !hp.bases) throw std::runtime_error("arg: null bases");
-        // bases in page-locked memory (mtsv_host_alloc / mtsv_host_register) go to the GPU from where they lie
-        const bool pin = nb && host_pinned(hp.bases + hp.read_off[0], nb) && !getenv("MTSV_STAGE_ALWAYS");
-        pv.push_back(PartView{hp.bases, hp.read_off, hp.n, n, total_bases, pin});
-        n += hp.n;
-        total_bases += nb;
-    }
-    const uint64_t first_base = 0;
-    auto part_of = [&](uint64_t r) {  // the part read r lies in (r == n: the last part)
-        size_t k = pv.size() - 1;
-        while (k > 0 && pv[k].first > r) k--;
-        return k;
-    };
-    auto RO = [&](uint64_t r) {  // virtual offset of read r's first base (r == n: the end of the batch)
-        if (pv.empty()) return (uint64_t)0;
-        const PartView& v = pv[part_of(r)];
-        return v.virt + (v.off[r - v.first] - v.off[0]);
-    };
-    bool any_staged = false, any_direct = false;
-    for (auto& v : pv) (v.pinned ? any_direct : any_staged) = true;
-    const bool direct = !any_staged;
-    if (trace) fprintf(stderr, "[run_host] input %s%s\n", direct ? "page-locked: copied from the caller's buffer" : "pageable: staged",
-                       any_staged && any_direct ? " (some parts page-locked)" : "");
-
-    // ---- arenas: segments of at most kArenaBases bases / kArenaReads reads (u32 offsets inside a segment) ----
-    host_room(n, total_bases, trace);
-    constexpr uint64_t kChunkMax = 32ull << 20, kChunkMin = 4ull << 20;
-    // The bases cross PCIe as 4-bit codes, packed on the host chunk by chunk into page-locked staging buffers while the
-    // chunk before is on its way -- when the process has the CPUs for it (host_pack.hpp).  Otherwise, and with
-    // MTSV_H2D_PLAIN=1: the bytes as they are (from page-locked memory in place) and k_normalise on the device.
-    // (one host batch at a time has the packer: a second one that runs beside it in this process -- another device of
-    //  mtsv_bin_batch_multi, another worker -- would wait for the pool chunk by chunk, and sends its bytes plain)
-    static std::atomic<int> host_runs{0};
-    struct HostRun {
-        std::atomic<int>& c;
-        const int mine;
-        explicit HostRun(std::atomic<int>& c_) : c(c_), mine(++c_) {}
-        ~HostRun() { c--; }
-    } host_run{host_runs};
-    const bool packed = !getenv("MTSV_H2D_PLAIN") && pack_threads() >= kPackWorthwhile && host_run.mine == 1;
-    if ((packed || !direct) && !h_stage[kStage - 1].p)
-        for (auto& hs : h_stage)
-            if (!hs.p) hs.renew(kChunkMax + 64);
-
-    struct Chunk {
-        uint64_t begin = 0, end = 0;  // reads
-        uint32_t max_len = 0, seg = 0;
-        hipEvent_t ev = nullptr;
-        bool complete = false;
-    };
-    struct Range {
-        uint64_t begin = 0, end = 0;
-        bool done = false;
-        Batch* lane = nullptr;
-        uint64_t hit_off = 0, hit_cnt = 0;
-        uint64_t a_off = 0, a_cnt = 0;  // its assignments: they stay in the lane until mtsv_batch_download_assignments
-    };
-    std::mutex mu;  // chunks, ranges, cursors, commit state
-    std::condition_variable cv;
-    std::vector<Chunk> chunks;            // issued copies, in read order
-    std::vector<uint64_t> seg_begin{0};   // first read of every segment (feeder appends)
-    uint64_t n_complete = 0;              // chunks [0, n_complete) have arrived
-    bool issued_all = n == 0;
-    std::vector<Range> ranges;
-    uint64_t next_read = 0;    // first read no lane has taken
-    uint64_t next_commit = 0;  // next range whose hits go to the host
-    uint64_t done_prefix = 0;  // reads [0, done_prefix) are through the kernels (arena reuse)
-    int busy_lanes = 0;
-    bool abort = false;
-    std::exception_ptr first_err;
-    auto fail = [&](std::exception_ptr e) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!first_err) first_err = e;
-        abort = true;
-        cv.notify_all();
-    };
-    auto event_for = [&](size_t k) { return chunk_ev.at(k, hipEventDisableTiming); };
-
-    n_reads = n;
-    max_len = 0;
-    resident = codes_resident = mapped = false;  // (what upload() or take_reads() left is not this batch)
-    if (trace) fprintf(stderr, "[run_host] entered; begin_run at %.2f ms\n", (now_s() - t_entry) * 1e3);
-    begin_run(p, read_base);
-    staged_hits = 0;
-    // (MTSV_ASSIGN_ONLY: the hits stay on the device, no hit byte crosses to the host)
-    const bool stage_hits = !keep_on_device && !assign_only();
-    if (assign_only() && h_hits_stage) {  // no hit will be staged: a pinned array left from an earlier run goes back to the pool
-        pinned_hits_release(h_hits_stage);
-        h_hits_stage = nullptr;
-        h_hits_cap = 0;
-    }
-    if (!h_hits_stage && stage_hits && !flags_only()) {
-        // expect about as many hits as the last run produced (first run: one per read)
-        // (a fresh page-locked array costs ~60 us per MB to create and is slow on its first copy: ask for little more than
-        //  the last batch needed, so that the array that batch returned to the pool fits again)
-        h_hits_stage = pinned_hits_alloc(last_total_hits ? last_total_hits + last_total_hits / 64 : n + n / 8, &h_hits_cap);
-    }
-    const bool stage_assign = assign.mode != MTSV_ASSIGN_OFF;
-    const uint64_t a_rec = assign.rec_bytes();
-    if (stage_assign && !h_assign_stage) {
-        uint64_t cap = 0;  // (in 32-byte hits: two 16-byte records each, or four 24-byte ones in three)
-        h_assign_stage = (uint8_t*)pinned_hits_alloc(((last_total_assign ? last_total_assign + last_total_assign / 64 : n + n / 8) * a_rec + 31) / 32, &cap);
-        h_assign_cap = cap * 32 / a_rec;
-    }
-    if (trace) fprintf(stderr, "[run_host] result array of %llu hits ready at %.2f ms\n", (unsigned long long)h_hits_cap, (now_s() - t_entry) * 1e3);
-    const uint64_t n_lanes_used = n >= ls.size() * kLaneMinReads ? ls.size() : 1;
-    lanes_used = n_lanes_used;
-
-    // ---- feeder ----
-    // Only the WATCHER thread looks at the copies' events, by polling, and publishes what has arrived (lanes that
-    // blocked in hipEventSynchronize while a third lane sat in hipStreamSynchronize kept that lane from returning
-    // for 10 ms at a time).
-    auto watcher = [&]() {
-        try {
-            HIP_CHECK(hipSetDevice(di->device));
-            size_t c = 0;
-            for (;;) {
-                size_t upto;
-                bool last;
-                std::vector<hipEvent_t> evs;
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    if (abort) return;
-                    upto = chunks.size();
-                    last = issued_all;
-                    for (size_t i = c; i < upto; i++) evs.push_back(chunks[i].ev);
-                }
-                const size_t c0 = c;
-                while (c < upto) {
-                    const hipError_t q = hipEventQuery(evs[c - c0]);
-                    if (q == hipSuccess) c++;
-                    else if (q == hipErrorNotReady) break;
-                    else throw_hip(q, "hipEventQuery(chunk)", __FILE__, __LINE__);
-                }
-                if (c != c0) {
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        n_complete = c;
-                    }
-                    cv.notify_all();
-                }
-                if (last && c == upto) return;
-                std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
-        } catch (...) {
-            fail(std::current_exception());
-        }
-    };
-    auto feeder = [&]() {
-        try {
-            HIP_CHECK(hipSetDevice(di->device));
-            uint64_t r = 0, seg = 0, seg_first_base = first_base, seg_first_read = 0;
-            uint64_t chunk_bytes = kChunkMin;
-            size_t k = 0;
-            uint8_t prev_code = 0;  // packed transfer: the code of the segment's last base so far (it may share a byte with the next)
-            while (r < n) {
-                // the chunk: whole reads, about chunk_bytes of bases, inside the current segment
-                uint64_t e = r;
-                {
-                    // largest e with read_off[e] - read_off[r] <= chunk_bytes (at least one read)
-                    uint64_t lo = r + 1, hi = n;
-                    hi = pv[part_of(r)].first + pv[part_of(r)].n;  // a chunk is copied from one part
-                    const uint64_t lim = RO(r) + chunk_bytes;
-                    if (RO(hi) > lim) {
-                        while (lo < hi) {
-                            const uint64_t mid = (lo + hi + 1) / 2;
-                            if (RO(mid) <= lim) lo = mid;
-                            else hi = mid - 1;
-                        }
-                        hi = lo;
-                    }
-                    e = hi;
-                }
-                Arena* ar = &arena[seg & 1];
-                if (RO(e) - seg_first_base > ar->cap_bases || e - seg_first_read > ar->cap_reads) {
-                    // does not fit the segment any more: shorten to what fits, or open the next segment
-                    uint64_t lo = r, hi = e;
-                    while (lo < hi) {
-                        const uint64_t mid = (lo + hi + 1) / 2;
-                        if (RO(mid) - seg_first_base <= ar->cap_bases && mid - seg_first_read <= ar->cap_reads) lo = mid;
-                        else hi = mid - 1;
-                    }
-                    if (lo == r) {
-                        if (r == seg_first_read) throw std::runtime_error("limit: one read holds more bases than an input segment (" + std::to_string(ar->cap_bases) + ")");
-                        seg++;
-                        seg_first_base = RO(r);
-                        seg_first_read = r;
-                        ar = &arena[seg & 1];
-                        {
-                            std::lock_guard<std::mutex> lk(mu);
-                            seg_begin.push_back(r);
-                        }
-                        cv.notify_all();  // lanes waiting for more reads of the closed segment take what it has
-                        if (seg >= 2) {  // the arena's previous tenant (segment seg - 2) must be through the kernels
-                            std::unique_lock<std::mutex> lk(mu);
-                            cv.wait(lk, [&] { return abort || done_prefix >= seg_begin[seg - 1]; });
-                            if (abort) return;
-                        }
-                        continue;  // cut the chunk again inside the new segment
-                    }
-                    e = lo;
-                }
-                const PartView& src_part = pv[part_of(r)];
-                const uint64_t* poff = src_part.off + (r - src_part.first);  // this chunk's offsets inside its part
-                const uint64_t cnt = e - r, b0 = RO(r), nb = RO(e) - b0;
-                const uint64_t dst_b = b0 - seg_first_base, dst_r = r - seg_first_read;
-                // offsets relative to the segment's first base; h_off_all[seg ... ] holds them at index (read + seg) so that
-                // every segment has its own closing entry
-                uint32_t* ho = h_off_all.p + r + seg;
-                if (r + seg + cnt + 1 > h_off_all.cap) throw std::runtime_error("internal: more input segments than the offset array was sized for");
-                uint32_t ml = 0;
-                if (r == seg_first_read) ho[0] = 0;  // (else the previous chunk wrote this entry; a lane may be reading it)
-                {
-                    // (on the packer's threads when it runs: a quarter of a million reads per chunk were 0.15 ms of the
-                    //  feeder's 0.56 per chunk)
-                    std::atomic<uint32_t> ml_all{0};
-                    std::atomic<bool> bad{false};
-                    auto narrow = [&](uint64_t i0, uint64_t i1) {  // entries i0 + 1 .. i1
-                        uint32_t m = 0;
-                        for (uint64_t i = i0 + 1; i <= i1; i++) {
-                            if (poff[i] < poff[i - 1]) bad.store(true);
-                            const uint32_t v = (uint32_t)(b0 + (poff[i] - poff[0]) - seg_first_base);
-                            m = std::max(m, (uint32_t)std::min<uint64_t>(poff[i] - poff[i - 1], UINT32_MAX));  // (a length of 2^32 must not read as 0)
-                            ho[i] = v;
-                        }
-                        uint32_t cur = ml_all.load();
-                        while (m > cur && !ml_all.compare_exchange_weak(cur, m)) {}
-                    };
-                    if (packed && cnt >= (1u << 16)) pack_pool_for(cnt, 1u << 14, narrow);
-                    else narrow(0, cnt);
-                    if (bad.load()) throw std::runtime_error("arg: read_off is not ascending");
-                    ml = ml_all.load();
-                }
-                // before anything is staged: the cut takes at least one read, so one long read makes nb larger than h_stage
-                if (ml > kMaxReadLen)
-                    throw std::runtime_error("limit: read of " + std::to_string(ml) + " bases; this build verifies reads up to " +
-                                             std::to_string(kMaxReadLen));
-                const double t0 = now_s();
-                hipEvent_t ev = event_for(k);
-                if (nb) {
-                    const uint8_t* src = src_part.bases + poff[0];
-                    if (packed || !src_part.pinned) {
-                        uint8_t* hs = h_stage[k % kStage].p;
-                        if (k >= kStage) {  // its last copy must have left (polled, like the watcher)
-                            for (;;) {
-                                const hipError_t q = hipEventQuery(chunk_ev[k - kStage]);
-                                if (q == hipSuccess) break;
-                                if (q != hipErrorNotReady) throw_hip(q, "hipEventQuery(stage)", __FILE__, __LINE__);
-                                std::this_thread::sleep_for(std::chrono::microseconds(20));
-                            }
-                        }
-                        if (packed) {
-                            if (dst_b == 0) prev_code = 0;  // a new segment
-                            prev_code = pack_chunk(hs, src, dst_b, nb, prev_code);
-                        } else {
-                            parallel_copy(hs, src, nb);
-                        }
-                        src = hs;
-                    }
-                    if (packed)
-                        HIP_CHECK(hipMemcpyAsync(ar->d_packed.p + (dst_b >> 1), src, ((dst_b + nb + 1) >> 1) - (dst_b >> 1), hipMemcpyHostToDevice, copy_stream));
-                    else
-                        HIP_CHECK(hipMemcpyAsync(ar->d_bases.p + dst_b, src, nb, hipMemcpyHostToDevice, copy_stream));
-                }
-                HIP_CHECK(hipMemcpyAsync(ar->d_off.p + dst_r, ho, (cnt + 1) * 4, hipMemcpyHostToDevice, copy_stream));
-                HIP_CHECK(hipEventRecord(ev, copy_stream));
-                if (trace) fprintf(stderr, "[run_host] chunk %zu: reads %llu..%llu (%.1f MB, segment %llu) issued at %.2f ms (host side %.2f ms)\n", k, (unsigned long long)r, (unsigned long long)e, nb / 1e6, (unsigned long long)seg, (now_s() - run_t0) * 1e3, (now_s() - t0) * 1e3);
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    Chunk c;
-                    c.begin = r;
-                    c.end = e;
-                    c.max_len = ml;
-                    c.seg = (uint32_t)seg;
-                    c.ev = ev;
-                    chunks.push_back(c);
-                    if (e == n) issued_all = true;
-                }
-                cv.notify_all();
-                r = e;
-                k++;
-                chunk_bytes = std::min(kChunkMax, chunk_bytes * 2);
-            }
-        } catch (...) {
-            fail(std::current_exception());
-        }
-    };
-
-    // ---- lanes ----
-    auto commit_ready = [&]() {  // mu held: hits of finished ranges leave for the host in read order
-        while (next_commit < ranges.size() && ranges[next_commit].done) {
-            Range& rg = ranges[next_commit];
-            if (rg.hit_cnt && stage_hits) {
-                stage_reserve(staged_hits + rg.hit_cnt);
-                HIP_CHECK(hipMemcpyAsync(h_hits_stage + staged_hits, rg.lane->d_hits.p + rg.hit_off, rg.hit_cnt * sizeof(mtsv_hit),
-                                         hipMemcpyDeviceToHost, copy_stream2));
-                staged_hits += rg.hit_cnt;
-            }
-            if (rg.a_cnt && stage_assign) {
-                assign_stage_reserve(staged_assign + rg.a_cnt);
-                HIP_CHECK(hipMemcpyAsync(h_assign_stage + staged_assign * a_rec, rg.lane->d_assign.p + rg.a_off * a_rec, rg.a_cnt * a_rec,
-                                         hipMemcpyDeviceToHost, copy_stream2));
-                staged_assign += rg.a_cnt;
-            }
-            segments.push_back(Segment{rg.lane, rg.hit_off, rg.hit_cnt, 0, 0, rg.a_off, rg.a_cnt});
-            done_prefix = rg.end;
-            next_commit++;
-        }
-    };
-    // (the first ranges: with the bases packed the reads arrive faster than the device takes them, and fewer, larger ranges
-    //  are worth more than an early start -- same-box medians 31.1-31.3 ms per step against 31.8-32.4 with 256 Ki; with the
-    //  plain transfer the order is the other way round, 36.4 against 37.0)
-    uint64_t ramp_floor = packed ? 768 << 10 : 256 << 10;
-    if (const char* e = getenv("MTSV_RAMP_FLOOR")) ramp_floor = std::max<uint64_t>(4096, strtoull(e, nullptr, 10));
-    uint64_t idle_take = 64 << 10;  // an idle device starts on this little
-    if (const char* e = getenv("MTSV_IDLE_TAKE")) idle_take = std::max<uint64_t>(1024, strtoull(e, nullptr, 10));
-    auto lane_main = [&](Batch* lane) {
-        try {
-            HIP_CHECK(hipSetDevice(di->device));
-            uint64_t last_done = ~0ull;  // the last range this lane finished
-            for (;;) {
-                uint64_t k = 0, rb = 0, re = 0, seg_first = 0;
-                uint32_t seg = 0, ml = 0;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    // The lane's result array only has to hold hits until they have left for the host: once it is half
-                    // full and everything in it has been committed, start again at its beginning (a 100 M-read host
-                    // batch would otherwise pile a third of its hits up on the device).
-                    if (!keep_on_device && lane->n_hits_total > lane->d_hits.cap / 2 && (last_done == ~0ull || last_done < next_commit)) {
-                        HIP_CHECK(hipStreamSynchronize(copy_stream2));
-                        lane->n_hits_total = 0;
-                    }
-                    for (;;) {
-                        if (abort || next_read >= n) return;  // failed elsewhere / every read taken
-                        const uint64_t arrived = n_complete ? chunks[n_complete - 1].end : 0;
-                        const bool all_arrived = issued_all && n_complete == chunks.size();
-                        // the segment next_read lies in: a range stays inside one
-                        size_t sg = seg_begin.size() - 1;
-                        while (seg_begin[sg] > next_read) sg--;
-                        const uint64_t seg_end = sg + 1 < seg_begin.size() ? seg_begin[sg + 1] : n;
-                        const uint64_t avail = std::min(arrived, seg_end) > next_read ? std::min(arrived, seg_end) - next_read : 0;
-                        const uint64_t take = range_take(n, next_read, ws_reads, ramp_floor, idle_take, n_lanes_used, avail, all_arrived || arrived >= seg_end, busy_lanes);
-                        if (take) {
-                            rb = next_read;
-                            re = next_read + take;
-                            next_read = re;
-                            seg = (uint32_t)sg;
-                            seg_first = seg_begin[sg];
-                            for (size_t c = 0; c < n_complete; c++)  // (a few dozen chunks)
-                                if (chunks[c].end > rb && chunks[c].begin < re) ml = std::max(ml, chunks[c].max_len);
-                            k = ranges.size();
-                            ranges.emplace_back();
-                            ranges[k].begin = rb;
-                            ranges[k].end = re;
-                            busy_lanes++;
-                            break;
-                        }
-                        cv.wait(lk);  // for the next copy to arrive (the feeder watches them), or for a lane to finish (the idle rule)
-                    }
-                }
-                cv.notify_all();
-                const Arena& ar = arena[seg & 1];
-                const uint32_t* ho = h_off_all.p + rb + seg;  // offsets of reads rb .. re inside segment seg
-                const uint32_t* dso = ar.d_off.p + (rb - seg_first);
-                const uint64_t before = lane->n_hits_total, a_before = lane->n_assign_total;
-                const double t0 = now_s();
-                // base normalisation (binner.rs:88-100) in place, on the lane's own stream: a kernel on the copy
-                // stream would queue behind the persistent verification kernels of the other lanes
-                if (packed) launch_unpack(lane->stream, ar.d_packed.p, ar.d_bases.p, ho[0], ho[re - rb]);
-                else launch_normalise(lane->stream, ar.d_bases.p, ar.d_bases.p, ho[0], ho[re - rb]);
-                lane->run_slice(p, ar.d_bases.p, dso, ho, re - rb, ml, read_base + rb);
-                if (trace) fprintf(stderr, "[run_host] range %llu (reads %llu..%llu): kernels %.1f ms, done at %.1f ms\n", (unsigned long long)k, (unsigned long long)rb, (unsigned long long)re, (now_s() - t0) * 1e3, (now_s() - run_t0) * 1e3);
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    ranges[k].lane = lane;
-                    ranges[k].hit_off = before;
-                    ranges[k].hit_cnt = lane->n_hits_total - before;
-                    ranges[k].a_off = a_before;
-                    ranges[k].a_cnt = lane->n_assign_total - a_before;
-                    ranges[k].done = true;
-                    last_done = k;
-                    max_len = std::max(max_len, ml);
-                    busy_lanes--;
-                    commit_ready();
-                }
-                cv.notify_all();
-            }
-        } catch (...) {
-            fail(std::current_exception());
-        }
-    };
-
-    commit_mu = &mu;
-    std::vector<std::thread> th;
-    th.emplace_back(feeder);
-    th.emplace_back(watcher);
-    for (uint64_t i = 1; i < n_lanes_used; i++) th.emplace_back(lane_main, ls[i]);
-    lane_main(this);
-    for (auto& t : th) t.join();
-    commit_mu = nullptr;
-    if (trace) fprintf(stderr, "[run_host] threads joined at %.1f ms\n", (now_s() - run_t0) * 1e3);
-    if (first_err) {
-        (void)hipStreamSynchronize(copy_stream);
-        (void)hipStreamSynchronize(copy_stream2);
-        std::rethrow_exception(first_err);
-    }
-    end_run();
-    HIP_CHECK(hipStreamSynchronize(copy_stream2));
-    staged_valid = stage_hits && staged_hits == total_hits;
-    host_hits_dropped = !stage_hits && !keep_on_device;
-    if (stage_assign) {
-        uint64_t total_a = 0;
-        for (auto& sg : segments) total_a += sg.a_count;
-        assign_staged_valid = staged_assign == total_a;
-        if (!assign_staged_valid) throw std::runtime_error("internal: run_host staged " + std::to_string(staged_assign) + " of " + std::to_string(total_a) + " assignments");
-    }
-    last_run = seg_begin.size() == 1 ? kRunHostOneSegment : kRunHostSegments;
-    if (trace) fprintf(stderr, "[run_host] hits on the host at %.1f ms (%llu ranges, %llu chunks); %.1f ms since the call began\n", (now_s() - run_t0) * 1e3, (unsigned long long)ranges.size(), (unsigned long long)chunks.size(), (now_s() - t_entry) * 1e3);
-    if (!staged_valid && stage_hits) throw std::runtime_error("internal: run_host staged " + std::to_string(staged_hits) + " of " + std::to_string(total_hits) + " hits");
-}
-
-// pinned result array of run_host: grown geometrically through the pool (mu of run_host held)
-void Batch::stage_reserve(uint64_t n_hits_needed) {
-    if (n_hits_needed <= h_hits_cap) return;
-    if (getenv("MTSV_TRACE")) fprintf(stderr, "[run_host] result array grows %llu -> %llu hits\n", (unsigned long long)h_hits_cap, (unsigned long long)n_hits_needed);
-    HIP_CHECK(hipStreamSynchronize(copy_stream2));
-    uint64_t ncap = 0;
-    mtsv_hit* nh = pinned_hits_alloc(std::max<uint64_t>(2 * h_hits_cap, n_hits_needed), &ncap);
-    if (staged_hits) memcpy(nh, h_hits_stage, staged_hits * sizeof(mtsv_hit));
-    if (h_hits_stage) pinned_hits_release(h_hits_stage);
-    h_hits_stage = nh;
-    h_hits_cap = ncap;
-}
-
-// the same for the assignments' pinned array (records of the grain's size in pool units of 32 bytes)
-void Batch::assign_stage_reserve(uint64_t n_needed) {
-    if (n_needed <= h_assign_cap) return;
-    if (getenv("MTSV_TRACE")) fprintf(stderr, "[run_host] assignment array grows %llu -> %llu records\n", (unsigned long long)h_assign_cap, (unsigned long long)n_needed);
-    HIP_CHECK(hipStreamSynchronize(copy_stream2));
-    uint64_t ncap = 0;
-    const uint64_t rec = assign.rec_bytes();
-    auto* na = (uint8_t*)pinned_hits_alloc((std::max<uint64_t>(2 * h_assign_cap, n_needed) * rec + 31) / 32, &ncap);
-    if (staged_assign) memcpy(na, h_assign_stage, staged_assign * rec);
-    if (h_assign_stage) pinned_hits_release(h_assign_stage);
-    h_assign_stage = na;
-    h_assign_cap = ncap * 32 / rec;
+void PinnedStage::drop() {
+    pinned_hits_release(hand_out());
+    staged = 0;
 }
 
 // The result array is pinned host memory from the pool; the caller owns it until mtsv_hits_free.
 void Batch::download(mtsv_hit** hits, uint64_t* n) {
     HIP_CHECK(hipSetDevice(di->device));
-    last_total_hits = total_hits;
+    hits_stage.last_total = total_hits;
     if (assign.mode != MTSV_ASSIGN_ONLY && host_hits_dropped)
         throw std::runtime_error("arg: the last run was a host batch in MTSV_ASSIGN_ONLY, which kept none of its hits: run again in the new mode");
     if (assign.mode == MTSV_ASSIGN_ONLY) {  // the hits stay where they are
@@ -1620,12 +1078,9 @@ void Batch::download(mtsv_hit** hits, uint64_t* n) {
         *n = 0;
         return;
     }
-    if (staged_valid && h_hits_stage) {  // run_host already brought them over
-        *hits = h_hits_stage;
+    if (hits_stage.valid && hits_stage.p) {  // run_host already brought them over
+        *hits = (mtsv_hit*)hits_stage.hand_out();
         *n = total_hits;
-        h_hits_stage = nullptr;
-        h_hits_cap = 0;
-        staged_valid = false;
         return;
     }
     uint64_t cap = 0;
@@ -1647,7 +1102,7 @@ void Batch::download(mtsv_hit** hits, uint64_t* n) {
 void Batch::download_into(mtsv_hit* dst, uint64_t n) {
     HIP_CHECK(hipSetDevice(di->device));
     if (n != total_hits) throw std::runtime_error("internal: download_into of " + std::to_string(n) + " hits, the run produced " + std::to_string(total_hits));
-    last_total_hits = total_hits;
+    hits_stage.last_total = total_hits;
     hipStream_t cs = copy_stream2 ? copy_stream2.s : stream.s;
     uint64_t at = 0;
     for (auto& sg : segments) {

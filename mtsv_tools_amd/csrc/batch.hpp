@@ -1,4 +1,4 @@
-// batch.hpp -- device workspace of one read batch (see batch.hip; the pass driver: batch_pass.hip).
+// batch.hpp -- device workspace of one read batch (see batch.hip; the pass driver: batch_pass.hip; the host run: batch_host.hip).
 #pragma once
 #include <condition_variable>
 #include <memory>
@@ -13,6 +13,34 @@
 
 namespace mtsv {
 
+// result arrays in pinned host memory, recycled through a pool (mtsv_hits_free returns them)
+mtsv_hit* pinned_hits_alloc(uint64_t n_hits, uint64_t* cap_hits);
+bool pinned_hits_release(void* p);  // false: p is not a pool array
+
+// A pool array that a host run fills in read order while later ranges still compute -- the hits, the assignments -- and that
+// the download then hands to the caller as it is.  The pool counts in 32-byte hits: records of `rec` bytes are rounded up to
+// those units on the way in and the capacity is turned back into records on the way out; with 32-byte hits both are the
+// identity, so one body gives both arrays the sizes they had with one body each.
+struct PinnedStage {
+    uint8_t* p = nullptr;
+    uint64_t cap = 0, staged = 0;  // records the array holds; records copied into it so far
+    uint64_t rec;                  // bytes per record
+    uint64_t last_total = 0;       // records of the last run that was downloaded: what begin() expects of the next
+    bool valid = false;            // the last run staged all of its records
+    const char *name, *unit;       // (trace)
+    PinnedStage(uint64_t rec_, const char* name_, const char* unit_) : rec(rec_), name(name_), unit(unit_) {}
+    PinnedStage(const PinnedStage&) = delete;
+    PinnedStage& operator=(const PinnedStage&) = delete;
+    ~PinnedStage() { drop(); }
+    // an array if there is none, for about the records of the last run (first run: expected_first)
+    void begin(uint64_t expected_first);
+    // room for `need` records: after `stream` is through with the old array a larger one takes over what has been staged
+    void reserve(uint64_t need, hipStream_t stream);
+    uint8_t* at(uint64_t record) const { return p + record * rec; }
+    void* hand_out();  // the array is the caller's; the stage holds nothing
+    void drop();       // the array goes back to the pool
+};
+
 struct Batch {
     mtsv_index* ix;
     DeviceIndex* di;
@@ -20,9 +48,7 @@ struct Batch {
     // the streams first, so that they are destroyed after the arrays.  copy_stream (the reads' transfer) and copy_stream2
     // (results to the host) are created by the first host batch, at high priority (host_room).
     DevStream stream, copy_stream, copy_stream2;
-    mtsv_hit* h_hits_stage = nullptr;  // pinned (pool): run_host copies every slice's hits here while later slices run
-    uint64_t h_hits_cap = 0, staged_hits = 0, last_total_hits = 0;
-    bool staged_valid = false;
+    PinnedStage hits_stage{sizeof(mtsv_hit), "result", "hits"};  // run_host copies every range's hits here while later ranges run
     // run_host: the input arenas in HBM (the whole host batch, or segments of it taking turns), filled in read order by one
     // feeder thread on copy_stream; page-locked staging chunks for bases that lie in ordinary memory
     struct Arena {
@@ -39,7 +65,7 @@ struct Batch {
     static constexpr int kStage = 4;
     HostBuf<uint8_t> h_stage[kStage];
     DevEventList chunk_ev;  // one per copy chunk (hipEventDisableTiming), kept between runs
-    std::mutex* commit_mu = nullptr;  // set while run_host's threads may touch the lanes' result arrays
+    std::mutex* commit_mu = nullptr;  // set while run_host's threads may touch the lanes' result arrays (HostRun::run_threads)
     uint64_t max_reads, max_bases;
     // entries of each of the ten seed-hit arrays (d_hit_row .. d_worklist).  Above zero: all ten exist at that size, on every
     // path; zero after a growth that failed, and then the next run begins with the first size again (hit_cap_first)
@@ -276,11 +302,8 @@ struct Batch {
     Assignments assign;
     // run_host: a finished range's assignments leave for this pinned array (pool) on the result copy stream, in read order,
     // like its hits; mtsv_batch_download_assignments hands the array out.  (owner only)
-    uint8_t* h_assign_stage = nullptr;  // records of assign.rec_bytes()
-    uint64_t h_assign_cap = 0, staged_assign = 0, last_total_assign = 0;
-    bool assign_staged_valid = false;
+    PinnedStage assign_stage{sizeof(mtsv_assignment), "assignment", "records"};  // records of assign.rec_bytes() (set_assignment_grain)
     bool host_hits_dropped = false;  // the last run was a host batch in MTSV_ASSIGN_ONLY: its hits were never staged and the lanes' arrays were recycled
-    void assign_stage_reserve(uint64_t n_needed);
     DevBuf<uint8_t> d_assign;  // the lane's assignments (records of the grain), those of a pass behind those of the passes before;
                                // grows keeping its contents (collapse_room)
     uint64_t n_assign_total = 0;
@@ -331,7 +354,7 @@ struct Batch {
     void collapse_begin();  // a run begins: no assignments, counts and times zero
     void collapse_trace(const char* what);
     void reset_lane();
-    void stage_reserve(uint64_t n_hits_needed);
+    struct HostRun;  // a host run and its threads (batch_host.hip; DESIGN.md, "Host buffers in, host hits out")
     void host_room(uint64_t n, uint64_t total_bases, bool trace);
     void finish_lane();
     void size_hit_workspace(uint64_t cap);  // the ten seed-hit arrays at `cap` entries, contents not kept
@@ -364,11 +387,10 @@ struct Batch {
     void stage_commit(Pass& ps);
 };
 
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 extern int g_default_verify_mode;  // mtsv_set_default_verify_mode
 
-// result arrays in pinned host memory, recycled through a pool (mtsv_hits_free returns them)
-mtsv_hit* pinned_hits_alloc(uint64_t n_hits, uint64_t* cap_hits);
-bool pinned_hits_release(void* p);  // false: p is not a pool array
 // page-locked host memory for the callers' read buffers (mtsv_host_alloc & co.)
 void* host_pinned_alloc(uint64_t bytes);
 void host_pinned_free(void* p);

@@ -1,7 +1,7 @@
 // pass_plan.hpp -- the three policies of the driver that are arithmetic on host integers: how a slice is cut into passes
 // (Batch::run_slice), how a resident range is cut into the lanes' chunks (Batch::run_range), and how many reads a lane of a
-// host run takes next (Batch::run_host_parts).  Plain inputs, plain results; includes nothing of HIP, so that
-// tools/pass_plan_check.cpp runs them on the CPU under the sanitizers.
+// host run takes next (Batch::HostRun::take_range; what has arrived for it: host_feed.hpp).  Plain inputs, plain results;
+// includes nothing of HIP, so that tools/pass_plan_check.cpp runs them on the CPU under the sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstdint>
