@@ -902,6 +902,77 @@ int mtsv_batch_place_hits(mtsv_batch *b, const mtsv_hit *hits, uint64_t n_hits, 
 int mtsv_format_placements(const mtsv_placement *pl, uint64_t n, const uint32_t *ops, const char *ids, const uint64_t *id_off,
                            uint64_t n_reads, char **out, uint64_t *out_len);
 
+/* ---- pileup: what the reads show at every reference position (pile.hip, k_pile.hip) ------------------------------------------
+ * The alignments above are per hit.  An mtsv_pileup adds them up per reference POSITION: how many reads match there, how many
+ * show an A, C, G, T or N instead, how many skip the position, and how many carry extra bases in front of it.  It is bound to a
+ * device and to an optional list of TaxIDs (n_taxa == 0: every reference).
+ *   A reference is a (tax_id, gi) of length L = end - start of its bin.  It owns L + 1 SLOTS: positions 0 .. L-1, and slot L,
+ *   which can only take insertions (a read base behind the bin's last base).  A slot has eight u32 counters n[0 .. 8):
+ *   n[0] match, n[1 .. 4] a read A, C, G, T over another base, n[5] a read N, n[6] deletion, n[7] insertion.
+ *   For a hit and its placement (ref_start, the ops in reference order, as mtsv_batch_place_hits defines them) and P the read's
+ *   codes on the hit's strand -- forward, or reverse complement with N staying N -- the ops are walked with i = 0, j = ref_start:
+ *     a run of n '='   adds 1 to n[0] of positions j .. j+n-1; i += n, j += n
+ *     each 'X'         adds 1 to n[1 + P[i]] of position j; i++, j++
+ *     each 'D'         adds 1 to n[6] of position j; j++
+ *     a run of n 'I'   adds 1 to n[7] of slot j, once per run; i += n
+ *   depth(pos) = n[0] + ... + n[6].  ref is the text's code at the position (0 .. 4 for A, C, G, T, N); slot L has 0xff.
+ *   A hit COUNTS when edit <= m + edit_slack, the sum saturating, m the smallest edit among the hits OF THIS CALL that carry the
+ *   same read -- every hit of the call, also one on a reference the list does not select; a slack of 0xffffffff: all hits.  The
+ *   best is per call: the binner calls once per chunk run, so a read's best there is its best in that chunk, not over the
+ *   database.  A hit on a reference whose TaxID the list does not select is SKIPPED and counted in *n_skipped; *n_piled: the
+ *   hits that were walked.
+ * mtsv_pileup_add_run: hits == NULL piles the hits of the workspace's last run where they lie; otherwise `hits` are n_hits
+ *   caller-given hits against the resident batch -- exactly as in mtsv_batch_place_hits, with its preconditions.  The hits are
+ *   placed (on the workspace's stream; no placement and no op comes to the host), then walked.  References are learnt from the
+ *   workspace's index at each call: the selected bins whose (tax_id, gi) the accumulator does not hold yet form a new SEGMENT
+ *   with device arrays of its own -- counters, and ref codes copied from the resident text on the device; nothing that exists
+ *   is reallocated.  A chunk that is loaded again, as a new handle, finds its references by key and adds no segment.  Zero hits:
+ *   nothing is launched, device_ms is 0 and no reference is learnt.  device_ms (may be NULL, as n_piled and n_skipped): the
+ *   device time of the placement, the best-edit pass and the pile kernel.
+ *   Memory: 32 bytes of counters and one of ref code per slot, 33 bytes per reference base -- a database of 3e9 bases would
+ *   take 99 GB, which is why the TaxID list exists.
+ * mtsv_pileup_reset: counters and the two hit totals zero, the references and segments stay.
+ * mtsv_pileup_info: n_refs references in n_slots slots of n_segments segments and device_bytes; hits_piled, hits_skipped.
+ * mtsv_pileup_download (tests): one reference's counters as [slot][8] u32 and its ref codes, L + 1 slots; both malloc'd,
+ *   mtsv_free.  MTSV_E_ARG for a (tax_id, gi) the accumulator does not hold.
+ * mtsv_pileup_sites: a slot is a SITE when depth + n[7] > 0, depth >= min_depth, and some channel c in 1 .. 7 has
+ *   n[c] >= min_alt and n[c] * 1000000 >= min_alt_ppm * depth, in 64-bit integers.  (0, 0, 0) returns every touched slot.
+ *   Rows ascend by (tax_id, gi, pos) as unsigned; malloc'd, mtsv_free; the accumulator is unchanged.  device_ms (may be NULL):
+ *   the device time of the kernels.
+ * mtsv_format_variants (host only, needs no device): the header line
+ *     taxid \t gi \t pos \t ref \t depth \t match \t A \t C \t G \t T \t N \t del \t ins
+ *   then one such line per row; pos is 0-based, like START of mtsv_format_placements; ref is one of ACGTN, or `.` for slot L.
+ * On the device (k_pile.hip): channel 0 is a difference array -- a run of '=' adds +1 at its first position and -1 at the slot
+ *   behind its last, which lies in the same reference because slot L exists -- so a clean read costs two atomics; sites and
+ *   download integrate it, per tile of MTSV_PILE_TILE slots (tests; a power of two, 64 .. 1024, read at create) with the prefix
+ *   carried from tile to tile.  Every atomic is an integer add or min: the counters are exact and depend on neither the tile
+ *   nor the order of execution.  MTSV_PILE_TIMING=1: one line per add_run and sites on stderr with the steps' times.
+ * Refusals of add_run, each leaving the accumulator byte for byte as it was, no segment added and no counter changed:
+ *   everything mtsv_batch_place_hits refuses, with its codes and texts (a read above 256 bases, an unknown (tax_id, gi), an
+ *   offset beyond the bin, a read that is not resident, a strand above 1, an unplaceable hit, a host batch, no completed run).
+ *   MTSV_E_ARG: a null handle; a workspace on another device; a (tax_id, gi) the accumulator holds with another length.
+ *   MTSV_E_LIMIT: a segment of 2^32 slots or more; a total of piled hits that would reach 2^32 (the counters are 32 bits).
+ *   MTSV_E_NOMEM: a segment the device has no room for ("the pileup segment" for MTSV_ALLOC_REFUSE). */
+typedef struct mtsv_pileup mtsv_pileup;
+typedef struct {
+    uint32_t tax_id, gi, pos;
+    uint8_t ref, _pad[3];
+    uint32_t n[8];
+} mtsv_pile_site; /* 48 bytes */
+typedef struct {
+    uint64_t n_refs, n_slots, n_segments, device_bytes, hits_piled, hits_skipped;
+} mtsv_pileup_info_t;
+int mtsv_pileup_create(int hip_device, const uint32_t *taxa, uint64_t n_taxa, mtsv_pileup **out);
+void mtsv_pileup_free(mtsv_pileup *p);
+int mtsv_pileup_reset(mtsv_pileup *p);
+int mtsv_pileup_add_run(mtsv_pileup *p, mtsv_batch *b, const mtsv_hit *hits, uint64_t n_hits, uint32_t edit_slack,
+                        uint64_t *n_piled, uint64_t *n_skipped, float *device_ms);
+int mtsv_pileup_info(const mtsv_pileup *p, mtsv_pileup_info_t *info);
+int mtsv_pileup_download(mtsv_pileup *p, uint32_t tax_id, uint32_t gi, uint32_t **counts, uint8_t **ref, uint64_t *n_slots);
+int mtsv_pileup_sites(mtsv_pileup *p, uint32_t min_depth, uint32_t min_alt, uint32_t min_alt_ppm, mtsv_pile_site **rows,
+                      uint64_t *n_rows, float *device_ms);
+int mtsv_format_variants(const mtsv_pile_site *rows, uint64_t n_rows, char **out, uint64_t *out_len);
+
 /* ---- result lines (host) ---------------------------------------------------------------- */
 /* write_assignments for a whole batch: hits ordered by read; ids = NUL-separated read ids,
  * id_off[n_reads+1].  Lines are appended to a malloc'd buffer (*out, *out_len), one per read with

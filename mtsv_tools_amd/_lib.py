@@ -102,6 +102,19 @@ PLACEMENT_DTYPE = np.dtype({"names": ["read", "tax_id", "gi", "edit", "strand", 
                             "offsets": [0, 8, 12, 16, 20, 24, 28, 32, 40], "itemsize": 48})
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # BAM's op codes: an op is len << 4 | code
 
+# mtsv_pile_site: 3 * 4 + 1 + 3 pad + 8 * 4 = 48 bytes; n: match, A, C, G, T, N, del, ins
+PILE_SITE_DTYPE = np.dtype({"names": ["tax_id", "gi", "pos", "ref", "n"], "formats": ["<u4", "<u4", "<u4", "u1", ("<u4", (8,))],
+                            "offsets": [0, 4, 8, 12, 16], "itemsize": 48})
+PILE_REF_NONE = 0xff  # the ref code of a reference's last slot, which takes insertions only
+
+
+class PileupInfo(C.Structure):  # mtsv_pileup_info_t
+    _fields_ = [("n_refs", C.c_uint64), ("n_slots", C.c_uint64), ("n_segments", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("hits_piled", C.c_uint64), ("hits_skipped", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
 
 class TaxonomyInfo(C.Structure):  # mtsv_taxonomy_info_t
     _fields_ = [("n_nodes", C.c_uint64), ("n_implied_roots", C.c_uint64), ("n_ranks", C.c_uint32), ("max_depth", C.c_uint32)]
@@ -143,6 +156,8 @@ EXPORTS = [
     "mtsv_coverage_create", "mtsv_coverage_free", "mtsv_coverage_add_index", "mtsv_coverage_add_refs", "mtsv_coverage_reset",
     "mtsv_coverage_add_fold", "mtsv_coverage_rows", "mtsv_format_coverage_report",
     "mtsv_batch_place_hits", "mtsv_format_placements",
+    "mtsv_pileup_create", "mtsv_pileup_free", "mtsv_pileup_reset", "mtsv_pileup_add_run", "mtsv_pileup_info", "mtsv_pileup_download",
+    "mtsv_pileup_sites", "mtsv_format_variants",
 ]
 
 _lib = None
@@ -262,6 +277,15 @@ def lib():
         L.mtsv_format_coverage_report.argtypes = [vp, u64, C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_batch_place_hits.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_format_placements.argtypes = [vp, u64, vp, C.c_char_p, vp, u64, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_pileup_create.argtypes = [i32, vp, u64, C.POINTER(vp)]
+        L.mtsv_pileup_free.argtypes = [vp]
+        L.mtsv_pileup_free.restype = None
+        L.mtsv_pileup_reset.argtypes = [vp]
+        L.mtsv_pileup_add_run.argtypes = [vp, vp, vp, u64, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_pileup_info.argtypes = [vp, C.POINTER(PileupInfo)]
+        L.mtsv_pileup_download.argtypes = [vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_pileup_sites.argtypes = [vp, u32, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_format_variants.argtypes = [vp, u64, C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
 
@@ -931,6 +955,80 @@ def format_coverage_report(rows):
     _check(lib().mtsv_format_coverage_report(out_rows.ctypes.data, len(out_rows), C.byref(out), C.byref(n)))
     try:
         return C.string_at(out.value, n.value)
+    finally:
+        lib().mtsv_free(out)
+
+
+class Pileup:
+    """Owning handle of an mtsv_pileup: per reference position the counters match, A, C, G, T, N, del, ins of the placed hits it
+    is given.  Bound to a device and to a list of TaxIDs (None or empty: every reference).  MTSV_PILE_TILE, MTSV_TRACE and
+    MTSV_PILE_TIMING are read when it is created."""
+
+    def __init__(self, device=0, taxa=None):
+        self.h = C.c_void_p()
+        t = np.ascontiguousarray([] if taxa is None else list(taxa), dtype=np.uint32)
+        _check(lib().mtsv_pileup_create(device, t.ctypes.data if len(t) else None, len(t), C.byref(self.h)))
+
+    def reset(self):
+        """mtsv_pileup_reset: counters zero, the references stay"""
+        _check(lib().mtsv_pileup_reset(self.h))
+
+    def add_run(self, batch, hits=None, slack=0):
+        """mtsv_pileup_add_run: the hits of the Batch's last run where they lie (hits None), or the given HIT_DTYPE hits against
+        its resident batch, within `slack` edits of their read's smallest edit in this call (SLACK_ALL: all of them);
+        returns (hits piled, hits skipped, device ms)"""
+        piled, skipped, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        if hits is None:
+            ptr, cnt = None, 0
+        else:
+            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+            ptr, cnt = hits.ctypes.data, len(hits)
+        _check(lib().mtsv_pileup_add_run(self.h, batch.h, ptr, cnt, int(slack), C.byref(piled), C.byref(skipped), C.byref(ms)))
+        return piled.value, skipped.value, ms.value
+
+    def info(self):
+        """mtsv_pileup_info as a dict"""
+        out = PileupInfo()
+        _check(lib().mtsv_pileup_info(self.h, C.byref(out)))
+        return out.as_dict()
+
+    def download(self, tax_id, gi):
+        """(the reference's counters as a uint32 array [slot][8], channel 0 integrated; its ref codes, uint8 per slot)"""
+        cnt, ref, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(lib().mtsv_pileup_download(self.h, int(tax_id), int(gi), C.byref(cnt), C.byref(ref), C.byref(n)))
+        try:
+            counts = np.frombuffer((C.c_ubyte * (n.value * 32)).from_address(cnt.value), dtype="<u4").reshape(n.value, 8).copy()
+            codes = np.frombuffer((C.c_ubyte * n.value).from_address(ref.value), dtype=np.uint8).copy()
+            return counts, codes
+        finally:
+            lib().mtsv_free(cnt)
+            lib().mtsv_free(ref)
+
+    def sites(self, min_depth=0, min_alt=0, min_alt_ppm=0):
+        """mtsv_pileup_sites: (the sites as a PILE_SITE_DTYPE array ascending by (tax_id, gi, pos), device ms)"""
+        out, n, ms = C.c_void_p(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_pileup_sites(self.h, int(min_depth), int(min_alt), int(min_alt_ppm), C.byref(out), C.byref(n), C.byref(ms)))
+        return _records_from(out, n.value, PILE_SITE_DTYPE), ms.value
+
+    def close(self):
+        if self.h is not None and _lib is not None:
+            _lib.mtsv_pileup_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def format_variants(rows):
+    """mtsv_format_variants: the TSV of mtsv-binner --variants, as one str"""
+    r = np.ascontiguousarray(rows, dtype=PILE_SITE_DTYPE)
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_variants(r.ctypes.data, len(r), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value).decode()
     finally:
         lib().mtsv_free(out)
 

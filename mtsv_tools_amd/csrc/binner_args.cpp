@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <thread>
@@ -111,7 +112,19 @@ void print_help() {
            "READ_ID<TAB>TAXID<TAB>GI<TAB>+|-<TAB>START<TAB>END<TAB>EDIT<TAB>CIGAR: the strand, the half-open interval of the\n"
            "match inside the GI on the forward strand, and the edit script with = X I D, in reference order.  Lines come chunk\n"
            "by chunk, batch by batch; each stands for itself, so the file may be sorted.  Reads of up to 256 bases.  Every other\n"
-           "output is what it is without the flag)\n");
+           "output is what it is without the flag),\n"
+           "--variants TSV [--variant-taxa T1,T2,..] [--variant-slack N|all] [--min-depth N] [--min-alt-reads N] [--min-alt-frac F]\n"
+           "(only with --fold-on-gpu, not with --dedup: after every chunk's run over a batch of reads the hits it accepted are\n"
+           "aligned on the GPU and their edit scripts added up per reference position, in one accumulator for the whole run; after\n"
+           "the last read TSV gets a header and one line per variant site, taxid, gi, pos (0-based), ref, depth, match, A, C, G, T,\n"
+           "N, del, ins: how many reads match the reference there, show another base, skip the position, or carry extra bases in\n"
+           "front of it (ref `.`: behind the sequence's last base).  A hit counts when its edit distance is within\n"
+           "--variant-slack (default 0) of its read's smallest in that chunk; all: every hit.  A position is listed when its depth\n"
+           "is at least --min-depth (default 1) and a count other than match is at least --min-alt-reads (default 1) and at least\n"
+           "--min-alt-frac (0 .. 1, default 0) of the depth: by default every position where any read disagrees.  --variant-taxa:\n"
+           "only references of these TaxIDs are counted; the counters take 33 bytes of device memory per reference base of the\n"
+           "chunks, so a large database needs the list.  With --alignments as well the hits are aligned twice.  Reads of up to 256\n"
+           "bases.  Every other output is what it is without the flag)\n");
 }
 
 // a number in 0 .. 2^32 - 1, or the usage error of `flag`
@@ -224,6 +237,18 @@ void check_combinations(const Args& a) {
         if (!a.fold_gpu) refuse("'--alignments <FILE>' requires '--fold-on-gpu': the hits are aligned where a chunk's run leaves them, on the device");
         if (a.dedup) refuse("'--alignments <FILE>' cannot be used with '--dedup': only the representatives of identical reads are binned");
         if (a.alignments == a.results) refuse("'--alignments <FILE>' and '-m/--results <RESULTS>' name the same file");
+    }
+    if (a.variants.empty()) {
+        if (!a.variant_taxa.empty()) usage_error("The argument '--variant-taxa <T1,T2,..>' requires '--variants <TSV>'");
+        if (!a.variant_slack.empty()) usage_error("The argument '--variant-slack <N|all>' requires '--variants <TSV>'");
+        if (!a.min_depth.empty()) usage_error("The argument '--min-depth <N>' requires '--variants <TSV>'");
+        if (!a.min_alt_reads.empty()) usage_error("The argument '--min-alt-reads <N>' requires '--variants <TSV>'");
+        if (!a.min_alt_frac.empty()) usage_error("The argument '--min-alt-frac <F>' requires '--variants <TSV>'");
+    } else {
+        if (!a.fold_gpu) refuse("'--variants <TSV>' requires '--fold-on-gpu': the hits are aligned where a chunk's run leaves them, on the device");
+        if (a.dedup) refuse("'--variants <TSV>' cannot be used with '--dedup': only the representatives of identical reads are binned");
+        if (a.variants == a.results) refuse("'--variants <TSV>' and '-m/--results <RESULTS>' name the same file");
+        if (a.variants == a.alignments) refuse("'--variants <TSV>' and '--alignments <FILE>' name the same file");
     }
     if (a.merge_gpu) require_chunks_on_one_device(a, "--merge-on-gpu", "every chunk is made resident on that device");
     if (a.fold_gpu) {
@@ -371,6 +396,12 @@ Args parse_args(int argc, char** argv) {
         else if (key == "--coverage") a.coverage = val();
         else if (key == "--coverage-slack") a.coverage_slack = val();
         else if (key == "--alignments") a.alignments = val();
+        else if (key == "--variants") a.variants = val();
+        else if (key == "--variant-taxa") a.variant_taxa = val();
+        else if (key == "--variant-slack") a.variant_slack = val();
+        else if (key == "--min-depth") a.min_depth = val();
+        else if (key == "--min-alt-reads") a.min_alt_reads = val();
+        else if (key == "--min-alt-frac") a.min_alt_frac = val();
         else if (key == "--fold-reads") a.fold_reads = parse_reads(val(), "--fold-reads", 0xffffffffull);
         else if (key == "-h" || key == "--help") {
             print_help();
@@ -418,6 +449,25 @@ Run resolve(const Args& a) {
     run.coverage = a.coverage;
     run.alignments = a.alignments;
     if (!a.coverage_slack.empty()) run.coverage_slack = a.coverage_slack == "all" ? 0xffffffffu : parse_u32_flag(a.coverage_slack, "--coverage-slack");
+    run.variants = a.variants;
+    if (!a.variant_taxa.empty())
+        for (const std::string& tok : split_list(a.variant_taxa, ',', true)) {
+            char* e = nullptr;
+            errno = 0;
+            const unsigned long long t = strtoull(tok.c_str(), &e, 10);
+            if (tok.empty() || tok[0] == '-' || *e || errno || t > 0xffffffffull)
+                usage_error("Invalid value for '--variant-taxa <T1,T2,..>': a comma-separated list of TaxIDs is expected");
+            run.variant_taxa.push_back((uint32_t)t);
+        }
+    if (!a.variant_slack.empty()) run.variant_slack = a.variant_slack == "all" ? 0xffffffffu : parse_u32_flag(a.variant_slack, "--variant-slack");
+    if (!a.min_depth.empty()) run.min_depth = parse_u32_flag(a.min_depth, "--min-depth");
+    if (!a.min_alt_reads.empty()) run.min_alt_reads = parse_u32_flag(a.min_alt_reads, "--min-alt-reads");
+    if (!a.min_alt_frac.empty()) {
+        char* e = nullptr;
+        const double f = strtod(a.min_alt_frac.c_str(), &e);
+        if (*e || e == a.min_alt_frac.c_str() || !(f >= 0.0 && f <= 1.0)) usage_error("Invalid value for '--min-alt-frac <F>': a fraction between 0 and 1 is expected");
+        run.min_alt_ppm = (uint32_t)llround(f * 1e6);
+    }
     resolve_params(a, run);
     if (run.interleaved && (run.read_offset & 1)) refuse("'--interleaved' needs an even '--read-offset': the reads are skipped pair by pair");
     resolve_results(a, run);

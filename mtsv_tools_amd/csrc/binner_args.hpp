@@ -17,6 +17,7 @@ struct Args {
     std::string pair_mode, max_insert, unpaired_penalty;  // --pair-mode, --max-insert, --unpaired-penalty: "" when not given
     std::string coverage, coverage_slack;                 // --coverage, --coverage-slack: "" when not given
     std::string alignments;                               // --alignments: "" when not given
+    std::string variants, variant_taxa, variant_slack, min_depth, min_alt_reads, min_alt_frac;  // --variants and its sub-flags: "" when not given
     uint64_t fold_reads = 16ull << 20;  // --fold-reads: reads per super-batch of --fold-on-gpu (every chunk is loaded once per super-batch)
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
@@ -53,12 +54,17 @@ struct Run {
     std::string coverage;                  // --coverage: "" : not asked for
     uint32_t coverage_slack = 0;           // --coverage-slack: 0xffffffff for `all`
     std::string alignments;                // --alignments: "" : not asked for
+    std::string variants;                  // --variants: "" : not asked for
+    std::vector<uint32_t> variant_taxa;    // --variant-taxa: empty: every reference
+    uint32_t variant_slack = 0;            // --variant-slack: 0xffffffff for `all`
+    uint32_t min_depth = 1, min_alt_reads = 1, min_alt_ppm = 0;  // --min-depth, --min-alt-reads, --min-alt-frac as parts per million
     uint64_t batch_reads = 0, fold_reads = 0;
 
     bool have_results() const { return !results.empty(); }
     bool have_report() const { return !report.empty(); }
     bool have_coverage() const { return !coverage.empty(); }
     bool have_alignments() const { return !alignments.empty(); }
+    bool have_variants() const { return !variants.empty(); }
     bool merged() const { return mode == Mode::merged; }
     bool folded() const { return mode == Mode::folded; }
     bool chunked() const { return index_paths.size() > 1; }

@@ -27,6 +27,9 @@
 // --alignments: after every run of a chunk over a piece, the hits the run left on the device are placed
 // (mtsv_batch_place_hits with no hits given) and their lines, under the piece's read IDs, appended to the file: chunk by
 // chunk, piece by piece.  Nothing else reads the placements, so every other output is what it is without the flag.
+// --variants: one mtsv_pileup for the whole run.  After every run of a chunk over a piece, next to the placement of --alignments,
+// the hits the run left on the device are piled (mtsv_pileup_add_run with no hits given: placed again, nothing comes to the
+// host); a read's best edit is therefore its best in that chunk.  finish() asks for the sites once and writes them.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -94,6 +97,7 @@ class FoldedRun {
     bool pair_piece(size_t k, const ReadBlock& rb, mtsv_fold* f);
     bool cover_piece(const ReadBlock& rb, mtsv_fold* f);
     bool align_piece(const ReadBlock& rb, mtsv_batch* ws);
+    bool pile_piece(mtsv_batch* ws);
     bool input_error(const std::string& what);
     bool write_sides(const ReadBlock& rb, mtsv_fold* f);
     void print_timing() const;
@@ -123,6 +127,9 @@ class FoldedRun {
     int align_fd_ = -1;                  // --alignments
     uint64_t alignments_ = 0;
     float place_device_ms_ = 0;
+    PileupPtr pileup_;                   // --variants
+    uint64_t piled_ = 0, pile_skipped_ = 0, variant_sites_ = 0;
+    float pile_device_ms_ = 0, sites_device_ms_ = 0;
     TaxaSum taxa_;
     uint64_t dedup_reads_ = 0, dedup_distinct_ = 0;
     uint64_t super_reads_ = 0, n_super_ = 0, reads_done_ = 0, reads_matched_ = 0;
@@ -205,6 +212,7 @@ bool FoldedRun::run_chunk(size_t c, bool more) {
         if (rc == MTSV_OK) rc = mtsv_batch_run(ws.get(), &run_.params);
         t_run_ += now_s() - t0;
         if (rc == MTSV_OK && align_fd_ >= 0 && !align_piece(rb, ws.get())) return false;
+        if (rc == MTSV_OK && pileup_ && !pile_piece(ws.get())) return false;
         t0 = now_s();
         float ms = 0;
         if (rc == MTSV_OK) rc = mtsv_fold_add_run((run_.dedup ? rep_folds_[k] : folds_[k]).get(), ws.get(), &ms);
@@ -275,6 +283,17 @@ bool FoldedRun::align_piece(const ReadBlock& rb, mtsv_batch* ws) {
         code_.set(11);
         return false;
     }
+    return true;
+}
+
+// --variants: the hits of the run that has just ended on ws into the run's pileup
+bool FoldedRun::pile_piece(mtsv_batch* ws) {
+    uint64_t piled = 0, skipped = 0;
+    float ms = 0;
+    if (mtsv_pileup_add_run(pileup_.get(), ws, nullptr, 0, run_.variant_slack, &piled, &skipped, &ms) != MTSV_OK) return code_.lib_error();
+    piled_ += piled;
+    pile_skipped_ += skipped;
+    pile_device_ms_ += ms;
     return true;
 }
 
@@ -441,6 +460,9 @@ void FoldedRun::print_timing() const {
     if (run_.interleaved) fprintf(stderr, "[cli pair timing] pair device %.3f ms\n", pair_device_ms_);
     if (run_.have_coverage()) fprintf(stderr, "[cli coverage timing] coverage device %.3f ms\n", coverage_device_ms_);
     if (run_.have_alignments()) fprintf(stderr, "[cli alignments timing] alignments %llu, place device %.3f ms\n", (unsigned long long)alignments_, place_device_ms_);
+    if (run_.have_variants())
+        fprintf(stderr, "[cli variants timing] hits piled %llu, skipped %llu, sites %llu; place and pile device %.3f ms, sites device %.3f ms\n",
+                (unsigned long long)piled_, (unsigned long long)pile_skipped_, (unsigned long long)variant_sites_, pile_device_ms_, sites_device_ms_);
 }
 
 // every way out of the folded run ends alike: the process leaves at once, or (MTSV_CLI_CLEAN_EXIT=1) frees what it holds --
@@ -460,6 +482,11 @@ int FoldedRun::run() {
     logmsg("INFO", "Beginning queries.");
     const double t_begin = now_s();
     if (run_.have_coverage() && mtsv_coverage_create(dev_, out(coverage_)) != MTSV_OK) {
+        code_.lib_error();
+        return leave(code_.get());
+    }
+    if (run_.have_variants() &&
+        mtsv_pileup_create(dev_, run_.variant_taxa.empty() ? nullptr : run_.variant_taxa.data(), run_.variant_taxa.size(), out(pileup_)) != MTSV_OK) {
         code_.lib_error();
         return leave(code_.get());
     }
@@ -498,6 +525,9 @@ int FoldedRun::run() {
     };
     end.taxa = &taxa_;
     end.coverage = coverage_.get();
+    end.pileup = pileup_.get();
+    end.variant_sites = &variant_sites_;
+    end.variant_sites_ms = &sites_device_ms_;
     if (const int c = finish(run_, out_, end)) return leave(c);
     print_timing();
     return leave(0);

@@ -29,6 +29,9 @@ struct DupmapFree {
 struct CoverageFree {
     void operator()(mtsv_coverage* q) const { mtsv_coverage_free(q); }
 };
+struct PileupFree {
+    void operator()(mtsv_pileup* q) const { mtsv_pileup_free(q); }
+};
 struct ArrayFree {
     void operator()(void* q) const { mtsv_free(q); }
 };
@@ -37,6 +40,7 @@ using BatchPtr = std::unique_ptr<mtsv_batch, BatchFree>;
 using FoldPtr = std::unique_ptr<mtsv_fold, FoldFree>;
 using DupmapPtr = std::unique_ptr<mtsv_dupmap, DupmapFree>;
 using CoveragePtr = std::unique_ptr<mtsv_coverage, CoverageFree>;
+using PileupPtr = std::unique_ptr<mtsv_pileup, PileupFree>;
 template <class T>
 using ArrayPtr = std::unique_ptr<T, ArrayFree>;  // what the library hands out for mtsv_free
 

@@ -91,6 +91,27 @@ int finish(const Run& run, Outputs& outputs, const RunEnd& end) {
         }
         mark("coverage report written");
     }
+    if (run.have_variants()) {
+        ArrayPtr<mtsv_pile_site> rows;
+        ArrayPtr<char> text;
+        uint64_t n_rows = 0, text_len = 0;
+        float ms = 0;
+        int rc = end.pileup ? mtsv_pileup_sites(end.pileup, run.min_depth, run.min_alt_reads, run.min_alt_ppm, out(rows), &n_rows, &ms) : MTSV_E_ARG;
+        if (rc == MTSV_OK) rc = mtsv_format_variants(rows.get(), n_rows, out(text), &text_len);
+        if (rc != MTSV_OK) {
+            logmsg("ERROR", std::string("Error running query: ") + (end.pileup ? mtsv_last_error() : "no pileup was counted"));
+            return 2;
+        }
+        FILE* vf = fopen(run.variants.c_str(), "wb");
+        const bool written = vf && fwrite(text.get(), 1, text_len, vf) == text_len;
+        if ((vf && fclose(vf) != 0) || !written) {
+            logmsg("ERROR", "Error writing to variants file");
+            return 11;
+        }
+        if (end.variant_sites) *end.variant_sites = n_rows;
+        if (end.variant_sites_ms) *end.variant_sites_ms = ms;
+        mark("variant sites written");
+    }
     char msg[160];
     snprintf(msg, sizeof msg, "All worker and result consumer threads terminated. Took %.3f seconds.", now_s() - end.t_begin);
     logmsg("INFO", msg);

@@ -16,6 +16,7 @@
 #include "dev_index.hpp"
 #include "fold.hpp"
 #include "mgindex.hpp"
+#include "pile.hpp"
 
 using namespace mtsv;
 
@@ -47,6 +48,15 @@ static int fail_arg(const char* msg) {
     } catch (const std::exception& e) {      \
         return fail(e);                      \
     }
+
+// a vector as an array for mtsv_free
+template <class T>
+static T* malloc_copy(const std::vector<T>& v) {
+    T* mem = (T*)malloc(std::max<size_t>(v.size(), 1) * sizeof(T));
+    if (!mem) throw std::bad_alloc();
+    if (!v.empty()) memcpy(mem, v.data(), v.size() * sizeof(T));
+    return mem;
+}
 
 namespace {
 struct SplitMix64 {
@@ -791,6 +801,82 @@ int mtsv_format_coverage_report(const mtsv_ref_coverage* rows, uint64_t n_rows, 
         if (!p) throw std::bad_alloc();
         memcpy(p, text.c_str(), text.size() + 1);
         *out = p;
+        *out_len = text.size();
+    })
+}
+
+// ---- pileup per reference position (pile.hip, k_pile.hip, pile_refs.hpp) ----
+static_assert(sizeof(mtsv_pile_site) == 48, "the pileup row");
+int mtsv_pileup_create(int hip_device, const uint32_t* taxa, uint64_t n_taxa, mtsv_pileup** out) {
+    if (!out || (n_taxa && !taxa)) return fail_arg("null argument");
+    GUARD(*out = new mtsv_pileup(hip_device, taxa, n_taxa))
+}
+
+void mtsv_pileup_free(mtsv_pileup* p) { delete p; }
+
+int mtsv_pileup_reset(mtsv_pileup* p) {
+    if (!p) return fail_arg("null argument");
+    GUARD(p->impl.reset())
+}
+
+int mtsv_pileup_add_run(mtsv_pileup* p, mtsv_batch* b, const mtsv_hit* hits, uint64_t n_hits, uint32_t edit_slack, uint64_t* n_piled, uint64_t* n_skipped,
+                        float* device_ms) {
+    if (!p || !b) return fail_arg("null argument");
+    GUARD(p->impl.add_run(b->impl, hits, n_hits, edit_slack, n_piled, n_skipped, device_ms))
+}
+
+int mtsv_pileup_info(const mtsv_pileup* p, mtsv_pileup_info_t* info) {
+    if (!p || !info) return fail_arg("null argument");
+    GUARD(p->impl.info(info))
+}
+
+int mtsv_pileup_download(mtsv_pileup* p, uint32_t tax_id, uint32_t gi, uint32_t** counts, uint8_t** ref, uint64_t* n_slots) {
+    if (!p || !counts || !ref || !n_slots) return fail_arg("null argument");
+    GUARD({
+        std::vector<uint32_t> c;
+        std::vector<uint8_t> r;
+        p->impl.download(tax_id, gi, c, r);
+        uint32_t* cm = malloc_copy(c);
+        uint8_t* rm = nullptr;
+        try {
+            rm = malloc_copy(r);
+        } catch (...) {
+            free(cm);
+            throw;
+        }
+        *counts = cm;
+        *ref = rm;
+        *n_slots = r.size();
+    })
+}
+
+int mtsv_pileup_sites(mtsv_pileup* p, uint32_t min_depth, uint32_t min_alt, uint32_t min_alt_ppm, mtsv_pile_site** rows, uint64_t* n_rows, float* device_ms) {
+    if (!p || !rows || !n_rows) return fail_arg("null argument");
+    GUARD({
+        std::vector<mtsv_pile_site> r;
+        p->impl.sites(min_depth, min_alt, min_alt_ppm, r, device_ms);
+        *rows = malloc_copy(r);
+        *n_rows = r.size();
+    })
+}
+
+int mtsv_format_variants(const mtsv_pile_site* rows, uint64_t n_rows, char** out, uint64_t* out_len) {
+    if ((!rows && n_rows) || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        std::string text = "taxid\tgi\tpos\tref\tdepth\tmatch\tA\tC\tG\tT\tN\tdel\tins\n";
+        char line[256];
+        for (uint64_t i = 0; i < n_rows; i++) {
+            const mtsv_pile_site& s = rows[i];
+            uint64_t depth = 0;
+            for (int c = 0; c < 7; c++) depth += s.n[c];
+            snprintf(line, sizeof line, "%u\t%u\t%u\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", s.tax_id, s.gi, s.pos, s.ref < 5 ? "ACGTN"[s.ref] : '.',
+                     (unsigned long long)depth, s.n[0], s.n[1], s.n[2], s.n[3], s.n[4], s.n[5], s.n[6], s.n[7]);
+            text += line;
+        }
+        char* q = (char*)malloc(text.size() + 1);
+        if (!q) throw std::bad_alloc();
+        memcpy(q, text.c_str(), text.size() + 1);
+        *out = q;
         *out_len = text.size();
     })
 }

@@ -549,5 +549,35 @@ void launch_place_map(hipStream_t s, const DevHit* hits, uint32_t n, const uint6
 void launch_place(hipStream_t s, uint32_t words, uint32_t blocks, const DevHit* hits, uint32_t n, const uint32_t* hit_bin, const uint32_t* hit_read,
                   const DevBin* bins, uint32_t n_bins, const uint8_t* text, const uint8_t* codes, const uint32_t* read_off, const uint32_t* off,
                   uint32_t* ring, uint32_t ring_cols, uint32_t* ops, void* out, uint64_t* ctr);
+// k_pile.hip: the pileup of placed hits, as the head of k_pile.hip defines it.  hits, hit_bin, hit_read, out and ops are the
+// placer's arrays after a placement that was not refused; bin_cnt[b]: the counters of bin b's reference ([slot][8] u32, the
+// bin's length + 1 slots), or null for a bin the pileup does not select; best: n_reads u32, set by the caller to all ones.
+// ctr: kPileCounters u64, zeroed by the caller.
+//   best:   best[hit_read[i]] = the smallest edit among the hits of a read
+//   count:  [kPileCtrSkipped] += hits in bins without counters, [kPileCtrCounted] += the others with edit <= best + slack
+//           (saturating); nothing else is written
+//   pile:   the counted hits' ops walked into the counters; [kPileCtrBroken] += scripts that would leave their reference (none)
+//   ref:    ref[s] for the n_slots slots of a new segment of n_refs references: ref_off[n_refs + 1] their first slots
+//           (ref_off[n_refs] = n_slots), text_start[r] the text position of reference r's first base; 0xff for a last slot
+//   tile_sums, (launch_scan: tile_pre[pile_tiles + 1]), sites_count, (launch_scan: tile_off), sites_rows; dump: the sites of a
+//           segment under (min_depth, min_alt, min_alt_ppm) as 48-byte rows in slot order, ref_key[r] = tax_id << 32 | gi; dump
+//           writes slots lo .. hi - 1 as [slot - lo][8] with channel 0 integrated.  tile: a power of two, 64 .. kPileTileMax
+constexpr uint32_t kPileTileMax = 1024, kPileTile = 1024;
+constexpr uint32_t kPileCtrCounted = 0, kPileCtrSkipped = 1, kPileCtrBroken = 2, kPileCounters = 3;
+void launch_pile_best(hipStream_t s, const DevHit* hits, uint32_t n, const uint32_t* hit_read, uint32_t n_reads, uint32_t* best);
+void launch_pile_count(hipStream_t s, const DevHit* hits, uint32_t n, const uint32_t* hit_bin, const uint32_t* hit_read, uint32_t n_bins, uint32_t n_reads,
+                       const uint32_t* best, uint32_t slack, uint32_t* const* bin_cnt, uint64_t* ctr);
+void launch_pile(hipStream_t s, const DevHit* hits, uint32_t n, const uint32_t* hit_bin, const uint32_t* hit_read, const DevBin* bins, uint32_t n_bins,
+                 uint32_t n_reads, const uint32_t* best, uint32_t slack, uint32_t* const* bin_cnt, const uint8_t* codes, const uint32_t* read_off,
+                 const void* out, const uint32_t* ops, uint64_t n_ops_total, uint64_t* ctr);
+void launch_pile_ref(hipStream_t s, const uint8_t* text, const uint32_t* ref_off, const uint32_t* text_start, uint32_t n_refs, uint32_t n_slots, uint8_t* ref);
+uint32_t pile_tiles(uint32_t n_slots, uint32_t tile);
+void launch_pile_tile_sums(hipStream_t s, const uint32_t* cnt, uint32_t n_slots, uint32_t tile, uint32_t* tile_sum);
+void launch_pile_sites_count(hipStream_t s, const uint32_t* cnt, uint32_t n_slots, uint32_t tile, const uint32_t* tile_pre, uint32_t min_depth, uint32_t min_alt,
+                             uint32_t min_alt_ppm, uint32_t* tile_cnt);
+void launch_pile_sites_rows(hipStream_t s, const uint32_t* cnt, uint32_t n_slots, uint32_t tile, const uint32_t* tile_pre, uint32_t min_depth, uint32_t min_alt,
+                            uint32_t min_alt_ppm, const uint32_t* tile_off, const uint32_t* ref_off, const uint64_t* ref_key, uint32_t n_refs, const uint8_t* ref,
+                            void* rows, uint64_t n_rows);
+void launch_pile_dump(hipStream_t s, const uint32_t* cnt, uint32_t n_slots, uint32_t tile, const uint32_t* tile_pre, uint32_t lo, uint32_t hi, uint32_t* dump);
 
 }  // namespace mtsv

@@ -1,5 +1,6 @@
 // place.hip -- mtsv_batch_place_hits (include/mtsv_amd.h): the alignments of a workspace's hits, by the kernels of k_place.hip.
-// A call stops twice on the host: after the map pass, which writes scratch and counters only, and after the placement kernel,
+// A call is three steps -- map_hits, place_mapped, and the copies to the host -- of which mtsv_pileup_add_run (pile.hip) takes
+// the first two and reads placements and ops where they lie.  A call stops twice on the host: after the map pass, which writes scratch and counters only, and after the placement kernel,
 // which writes the placer's own arrays only.  Of the workspace nothing is written but the codes of an uploaded batch, with the
 // bytes run() writes there: hits, assignments, statistics, flags and report are what they were, and a call that is refused at
 // either stop leaves the workspace as it was; nothing is handed out before the second stop.
@@ -85,11 +86,18 @@ void Placer::build_table(Batch& b) {
     table_ready = true;
 }
 
-void Placer::place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placement** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops_total,
-                   float* device_ms) {
-    if (device_ms) *device_ms = 0;
-    const double t0 = timing ? now_ms() : 0;
+mtsv_hit Placer::hit_at(uint64_t k) const {
+    mtsv_hit h{};
+    HIP_CHECK(hipMemcpy(&h, d_in.p + k, sizeof h, hipMemcpyDeviceToHost));
+    return h;
+}
+
+// The first half of a placement, up to the first refusal point: the hits next to each other in d_in, each with its bin, its
+// read and its op slots.  Nothing is placed yet.
+void Placer::map_hits(Batch& b, const mtsv_hit* hits, uint64_t n_hits, Placed& r) {
+    r = Placed{};
     const bool own = hits == nullptr;  // the hits of the workspace's last run, where they lie
+    r.own = own;
     if (!b.resident)
         throw std::runtime_error(b.last_run == Batch::kRunHostOneSegment || b.last_run == Batch::kRunHostSegments
                                      ? "arg: the workspace's last run was a host batch (hits are placed against a resident batch: mtsv_batch_upload / _take_reads / "
@@ -108,15 +116,7 @@ void Placer::place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placeme
     if (n >= (1ull << 32)) throw std::runtime_error("limit: " + std::to_string(n) + " hits, 2^32 or more, in mtsv_batch_place_hits");
     HIP_CHECK(hipSetDevice(device));
     if (!table_ready) build_table(b);
-    PoolArray h_out(n * kPlacementBytes);
-    if (!n) {  // nothing is launched
-        PoolArray h_ops(0);
-        *out = (mtsv_placement*)h_out.hand_out();
-        *ops = (uint32_t*)h_ops.hand_out();
-        *n_out = 0;
-        *n_ops_total = 0;
-        return;
-    }
+    if (!n) return;  // nothing is launched
     hipStream_t s = b.stream;
     if (!ev.created()) ev.create();
     const uint32_t N = (uint32_t)n;
@@ -155,11 +155,6 @@ void Placer::place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placeme
     HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     HIP_CHECK(hipGetLastError());
-    auto hit_at = [&](uint64_t k) {
-        mtsv_hit h{};
-        HIP_CHECK(hipMemcpy(&h, d_in.p + k, sizeof h, hipMemcpyDeviceToHost));
-        return h;
-    };
     // ---- the first refusal point ----
     if (ctr[kPlaceCtrUnknown] || ctr[kPlaceCtrRange] || ctr[kPlaceCtrAbsent] || ctr[kPlaceCtrStrand]) {
         std::string first;
@@ -173,6 +168,17 @@ void Placer::place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placeme
         throw std::runtime_error("limit: the hits' edit scripts may take " + std::to_string(total_ops) + " op slots, 2^32 or more, in mtsv_batch_place_hits");
     if (total_ops < n || span > 2ull * kMaxRegisterReadLen)
         throw std::runtime_error("internal: " + std::to_string(n) + " hits gave " + std::to_string(total_ops) + " op slots and a span of " + std::to_string(span));
+    r.n = n;
+    r.total_ops = total_ops;
+    r.span = span;
+}
+
+// The second half, up to the second refusal point: the ring, the kernel, and placements and ops valid in d_out and d_ops.
+void Placer::place_mapped(Batch& b, Placed& r) {
+    hipStream_t s = b.stream;
+    const uint64_t n = r.n, total_ops = r.total_ops, span = r.span;
+    const uint32_t N = (uint32_t)n;
+    uint64_t ctr[kPlaceCounters + 1] = {};
     // ---- the ring: a power of two of columns that holds every path with the column to its left ----
     const uint32_t words = myers_words(b.max_len);
     const uint32_t cols = std::max(pow2_at_least(span + 2), ring_env);
@@ -182,7 +188,6 @@ void Placer::place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placeme
     d_ring.room(s, lane_words * blocks * place_threads(), "the placement ring");
     d_ops.room(s, total_ops, "the edit scripts");
     d_out.room(s, n * kPlacementBytes, "the placements");
-    PoolArray h_ops(total_ops * sizeof(uint32_t));
     HIP_CHECK(hipMemsetAsync(d_ops.p, 0, total_ops * sizeof(uint32_t), s));  // (the slots a hit leaves unused are handed out too)
     HIP_CHECK(hipEventRecord(ev[2], s));
     launch_place(s, words, blocks, d_in.p, N, d_hit_bin.p, d_hit_read.p, b.di->d_bins, b.di->view.n_bins, b.di->d_text, b.d_codes.p, b.d_read_off.p, d_off.p,
@@ -202,6 +207,41 @@ void Placer::place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placeme
         throw std::runtime_error("arg: " + std::to_string(ctr[kPlaceCtrUnplaceable]) + " of " + std::to_string(n) +
                                  " hits are unplaceable: no column of their bin's text behind the offset reaches the edit they carry" + first);
     }
+    r.words = words;
+    r.cols = cols;
+    r.blocks = blocks;
+    r.columns = ctr[kPlaceCtrColumns];
+}
+
+void Placer::place_on_device(Batch& b, const mtsv_hit* hits, uint64_t n_hits, Placed& r) {
+    map_hits(b, hits, n_hits, r);
+    if (!r.n) return;
+    place_mapped(b, r);
+    HIP_CHECK(hipEventElapsedTime(&r.ms_map, ev[0], ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&r.ms_place, ev[2], ev[3]));
+}
+
+void Placer::place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placement** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops_total,
+                   float* device_ms) {
+    if (device_ms) *device_ms = 0;
+    const double t0 = timing ? now_ms() : 0;
+    Placed r;
+    map_hits(b, hits, n_hits, r);
+    const uint64_t n = r.n, total_ops = r.total_ops;
+    const bool own = r.own;
+    PoolArray h_out(n * kPlacementBytes);
+    if (!n) {  // nothing is launched
+        PoolArray h_ops(0);
+        *out = (mtsv_placement*)h_out.hand_out();
+        *ops = (uint32_t*)h_ops.hand_out();
+        *n_out = 0;
+        *n_ops_total = 0;
+        return;
+    }
+    PoolArray h_ops(total_ops * sizeof(uint32_t));
+    place_mapped(b, r);
+    hipStream_t s = b.stream;
+    const uint32_t words = r.words, cols = r.cols, blocks = r.blocks;
     HIP_CHECK(hipMemcpyAsync(h_out.p, d_out.p, n * kPlacementBytes, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(h_ops.p, d_ops.p, total_ops * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipEventRecord(ev[4], s));
@@ -211,10 +251,10 @@ void Placer::place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placeme
     HIP_CHECK(hipEventElapsedTime(&ms_place, ev[2], ev[3]));
     HIP_CHECK(hipEventElapsedTime(&ms_down, ev[3], ev[4]));
     if (device_ms) *device_ms = ms_map + ms_place + ms_down;
-    const uint64_t ring_bytes = ctr[kPlaceCtrColumns] * 2 * words * 4;
+    const uint64_t ring_bytes = r.columns * 2 * words * 4;
     if (trace)
         fprintf(stderr, "[place] %llu hits (%s), %llu op slots, %u words, ring of %u columns x %u workgroups, %llu columns stored: %.3f ms\n", (unsigned long long)n,
-                own ? "the last run's" : "given", (unsigned long long)total_ops, words, cols, blocks, (unsigned long long)ctr[kPlaceCtrColumns],
+                own ? "the last run's" : "given", (unsigned long long)total_ops, words, cols, blocks, (unsigned long long)r.columns,
                 ms_map + ms_place + ms_down);
     // MTSV_PLACE_TIMING=1: where a call spends its time (tools/place_ab.py reads this line)
     if (timing)

@@ -36,11 +36,26 @@ struct Placer {
     Placer(const Placer&) = delete;
     Placer& operator=(const Placer&) = delete;
 
+    // what a placement left on the device: n placements in d_out (hit k of d_in, with d_hit_bin[k] and d_hit_read[k]), their
+    // ops in d_ops[0 .. total_ops)
+    struct Placed {
+        uint64_t n = 0, total_ops = 0, span = 0, columns = 0;
+        bool own = false;
+        uint32_t words = 0, cols = 0, blocks = 0;
+        float ms_map = 0, ms_place = 0;
+    };
+
     void place(Batch& b, const mtsv_hit* hits, uint64_t n_hits, mtsv_placement** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops_total,
                float* device_ms);
+    // place() without its copies to the host: every refusal of place(), then placements and ops valid on the device and the
+    // stream idle.  r.n == 0: nothing was launched.
+    void place_on_device(Batch& b, const mtsv_hit* hits, uint64_t n_hits, Placed& r);
 
    private:
     void build_table(Batch& b);
+    void map_hits(Batch& b, const mtsv_hit* hits, uint64_t n_hits, Placed& r);
+    void place_mapped(Batch& b, Placed& r);
+    mtsv_hit hit_at(uint64_t k) const;
 };
 
 }  // namespace mtsv
