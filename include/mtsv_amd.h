@@ -733,6 +733,88 @@ int mtsv_fold_lca(mtsv_fold *f, const mtsv_taxonomy *tx, uint32_t edit_slack, mt
 int mtsv_format_clade_report(const mtsv_clade_stats *rows, uint64_t n_rows, uint64_t total_reads, const mtsv_taxonomy *tx,
                              char **out, uint64_t *out_len);
 
+/* ---- abundance: how much of each taxon, by expectation-maximisation over the ambiguous reads (abund.hip, k_abund.hip) -------
+ * The taxa report counts a read with twelve tied taxa twelve times and the LCA moves it to a genus or the root.
+ * mtsv_fold_abundance shares every read among its taxa in proportion to (current abundance of the taxon) x (how well the read
+ * fits it), re-estimates the abundances from the shares, and repeats -- the EM of Pathoscope, Bracken and Centrifuge.  The
+ * definition is exact, and integer wherever an order of operations could matter, so every tier and tile gives the same bits
+ * and a plain restatement with Python's int and float reproduces them (tests/abund_ref.py).
+ *
+ * Inputs: a fold f of any grain (N = its n_reads, U its TaxID union); a weight table w[0 .. n_w) of uint32_t in units of 2^-32,
+ * 1 <= n_w <= 255; edit_slack; max_iters; tol.
+ * Entries.  For a read r with records, e(r,t) is the smallest edit among r's records with TaxID t (the wide grains repeat a
+ *   TaxID), m(r) the smallest edit of all r's records, d(r,t) = e(r,t) - m(r).  t ENTERS r when d <= edit_slack (0xffffffff:
+ *   all, as in mtsv_fold_lca).  W(0) = 2^32 and W(d) = w[min(d, n_w) - 1] for d >= 1: the weight of the difference to the
+ *   read's best, which leaves the shares as the edit itself would and keeps the best taxon's weight at exactly 1.
+ * Mass.  A_k[t] is a uint64_t in units of 2^-32 reads.  A_0[t] = S for every TaxID that enters some read; S = 2^32 (one read)
+ *   unless MTSV_ABUND_START_MASS (tests; 1 .. 2^32, read by mtsv_fold_create) says otherwise.
+ * One iteration, for every read r and every entering t:
+ *   1. x_t = (A_k[t] * W(d)) >> 48, a 128-bit product            (on the device: A >> 16 for d = 0, else
+ *                                                                  __umul64hi(A, (uint64_t)W << 32) >> 16)
+ *   2. s = the sum of x_t, an integer: the order of the additions does not matter
+ *   3. if s == 0: x_t = W(d) >> 17 and s their sum -- the shares of a uniform prior; d = 0 makes that s >= 2^15
+ *   4. q_t = (uint64_t)(((double)x_t / (double)s) * 4294967296.0): an IEEE double division, a multiplication by a power of
+ *      two, a truncation.  x_t < 2^47 converts exactly; s < 2^63 is rounded once by the conversion
+ *   5. A_{k+1}[t] += q_t, an integer add: the order of the adds does not matter
+ *   Floating point is used only in step 4, per element (the library is built with -ffp-contract=off and without fast-math).
+ * Stopping.  After iteration k + 1, L1 = sum over t of |A_{k+1}[t] - A_k[t]|; the loop stops when L1 <= tol or after max_iters
+ *   iterations.  The check is made after every iteration, so the number of iterations is part of the result.  max_iters = 0
+ *   is legal: A stays A_0, and the assignment below is by smallest edit.
+ * Hard assignment, under the final A: read r is ASSIGNED to the entering t with the largest x_t (the fallback of step 3
+ *   included), ties to the smallest TaxID as unsigned; its record is (r, t, e(r,t)).
+ * Limits, both MTSV_E_LIMIT before anything is written: 2^31 or more reads with a record (keeps A below 2^63); a read with
+ *   65536 or more entering taxa (keeps s below 2^63).
+ * Example.  Records (read, tax, edit) (0,5,0) (1,5,1) (1,7,1) (2,5,2) (2,7,0) (3,9,3), w = {2^31, 2^30, ...}, slack all, tol 0:
+ *   after iteration 1  A[5] = 7301444403  A[7] = 5583457484  A[9] = 4294967296  L1 = 4294967295
+ *   after iteration 2  A[5] = 7786955038  A[7] = 5097946848  A[9] = 4294967296  L1 = 971021271
+ *   after iteration 3  A[5] = 8077478865  A[7] = 4807423021  A[9] = 4294967296  L1 = 581047654
+ *   and then reads 0, 1 go to TaxID 5, read 2 to 7, read 3 to 9; total_mass 17179869182.
+ *
+ * mtsv_fold_abundance: f is never changed.  Any of rows, info, out may be NULL; rows needs n_rows.
+ *   rows: one row per TaxID that enters at least one read, ascending tax_id; malloc'd, mtsv_free.  mass = the final A;
+ *     reads_any = the reads the taxon enters; reads_unique = those where it is the only one entering; assigned = the reads of
+ *     the hard assignment.
+ *   info: reads = the reads with a record; entries = the sum of entering taxa over reads; taxa = the rows; total_mass = the
+ *     sum of mass; l1_change = the last L1 (0 with zero iterations); iterations; converged = 1 when the loop stopped on tol.
+ *   out: another fold of the same device at MTSV_GRAIN_TAXID.  It becomes a fold as after mtsv_fold_reset(out, N) that holds
+ *     the assigned records, its union the TaxIDs present, exactly as mtsv_fold_lca fills its out; everything a fold offers
+ *     then works on it.
+ *   device_ms (may be NULL): device time of the kernels.
+ * MTSV_E_ARG, with both folds as they were: a null f or w; n_w outside 1..255; rows without n_rows; out == f; out on another
+ *   device or of a wide grain.  An empty f gives zero rows, a zeroed info, an empty out, and no launch.  A record whose TaxID is
+ *   not in f's union is an internal error, MTSV_E_DEVICE.  A refused device allocation leaves both folds as they were
+ *   (MTSV_ALLOC_REFUSE names: "the abundance entries", "the abundance masses").
+ * On the device (k_abund.hip).  Prepare, once per call, in tiles of MTSV_ABUND_TILE records (a power of two, 64..1024): the
+ *   records become a compact entry list -- per read its offset; per entry the union slot, d clipped to n_w as a byte, e(r,t) --
+ *   with reads_any, reads_unique and a work list of the reads of more than MTSV_ABUND_LANE_MAX entries (default 16, 0..1024;
+ *   0 sends every read on).  An iteration streams about 5 bytes per entry: a persistent step kernel in which a lane takes
+ *   each short read and a wavefront each listed read; the adds go to per-workgroup 64-bit counters in LDS, flushed with one
+ *   global add per non-zero counter, when the union has at most MTSV_ABUND_DENSE_MAX TaxIDs (default 8192 = 64 KiB, 0..8192;
+ *   0: never), else they are global 64-bit atomic adds.  A delta kernel computes L1, moves A_{k+1} to A_k and zeroes A_{k+1};
+ *   the host reads 8 bytes per iteration.  A final kernel does the hard assignment in the same two tiers.  All knobs are
+ *   read by mtsv_fold_create; results depend on none of them except MTSV_ABUND_START_MASS.  MTSV_ABUND_TIMING=1 prints the
+ *   steps' times to stderr.
+ * Not done here: mtsv-binner --fold-on-gpu, whose super-batches are separate folds (EM masses do not add across pieces);
+ *   genome-length normalisation; a roll-up of masses through a taxonomy.
+ * mtsv_abundance_weights (host only): x = 1.0; for d = 1 .. n_w: x = x * q, w[d - 1] = min((uint64_t)floor(x * 2^32),
+ *   2^32 - 1).  MTSV_E_ARG unless 0 < q <= 1 and 1 <= n_w <= 255.
+ * mtsv_format_abundance (host only): the TSV `taxid mass abundance_pct reads_any reads_unique assigned`, a header line and one
+ *   line per row; mass is (double)mass / 2^32 as %.6f, abundance_pct (double)mass * 100 / (double)max(total_mass, 1) as %.4f.
+ *   *out malloc'd, mtsv_free. */
+typedef struct {
+    uint32_t tax_id, _pad;
+    uint64_t mass, reads_any, reads_unique, assigned;
+} mtsv_abundance_row; /* 40 bytes */
+typedef struct {
+    uint64_t reads, entries, taxa, total_mass, l1_change;
+    uint32_t iterations, converged;
+} mtsv_abundance_info; /* 48 bytes */
+int mtsv_fold_abundance(mtsv_fold *f, const uint32_t *w, uint32_t n_w, uint32_t edit_slack, uint32_t max_iters, uint64_t tol,
+                        mtsv_fold *out, mtsv_abundance_row **rows, uint64_t *n_rows, mtsv_abundance_info *info, float *device_ms);
+int mtsv_abundance_weights(double q, uint32_t n_w, uint32_t *w);
+int mtsv_format_abundance(const mtsv_abundance_row *rows, uint64_t n_rows, const mtsv_abundance_info *info, char **out,
+                          uint64_t *out_len);
+
 /* ---- paired-end reads: the mates' assignments joined (pair.hip, k_pair.hip) ------------------------------------------------
  * The two mates of a fragment come from one organism, and from one reference sequence a few hundred bases apart.  A fold whose
  * reads are numbered so that reads 2p and 2p + 1 are the mates of pair p (mate 0 and mate 1) is joined into a fold of PAIRS:

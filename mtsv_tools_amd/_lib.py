@@ -92,6 +92,10 @@ RANK_UNKNOWN = 0xffffffff  # MTSV_RANK_UNKNOWN
 SLACK_ALL = 0xffffffff  # edit_slack of mtsv_fold_lca: every TaxID of a read enters
 PAIR_BOTH, PAIR_EITHER, PAIR_PROPER = 0, 1, 2  # MTSV_PAIR_*
 
+# mtsv_abundance_row: 4 + 4 pad + 4 * 8 = 40 bytes
+ABUNDANCE_ROW_DTYPE = np.dtype({"names": ["tax_id", "mass", "reads_any", "reads_unique", "assigned"], "formats": ["<u4", "<u8", "<u8", "<u8", "<u8"],
+                                "offsets": [0, 8, 16, 24, 32], "itemsize": 40})
+
 # mtsv_ref_coverage: 4 + 4 + 5 * 8 = 48 bytes
 REF_COVERAGE_DTYPE = np.dtype({"names": ["tax_id", "gi", "length", "reads", "alignments", "aligned_bases", "covered_bases"],
                                "formats": ["<u4", "<u4", "<u8", "<u8", "<u8", "<u8", "<u8"], "offsets": [0, 4, 8, 16, 24, 32, 40], "itemsize": 48})
@@ -118,6 +122,14 @@ class PileupInfo(C.Structure):  # mtsv_pileup_info_t
 
 class TaxonomyInfo(C.Structure):  # mtsv_taxonomy_info_t
     _fields_ = [("n_nodes", C.c_uint64), ("n_implied_roots", C.c_uint64), ("n_ranks", C.c_uint32), ("max_depth", C.c_uint32)]
+
+
+class AbundanceInfo(C.Structure):  # mtsv_abundance_info: 5 * 8 + 2 * 4 = 48 bytes
+    _fields_ = [("reads", C.c_uint64), ("entries", C.c_uint64), ("taxa", C.c_uint64), ("total_mass", C.c_uint64), ("l1_change", C.c_uint64),
+                ("iterations", C.c_uint32), ("converged", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class PairStats(C.Structure):  # mtsv_pair_stats
@@ -153,6 +165,7 @@ EXPORTS = [
     "mtsv_fold_lca", "mtsv_format_clade_report",
     "mtsv_dupmap_create", "mtsv_dupmap_free", "mtsv_batch_take_unique", "mtsv_dupmap_download", "mtsv_fold_expand",
     "mtsv_fold_pair",
+    "mtsv_fold_abundance", "mtsv_abundance_weights", "mtsv_format_abundance",
     "mtsv_coverage_create", "mtsv_coverage_free", "mtsv_coverage_add_index", "mtsv_coverage_add_refs", "mtsv_coverage_reset",
     "mtsv_coverage_add_fold", "mtsv_coverage_rows", "mtsv_format_coverage_report",
     "mtsv_batch_place_hits", "mtsv_format_placements",
@@ -259,6 +272,9 @@ def lib():
         L.mtsv_taxonomy_rank_name.restype = C.c_char_p
         L.mtsv_fold_lca.argtypes = [vp, vp, u32, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_float)]
         L.mtsv_format_clade_report.argtypes = [vp, u64, u64, vp, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_fold_abundance.argtypes = [vp, vp, u32, u32, u32, u64, vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(AbundanceInfo), C.POINTER(C.c_float)]
+        L.mtsv_abundance_weights.argtypes = [C.c_double, u32, vp]
+        L.mtsv_format_abundance.argtypes = [vp, u64, C.POINTER(AbundanceInfo), C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_dupmap_create.argtypes = [i32, C.POINTER(vp)]
         L.mtsv_dupmap_free.argtypes = [vp]
         L.mtsv_dupmap_free.restype = None
@@ -832,6 +848,18 @@ class Fold:
                                    C.byref(n), C.byref(total), C.byref(ms)))
         return (_records_from(ptr, n.value, CLADE_STATS_DTYPE) if rows else None), total.value, ms.value
 
+    def abundance(self, weights, slack=SLACK_ALL, max_iters=100, tol=0, out=None, rows=True):
+        """mtsv_fold_abundance: expectation-maximisation over the reads' entering taxa (those within `slack` edits of the read's
+        smallest; SLACK_ALL: all).  weights: the table of abundance_weights, 1 .. 255 uint32 in units of 2^-32; tol: the L1
+        change, in units of 2^-32 reads, at which the loop stops.  out: another Fold of this device at GRAIN_TAXID that takes
+        one record (read, assigned TaxID, its smallest edit) per read.  Returns (rows as an ABUNDANCE_ROW_DTYPE array ascending
+        by tax_id, or None without rows; the info as a dict; device ms)"""
+        w = np.ascontiguousarray(weights, dtype="<u4")
+        ptr, n, info, ms = C.c_void_p(), C.c_uint64(), AbundanceInfo(), C.c_float()
+        _check(lib().mtsv_fold_abundance(self.h, w.ctypes.data, len(w), int(slack), int(max_iters), int(tol), out.h if out is not None else None,
+                                         C.byref(ptr) if rows else None, C.byref(n), C.byref(info), C.byref(ms)))
+        return (_records_from(ptr, n.value, ABUNDANCE_ROW_DTYPE) if rows else None), info.as_dict(), ms.value
+
     def pair(self, mode, max_insert=0, unpaired_edits=0, out=None):
         """mtsv_fold_pair: reads 2p and 2p + 1 of this fold are the mates of pair p; the Fold out (this device, GRAIN_TAXID)
         becomes the fold of the pairs: one record (p, TaxID, edit) per TaxID that PAIR_BOTH, PAIR_EITHER or PAIR_PROPER keeps.
@@ -1065,6 +1093,27 @@ class Taxonomy:
             self.close()
         except Exception:
             pass
+
+
+def abundance_weights(q, n_w=64):
+    """mtsv_abundance_weights: w[d - 1] = min(floor(q^d * 2^32), 2^32 - 1) for d = 1 .. n_w, as a uint32 array; 0 < q <= 1"""
+    w = np.zeros(max(int(n_w), 1), dtype="<u4")
+    _check(lib().mtsv_abundance_weights(float(q), int(n_w), w.ctypes.data))
+    return w[:int(n_w)]
+
+
+def format_abundance(rows, info):
+    """mtsv_format_abundance: the TSV of mtsv-collapse --abundance, as bytes; info: the dict of Fold.abundance (total_mass is used)"""
+    out_rows = np.zeros(len(rows), dtype=ABUNDANCE_ROW_DTYPE)
+    for f in ABUNDANCE_ROW_DTYPE.names:
+        out_rows[f] = rows[f]
+    c_info = AbundanceInfo(**{k: int(v) for k, v in info.items()})
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_abundance(out_rows.ctypes.data, len(out_rows), C.byref(c_info), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value)
+    finally:
+        lib().mtsv_free(out)
 
 
 def format_clade_report(rows, total_reads, tx=None):

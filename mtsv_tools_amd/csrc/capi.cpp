@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mtsv_amd.h"
+#include "abund_rows.hpp"
 #include "batch.hpp"
 #include "cover.hpp"
 #include "dedup.hpp"
@@ -708,6 +709,38 @@ int mtsv_fold_lca(mtsv_fold* f, const mtsv_taxonomy* tx, uint32_t edit_slack, mt
             *rows = mem;
             *n_rows = r.size();
         }
+    })
+}
+
+// ---- abundance by expectation-maximisation (abund.hip, k_abund.hip, abund_rows.hpp) ----
+int mtsv_fold_abundance(mtsv_fold* f, const uint32_t* w, uint32_t n_w, uint32_t edit_slack, uint32_t max_iters, uint64_t tol, mtsv_fold* out,
+                        mtsv_abundance_row** rows, uint64_t* n_rows, mtsv_abundance_info* info, float* device_ms) {
+    if (!f || !w) return fail_arg("null argument");
+    if (rows && !n_rows) return fail_arg("rows without n_rows");
+    GUARD({
+        std::vector<mtsv_abundance_row> r;
+        f->impl.abundance(w, n_w, edit_slack, max_iters, tol, out ? &out->impl : nullptr, rows ? &r : nullptr, info, device_ms);
+        if (rows) {
+            *rows = malloc_copy(r);
+            *n_rows = r.size();
+        }
+    })
+}
+
+int mtsv_abundance_weights(double q, uint32_t n_w, uint32_t* w) {
+    if (!w) return fail_arg("null argument");
+    GUARD(abundance_weights(q, n_w, w))
+}
+
+int mtsv_format_abundance(const mtsv_abundance_row* rows, uint64_t n_rows, const mtsv_abundance_info* info, char** out, uint64_t* out_len) {
+    if ((!rows && n_rows) || !info || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        const std::string text = format_abundance(rows, n_rows, info);
+        char* p = (char*)malloc(text.size() + 1);
+        if (!p) throw std::bad_alloc();
+        memcpy(p, text.c_str(), text.size() + 1);
+        *out = p;
+        *out_len = text.size();
     })
 }
 

@@ -19,6 +19,14 @@
 // lines, READ_ID:LCA=EDIT in the order of -o's, are --lca-output, and the reads per clade, --clade-report.  -o and --report
 // are what they are without these options.  The host path has no such step: where --on-gpu alone would hand the input to
 // it, a run with --taxonomy ends with the reason on stderr, exit code 2 and none of the two files.
+//
+// --abundance <TSV> [--reassigned <PATH>] (only with --on-gpu): how much of each taxon.  mtsv_fold_abundance (k_abund.hip)
+// runs expectation-maximisation over the ambiguous reads of the same fold: a read is shared among its taxa in proportion to the
+// taxon's current abundance times --abundance-mismatch Q (default 0.25) to the power of the edits above the read's best, for
+// up to --abundance-iters iterations (100) or until the masses move by no more than --abundance-tol reads (0.01);
+// --abundance-slack N keeps only the taxa within N edits of the read's best (default all).  --abundance is the TSV of masses and
+// counts, --reassigned the lines READ_ID:TAXID=EDIT of the one taxon every read is assigned to, in the order of -o's.  -o and
+// --report are unchanged; refused input ends as with --taxonomy.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -109,6 +117,15 @@ struct LcaOptions {
     bool on() const { return !taxonomy.empty(); }
 };
 
+struct AbundOptions {
+    std::string table, reassigned;
+    double mismatch = 0.25;
+    uint32_t slack = 0xffffffffu, iters = 100;
+    uint64_t tol = 42949672;  // floor(0.01 * 2^32)
+    bool on() const { return !table.empty(); }
+};
+constexpr uint32_t kAbundWeights = 64;
+
 bool write_file(const std::string& path, const char* p, uint64_t len) {
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -118,12 +135,12 @@ bool write_file(const std::string& path, const char* p, uint64_t len) {
 
 // mtsv-collapse --on-gpu.  Returns the exit code, or kGpuFallBack with nothing written.
 int run_on_gpu(const std::vector<std::string>& files, const std::string& out_path, const std::string& report, bool by_gi, int device, bool verbose,
-               const LcaOptions& lca) {
+               const LcaOptions& lca, const AbundOptions& abund) {
     namespace mc = mtsv_collapse;
     const bool timing = getenv("MTSV_COLLAPSE_TIMING") != nullptr;
     auto fall_back = [&](const std::string& why) {
-        if (lca.on()) {  // (the host path has no LCA step)
-            fprintf(stderr, "mtsv-collapse: --on-gpu: %s; --taxonomy needs the device path\n", why.c_str());
+        if (lca.on() || abund.on()) {  // (the host path has no LCA step and no abundance step)
+            fprintf(stderr, "mtsv-collapse: --on-gpu: %s; %s needs the device path\n", why.c_str(), lca.on() ? "--taxonomy" : "--abundance");
             return 2;
         }
         if (verbose) fprintf(stderr, "mtsv-collapse: --on-gpu: %s; the host path takes the input\n", why.c_str());
@@ -269,6 +286,38 @@ int run_on_gpu(const std::vector<std::string>& files, const std::string& out_pat
         if (want_lines && mtsv_fold_format_text(tax.per_read, ids.data(), id_off.data(), n_reads, &lca_text, &lca_len, nullptr) != MTSV_OK)
             return lca_error("mtsv_fold_format_text (LCA lines)");
     }
+    // ---- the abundances and the reads' one taxon, from the same fold; both texts are complete before a file is created ----
+    char *abund_text = nullptr, *reassigned_text = nullptr;
+    uint64_t abund_len = 0, reassigned_len = 0;
+    TextCloser abund_hold{abund_text, reassigned_text};
+    struct FoldCloser {
+        mtsv_fold* f = nullptr;
+        ~FoldCloser() { mtsv_fold_free(f); }
+    } assigned;
+    if (abund.on()) {
+        auto abund_error = [&](const char* what) {
+            mtsv_free(text);
+            mtsv_free(rep_text);
+            return device_error(what);
+        };
+        uint32_t w[kAbundWeights];
+        if (mtsv_abundance_weights(abund.mismatch, kAbundWeights, w) != MTSV_OK) return abund_error("mtsv_abundance_weights");
+        const bool want_lines = !abund.reassigned.empty();
+        if (want_lines && mtsv_fold_create(device, MTSV_GRAIN_TAXID, &assigned.f) != MTSV_OK) return abund_error("no fold for the reads' assignments");
+        mtsv_abundance_row* rows = nullptr;
+        uint64_t n_rows = 0;
+        mtsv_abundance_info info;
+        if (mtsv_fold_abundance(fold, w, kAbundWeights, abund.slack, abund.iters, abund.tol, assigned.f, &rows, &n_rows, &info, nullptr) != MTSV_OK)
+            return abund_error("mtsv_fold_abundance");
+        const int rc = mtsv_format_abundance(rows, n_rows, &info, &abund_text, &abund_len);
+        mtsv_free(rows);
+        if (rc != MTSV_OK) return abund_error("mtsv_format_abundance");
+        if (want_lines && mtsv_fold_format_text(assigned.f, ids.data(), id_off.data(), n_reads, &reassigned_text, &reassigned_len, nullptr) != MTSV_OK)
+            return abund_error("mtsv_fold_format_text (reassigned lines)");
+        if (verbose)
+            fprintf(stderr, "mtsv-collapse: --abundance: %llu reads, %llu entries, %llu taxa, %u iterations, %s\n", (unsigned long long)info.reads,
+                    (unsigned long long)info.entries, (unsigned long long)info.taxa, info.iterations, info.converged ? "converged" : "stopped at the cap");
+    }
     const double t4 = now_ms();
     FILE* out = fopen(out_path.c_str(), "wb");
     if (!out) {
@@ -304,6 +353,15 @@ int run_on_gpu(const std::vector<std::string>& files, const std::string& out_pat
             return 101;
         }
     }
+    if (abund.on()) {
+        const bool ok = write_file(abund.table, abund_text, abund_len) && (abund.reassigned.empty() || write_file(abund.reassigned, reassigned_text, reassigned_len));
+        if (!ok) {
+            remove(abund.table.c_str());
+            if (!abund.reassigned.empty()) remove(abund.reassigned.c_str());
+            fprintf(stderr, "thread 'main' panicked: Unable to write the abundance table or the reassigned lines\n");
+            return 101;
+        }
+    }
     const double t5 = now_ms();
     // MTSV_COLLAPSE_TIMING=1: where the device path spends its time (tools/collapse_ab.py reads this line)
     if (timing)
@@ -323,6 +381,8 @@ int main(int argc, char** argv) {
     int device = 0;
     LcaOptions lca;
     bool slack_given = false;
+    AbundOptions abund;
+    const char* abund_given[4] = {nullptr, nullptr, nullptr, nullptr};  // the options that need --abundance, as they were met
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         auto val = [&]() -> std::string {
@@ -352,7 +412,47 @@ int main(int argc, char** argv) {
             lca.slack = (uint32_t)n;
             slack_given = true;
         }
-        else if (k == "--device") {
+        else if (k == "--abundance") abund.table = val();
+        else if (k == "--reassigned") abund.reassigned = val();
+        else if (k == "--abundance-mismatch") {
+            const std::string v = val();
+            char* end = nullptr;
+            abund.mismatch = strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(abund.mismatch > 0.0) || !(abund.mismatch <= 1.0)) {
+                fprintf(stderr, "error: Invalid value for '--abundance-mismatch <Q>': %s\n", v.c_str());
+                return 1;
+            }
+            abund_given[0] = "--abundance-mismatch <Q>";
+        } else if (k == "--abundance-slack") {
+            const std::string v = val();
+            uint64_t n = 0;
+            if (v == "all") n = 0xffffffffull;
+            else if (!parse_u64(v, 0xffffffffull, &n)) {
+                fprintf(stderr, "error: Invalid value for '--abundance-slack <N|all>': %s\n", v.c_str());
+                return 1;
+            }
+            abund.slack = (uint32_t)n;
+            abund_given[1] = "--abundance-slack <N|all>";
+        } else if (k == "--abundance-iters") {
+            const std::string v = val();
+            uint64_t n = 0;
+            if (!parse_u64(v, 0xffffffffull, &n)) {
+                fprintf(stderr, "error: Invalid value for '--abundance-iters <N>': %s\n", v.c_str());
+                return 1;
+            }
+            abund.iters = (uint32_t)n;
+            abund_given[2] = "--abundance-iters <N>";
+        } else if (k == "--abundance-tol") {
+            const std::string v = val();
+            char* end = nullptr;
+            const double reads = strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(reads >= 0.0) || !(reads < 4294967296.0)) {  // (reads * 2^32 must fit 64 bits)
+                fprintf(stderr, "error: Invalid value for '--abundance-tol <READS>': %s\n", v.c_str());
+                return 1;
+            }
+            abund.tol = (uint64_t)(reads * 4294967296.0);  // (the product is exact but for its exponent: the cast is the floor)
+            abund_given[3] = "--abundance-tol <READS>";
+        } else if (k == "--device") {
             const std::string v = val();
             char* end = nullptr;
             const long d = strtol(v.c_str(), &end, 10);
@@ -364,7 +464,8 @@ int main(int argc, char** argv) {
             device_given = true;
         } else if (k == "-h" || k == "--help") {
             printf("mtsv-collapse -o <OUTPUT> [--mode taxid|taxid-gi] [--report <TSV>] [-t N] [--on-gpu [--device N] [--taxonomy <nodes.dmp> "
-                   "[--lca-output <PATH>] [--clade-report <TSV>] [--lca-slack <N|all>]]] <FILES>...\n");
+                   "[--lca-output <PATH>] [--clade-report <TSV>] [--lca-slack <N|all>]] [--abundance <TSV> [--abundance-mismatch <Q>] "
+                   "[--abundance-slack <N|all>] [--abundance-iters <N>] [--abundance-tol <READS>] [--reassigned <PATH>]]] <FILES>...\n");
             return 0;
         } else if (!k.empty() && k[0] == '-') {
             fprintf(stderr, "error: Found argument '%s' which wasn't expected\n", k.c_str());
@@ -394,9 +495,24 @@ int main(int argc, char** argv) {
             fprintf(stderr, "error: The argument '%s' requires '--taxonomy <nodes.dmp>'\n", o.first);
             return 1;
         }
+    if (abund.on() && !on_gpu) {
+        fprintf(stderr, "error: The argument '--abundance <TSV>' requires '--on-gpu'\n");
+        return 1;
+    }
+    if (!abund.on()) {
+        if (!abund.reassigned.empty()) {
+            fprintf(stderr, "error: The argument '--reassigned <PATH>' requires '--abundance <TSV>'\n");
+            return 1;
+        }
+        for (const char* o : abund_given)
+            if (o) {
+                fprintf(stderr, "error: The argument '%s' requires '--abundance <TSV>'\n", o);
+                return 1;
+            }
+    }
     const bool by_gi = mode == "taxid-gi";
     if (on_gpu) {
-        const int rc = run_on_gpu(files, out_path, report, by_gi, device, verbose, lca);
+        const int rc = run_on_gpu(files, out_path, report, by_gi, device, verbose, lca, abund);
         if (rc != kGpuFallBack) return rc;
     }
 

@@ -34,6 +34,10 @@ Fold::Fold(int device_, int grain_) : device(device_), grain(grain_) {
     lca_tile = tile_from_env("MTSV_LCA_TILE", kLcaTile, 64, kLcaTileMax);
     pair_tile = tile_from_env("MTSV_PAIR_TILE", kPairTile, 64, kPairTileMax);
     if (const char* e = getenv("MTSV_PAIR_LANE_MAX")) pair_lane_max = (uint32_t)std::min<uint64_t>(strtoull(e, nullptr, 10), kPairLaneMaxMax);
+    abund_tile = tile_from_env("MTSV_ABUND_TILE", kAbundTile, 64, kAbundTileMax);
+    if (const char* e = getenv("MTSV_ABUND_LANE_MAX")) abund_lane_max = (uint32_t)std::min<uint64_t>(strtoull(e, nullptr, 10), kAbundLaneMaxMax);
+    if (const char* e = getenv("MTSV_ABUND_DENSE_MAX")) abund_dense_max = (uint32_t)std::min<uint64_t>(strtoull(e, nullptr, 10), kAbundDenseMax);
+    if (const char* e = getenv("MTSV_ABUND_START_MASS")) abund_start_mass = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 10), 1), 1ull << 32);
     trace = getenv("MTSV_TRACE") != nullptr;
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -47,6 +51,7 @@ Fold::~Fold() {
     parser.reset();
     lca_state.reset();
     pair_state.reset();
+    abund_state.reset();
     if (stream) (void)hipStreamDestroy(stream);
 }
 

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "../../include/mtsv_amd.h"
+#include "abund.hpp"
 #include "batch.hpp"
 #include "lca.hpp"
 #include "pair.hpp"
@@ -44,6 +45,11 @@ struct Fold {
     uint32_t pair_tile = kPairTile;          // MTSV_PAIR_TILE, read at creation (tests)
     uint32_t pair_lane_max = kPairLaneMax;   // MTSV_PAIR_LANE_MAX, read at creation (tests): 0 sends every window to the wavefront tier
     std::unique_ptr<PairState> pair_state;   // created by the first pair
+    uint32_t abund_tile = kAbundTile;            // MTSV_ABUND_TILE, read at creation (tests)
+    uint32_t abund_lane_max = kAbundLaneMax;     // MTSV_ABUND_LANE_MAX, read at creation (tests): 0 sends every read to the wavefront tier
+    uint32_t abund_dense_max = kAbundDenseMax;   // MTSV_ABUND_DENSE_MAX, read at creation: the largest union whose adds go through LDS; 0: none
+    uint64_t abund_start_mass = 1ull << 32;      // MTSV_ABUND_START_MASS, read at creation (tests): A_0 of an entering TaxID, 1 .. 2^32
+    std::unique_ptr<AbundState> abund_state;     // created by the first abundance
 
     Fold(int device, int grain);
     ~Fold();
@@ -71,6 +77,12 @@ struct Fold {
     // k_pair.hip) into `out` (a fold of this device at MTSV_GRAIN_TAXID, not this one), which becomes as after reset(n_reads / 2)
     // with those records and this fold's TaxID union; stats may be null; this fold is not changed
     void pair(int mode, uint32_t max_insert, uint32_t unpaired_edits, Fold* out, mtsv_pair_stats* stats, float* device_ms);
+    // abundance by expectation-maximisation over the reads' entering taxa (abund.hip, k_abund.hip; the definition is in
+    // include/mtsv_amd.h): one record (read, assigned TaxID, its smallest edit) per read into `out` (may be null; a fold of this
+    // device at MTSV_GRAIN_TAXID, not this one), which becomes as after reset(n_reads) with those records; a row per entering
+    // TaxID (rows and info may be null); this fold is not changed
+    void abundance(const uint32_t* w, uint32_t n_w, uint32_t edit_slack, uint32_t max_iters, uint64_t tol, Fold* out, std::vector<mtsv_abundance_row>* rows,
+                   mtsv_abundance_info* info, float* device_ms);
 
     // A write of a whole new record list (fold_in, lca, pair, DupMap::expand) is staged: dst is the array that is not current, or,
     // when that is too small, the first of a new pair, which the fold takes only with commit.  A Staged that is not

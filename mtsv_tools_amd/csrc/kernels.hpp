@@ -426,6 +426,51 @@ void launch_lca_span(hipStream_t s, int grain, const void* rec, uint32_t n, uint
 void launch_lca_walk(hipStream_t s, uint32_t n_slots, uint32_t n_nodes, uint32_t max_depth, const uint32_t* lo, const uint32_t* hi, const uint32_t* m,
                      const uint32_t* parent, const uint32_t* last, const uint32_t* tax, void* out, uint32_t* direct, uint64_t* ctr);
 void launch_lca_clade(hipStream_t s, uint32_t n_nodes, const uint32_t* last, const uint32_t* prefix, uint32_t* clade);
+// k_abund.hip: abundance by expectation-maximisation over a sorted assignment list (the definition: include/mtsv_amd.h).  Two
+// kinds of heads over the n records: a READ head (the read differs from the predecessor's; the reads with a record are numbered
+// by them, n_reads of them) and a RUN head (read or tax_id differs; a run is the records of one (read, tax_id), n_runs of them,
+// in key order, so the runs of a read are consecutive and ascend by tax_id).  A workgroup owns `tile` records (a power of two,
+// 64 .. kAbundTileMax).  ctr: kAbundCounters u64, zeroed by the caller.
+//   heads:  cnt_r[t] / cnt_p[t] = the read heads / run heads of tile t
+//   (launch_scan over each: off_r / off_p[0 .. tiles])
+//   min:    m[read] = the read's smallest edit, e_run[run] = the run's (both set to all ones by the caller); read_id[read];
+//           read_first[read] = its first run; run_tax[run], run_read[run]
+//   flag:   flag[run] = e_run - m[run_read] <= slack
+//   (launch_scan over flag: off[0 .. n_runs], off[n_runs] = the entries; the flagged runs of a read are its entries, consecutive)
+//   write:  read_off[0 .. n_reads]; per entry its place in the union u_tax (ent_slot), min(d, n_w) (ent_d) and e_run (ent_e);
+//           any[slot] += 1 per entry, uniq[slot] += 1 for the entry of a read with one (both zeroed by the caller); the reads of
+//           more than lane_max entries to list[ctr[kAbundCtrList]++]; ctr[kAbundCtrMissing] += entries whose TaxID u_tax does
+//           not hold, ctr[kAbundCtrLong] += reads of 65536 entries or more
+//   init:   mass[slot] = any[slot] ? start : 0, next[slot] = 0
+//   step:   one iteration: next[slot] += q per entry; dense: through per-workgroup counters in LDS (n_union <= kAbundDenseMax)
+//   delta:  *l1 (zeroed by the caller) += |next - mass|; mass = next; next = 0
+//   final:  out[read] = (read_id, tax of the entry with the largest x -- ties: the first --, its e) (16-byte records);
+//           assigned[slot] += 1 (zeroed by the caller)
+// w: the weight table, n_w entries.  `blocks`: the workgroups of the persistent kernels.
+constexpr uint32_t kAbundTileMax = 1024, kAbundTile = 1024, kAbundLaneMax = 16, kAbundLaneMaxMax = 1024, kAbundDenseMax = 8192;
+constexpr uint32_t kAbundEntriesMax = 65536;  // a read may have fewer than this many
+constexpr uint32_t kAbundCtrMissing = 0, kAbundCtrLong = 1, kAbundCtrList = 2, kAbundCounters = 3;
+struct AbundEntries {  // what an iteration reads
+    uint32_t n_reads, n_list, lane_max, n_union;
+    const uint32_t *read_off, *ent_slot, *list, *w;
+    const uint8_t* ent_d;
+};
+uint32_t abund_tiles(uint64_t n, uint32_t tile);
+void launch_abund_heads(hipStream_t s, int grain, const void* rec, uint32_t n, uint32_t tile, uint32_t* cnt_r, uint32_t* cnt_p);
+void launch_abund_min(hipStream_t s, int grain, const void* rec, uint32_t n, uint32_t tile, const uint32_t* off_r, const uint32_t* off_p,
+                      uint32_t n_reads, uint32_t n_runs, uint32_t* m, uint32_t* e_run, uint64_t* read_id, uint32_t* read_first, uint32_t* run_tax,
+                      uint32_t* run_read);
+void launch_abund_flag(hipStream_t s, uint32_t n_runs, const uint32_t* e_run, const uint32_t* m, const uint32_t* run_read, uint32_t slack,
+                       uint32_t* flag);
+void launch_abund_write(hipStream_t s, uint32_t n_reads, uint32_t n_runs, const uint32_t* off, const uint32_t* e_run, const uint32_t* m,
+                        const uint32_t* run_tax, const uint32_t* run_read, const uint32_t* read_first, const uint32_t* u_tax, uint32_t n_union,
+                        uint32_t n_w, uint32_t lane_max, uint32_t* read_off, uint32_t* ent_slot, uint8_t* ent_d, uint32_t* ent_e, uint32_t* any,
+                        uint32_t* uniq, uint32_t* list, uint64_t* ctr);
+void launch_abund_init(hipStream_t s, uint32_t n_union, const uint32_t* any, uint64_t start, uint64_t* mass, uint64_t* next);
+void launch_abund_step(hipStream_t s, uint32_t blocks, bool dense, const AbundEntries& en, const uint64_t* mass, uint64_t* next);
+void launch_abund_delta(hipStream_t s, uint32_t n_union, uint64_t* mass, uint64_t* next, uint64_t* l1);
+void launch_abund_final(hipStream_t s, uint32_t blocks, const AbundEntries& en, const uint64_t* mass, const uint32_t* ent_e, const uint64_t* read_id,
+                        const uint32_t* u_tax, void* out, uint32_t* assigned);
 // k_dedup.hip: the identical reads of a resident batch (codes 0..4, read_off[n_reads + 1]; codes readable to the end of the
 // aligned dword of its last base).  rep(j) = the smallest index of a read with j's length and codes.
 //   hash:     hash[j], 64 bits of the read's codes and length, independent of where the read lies
