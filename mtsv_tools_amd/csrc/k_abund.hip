@@ -1,14 +1,12 @@
 // k_abund.hip -- abundance by expectation-maximisation over a sorted list of assignment records (abund.hip, mtsv_fold_abundance;
 // the definition is in include/mtsv_amd.h).
 //
-// PREPARE, once per call, record-parallel in the tiled shape of k_lca.hip: a workgroup per tile of `tile` records, a stretch of
-// tile / 256 consecutive records per lane.  Two kinds of heads are counted at once, READ heads and RUN heads (a run: the records
-// of one (read, tax_id) -- the wide grains repeat a TaxID), packed into one word for the tile's prefix sum:
+// PREPARE, once per call, record-parallel in the tile scaffold of k_tile.hpp (the scheme in full is there).  Two kinds of
+// segments are counted at once, READS and RUNS (a run: the records of one (read, tax_id) -- the wide grains repeat a TaxID); the
+// run heads are the scaffold's second kind, with cells of their own:
 //   k_abund_heads  the read heads and the run heads of every tile                      (then launch_scan, twice)
-//   k_abund_min    two segmented minima of edit, m per read and e per run, by LDS atomicMin into the cell of the record's rank
-//                  among the tile's heads; a wavefront whose records share the rank reduces by shuffles first.  Segments
-//                  inside a tile are stored, the at most two per tile that a neighbour shares go out with one atomicMin each.
-//                  Heads write what is known of their read and run.
+//   k_abund_min    two segmented minima of edit, m[read slot] and e_run[run slot].  Heads write what is known of their read
+//                  and run.
 //   k_abund_flag   a lane per run: it ENTERS when e - m <= slack                          (then launch_scan: the entries' places)
 //   k_abund_write  a lane per run: the entry -- the place of its TaxID in the union (find_u32 once here, not per iteration), the
 //                  difference to the read's best clipped to the weight table as a byte, e -- and the per-taxon counts; the lane
@@ -28,7 +26,7 @@
 #include <algorithm>
 #include <string>
 
-#include "kernels_common.hpp"
+#include "k_tile.hpp"
 
 namespace mtsv {
 namespace {
@@ -40,88 +38,29 @@ static_assert(kAbundStretchMax <= 32, "the heads of a lane's stretch are kept as
 static_assert(kAbundTileMax < (1u << 16), "two head counts of a tile share a word");
 static_assert(kAbundDenseMax * sizeof(unsigned long long) <= 65536, "the dense counters fit the LDS of one workgroup");
 
-// What a lane knows of its tile: its stretch of positions [p0, p1), which of them are read heads and run heads (bit k: position
-// p0 + k), the heads of each kind in the tile before p0 and in the whole tile
-struct AbundLane {
-    uint64_t i0;
-    uint32_t nt, ipt, p0, p1;
-    uint32_t heads_r, heads_p, before_r, before_p, total_r, total_p;
+// a read head: the read differs from the predecessor's; a run head, the second kind: the read or the tax_id does
+struct AbundKey {
+    uint64_t read;
+    uint32_t tax;
 };
-
-// wsum: kAbundWaves u32 of LDS.  Holds a __syncthreads(): what the caller wrote to LDS before the call is visible after it.
 template <uint32_t W>
-__device__ inline AbundLane abund_lane(const uint32_t* __restrict__ rec, uint32_t n, uint32_t tile, uint32_t* wsum) {
-    AbundLane t;
-    t.i0 = (uint64_t)blockIdx.x * tile;
-    t.nt = (uint32_t)min((uint64_t)tile, (uint64_t)n - t.i0);
-    t.ipt = max(tile / kAbundThreads, 1u);
-    t.p0 = min(threadIdx.x * t.ipt, t.nt);
-    t.p1 = min(t.p0 + t.ipt, t.nt);
-    t.heads_r = t.heads_p = 0;
-    if (t.p0 < t.p1) {
-        const uint64_t first = t.i0 + t.p0;
-        uint64_t prev = first ? rec_read_of<W>(rec, first - 1) : 0;
-        uint32_t prev_tax = first ? rec[(first - 1) * W + 2] : 0;
-        for (uint32_t p = t.p0; p < t.p1; p++) {
-            const uint64_t read = rec_read_of<W>(rec, t.i0 + p);
-            const uint32_t tax = rec[(t.i0 + p) * W + 2];
-            const bool head_r = t.i0 + p == 0 || read != prev;
-            if (head_r) t.heads_r |= 1u << (p - t.p0);
-            if (head_r || tax != prev_tax) t.heads_p |= 1u << (p - t.p0);
-            prev = read;
-            prev_tax = tax;
-        }
+struct AbundHead {
+    const uint32_t* __restrict__ rec;
+    __device__ AbundKey key(uint64_t i) const { return AbundKey{rec_read_of<W>(rec, i), rec[i * W + 2]}; }
+    __device__ static uint32_t head(const AbundKey& prev, const AbundKey& cur) {
+        const bool r = prev.read != cur.read;
+        return (uint32_t)r | (uint32_t)(r || prev.tax != cur.tax) << 1;
     }
-    const uint32_t mine = (uint32_t)__popc(t.heads_r) << 16 | (uint32_t)__popc(t.heads_p);  // (each at most 1024 per tile)
-    uint32_t incl = mine;
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-        if ((int)lane_id() >= d) incl += up;
-    }
-    const uint32_t wave = threadIdx.x / kWave;
-    if (lane_id() == (uint32_t)kWave - 1) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - mine, total = 0;
-    for (uint32_t w = 0; w < kAbundWaves; w++) {
-        const uint32_t s = wsum[w];
-        if (w < wave) before += s;
-        total += s;
-    }
-    t.before_r = before >> 16;
-    t.before_p = before & 0xffffu;
-    t.total_r = total >> 16;
-    t.total_p = total & 0xffffu;
-    return t;
-}
-
-// the rank of position p0 + k among the tile's heads of a kind: 0 for the records in front of the tile's first head
-__device__ inline uint32_t abund_rank(uint32_t heads, uint32_t before, uint32_t k) { return before + (uint32_t)__popc(heads & (0xffffffffu >> (31 - k))); }
-
-// cell[r] = min(cell[r], v) for the lanes with act set.  Called by every lane of the wavefront together.  When all its active
-// lanes share r -- a read of thousands of records -- the wavefront reduces by shuffles and one lane goes to LDS.
-__device__ inline void abund_lds_min(uint32_t* cell, bool act, uint32_t r, uint32_t v) {
-    const unsigned long long am = __ballot(act);
-    if (!am) return;
-    const uint32_t leader = (uint32_t)__builtin_ctzll(am);
-    const uint32_t r0 = (uint32_t)__shfl((int)r, (int)leader);
-    const unsigned long long same = __ballot(act && r == r0);
-    if (same == am && __popcll(am) > 1) {
-        uint32_t x = act ? v : 0xffffffffu;
-        for (int d = kWave / 2; d > 0; d >>= 1) x = min(x, (uint32_t)__shfl_xor((int)x, d));
-        if (lane_id() == leader) atomicMin(&cell[r0], x);
-    } else if (act) {
-        atomicMin(&cell[r], v);
-    }
-}
+};
 
 template <uint32_t W>
 __global__ __launch_bounds__(kAbundThreads) void k_abund_heads(const uint32_t* __restrict__ rec, uint32_t n, uint32_t tile, uint32_t* __restrict__ cnt_r,
                                                               uint32_t* __restrict__ cnt_p) {
     __shared__ uint32_t wsum[kAbundWaves];
-    const AbundLane t = abund_lane<W>(rec, n, tile, wsum);
+    const auto t = tile_lane<kAbundThreads, 2>(n, tile, wsum, AbundHead<W>{rec});
     if (threadIdx.x == 0) {
-        cnt_r[blockIdx.x] = t.total_r;
-        cnt_p[blockIdx.x] = t.total_p;
+        cnt_r[blockIdx.x] = t.total;
+        cnt_p[blockIdx.x] = t.total2;
     }
 }
 
@@ -137,7 +76,7 @@ __global__ __launch_bounds__(kAbundThreads) void k_abund_min(const uint32_t* __r
         smin_r[r] = 0xffffffffu;
         smin_p[r] = 0xffffffffu;
     }
-    const AbundLane t = abund_lane<W>(rec, n, tile, wsum);
+    const auto t = tile_lane<kAbundThreads, 2>(n, tile, wsum, AbundHead<W>{rec});
     // the heads before the tile: rank r is slot base + r - 1 (a list begins with a head of both kinds: base + r >= 1)
     const uint32_t base_r = off_r[blockIdx.x], base_p = off_p[blockIdx.x];
     for (uint32_t k = 0; k < t.ipt; k++) {  // (ipt is the same in every lane)
@@ -145,47 +84,33 @@ __global__ __launch_bounds__(kAbundThreads) void k_abund_min(const uint32_t* __r
         uint32_t rr = 0, rp = 0, e = 0;
         if (act) {
             const uint64_t i = t.i0 + t.p0 + k;
-            rr = abund_rank(t.heads_r, t.before_r, k);
-            rp = abund_rank(t.heads_p, t.before_p, k);
+            rr = tile_rank(t.heads, t.before, k);
+            rp = tile_rank(t.heads2, t.before2, k);
             e = rec[i * W + W - 1];
             const uint64_t slot_r = (uint64_t)base_r + rr - 1, slot_p = (uint64_t)base_p + rp - 1;
-            if ((t.heads_p >> k & 1) && slot_p < n_runs && slot_r < n_reads) {
+            if ((t.heads2 >> k & 1) && slot_p < n_runs && slot_r < n_reads) {
                 run_tax[slot_p] = rec[i * W + 2];
                 run_read[slot_p] = (uint32_t)slot_r;
-                if (t.heads_r >> k & 1) {
+                if (t.heads >> k & 1) {
                     read_id[slot_r] = rec_read_of<W>(rec, i);
                     read_first[slot_r] = (uint32_t)slot_p;
                 }
             }
         }
-        abund_lds_min(smin_r, act, rr, e);
-        abund_lds_min(smin_p, act, rp, e);
+        seg_lds_reduce<false>(smin_r, act, rr, e);
+        seg_lds_reduce<false>(smin_p, act, rp, e);
     }
     __syncthreads();
-    // the segments: rank 0 is there when the tile's first record is no head -- it began in an earlier tile; the tile's last
-    // segment goes on in the next tile when the record behind the tile is no head
-    const uint64_t next = t.i0 + t.nt;
-    bool on_r = false, on_p = false;
-    if (next < n) {
-        on_r = rec_read_of<W>(rec, next) == rec_read_of<W>(rec, next - 1);
-        on_p = on_r && rec[next * W + 2] == rec[(next - 1) * W + 2];
-    }
-    for (uint32_t r = threadIdx.x; r <= t.total_r; r += kAbundThreads) {
+    tile_flush<kAbundThreads, 0>(t, n, base_r, n_reads, AbundHead<W>{rec}, [&](uint64_t slot, uint32_t r, bool shared) {
         const uint32_t v = smin_r[r];
-        if (r == 0 && (v == 0xffffffffu || base_r == 0)) continue;  // (no record in front of the first head; v is all ones then)
-        const uint64_t slot = (uint64_t)base_r + r - 1;
-        if (slot >= n_reads) continue;
-        if (r == 0 || (r == t.total_r && on_r)) atomicMin(&m[slot], v);
+        if (shared) atomicMin(&m[slot], v);
         else m[slot] = v;
-    }
-    for (uint32_t r = threadIdx.x; r <= t.total_p; r += kAbundThreads) {
+    });
+    tile_flush<kAbundThreads, 1>(t, n, base_p, n_runs, AbundHead<W>{rec}, [&](uint64_t slot, uint32_t r, bool shared) {
         const uint32_t v = smin_p[r];
-        if (r == 0 && (v == 0xffffffffu || base_p == 0)) continue;
-        const uint64_t slot = (uint64_t)base_p + r - 1;
-        if (slot >= n_runs) continue;
-        if (r == 0 || (r == t.total_p && on_p)) atomicMin(&e_run[slot], v);
+        if (shared) atomicMin(&e_run[slot], v);
         else e_run[slot] = v;
-    }
+    });
 }
 
 __global__ __launch_bounds__(kAbundThreads) void k_abund_flag(uint32_t n_runs, const uint32_t* __restrict__ e_run, const uint32_t* __restrict__ m,

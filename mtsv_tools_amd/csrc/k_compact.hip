@@ -18,7 +18,7 @@
 // the end of the code buffer (never what it holds) is the allocation's, as after upload() + run().
 #include <hip/hip_runtime.h>
 
-#include "kernels_common.hpp"
+#include "k_tile.hpp"
 
 namespace mtsv {
 namespace {
@@ -47,14 +47,6 @@ __device__ inline bool compact_read(uint32_t r, uint32_t n, const unsigned long 
     }
     *mask = m;
     return (m >> lane) & 1ull;
-}
-
-__device__ inline uint32_t compact_wave_incl(uint32_t v) {
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d);
-        if ((int)lane_id() >= d) v += o;
-    }
-    return v;
 }
 
 // result: [0] survivors, [1] their bases (k_compact_sums), [2] the longest survivor (zeroed by the caller)
@@ -140,7 +132,7 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact_copy(uint32_t n, co
     uint32_t start, len;
     const bool kept = compact_read(r, n, words, off, keep_matched, &mask, &start, &len);
     const uint32_t mine = kept ? len : 0;
-    const uint32_t incl = compact_wave_incl(mine);
+    const uint32_t incl = wave_incl_sum(mine);
     if (lane == kWave - 1) s_len[wave] = incl;
     if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(mask);
     __syncthreads();

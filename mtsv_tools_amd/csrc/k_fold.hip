@@ -29,7 +29,7 @@
 
 #include <string>
 
-#include "kernels_common.hpp"
+#include "k_tile.hpp"
 
 namespace mtsv {
 namespace {
@@ -182,29 +182,17 @@ __global__ __launch_bounds__(kFoldThreads) void k_fold(const uint32_t* __restric
     }
     __syncthreads();
 
-    // the survivors before every position: a stretch of positions per lane, the lanes' sums scanned by wavefront
+    // the survivors before every position: a stretch of positions per lane, the lanes' sums by block_excl_sum
     const uint32_t ipt = (tile + kFoldThreads - 1) / kFoldThreads;
     const uint32_t p0 = min(threadIdx.x * ipt, nt), p1 = min(p0 + ipt, nt);
     uint32_t mine = 0;
     for (uint32_t p = p0; p < p1; p++) mine += flag[p];
-    uint32_t incl = mine;
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-        if ((int)lane_id() >= d) incl += up;
-    }
-    const uint32_t wave = threadIdx.x / kWave;
-    if (lane_id() == (uint32_t)kWave - 1) misc[4 + wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - mine, total = 0;
-    for (uint32_t w = 0; w < kFoldThreads / kWave; w++) {
-        const uint32_t s = misc[4 + w];
-        if (w < wave) before += s;
-        total += s;
-    }
+    const BlockSum sum = block_excl_sum<kFoldThreads>(mine, misc + 4);
     if (!WRITE) {
-        if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+        if (threadIdx.x == 0) tile_cnt[blockIdx.x] = sum.total;
         return;
     }
+    uint32_t before = sum.before;
     for (uint32_t p = p0; p < p1; p++) {
         const uint32_t f = flag[p];
         flag[p] = f ? before : kFoldDropped;

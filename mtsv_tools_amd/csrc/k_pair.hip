@@ -1,9 +1,9 @@
 // k_pair.hip -- the two mates of a read pair joined into one list of (pair, tax_id, edit) records (pair.hip, mtsv_fold_pair).
 //
 // The list is a fold's: n records of 4 or 6 words ordered by (read, tax_id[, gi, offset]), reads 2p and 2p + 1 the mates of
-// pair p.  A RUN is the records of one (read, tax_id); its first record is its HEAD, and the heads before a record, counted
-// over the list, number its run (its SLOT).  NONE is all ones: edits are below 2^31 (counted here, refused by the host), so
-// no sum of two reaches it.
+// pair p.  A RUN is the records of one (read, tax_id): the segment of the tile scaffold of k_tile.hpp, where HEAD, SLOT and
+// the rule of what a tile stores and what it sends with an atomic are described.  NONE is all ones: edits are below 2^31
+// (counted here, refused by the host), so no sum of two reaches it.
 //   k_pair_bounds  a lane per read r in 0 .. 2P: off[r] = the first record with read >= r (a lower bound on the read field)
 //   k_pair_join    a lane per record.  It finds its WINDOW in the other mate's stretch [off[r ^ 1], off[(r ^ 1) + 1]) by binary
 //                  searches: BOTH / EITHER the records with its tax_id (only heads search; a head of mate 1 only in EITHER,
@@ -18,10 +18,8 @@
 //   k_pair_wave    a wavefront per entry of the work list, in a grid that strides it: the lanes stride the window, the
 //                  minimum comes by shuffles, lane 0 stores val[i] (PROPER) or add[i]
 //   k_pair_heads   tile_cnt[t] = the heads of tile t                                          (then launch_scan: tile_off)
-//   k_pair_min     the segmented minimum of val by run, as k_lca_min does it: an LDS atomicMin per record into the cell of
-//                  its rank among the tile's heads, a wavefront of one rank reduced by shuffles first; runs inside the tile are
-//                  stored, the at most two that a neighbour shares go out by atomicMin.  Heads write (read, tax_id, add) of
-//                  their slot.
+//   k_pair_min     m[slot] = the segmented minimum of val by run; a cell that holds NONE sends no atomic.  Heads write
+//                  (read, tax_id, add) of their slot.
 //   k_pair_flags   a lane per slot: its value m + add, or NONE; flag_a: a run of mate 0 with a value, flag_b: one of mate 1
 //                  (EITHER: the taxa only mate 1 hit)                            (then launch_scan over each: pos_a, pos_b)
 //   k_pair_write   a lane per slot: (read >> 1, tax_id, value) to its place in list A or list B.  Both are ordered by
@@ -33,7 +31,7 @@
 
 #include <string>
 
-#include "kernels_common.hpp"
+#include "k_tile.hpp"
 
 namespace mtsv {
 namespace {
@@ -49,11 +47,21 @@ __device__ inline uint32_t pair_edit_of(const uint32_t* __restrict__ rec, uint64
     return rec[i * W + W - 1];
 }
 
-// record i begins a run: its (read, tax_id) differs from its predecessor's
+// a segment is a run: a record is a head when its (read, tax_id) differs from its predecessor's
+struct PairKey {
+    uint64_t read;
+    uint32_t tax;
+};
+template <uint32_t W>
+struct PairHead {
+    const uint32_t* __restrict__ rec;
+    __device__ PairKey key(uint64_t i) const { return PairKey{rec_read_of<W>(rec, i), rec[i * W + 2]}; }
+    __device__ static uint32_t head(const PairKey& prev, const PairKey& cur) { return prev.read != cur.read || prev.tax != cur.tax; }
+};
+// record i begins a run
 template <uint32_t W>
 __device__ inline bool pair_is_head(const uint32_t* __restrict__ rec, uint64_t i) {
-    if (i == 0) return true;
-    return rec_read_of<W>(rec, i) != rec_read_of<W>(rec, i - 1) || rec[i * W + 2] != rec[(i - 1) * W + 2];
+    return tile_heads_at(PairHead<W>{rec}, i) & 1;
 }
 
 // the first record of [b, e) whose tax_id is not below t (UPPER: is above t)
@@ -196,51 +204,10 @@ __global__ __launch_bounds__(kPairThreads) void k_pair_wave(const uint32_t* __re
     }
 }
 
-// What a lane knows of its tile (k_lca.hip's LcaLane, heads by (read, tax_id)): its stretch of positions [p0, p1), which of
-// them are heads (bit k: position p0 + k), the heads of the tile before p0, the heads of the tile
-struct PairLane {
-    uint64_t i0;
-    uint32_t nt, ipt, p0, p1, heads, before, total;
-};
-
-// wsum: kPairWaves u32 of LDS.  Holds a __syncthreads(): what the caller wrote to LDS before the call is visible after it.
-template <uint32_t W>
-__device__ inline PairLane pair_lane(const uint32_t* __restrict__ rec, uint32_t n, uint32_t tile, uint32_t* wsum) {
-    PairLane t;
-    t.i0 = (uint64_t)blockIdx.x * tile;
-    t.nt = (uint32_t)min((uint64_t)tile, (uint64_t)n - t.i0);
-    t.ipt = max(tile / kPairThreads, 1u);
-    t.p0 = min(threadIdx.x * t.ipt, t.nt);
-    t.p1 = min(t.p0 + t.ipt, t.nt);
-    t.heads = 0;
-    for (uint32_t p = t.p0; p < t.p1; p++)
-        if (pair_is_head<W>(rec, t.i0 + p)) t.heads |= 1u << (p - t.p0);
-    const uint32_t mine = (uint32_t)__popc(t.heads);
-    uint32_t incl = mine;
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-        if ((int)lane_id() >= d) incl += up;
-    }
-    const uint32_t wave = threadIdx.x / kWave;
-    if (lane_id() == (uint32_t)kWave - 1) wsum[wave] = incl;
-    __syncthreads();
-    t.before = incl - mine;
-    t.total = 0;
-    for (uint32_t w = 0; w < kPairWaves; w++) {
-        const uint32_t s = wsum[w];
-        if (w < wave) t.before += s;
-        t.total += s;
-    }
-    return t;
-}
-
-// the rank of position p0 + k among the tile's heads: 0 for the records in front of the tile's first head
-__device__ inline uint32_t pair_rank(const PairLane& t, uint32_t k) { return t.before + (uint32_t)__popc(t.heads & (0xffffffffu >> (31 - k))); }
-
 template <uint32_t W>
 __global__ __launch_bounds__(kPairThreads) void k_pair_heads(const uint32_t* __restrict__ rec, uint32_t n, uint32_t tile, uint32_t* __restrict__ tile_cnt) {
     __shared__ uint32_t wsum[kPairWaves];
-    const PairLane t = pair_lane<W>(rec, n, tile, wsum);
+    const auto t = tile_lane<kPairThreads>(n, tile, wsum, PairHead<W>{rec});
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = t.total;
 }
 
@@ -252,52 +219,28 @@ __global__ __launch_bounds__(kPairThreads) void k_pair_min(const uint32_t* __res
     __shared__ uint32_t wsum[kPairWaves];
     __shared__ uint32_t smin[kPairTileMax + 1];  // by rank among the tile's heads
     for (uint32_t r = threadIdx.x; r <= tile; r += kPairThreads) smin[r] = kPairNone;
-    const PairLane t = pair_lane<W>(rec, n, tile, wsum);
+    const auto t = tile_lane<kPairThreads>(n, tile, wsum, PairHead<W>{rec});
     const uint32_t base = tile_off[blockIdx.x];  // the heads before the tile: rank r is slot base + r - 1
     for (uint32_t k = 0; k < t.ipt; k++) {       // (ipt is the same in every lane)
         const bool act = t.p0 + k < t.p1;
         uint32_t r = 0, v = kPairNone;
         if (act) {
             const uint64_t i = t.i0 + t.p0 + k;
-            r = pair_rank(t, k);
+            r = tile_rank(t.heads, t.before, k);
             v = val[i];
             if (t.heads >> k & 1) {
                 const uint64_t slot = (uint64_t)base + r - 1;
                 if (slot < n_slots_cap) slot_rec[slot] = make_uint4(rec[i * W], rec[i * W + 1], rec[i * W + 2], add[i]);
             }
         }
-        // cell[r] = min(cell[r], v): a wavefront whose records all share r -- a run of thousands -- sends one lane to LDS
-        const unsigned long long am = __ballot(act);
-        if (am) {
-            const uint32_t leader = (uint32_t)__builtin_ctzll(am);
-            const uint32_t r0 = (uint32_t)__shfl((int)r, (int)leader);
-            const unsigned long long same = __ballot(act && r == r0);
-            if (same == am && __popcll(am) > 1) {
-                uint32_t x = act ? v : kPairNone;
-                for (int d = kWave / 2; d > 0; d >>= 1) x = min(x, (uint32_t)__shfl_xor((int)x, d));
-                if (lane_id() == leader) atomicMin(&smin[r0], x);
-            } else if (act) {
-                atomicMin(&smin[r], v);
-            }
-        }
+        seg_lds_reduce<false>(smin, act, r, v);
     }
     __syncthreads();
-    // the tile's last record and the one behind it are of one run: the tile's last run goes on in the next tile
-    const uint64_t next = t.i0 + t.nt;
-    const bool goes_on = next < n && !pair_is_head<W>(rec, next);
-    // the runs: rank 0 is there when the tile's first record is no head -- it began in an earlier tile, so base >= 1
-    const bool first_is_head = pair_is_head<W>(rec, t.i0);
-    for (uint32_t r = threadIdx.x; r <= t.total; r += kPairThreads) {
+    tile_flush<kPairThreads>(t, n, base, n_slots_cap, PairHead<W>{rec}, [&](uint64_t slot, uint32_t r, bool shared) {
         const uint32_t v = smin[r];
-        if (r == 0 && (first_is_head || base == 0)) continue;  // (no record in front of the first head)
-        const uint64_t slot = (uint64_t)base + r - 1;
-        if (slot >= n_slots_cap) continue;
-        if (r == 0 || (r == t.total && goes_on)) {
-            if (v != kPairNone) atomicMin(&m[slot], v);
-        } else {
-            m[slot] = v;
-        }
-    }
+        if (!shared) m[slot] = v;
+        else if (v != kPairNone) atomicMin(&m[slot], v);
+    });
 }
 
 // m[s] becomes the slot's value; flag_b may be null (no list B)

@@ -34,7 +34,7 @@
 
 #include <string>
 
-#include "kernels_common.hpp"
+#include "k_tile.hpp"
 
 namespace mtsv {
 namespace {
@@ -135,29 +135,17 @@ __global__ __launch_bounds__(kParseThreads) void k_parse(const uint8_t* __restri
     }
     __syncthreads();
 
-    // ---- the token starts: a stretch of bytes per lane, the lanes' counts scanned by wavefront ----
+    // ---- the token starts: a stretch of bytes per lane, the lanes' counts summed by block_excl_sum ----
     const uint32_t ipt = max(tile / kParseThreads, 1u);
     const uint32_t p0 = min(threadIdx.x * ipt, nt), p1 = min(p0 + ipt, nt);
     uint32_t mine = 0;
     for (uint32_t p = p0; p < p1; p++) mine += mark[p] | (buf[kParsePre - 1 + p] == ',');
-    uint32_t incl = mine;
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-        if ((int)lane_id() >= d) incl += up;
-    }
-    const uint32_t wave = threadIdx.x / kWave;
-    if (lane_id() == (uint32_t)kWave - 1) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - mine, total = 0;
-    for (uint32_t w = 0; w < kParseThreads / kWave; w++) {
-        const uint32_t s = wsum[w];
-        if (w < wave) before += s;
-        total += s;
-    }
+    const BlockSum sum = block_excl_sum<kParseThreads>(mine, wsum);
     if (!WRITE) {
-        if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+        if (threadIdx.x == 0) tile_cnt[blockIdx.x] = sum.total;
         return;
     }
+    uint32_t before = sum.before;
 
     // ---- every start's token: parsed from LDS, written at tile_off + rank ----
     const uint64_t base = tile_off[blockIdx.x], end = min((uint64_t)tile_off[blockIdx.x + 1], (uint64_t)n_tok);

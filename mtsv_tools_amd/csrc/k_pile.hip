@@ -29,7 +29,7 @@
 
 #include <string>
 
-#include "kernels_common.hpp"
+#include "k_tile.hpp"
 
 namespace mtsv {
 namespace {
@@ -164,14 +164,6 @@ __global__ __launch_bounds__(kPileThreads) void k_pile_ref(const uint8_t* __rest
     ref[s] = p < len ? (uint8_t)min((uint32_t)text[(uint64_t)text_start[r] + p], 4u) : (uint8_t)0xff;
 }
 
-__device__ inline uint32_t pile_wave_incl_scan(uint32_t v) {
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d);
-        if ((int)lane_id() >= d) v += o;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kWave) void k_pile_tile_sums(const uint32_t* __restrict__ cnt, uint32_t n_slots, uint32_t tile,
                                                           uint32_t* __restrict__ tile_sum) {
     const uint64_t lo = (uint64_t)blockIdx.x * tile, end = min(lo + tile, (uint64_t)n_slots);
@@ -215,7 +207,7 @@ __global__ __launch_bounds__(kWave) void k_pile_sites(SitesArgs a) {
             x = p[0];
             y = p[1];
         }
-        const uint32_t incl = pile_wave_incl_scan(x.x);
+        const uint32_t incl = wave_incl_sum(x.x);
         x.x = carry + incl;
         carry += __shfl(incl, kWave - 1);
         if (M == kSitesDump) {

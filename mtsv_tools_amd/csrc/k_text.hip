@@ -27,7 +27,7 @@
 
 #include <string>
 
-#include "kernels_common.hpp"
+#include "k_tile.hpp"
 
 namespace mtsv {
 namespace {
@@ -210,33 +210,21 @@ __global__ __launch_bounds__(kTextThreads) void k_text_write(const uint32_t* __r
     // (the measure pass bounds a tile's text below 2^31 bytes)
     const uint32_t T = (uint32_t)min(E - B, (uint64_t)0x7fffffffu);
 
-    // ---- the records' offsets: a stretch of positions per lane, the lanes' sums scanned by wavefront ----
+    // ---- the records' offsets: a stretch of positions per lane, the lanes' sums by block_excl_sum ----
     for (uint32_t p = threadIdx.x; p < nt; p += kTextThreads) off[p] = rec_len[g0 + p];
     __syncthreads();
     const uint32_t ipt = (tile + kTextThreads - 1) / kTextThreads;
     const uint32_t p0 = min(threadIdx.x * ipt, nt), p1 = min(p0 + ipt, nt);
     uint32_t mine = 0;
     for (uint32_t p = p0; p < p1; p++) mine += off[p];
-    uint32_t incl = mine;
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-        if ((int)lane_id() >= d) incl += up;
-    }
-    const uint32_t wave = threadIdx.x / kWave;
-    if (lane_id() == (uint32_t)kWave - 1) misc[4 + wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - mine, total = 0;
-    for (uint32_t w = 0; w < kTextThreads / kWave; w++) {
-        const uint32_t s = misc[4 + w];
-        if (w < wave) before += s;
-        total += s;
-    }
+    const BlockSum sum = block_excl_sum<kTextThreads>(mine, misc + 4);
+    uint32_t before = sum.before;
     for (uint32_t p = p0; p < p1; p++) {
         const uint32_t v = off[p];
         off[p] = before;
         before += v;
     }
-    if (threadIdx.x == 0) off[nt] = total;
+    if (threadIdx.x == 0) off[nt] = sum.total;
     __syncthreads();
 
     // image coordinate c of the tile is byte G0 + c of the output; the tile's text is [shift, shift + T)

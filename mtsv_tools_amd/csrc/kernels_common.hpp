@@ -1,6 +1,7 @@
 // kernels_common.hpp -- device helpers shared by the kernel files of the hot path (k_seed.hip: normalise, search,
 // thin, expand, locate; k_coalesce.hip; k_verify.hip: SW prefilter, edit distance, selection, gather; k_report.hip),
-// and the two that k_report.hip, k_fold.hip and k_lca.hip share: find_u32, rec_read_of.
+// and the two that the record kernels share: find_u32, rec_read_of.  (The tile scaffold of k_pair.hip and k_abund.hip -- heads,
+// ranks, segmented minima -- and the block-wide sum of the tiled passes are in k_tile.hpp, which includes this file.)
 #pragma once
 #include <cstdlib>
 #include <stdexcept>

@@ -1,11 +1,15 @@
-"""-m gpu: the tiled passes (k_text, k_fold, k_parse, k_lca) at every tile size they accept, on the cases of tile_cases.py that
-are built onto their structural edges, and the upper levels of the text scan at small tiles.  (The pack's scan carry:
+"""-m gpu: the tiled passes (k_text, k_fold, k_parse, k_lca, k_pair, k_abund) at every tile size they accept, on the cases of
+tile_cases.py that are built onto their structural edges, the upper levels of the text scan at small tiles, and the tiles of
+the record kernels (k_lca.hip; k_tile.hpp) that hold no head or nothing but heads.  (The pack's scan carry:
 test_device_pack.py, next to the indexes it needs.)
 
 Expected values never come from the device or the library under test: they are the restatements' -- text_cases.text, fold_ref,
-parse_ref, lca_ref -- of the same lists (test_tile_ladders_cpu.py shows that the lists hold what they claim).  Every
+parse_ref, lca_ref, pair_ref, abund_ref -- of the same lists (test_tile_ladders_cpu.py shows that the lists hold what they claim).  Every
 comparison is exact.  The tile of every run, and in part 1 the number of tiles, is asserted from the trace lines, so that a
-change of a default cannot turn these into tests of one level unnoticed."""
+change of a default cannot turn these into tests of one level unnoticed.  (The trace line of the abundance does not name its
+tile: there the switch is set and nothing more can be asserted.  So for the abundance alone that purpose does not hold: were
+MTSV_ABUND_TILE ever ignored, its five ladder levels and its tile-64 cases would all run at the default tile of 1024 and pass
+unnoticed, until the tile is added to that trace line.)"""
 import random
 import re
 
@@ -13,18 +17,25 @@ import pytest
 
 import fold_ref as F
 import mtsv_tools_amd as M
+import pair_cases as PC
 import parse_ref as P
 import text_cases as TC
 import tile_cases as K
 from mtsv_tools_amd import _lib
+from test_abundance import as_array as abund_array
+from test_abundance import check as abund_check
 from test_fold import as_array, check_fold
 from test_lca import ALL, Tax, check
 from test_lca import as_array as lca_array
+from test_pair import DT, MODES
+from test_pair import check as pair_check
 from test_parse_text import add, n_tokens, refused
 
 pytestmark = pytest.mark.gpu
 
 GRAINS = TC.GRAINS
+LCA_LINE = r"\[lca\] \d+ records of \d+ reads over \d+ nodes \(\d+ TaxIDs, depth \d+\) in \d+ tiles of (\d+),"
+PAIR_LINE = r"\[pair\] mode \d+, \d+ records of \d+ pairs in \d+ runs, \d+ on the work list \(lane tier up to \d+\), tiles of (\d+) "
 TEXT_LINE = r"\[text\] (\d+) records -> (\d+) bytes in (\d+) tiles of (\d+) "
 SCAN_CHUNK = 2048          # tiles per workgroup of k_text_scan_sums / _apply; k_text_scan_top takes `per` of those per lane
 SCAN_LANES = 256
@@ -163,5 +174,95 @@ def test_lca_ladder(gname, T, monkeypatch, capfd, outlier):
             check(fold, outlier, recs, n_reads, slack, out=out)
     fold.close()
     out.close()
-    tiles = set(re.findall(r"\[lca\] \d+ records of \d+ reads over \d+ nodes \(\d+ TaxIDs, depth \d+\) in \d+ tiles of (\d+),", capfd.readouterr().err))
-    assert tiles == {str(T)}
+    assert set(re.findall(LCA_LINE, capfd.readouterr().err)) == {str(T)}
+
+
+# pairs: BOTH and EITHER at the TAXID grain, where every record is a run of its own and the reads' heads stand at the edges;
+# PROPER at the LONG grain, where the runs' heads do
+@pytest.mark.parametrize("T", K.PAIR_TILES)
+@pytest.mark.parametrize("mode,gname", [("both", "taxid"), ("either", "taxid"), ("proper", "long")])
+def test_pair_ladder(mode, gname, T, monkeypatch, capfd):
+    grain = GRAINS[gname]
+    fold = traced_fold(monkeypatch, "MTSV_PAIR_TILE", T, grain)
+    out = M.Fold(0, M.GRAIN_TAXID)
+    for name, (wide, n_reads) in K.run_cases(T).items():
+        if name.startswith("reads") != (gname == "taxid"):
+            continue
+        recs = K.narrow(wide) if gname == "taxid" else wide
+        fold.reset(n_reads)
+        fold.add_records(PC.as_array(grain, recs, DT))
+        pair_check(fold, recs, n_reads, MODES[mode], 50, 5, out=out)
+    fold.close()
+    out.close()
+    assert set(re.findall(PAIR_LINE, capfd.readouterr().err)) == {str(T)}
+
+
+# abundance: the reads' heads at the edges at every grain, the runs' heads at the two wide ones
+@pytest.mark.parametrize("T", K.ABUND_TILES)
+@pytest.mark.parametrize("gname", list(GRAINS))
+def test_abundance_ladder(gname, T, monkeypatch):
+    grain = GRAINS[gname]
+    fold = traced_fold(monkeypatch, "MTSV_ABUND_TILE", T, grain)
+    out = M.Fold(0, M.GRAIN_TAXID)
+    for name, (wide, n_reads) in K.run_cases(T, "gi").items():
+        if gname == "taxid" and not name.startswith("reads"):
+            continue
+        recs = K.narrow(wide) if gname == "taxid" else wide
+        fold.reset(n_reads)
+        fold.add_records(abund_array(grain, recs))
+        abund_check(fold, recs, n_reads, slack=1, max_iters=2, out=out)
+    fold.close()
+    out.close()
+
+
+# ---- 3. tiles of the record kernels without a head, and of nothing but heads ----
+
+EDGE_CASES = [(f"headless_{w}", K.HEADLESS_T) for w in K.HEADLESS_AT] + [("full", 64), ("full", 1024)]
+EDGE_IDS = [f"{name}-{T}" for name, T in EDGE_CASES]
+
+
+def edge_list(name, T, kernel):
+    """(records, n_reads) of an edge case for 'lca', 'pair', 'read' (the abundance at the TAXID grain, after narrow()) or 'abund'"""
+    if name == "full":
+        return K.full_tile_reads(T) if kernel == "lca" else K.full_tile_runs(T, "offset" if kernel == "pair" else "gi", one_run=kernel != "read")
+    at = K.HEADLESS_AT[name[len("headless_"):]]
+    return K.headless_reads(at) if kernel == "lca" else K.headless_runs(at, kernel)
+
+
+@pytest.mark.parametrize("name,T", EDGE_CASES, ids=EDGE_IDS)
+def test_lca_tiles_without_a_head_and_of_heads_alone(name, T, monkeypatch, capfd, outlier):
+    recs, n_reads = edge_list(name, T, "lca")
+    fold = traced_fold(monkeypatch, "MTSV_LCA_TILE", T, M.GRAIN_TAXID)
+    fold.reset(n_reads)
+    fold.add_records(lca_array(M.GRAIN_TAXID, recs))
+    for slack in (0, ALL):
+        check(fold, outlier, recs, n_reads, slack)
+    fold.close()
+    assert set(re.findall(LCA_LINE, capfd.readouterr().err)) == {str(T)}
+
+
+@pytest.mark.parametrize("name,T", EDGE_CASES, ids=EDGE_IDS)
+@pytest.mark.parametrize("mode", list(MODES))
+def test_pair_tiles_without_a_head_and_of_heads_alone(mode, name, T, monkeypatch, capfd):
+    recs, n_reads = edge_list(name, T, "pair")
+    fold = traced_fold(monkeypatch, "MTSV_PAIR_TILE", T, M.GRAIN_LONG)
+    fold.reset(n_reads)
+    fold.add_records(PC.as_array(M.GRAIN_LONG, recs, DT))
+    want = pair_check(fold, recs, n_reads, MODES[mode], 480, 5)
+    fold.close()
+    assert any(t == 5 for _, t, _ in want)                                           # the segment's pair is joined
+    assert set(re.findall(PAIR_LINE, capfd.readouterr().err)) == {str(T)}
+
+
+@pytest.mark.parametrize("name,T", EDGE_CASES, ids=EDGE_IDS)
+@pytest.mark.parametrize("gname", list(GRAINS))
+def test_abundance_tiles_without_a_head_and_of_heads_alone(gname, name, T, monkeypatch):
+    recs, n_reads = edge_list(name, T, "read" if gname == "taxid" else "abund")
+    if gname == "taxid":
+        recs = K.narrow(recs)
+    fold = traced_fold(monkeypatch, "MTSV_ABUND_TILE", T, GRAINS[gname])
+    fold.reset(n_reads)
+    fold.add_records(abund_array(GRAINS[gname], recs))
+    for slack in (1, ALL):
+        abund_check(fold, recs, n_reads, slack=slack, max_iters=2)
+    fold.close()

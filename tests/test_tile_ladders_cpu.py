@@ -4,8 +4,10 @@ library code beyond the record dtypes: coverage is computed from the lists, expe
 import numpy as np
 import pytest
 
+import abund_ref as AR
 import fold_ref as F
 import lca_ref as R
+import pair_ref as PR
 import parse_ref as P
 import text_cases as TC
 import tile_cases as K
@@ -107,6 +109,99 @@ def test_lca_expectations_pinned_by_hand_at_tile_64(outlier):
             assert all(K.leaf_parent(t) == 60 for _, t, _ in at0)                   # the smallest edit is a filler's
     recs, _ = cases["heads+0"]
     assert K.reads_of(recs) == [(0, 64), (64, 128), (128, 200)]
+
+
+# ---- runs: pairs and abundance ----
+
+def is_wide_list(recs, n_reads, vary):
+    """a list at the LONG grain, with vary 'gi' at the TAXID_GI grain as well"""
+    return (recs == sorted(recs) and len({r[:4 if vary == "offset" else 3] for r in recs}) == len(recs)
+            and recs[-1][0] < n_reads and n_reads % 2 == 0 and max(r[4] for r in recs) < 2 ** 31)
+
+
+@pytest.mark.parametrize("vary", ["offset", "gi"])
+@pytest.mark.parametrize("T", K.PAIR_TILES)
+def test_run_cases_hold_what_they_claim(T, vary):
+    assert K.PAIR_TILES == K.ABUND_TILES == K.LCA_TILES                              # the same edges: K.targets(T, d)
+    at_reads, at_runs, joined = set(), set(), 0
+    for name, (recs, n_reads) in K.run_cases(T, vary).items():
+        tg = set(K.targets(T, int(name[-2:])))
+        assert is_wide_list(recs, n_reads, vary) and 200 <= len(recs) <= max(3 * T + 50, 300), name
+        reads, runs = K.run_heads_of(recs)
+        if name.startswith("reads"):                                                # the side alone: no head but at the edges
+            assert reads == tg | {0} and runs == set(range(len(recs))), name
+            assert F.is_list(F.TAXID, K.narrow(recs)), name
+            at_reads |= tg
+            joined += len(PR.pair(PR.BOTH, K.narrow(recs)))
+        else:
+            assert runs == tg | {0} and reads == set(sorted(tg)[1::2]) | {0}, name
+            at_runs |= tg
+            joined += len(PR.pair(PR.PROPER, recs, 50)) if vary == "offset" else len(AR.entries(recs, 1))
+    assert K.missing(at_reads, T) == [] and K.missing(at_runs, T) == [] and joined > 0
+
+
+def segment_minimum(recs, a, b):
+    """(where the smallest edit of records [a, b) stands, the edit) -- it stands once"""
+    edits = [r[4] for r in recs[a:b]]
+    assert edits.count(min(edits)) == 1
+    return a + edits.index(min(edits)), min(edits)
+
+
+@pytest.mark.parametrize("where", list(K.HEADLESS_AT))
+def test_headless_tiles_hold_what_they_claim(where, outlier):
+    T, (a, b), at = K.HEADLESS_T, K.HEADLESS_SEG, K.HEADLESS_AT[where]
+    assert a // T == 0 and (b - 1) // T == 3 and at // T == {"tile1": 1, "tile2": 2, "tile0_last": 0}[where]
+    assert where != "tile0_last" or at == T - 1
+    headless = set(range(T, 3 * T))                                                # tiles 1 and 2
+    # lca: a read
+    recs, n_reads = K.headless_reads(at)
+    ev = K.lca_events(recs)
+    assert len(recs) == K.HEADLESS_N and (a, b) in K.reads_of(recs) and not headless & ev["heads"] and recs[-1][0] < n_reads
+    (c,) = [p for p in ev["c"] if a <= p < b]
+    assert at in ev["b"] and c in headless and c // T != at // T
+    assert {r: t for r, t, _ in R.per_read(outlier, recs, 0)}[recs[a][0]] == recs[at][1]
+    assert {r: t for r, t, _ in R.per_read(outlier, recs, ALL)}[recs[a][0]] == 100
+    # abundance at the TAXID grain: a read of runs of one record
+    recs, n_reads = K.headless_runs(at, "read")
+    reads, runs = K.run_heads_of(recs)
+    assert is_wide_list(recs, n_reads, "gi") and F.is_list(F.TAXID, K.narrow(recs)) and len(recs) == K.HEADLESS_N
+    assert {a, b} <= reads and not headless & reads and runs == set(range(len(recs))) and segment_minimum(recs, a, b) == (at, 1)
+    # pairs: the one run of an even read; its mate is the one record behind it
+    recs, n_reads = K.headless_runs(at, "pair")
+    reads, runs = K.run_heads_of(recs)
+    assert is_wide_list(recs, n_reads, "offset") and len(recs) == K.HEADLESS_N
+    assert {a, b, b + 1} <= reads and not headless & runs and segment_minimum(recs, a, b) == (at, 1)
+    pair, mate = recs[a][0] >> 1, recs[b]
+    assert recs[a][0] == 2 * pair and mate[0] == 2 * pair + 1 and {r[1:3] for r in recs[a:b + 1]} == {(5, 1)}
+    assert all(abs(r[3] - mate[3]) <= 480 for r in recs[a:b])
+    for mode in (PR.BOTH, PR.EITHER, PR.PROPER):
+        assert (pair, 5, 1 + mate[4]) in PR.pair(mode, recs, 480, 5)
+        assert (pair, 5, 3 + mate[4]) in PR.pair(mode, recs[:at] + recs[at + 1:], 480, 5)
+    # abundance at the wide grains: a run inside a read that has a run before it and one behind it
+    recs, n_reads = K.headless_runs(at, "abund")
+    reads, runs = K.run_heads_of(recs)
+    assert is_wide_list(recs, n_reads, "gi") and len(recs) == K.HEADLESS_N
+    assert {30, b + 10} <= reads and not set(range(31, b + 10)) & reads and {a, b} <= runs and not headless & runs
+    assert segment_minimum(recs, a, b) == (at, 2) and segment_minimum(recs, 30, b + 10) == (205, 1) and 205 // T == 3
+    read, tax = recs[a][:2]
+    assert AR.entries(recs, 1)[read][tax] == (1, 2) and tax not in AR.entries(recs[:at] + recs[at + 1:], 1)[read]
+
+
+@pytest.mark.parametrize("T", [64, 1024])
+def test_full_tiles_hold_what_they_claim(T, outlier):
+    heads = K.full_tile_heads(T)
+    assert set(range(T)) <= heads and T not in heads and min(h for h in heads if h >= T) == T + 9
+    recs, n_reads = K.full_tile_reads(T)
+    ev = K.lca_events(recs)
+    assert ev["heads"] == heads and T + 3 in ev["b"] and T + 6 in ev["c"] and recs[-1][0] < n_reads
+    for vary in ("offset", "gi"):
+        recs, n_reads = K.full_tile_runs(T, vary)
+        assert is_wide_list(recs, n_reads, vary) and K.run_heads_of(recs) == (heads, heads)
+        assert segment_minimum(recs, T - 1, T + 9) == (T + 3, 1)
+        assert recs[T - 1][0] % 2 == 0 and recs[T + 9][0] == recs[T - 1][0] + 1 and recs[T + 9][1] == recs[T - 1][1] == 5
+    recs, n_reads = K.full_tile_runs(T, "gi", one_run=False)
+    assert is_wide_list(recs, n_reads, "gi") and F.is_list(F.TAXID, K.narrow(recs))
+    assert K.run_heads_of(recs) == (heads, set(range(len(recs)))) and segment_minimum(recs, T - 1, T + 9) == (T + 3, 1)
 
 
 # ---- fold ----

@@ -1,7 +1,7 @@
-"""Cases built onto the structural edges of the tiled passes (k_lca, k_fold, k_text, k_parse), for every tile size the code
-accepts: shared by test_tile_ladders_cpu.py, which asserts that the cases hold what they claim, and test_tile_ladders.py,
+"""Cases built onto the structural edges of the tiled passes (k_lca, k_pair, k_abund, k_fold, k_text, k_parse), for every tile
+size the code accepts: shared by test_tile_ladders_cpu.py, which asserts that the cases hold what they claim, and test_tile_ladders.py,
 which runs them on the device.  Generators and coverage functions only: what a case must give comes from the restatements
-(lca_ref, fold_ref, text_cases.text, parse_ref), never from here.
+(lca_ref, pair_ref, abund_ref, fold_ref, text_cases.text, parse_ref), never from here.
 
 A stage runs 256 lanes over a tile of T items; a lane owns a STRETCH of s(T) = max(T / 256, 1) consecutive items (the
 ceiling for fold and text) and a wavefront 64 * s(T).  A structural edge of kind E in {s, 64 * s, T} is a position that is a
@@ -23,6 +23,8 @@ import text_cases as TC
 LANES = 256
 SIDES = (-1, 0, 1)
 LCA_TILES = (64, 128, 256, 512, 1024)
+PAIR_TILES = (64, 128, 256, 512, 1024)
+ABUND_TILES = (64, 128, 256, 512, 1024)
 FOLD_TILES = (2, 64, 128, 256, 512, 1024)
 TEXT_TILES = (2, 64, 128, 256, 512, 1024)
 PARSE_TILES = (64, 256, 1024, 4096, 8192, 16384)
@@ -181,6 +183,114 @@ def lca_events(recs):
             if par.count(pool) == 1 and other not in par and 60 in par:
                 ev[key].add(i + par.index(pool))
     return ev
+
+
+# ---- runs: pairs and abundance ------------------------------------------------------------------------------------------------
+# Wide records (read, tax_id, gi, offset, edit).  k_pair's segments are the RUNS of one (read, tax_id); k_abund counts read heads and
+# run heads.  Reads count up by one, so reads 2p and 2p + 1 are the mates of a pair, and a read's TaxIDs begin at 1 or 2 and go up
+# by 1 or 2, so mates share most of theirs.  Inside a run the key ascends by `vary`: "offset" (GI 1, the mates' records within
+# reach of each other: a list for the LONG grain) or "gi" (a list for both wide grains).
+
+def run_list(rng, n, run_heads, read_heads, vary="offset", edit=None, read0=0, tax5=range(0)):
+    """(records, n_reads): n records, a new read at `read_heads` and at 0, a new run at `run_heads` as well; edit: {position: edit}
+    for the records that do not get theirs by chance; read0: the first read; tax5: the positions (of whole reads of one run)
+    whose TaxID is 5"""
+    recs, read, tax, step = [], read0 - 1, 0, 0
+    for p in range(n):
+        if p == 0 or p in read_heads:
+            read, tax, step = read + 1, 1 + rng.randrange(2), 0
+        elif p in run_heads:
+            tax, step = tax + rng.randrange(1, 3), 0
+        else:
+            step += rng.randrange(1, 4)
+        t, e = 5 if p in tax5 else tax, (edit or {}).get(p, rng.randrange(6))
+        recs.append((read, t, 1, step, e) if vary == "offset" else (read, t, 1 + step, 3, e))
+    return recs, (read + 4) & ~1
+
+
+def narrow(recs):
+    """the (read, tax_id, edit) of wide records whose (read, tax_id) are distinct: the same list at the TAXID grain"""
+    out = [(r[0], r[1], r[4]) for r in recs]
+    assert len(set(r[:2] for r in out)) == len(out)
+    return out
+
+
+def run_heads_of(recs):
+    """(read heads, run heads) of a sorted list, from the records alone"""
+    reads = {p for p, r in enumerate(recs) if p == 0 or r[0] != recs[p - 1][0]}
+    return reads, {p for p, r in enumerate(recs) if p == 0 or r[:2] != recs[p - 1][:2]}
+
+
+@functools.lru_cache(maxsize=None)
+def run_cases(T, vary="offset"):
+    """{name: (records, n_reads)} per side d: the read heads at every edge and nowhere else, every record a run of its own
+    (reads: narrow() makes the TAXID grain's list of it); the run heads at every edge and nowhere else, every second of them a
+    read head (runs)"""
+    rng = random.Random(8000 + T + (vary == "gi"))
+    out = {}
+    for d in SIDES:
+        tg = targets(T, d)
+        n = max(200, tg[-1] + max(T // 2, 20))
+        out[f"reads{d:+d}"] = run_list(rng, n, set(range(n)), set(tg), vary)
+        out[f"runs{d:+d}"] = run_list(rng, n, set(tg), set(tg[1::2]), vary)
+    return out
+
+
+# The headless tile, at tile 64: a segment [40, 200) begins inside tile 0 and ends inside tile 3, so tiles 1 and 2 hold no head,
+# their only rank is 0 and one cell is the tile's first segment and its last at once.  Its smallest value is unique and stands
+# in tile 1, in tile 2 or at the last record of tile 0.
+HEADLESS_T, HEADLESS_SEG, HEADLESS_N = 64, (40, 200), 230
+HEADLESS_AT = {"tile1": 100, "tile2": 150, "tile0_last": 63}
+
+
+def headless_reads(at):
+    """(records, n_reads) for k_lca, at the TAXID grain: the segment is a read of 160 TaxIDs, its smallest edit at `at` and a
+    low outlier of the taxonomy OUTLIER in another tile without a head"""
+    a, b = HEADLESS_SEG
+    return _lca_list(random.Random(at), HEADLESS_N, [20, a, b, b + 12], {at: "b", 150 if at != 150 else 100: "c"})
+
+
+def headless_runs(at, kernel):
+    """(records, n_reads), wide.  kernel 'read': the segment is a read of 160 runs of one record, edits 3 but for a 1 at `at`.
+    kernel 'pair': the segment is the one run of read 2, edits 3 but for a 1 at `at`; its mate, read 3, is the one record behind
+    it, of the same TaxID and within 480 bases of every record of the run.  kernel 'abund': the segment is a run inside a read
+    [30, 210) that has a run before it and one behind it; the run's smallest edit, 2, stands at `at`, the read's, 1, at 205 in
+    tile 3, the other records have 4 (slack 1: the run enters by its smallest edit alone)"""
+    a, b = HEADLESS_SEG
+    rng = random.Random(at)
+    if kernel == "read":    # every record a run of its own, the segment is read 2: narrow() makes the TAXID grain's list of it
+        edit = {p: 3 for p in range(a, b)}
+        edit[at] = 1
+        return run_list(rng, HEADLESS_N, set(range(HEADLESS_N)), {20, a, b, b + 12}, "gi", edit)
+    if kernel == "pair":
+        edit = {p: 3 for p in range(a, b)}
+        edit[at] = 1
+        return run_list(rng, HEADLESS_N, {10, 20, 30, a, b, b + 1, b + 10, b + 20}, {20, a, b, b + 1, b + 20}, "offset", edit, tax5=range(a, b + 1))
+    edit = {p: 4 for p in range(30, b + 10)}
+    edit[at], edit[205] = 2, 1
+    return run_list(rng, HEADLESS_N, {10, 20, 30, a, b, b + 10, b + 20}, {10, 30, b + 10}, "gi", edit)
+
+
+# A whole tile of one-record segments, then a segment that begins at the tile's last position and goes on for nine records in
+# the next tile, its smallest edit at T + 3: every position of the tile is a head (of both kinds), `total` is the tile, and the
+# tile's last segment is a single record in it.
+def full_tile_heads(T):
+    return set(range(T)) | {T + 9, T + 12, T + 20}
+
+
+def full_tile_reads(T):
+    """(records, n_reads) for k_lca at the TAXID grain: the segments are reads; a low outlier at T + 6"""
+    return _lca_list(random.Random(T), T + 30, sorted(full_tile_heads(T)), {T + 3: "b", T + 6: "c"})
+
+
+def full_tile_runs(T, vary="offset", one_run=True):
+    """(records, n_reads), wide.  one_run: the segment is the one run of read T, an even read, and its mate, read T + 1, is a
+    run of the same TaxID behind it; otherwise every record is a run of its own (narrow() makes the TAXID grain's list of it)"""
+    heads = full_tile_heads(T)
+    edit = {p: 3 for p in range(T - 1, T + 9)}
+    edit[T + 3] = 1
+    return run_list(random.Random(T), T + 30, heads if one_run else set(range(T + 30)), heads, vary, edit, read0=1,
+                    tax5=range(T - 1, T + 12) if one_run else range(0))
 
 
 # ---- fold -----------------------------------------------------------------------------------------------------------------------
