@@ -1055,6 +1055,61 @@ int mtsv_pileup_sites(mtsv_pileup *p, uint32_t min_depth, uint32_t min_alt, uint
                       uint64_t *n_rows, float *device_ms);
 int mtsv_format_variants(const mtsv_pile_site *rows, uint64_t n_rows, char **out, uint64_t *out_len);
 
+/* ---- consensus: a sequence and call statistics per reference from the pileup (cons.hip, k_cons.hip) ------------------------
+ * What the organism in the sample looks like, and how close it is to the database entry: a consensus sequence per reference as
+ * FASTA, written on the device (about one byte per base crosses to the host), and one row of call statistics per reference.
+ * Parameters: min_depth, min_frac_ppm, min_breadth_ppm, fill (0 = `N`, 1 = the reference base in lower case), line_width
+ * (0 = no wrapping).  Let md = max(min_depth, 1).
+ *   The counters of a slot are the integrated n[0 .. 8) that mtsv_pileup_download shows.  For position p in 0 .. L-1 of a
+ *   reference: depth = n[0] + ... + n[6]; w is the channel in 0 .. 6 with the largest count, the lowest channel on equal
+ *   counts, so match wins a tie.  Each position falls into exactly one class:
+ *     LOW    depth < md                                                              emits the fill character
+ *     AMBIG  depth >= md and (w == 5, a read N, or n[w] * 1000000 < min_frac_ppm * depth in 64-bit integers)
+ *                                                                                    emits the fill character
+ *     REF    w == 0, otherwise         emits the reference base in upper case (ACGTN by ref code)
+ *     SUB    w in 1 .. 4, otherwise    emits ACGT[w - 1]
+ *     DEL    w == 6, otherwise         emits nothing
+ *   The fill character is `N` for fill == 0 and the reference base in lower case (acgtn) for fill == 1.
+ *   INSERTIONS CANNOT BE SPELLED: the pileup keeps how many reads insert in front of a slot, not which bases.  They are only
+ *   counted: slot j in 0 .. L is an INS SITE when n[7] >= md and 2 * n[7] > D, D = depth(j) for j < L and 0 for slot L.  The
+ *   consensus text never holds an inserted base.
+ *   The row of a reference, mtsv_cons_ref: covered counts the positions with depth >= md, sum_depth sums depth over the
+ *   positions, n_ref .. n_ambig count the classes, ins_sites the INS SITES.  length = covered + n_low and
+ *   covered = n_ref + n_sub + n_del + n_ambig.  cons_len = length - n_del.
+ *   A reference is EMITTED when covered >= 1 and covered * 1000000 >= min_breadth_ppm * length.  Rows and sequences are those
+ *   of the emitted references, ascending by (tax_id, gi) as unsigned, across segments.
+ *   FASTA for each emitted reference: `>` GI `-` TAXID `\n` (the header form mtsv-build reads), then the cons_len characters
+ *   in lines of line_width, the last line shorter, every line ended by `\n`; no empty line when cons_len is a multiple of the
+ *   width; the header line alone when cons_len == 0; one line when line_width == 0.
+ * mtsv_pileup_consensus: fasta == NULL gives rows only, and no layout or write kernel is launched; rows (with n_rows) may be
+ *   NULL too.  *fasta (fasta_len bytes, not terminated) and *rows are malloc'd, mtsv_free.  The accumulator is unchanged.  An
+ *   accumulator without segments returns empty text, zero rows and device_ms 0 without a launch.  device_ms (may be NULL): the
+ *   device time of the call pass, the layout and the write pass.  MTSV_PILE_TIMING=1: one line on stderr with the steps' times.
+ *   MTSV_E_ARG: fill > 1, min_frac_ppm > 1000000, a null handle.  MTSV_E_LIMIT: a segment whose text would reach 2^32 bytes.
+ *   MTSV_E_NOMEM: "the consensus calls", "the consensus text" (names for MTSV_ALLOC_REFUSE).  Each refusal leaves the
+ *   accumulator as it was.
+ * mtsv_format_consensus_stats (host only, needs no device): the header line
+ *     taxid gi length covered breadth_pct mean_depth cons_len ref sub del low ambiguous ins_sites identity_pct
+ *   (tab-separated), a line per row, and after a TaxID's rows one rollup line with gi `*` that takes the sums of that taxon's
+ *   rows, the three ratios taken of the sums.  breadth_pct = covered / length * 100, mean_depth = sum_depth / length,
+ *   identity_pct = ref / (ref + sub + del) * 100, each %.2f of doubles and 0.00 on a zero denominator.
+ * mtsv_pileup_add_counts: adds caller-given counts, [n_slots][8] u32, plain as mtsv_pileup_download gives them, to slots
+ *   first_slot .. first_slot + n_slots - 1 of a reference the accumulator already holds, by a kernel on the accumulator's
+ *   stream (channel 0 goes into the difference form); n_hits is added to hits_piled.  Pileups made on several nodes or days
+ *   are merged so before the consensus is called.  MTSV_E_ARG, the accumulator unchanged: any count above n_hits (with the
+ *   limit below, no counter can overflow); an unknown reference; a range beyond L + 1 slots; a nonzero channel 0 .. 6 in
+ *   slot L.  MTSV_E_LIMIT: a total of piled hits that would reach 2^32. */
+typedef struct {
+    uint32_t tax_id, gi, length, covered, n_ref, n_sub, n_del, n_low, n_ambig, ins_sites;
+    uint64_t sum_depth;
+} mtsv_cons_ref; /* 48 bytes */
+int mtsv_pileup_consensus(mtsv_pileup *p, uint32_t min_depth, uint32_t min_frac_ppm, uint32_t min_breadth_ppm, uint32_t fill,
+                          uint32_t line_width, char **fasta, uint64_t *fasta_len, mtsv_cons_ref **rows, uint64_t *n_rows,
+                          float *device_ms);
+int mtsv_format_consensus_stats(const mtsv_cons_ref *rows, uint64_t n_rows, char **out, uint64_t *out_len);
+int mtsv_pileup_add_counts(mtsv_pileup *p, uint32_t tax_id, uint32_t gi, uint32_t first_slot, uint64_t n_slots,
+                           const uint32_t *counts, uint64_t n_hits);
+
 /* ---- result lines (host) ---------------------------------------------------------------- */
 /* write_assignments for a whole batch: hits ordered by read; ids = NUL-separated read ids,
  * id_off[n_reads+1].  Lines are appended to a malloc'd buffer (*out, *out_len), one per read with

@@ -111,6 +111,11 @@ PILE_SITE_DTYPE = np.dtype({"names": ["tax_id", "gi", "pos", "ref", "n"], "forma
                             "offsets": [0, 4, 8, 12, 16], "itemsize": 48})
 PILE_REF_NONE = 0xff  # the ref code of a reference's last slot, which takes insertions only
 
+# mtsv_cons_ref: 10 * 4 + 8 = 48 bytes
+CONS_REF_DTYPE = np.dtype({"names": ["tax_id", "gi", "length", "covered", "n_ref", "n_sub", "n_del", "n_low", "n_ambig", "ins_sites", "sum_depth"],
+                           "formats": ["<u4"] * 10 + ["<u8"], "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40], "itemsize": 48})
+CONS_FILL_N, CONS_FILL_REF = 0, 1
+
 
 class PileupInfo(C.Structure):  # mtsv_pileup_info_t
     _fields_ = [("n_refs", C.c_uint64), ("n_slots", C.c_uint64), ("n_segments", C.c_uint64), ("device_bytes", C.c_uint64),
@@ -171,6 +176,7 @@ EXPORTS = [
     "mtsv_batch_place_hits", "mtsv_format_placements",
     "mtsv_pileup_create", "mtsv_pileup_free", "mtsv_pileup_reset", "mtsv_pileup_add_run", "mtsv_pileup_info", "mtsv_pileup_download",
     "mtsv_pileup_sites", "mtsv_format_variants",
+    "mtsv_pileup_consensus", "mtsv_format_consensus_stats", "mtsv_pileup_add_counts",
 ]
 
 _lib = None
@@ -301,6 +307,9 @@ def lib():
         L.mtsv_pileup_info.argtypes = [vp, C.POINTER(PileupInfo)]
         L.mtsv_pileup_download.argtypes = [vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
         L.mtsv_pileup_sites.argtypes = [vp, u32, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_pileup_consensus.argtypes = [vp, u32, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), C.POINTER(C.c_float)]
+        L.mtsv_format_consensus_stats.argtypes = [vp, u64, C.POINTER(vp), C.POINTER(u64)]
+        L.mtsv_pileup_add_counts.argtypes = [vp, u32, u32, u32, u64, vp, u64]
         L.mtsv_format_variants.argtypes = [vp, u64, C.POINTER(vp), C.POINTER(u64)]
         _lib = L
     return _lib
@@ -1038,6 +1047,26 @@ class Pileup:
         _check(lib().mtsv_pileup_sites(self.h, int(min_depth), int(min_alt), int(min_alt_ppm), C.byref(out), C.byref(n), C.byref(ms)))
         return _records_from(out, n.value, PILE_SITE_DTYPE), ms.value
 
+    def consensus(self, min_depth=1, min_frac_ppm=500000, min_breadth_ppm=0, fill=CONS_FILL_N, line_width=60, fasta=True):
+        """mtsv_pileup_consensus: (the FASTA text as bytes, or None with fasta=False; the emitted references' rows as a
+        CONS_REF_DTYPE array ascending by (tax_id, gi); device ms)"""
+        text, n_text, out, n, ms = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_float()
+        _check(lib().mtsv_pileup_consensus(self.h, int(min_depth), int(min_frac_ppm), int(min_breadth_ppm), int(fill), int(line_width),
+                                           C.byref(text) if fasta else None, C.byref(n_text) if fasta else None, C.byref(out), C.byref(n), C.byref(ms)))
+        rows = _records_from(out, n.value, CONS_REF_DTYPE)
+        if not fasta:
+            return None, rows, ms.value
+        try:
+            return C.string_at(text.value, n_text.value), rows, ms.value
+        finally:
+            lib().mtsv_free(text)
+
+    def add_counts(self, tax_id, gi, first_slot, counts, n_hits):
+        """mtsv_pileup_add_counts: counts [n_slots][8] uint32, plain as download gives them, added to the reference's slots from
+        first_slot; n_hits is added to hits_piled"""
+        c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1, 8)
+        _check(lib().mtsv_pileup_add_counts(self.h, int(tax_id), int(gi), int(first_slot), len(c), c.ctypes.data if len(c) else None, int(n_hits)))
+
     def close(self):
         if self.h is not None and _lib is not None:
             _lib.mtsv_pileup_free(self.h)
@@ -1055,6 +1084,17 @@ def format_variants(rows):
     r = np.ascontiguousarray(rows, dtype=PILE_SITE_DTYPE)
     out, n = C.c_void_p(), C.c_uint64()
     _check(lib().mtsv_format_variants(r.ctypes.data, len(r), C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value).decode()
+    finally:
+        lib().mtsv_free(out)
+
+
+def format_consensus_stats(rows):
+    """mtsv_format_consensus_stats: the TSV of mtsv-binner --consensus-stats, as one str"""
+    r = np.ascontiguousarray(rows, dtype=CONS_REF_DTYPE)
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mtsv_format_consensus_stats(r.ctypes.data if len(r) else None, len(r), C.byref(out), C.byref(n)))
     try:
         return C.string_at(out.value, n.value).decode()
     finally:

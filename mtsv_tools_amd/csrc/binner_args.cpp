@@ -124,7 +124,20 @@ void print_help() {
            "--min-alt-frac (0 .. 1, default 0) of the depth: by default every position where any read disagrees.  --variant-taxa:\n"
            "only references of these TaxIDs are counted; the counters take 33 bytes of device memory per reference base of the\n"
            "chunks, so a large database needs the list.  With --alignments as well the hits are aligned twice.  Reads of up to 256\n"
-           "bases.  Every other output is what it is without the flag)\n");
+           "bases.  Every other output is what it is without the flag),\n"
+           "--consensus FASTA [--consensus-stats TSV] [--consensus-min-depth N] [--consensus-min-frac F] [--consensus-min-breadth F]\n"
+           "[--consensus-fill n|ref] [--consensus-width N] (only with --fold-on-gpu, not with --dedup: the same accumulator as\n"
+           "--variants -- one per run, shared when both are given, described by --variant-taxa and --variant-slack -- is called\n"
+           "once, after the last read, on the GPU: FASTA gets a consensus sequence per reference with a covered position, headed\n"
+           ">GI-TAXID as mtsv-build reads it, in lines of --consensus-width (default 60; 0: one line).  A position whose depth is\n"
+           "below --consensus-min-depth (default 1), whose most frequent call is a read N or has less than --consensus-min-frac\n"
+           "(0 .. 1, default 0.5) of the depth is written as N (--consensus-fill n, the default) or as the reference base in lower\n"
+           "case (ref); otherwise the reference base, the substituted base, or nothing where most reads skip the position.\n"
+           "Insertions cannot be spelled: the accumulator counts the reads that insert in front of a position, not their bases; they\n"
+           "are only counted, as ins_sites.  A reference is left out when less than --consensus-min-breadth (0 .. 1, default 0) of\n"
+           "it is covered.  --consensus-stats: a header and one line per written reference and per TaxID (gi *), taxid, gi, length,\n"
+           "covered, breadth_pct, mean_depth, cons_len, ref, sub, del, low, ambiguous, ins_sites, identity_pct = ref / (ref + sub +\n"
+           "del).  Every other output is what it is without the flag)\n");
 }
 
 // a number in 0 .. 2^32 - 1, or the usage error of `flag`
@@ -239,8 +252,9 @@ void check_combinations(const Args& a) {
         if (a.alignments == a.results) refuse("'--alignments <FILE>' and '-m/--results <RESULTS>' name the same file");
     }
     if (a.variants.empty()) {
-        if (!a.variant_taxa.empty()) usage_error("The argument '--variant-taxa <T1,T2,..>' requires '--variants <TSV>'");
-        if (!a.variant_slack.empty()) usage_error("The argument '--variant-slack <N|all>' requires '--variants <TSV>'");
+        // (--variant-taxa and --variant-slack describe the run's one pileup: --consensus makes one too)
+        if (!a.variant_taxa.empty() && a.consensus.empty()) usage_error("The argument '--variant-taxa <T1,T2,..>' requires '--variants <TSV>'");
+        if (!a.variant_slack.empty() && a.consensus.empty()) usage_error("The argument '--variant-slack <N|all>' requires '--variants <TSV>'");
         if (!a.min_depth.empty()) usage_error("The argument '--min-depth <N>' requires '--variants <TSV>'");
         if (!a.min_alt_reads.empty()) usage_error("The argument '--min-alt-reads <N>' requires '--variants <TSV>'");
         if (!a.min_alt_frac.empty()) usage_error("The argument '--min-alt-frac <F>' requires '--variants <TSV>'");
@@ -249,6 +263,26 @@ void check_combinations(const Args& a) {
         if (a.dedup) refuse("'--variants <TSV>' cannot be used with '--dedup': only the representatives of identical reads are binned");
         if (a.variants == a.results) refuse("'--variants <TSV>' and '-m/--results <RESULTS>' name the same file");
         if (a.variants == a.alignments) refuse("'--variants <TSV>' and '--alignments <FILE>' name the same file");
+    }
+    if (a.consensus.empty()) {
+        const std::pair<const std::string*, const char*> sub[] = {{&a.consensus_stats, "--consensus-stats <TSV>"},   {&a.consensus_min_depth, "--consensus-min-depth <N>"},
+                                                                  {&a.consensus_min_frac, "--consensus-min-frac <F>"}, {&a.consensus_min_breadth, "--consensus-min-breadth <F>"},
+                                                                  {&a.consensus_fill, "--consensus-fill <n|ref>"},     {&a.consensus_width, "--consensus-width <N>"}};
+        for (const auto& f : sub)
+            if (!f.first->empty()) usage_error(std::string("The argument '") + f.second + "' requires '--consensus <FASTA>'");
+    } else {
+        if (!a.fold_gpu) refuse("'--consensus <FASTA>' requires '--fold-on-gpu': the hits are aligned where a chunk's run leaves them, on the device");
+        if (a.dedup) refuse("'--consensus <FASTA>' cannot be used with '--dedup': only the representatives of identical reads are binned");
+        // every consensus file against every other output file
+        const std::pair<const std::string*, const char*> mine[] = {{&a.consensus, "--consensus <FASTA>"}, {&a.consensus_stats, "--consensus-stats <TSV>"}};
+        const std::pair<const std::string*, const char*> others[] = {{&a.consensus, "--consensus <FASTA>"}, {&a.results, "-m/--results <RESULTS>"},
+                                                                     {&a.alignments, "--alignments <FILE>"}, {&a.variants, "--variants <TSV>"},
+                                                                     {&a.report, "--report <TSV>"},          {&a.coverage, "--coverage <TSV>"},
+                                                                     {&a.matched, "--matched <PATH>"},       {&a.unmatched, "--unmatched <PATH>"}};
+        for (const auto& m : mine)
+            for (const auto& o : others)
+                if (m.first != o.first && !m.first->empty() && *m.first == *o.first)
+                    refuse(std::string("'") + m.second + "' and '" + o.second + "' name the same file");
     }
     if (a.merge_gpu) require_chunks_on_one_device(a, "--merge-on-gpu", "every chunk is made resident on that device");
     if (a.fold_gpu) {
@@ -402,6 +436,13 @@ Args parse_args(int argc, char** argv) {
         else if (key == "--min-depth") a.min_depth = val();
         else if (key == "--min-alt-reads") a.min_alt_reads = val();
         else if (key == "--min-alt-frac") a.min_alt_frac = val();
+        else if (key == "--consensus") a.consensus = val();
+        else if (key == "--consensus-stats") a.consensus_stats = val();
+        else if (key == "--consensus-min-depth") a.consensus_min_depth = val();
+        else if (key == "--consensus-min-frac") a.consensus_min_frac = val();
+        else if (key == "--consensus-min-breadth") a.consensus_min_breadth = val();
+        else if (key == "--consensus-fill") a.consensus_fill = val();
+        else if (key == "--consensus-width") a.consensus_width = val();
         else if (key == "--fold-reads") a.fold_reads = parse_reads(val(), "--fold-reads", 0xffffffffull);
         else if (key == "-h" || key == "--help") {
             print_help();
@@ -462,11 +503,23 @@ Run resolve(const Args& a) {
     if (!a.variant_slack.empty()) run.variant_slack = a.variant_slack == "all" ? 0xffffffffu : parse_u32_flag(a.variant_slack, "--variant-slack");
     if (!a.min_depth.empty()) run.min_depth = parse_u32_flag(a.min_depth, "--min-depth");
     if (!a.min_alt_reads.empty()) run.min_alt_reads = parse_u32_flag(a.min_alt_reads, "--min-alt-reads");
-    if (!a.min_alt_frac.empty()) {
+    // a fraction as parts per million, rounded
+    auto parse_ppm = [](const std::string& v, const char* flag) {
         char* e = nullptr;
-        const double f = strtod(a.min_alt_frac.c_str(), &e);
-        if (*e || e == a.min_alt_frac.c_str() || !(f >= 0.0 && f <= 1.0)) usage_error("Invalid value for '--min-alt-frac <F>': a fraction between 0 and 1 is expected");
-        run.min_alt_ppm = (uint32_t)llround(f * 1e6);
+        const double f = strtod(v.c_str(), &e);
+        if (*e || e == v.c_str() || !(f >= 0.0 && f <= 1.0)) usage_error(std::string("Invalid value for '") + flag + " <F>': a fraction between 0 and 1 is expected");
+        return (uint32_t)llround(f * 1e6);
+    };
+    if (!a.min_alt_frac.empty()) run.min_alt_ppm = parse_ppm(a.min_alt_frac, "--min-alt-frac");
+    run.consensus = a.consensus;
+    run.consensus_stats = a.consensus_stats;
+    if (!a.consensus_min_depth.empty()) run.cons_min_depth = parse_u32_flag(a.consensus_min_depth, "--consensus-min-depth");
+    if (!a.consensus_min_frac.empty()) run.cons_min_frac_ppm = parse_ppm(a.consensus_min_frac, "--consensus-min-frac");
+    if (!a.consensus_min_breadth.empty()) run.cons_min_breadth_ppm = parse_ppm(a.consensus_min_breadth, "--consensus-min-breadth");
+    if (!a.consensus_width.empty()) run.cons_width = parse_u32_flag(a.consensus_width, "--consensus-width");
+    if (!a.consensus_fill.empty()) {
+        if (a.consensus_fill != "n" && a.consensus_fill != "ref") usage_error("Invalid value for '--consensus-fill <n|ref>': 'n' or 'ref' is expected");
+        run.cons_fill = a.consensus_fill == "ref" ? 1u : 0u;
     }
     resolve_params(a, run);
     if (run.interleaved && (run.read_offset & 1)) refuse("'--interleaved' needs an even '--read-offset': the reads are skipped pair by pair");

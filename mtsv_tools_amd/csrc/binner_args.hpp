@@ -18,6 +18,8 @@ struct Args {
     std::string coverage, coverage_slack;                 // --coverage, --coverage-slack: "" when not given
     std::string alignments;                               // --alignments: "" when not given
     std::string variants, variant_taxa, variant_slack, min_depth, min_alt_reads, min_alt_frac;  // --variants and its sub-flags: "" when not given
+    // --consensus and its sub-flags: "" when not given
+    std::string consensus, consensus_stats, consensus_min_depth, consensus_min_frac, consensus_min_breadth, consensus_fill, consensus_width;
     uint64_t fold_reads = 16ull << 20;  // --fold-reads: reads per super-batch of --fold-on-gpu (every chunk is loaded once per super-batch)
     std::vector<int> devices{0};
     uint64_t batch_reads = 1u << 17;  // parser blocks of ~40 MB; the GPU workers take up to 1 Mi reads of them per library call. End to end on 32 M reads: 64 Ki .., 128 Ki 70 M reads/s, 256 Ki 54, 512 Ki 37
@@ -55,9 +57,12 @@ struct Run {
     uint32_t coverage_slack = 0;           // --coverage-slack: 0xffffffff for `all`
     std::string alignments;                // --alignments: "" : not asked for
     std::string variants;                  // --variants: "" : not asked for
-    std::vector<uint32_t> variant_taxa;    // --variant-taxa: empty: every reference
-    uint32_t variant_slack = 0;            // --variant-slack: 0xffffffff for `all`
+    std::vector<uint32_t> variant_taxa;    // --variant-taxa: empty: every reference (of the run's one pileup: --variants, --consensus)
+    uint32_t variant_slack = 0;            // --variant-slack: 0xffffffff for `all` (the same)
     uint32_t min_depth = 1, min_alt_reads = 1, min_alt_ppm = 0;  // --min-depth, --min-alt-reads, --min-alt-frac as parts per million
+    std::string consensus, consensus_stats;  // --consensus, --consensus-stats: "" : not asked for
+    uint32_t cons_min_depth = 1, cons_min_frac_ppm = 500000, cons_min_breadth_ppm = 0;  // --consensus-min-depth, -min-frac, -min-breadth
+    uint32_t cons_fill = 0, cons_width = 60;                                            // --consensus-fill (0: n, 1: ref), --consensus-width
     uint64_t batch_reads = 0, fold_reads = 0;
 
     bool have_results() const { return !results.empty(); }
@@ -65,6 +70,8 @@ struct Run {
     bool have_coverage() const { return !coverage.empty(); }
     bool have_alignments() const { return !alignments.empty(); }
     bool have_variants() const { return !variants.empty(); }
+    bool have_consensus() const { return !consensus.empty(); }
+    bool have_pileup() const { return have_variants() || have_consensus(); }  // one pileup per run, shared by the two
     bool merged() const { return mode == Mode::merged; }
     bool folded() const { return mode == Mode::folded; }
     bool chunked() const { return index_paths.size() > 1; }

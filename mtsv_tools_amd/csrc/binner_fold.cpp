@@ -30,6 +30,8 @@
 // --variants: one mtsv_pileup for the whole run.  After every run of a chunk over a piece, next to the placement of --alignments,
 // the hits the run left on the device are piled (mtsv_pileup_add_run with no hits given: placed again, nothing comes to the
 // host); a read's best edit is therefore its best in that chunk.  finish() asks for the sites once and writes them.
+// --consensus: the same pileup -- one per run, made for either flag and shared by both -- called once by finish(), after the
+// sites, which leave it as it was.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -127,8 +129,9 @@ class FoldedRun {
     int align_fd_ = -1;                  // --alignments
     uint64_t alignments_ = 0;
     float place_device_ms_ = 0;
-    PileupPtr pileup_;                   // --variants
-    uint64_t piled_ = 0, pile_skipped_ = 0, variant_sites_ = 0;
+    PileupPtr pileup_;                   // --variants, --consensus
+    uint64_t piled_ = 0, pile_skipped_ = 0, variant_sites_ = 0, consensus_refs_ = 0, consensus_bytes_ = 0;
+    float consensus_device_ms_ = 0;
     float pile_device_ms_ = 0, sites_device_ms_ = 0;
     TaxaSum taxa_;
     uint64_t dedup_reads_ = 0, dedup_distinct_ = 0;
@@ -463,6 +466,10 @@ void FoldedRun::print_timing() const {
     if (run_.have_variants())
         fprintf(stderr, "[cli variants timing] hits piled %llu, skipped %llu, sites %llu; place and pile device %.3f ms, sites device %.3f ms\n",
                 (unsigned long long)piled_, (unsigned long long)pile_skipped_, (unsigned long long)variant_sites_, pile_device_ms_, sites_device_ms_);
+    if (run_.have_consensus())
+        fprintf(stderr, "[cli consensus timing] hits piled %llu, skipped %llu, references %llu, bytes %llu; place and pile device %.3f ms, consensus device %.3f ms\n",
+                (unsigned long long)piled_, (unsigned long long)pile_skipped_, (unsigned long long)consensus_refs_, (unsigned long long)consensus_bytes_,
+                pile_device_ms_, consensus_device_ms_);
 }
 
 // every way out of the folded run ends alike: the process leaves at once, or (MTSV_CLI_CLEAN_EXIT=1) frees what it holds --
@@ -485,7 +492,7 @@ int FoldedRun::run() {
         code_.lib_error();
         return leave(code_.get());
     }
-    if (run_.have_variants() &&
+    if (run_.have_pileup() &&
         mtsv_pileup_create(dev_, run_.variant_taxa.empty() ? nullptr : run_.variant_taxa.data(), run_.variant_taxa.size(), out(pileup_)) != MTSV_OK) {
         code_.lib_error();
         return leave(code_.get());
@@ -528,6 +535,9 @@ int FoldedRun::run() {
     end.pileup = pileup_.get();
     end.variant_sites = &variant_sites_;
     end.variant_sites_ms = &sites_device_ms_;
+    end.consensus_refs = &consensus_refs_;
+    end.consensus_bytes = &consensus_bytes_;
+    end.consensus_ms = &consensus_device_ms_;
     if (const int c = finish(run_, out_, end)) return leave(c);
     print_timing();
     return leave(0);

@@ -112,6 +112,38 @@ int finish(const Run& run, Outputs& outputs, const RunEnd& end) {
         if (end.variant_sites_ms) *end.variant_sites_ms = ms;
         mark("variant sites written");
     }
+    if (run.have_consensus()) {  // the same accumulator, called once; the sites above have not changed it
+        ArrayPtr<mtsv_cons_ref> rows;
+        ArrayPtr<char> fasta, text;
+        uint64_t n_rows = 0, fasta_len = 0, text_len = 0;
+        float ms = 0;
+        int rc = end.pileup ? mtsv_pileup_consensus(end.pileup, run.cons_min_depth, run.cons_min_frac_ppm, run.cons_min_breadth_ppm, run.cons_fill, run.cons_width,
+                                                    out(fasta), &fasta_len, out(rows), &n_rows, &ms)
+                            : MTSV_E_ARG;
+        if (rc == MTSV_OK && !run.consensus_stats.empty()) rc = mtsv_format_consensus_stats(rows.get(), n_rows, out(text), &text_len);
+        if (rc != MTSV_OK) {
+            logmsg("ERROR", std::string("Error running query: ") + (end.pileup ? mtsv_last_error() : "no pileup was counted"));
+            return 2;
+        }
+        FILE* ff = fopen(run.consensus.c_str(), "wb");
+        bool written = ff && fwrite(fasta.get(), 1, fasta_len, ff) == fasta_len;
+        if ((ff && fclose(ff) != 0) || !written) {
+            logmsg("ERROR", "Error writing to consensus file");
+            return 11;
+        }
+        if (!run.consensus_stats.empty()) {
+            FILE* sf = fopen(run.consensus_stats.c_str(), "wb");
+            written = sf && fwrite(text.get(), 1, text_len, sf) == text_len;
+            if ((sf && fclose(sf) != 0) || !written) {
+                logmsg("ERROR", "Error writing to consensus statistics file");
+                return 11;
+            }
+        }
+        if (end.consensus_refs) *end.consensus_refs = n_rows;
+        if (end.consensus_bytes) *end.consensus_bytes = fasta_len;
+        if (end.consensus_ms) *end.consensus_ms = ms;
+        mark("consensus written");
+    }
     char msg[160];
     snprintf(msg, sizeof msg, "All worker and result consumer threads terminated. Took %.3f seconds.", now_s() - end.t_begin);
     logmsg("INFO", msg);

@@ -37,13 +37,16 @@ struct RunEnd {
     TaxaSum* taxa = nullptr;                  // --report: the counts ...
     std::function<bool(TaxaSum&)> gather;     // ... or what still has to be added to them (false: a library error)
     mtsv_coverage* coverage = nullptr;        // --coverage: the run's accumulator
-    mtsv_pileup* pileup = nullptr;            // --variants: the run's accumulator
+    mtsv_pileup* pileup = nullptr;            // --variants, --consensus: the run's one accumulator
     uint64_t* variant_sites = nullptr;        // ... where finish() leaves the number of sites it wrote, and the device time
     float* variant_sites_ms = nullptr;
+    uint64_t* consensus_refs = nullptr;       // --consensus: the references and bytes finish() wrote, and the device time
+    uint64_t* consensus_bytes = nullptr;
+    float* consensus_ms = nullptr;
     std::function<void(const char*)> mark;    // MTSV_CLI_TIMING: a phase has ended
 };
 // The end of a run whose reads are all through: closes the results file and the partition files, logs the "Partitioned"
-// line and the run's own, writes the taxa report, the coverage report and the variant sites, logs "Took ... seconds.".  0, or the exit code
+// line and the run's own, writes the taxa report, the coverage report, the variant sites and the consensus, logs "Took ... seconds.".  0, or the exit code
 // (logged).
 int finish(const Run& run, Outputs& outputs, const RunEnd& end);
 

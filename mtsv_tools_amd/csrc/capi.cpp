@@ -12,6 +12,7 @@
 #include "../../include/mtsv_amd.h"
 #include "abund_rows.hpp"
 #include "batch.hpp"
+#include "cons_rows.hpp"
 #include "cover.hpp"
 #include "dedup.hpp"
 #include "dev_index.hpp"
@@ -912,6 +913,48 @@ int mtsv_format_variants(const mtsv_pile_site* rows, uint64_t n_rows, char** out
         *out = q;
         *out_len = text.size();
     })
+}
+
+// ---- consensus from the pileup (cons.hip, k_cons.hip, cons_rows.hpp) ----
+int mtsv_pileup_consensus(mtsv_pileup* p, uint32_t min_depth, uint32_t min_frac_ppm, uint32_t min_breadth_ppm, uint32_t fill, uint32_t line_width, char** fasta,
+                          uint64_t* fasta_len, mtsv_cons_ref** rows, uint64_t* n_rows, float* device_ms) {
+    if (!p || (fasta && !fasta_len) || (rows && !n_rows)) return fail_arg("null argument");
+    GUARD({
+        std::vector<char> text;
+        std::vector<mtsv_cons_ref> r;
+        p->impl.consensus(min_depth, min_frac_ppm, min_breadth_ppm, fill, line_width, fasta ? &text : nullptr, r, device_ms);
+        char* tm = fasta ? malloc_copy(text) : nullptr;
+        if (rows) {
+            try {
+                *rows = malloc_copy(r);
+            } catch (...) {
+                free(tm);
+                throw;
+            }
+        }
+        if (n_rows) *n_rows = r.size();
+        if (fasta) {
+            *fasta = tm;
+            *fasta_len = text.size();
+        }
+    })
+}
+
+int mtsv_format_consensus_stats(const mtsv_cons_ref* rows, uint64_t n_rows, char** out, uint64_t* out_len) {
+    if ((!rows && n_rows) || !out || !out_len) return fail_arg("null argument");
+    GUARD({
+        const std::string text = format_consensus_stats(rows, n_rows);
+        char* q = (char*)malloc(text.size() + 1);
+        if (!q) throw std::bad_alloc();
+        memcpy(q, text.c_str(), text.size() + 1);
+        *out = q;
+        *out_len = text.size();
+    })
+}
+
+int mtsv_pileup_add_counts(mtsv_pileup* p, uint32_t tax_id, uint32_t gi, uint32_t first_slot, uint64_t n_slots, const uint32_t* counts, uint64_t n_hits) {
+    if (!p || (n_slots && !counts)) return fail_arg("null argument");
+    GUARD(p->impl.add_counts(tax_id, gi, first_slot, n_slots, counts, n_hits))
 }
 
 int mtsv_format_clade_report(const mtsv_clade_stats* rows, uint64_t n_rows, uint64_t total_reads, const mtsv_taxonomy* tx, char** out,

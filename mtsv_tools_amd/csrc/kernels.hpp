@@ -624,5 +624,27 @@ void launch_pile_sites_rows(hipStream_t s, const uint32_t* cnt, uint32_t n_slots
                             uint32_t min_alt_ppm, const uint32_t* tile_off, const uint32_t* ref_off, const uint64_t* ref_key, uint32_t n_refs, const uint8_t* ref,
                             void* rows, uint64_t n_rows);
 void launch_pile_dump(hipStream_t s, const uint32_t* cnt, uint32_t n_slots, uint32_t tile, const uint32_t* tile_pre, uint32_t lo, uint32_t hi, uint32_t* dump);
+// k_cons.hip: the consensus of a pileup segment, as the head of k_cons.hip defines it; cnt, tile, tile_pre, ref_off, ref_key
+// and ref are k_pile.hip's.  md = max(min_depth, 1).
+//   call:    cells[n_refs][kConsCell] (zeroed by the caller) += covered, n_ref, n_sub, n_del, n_low, n_ambig, ins_sites, -, and
+//            sum_depth as a u64 at [8]; with call != null also call[n_slots] = the character a slot emits or 0, tile_cnt[t] = the
+//            characters of tile t, ref_pre[r] = the characters of its tile in front of reference r's first slot
+//   (launch_scan over tile_cnt: tile_off[0 .. tiles])
+//   layout:  lay[n_refs][kConsLay] = text_off (u64), header bytes, cons_len, characters in front of the reference, emitted,
+//            bytes (u64); total[0] = the text's bytes, total[1] = the emitted references.  One workgroup.
+//   write:   the headers and the characters of the emitted references into text[0 .. text_bytes), which begins on a 4-byte
+//            boundary; staged: tiles inside one reference put their bytes together in LDS and store whole dwords
+//   add:     counts[n][8], plain, added to the n slots from `first` of a reference of `slots` slots whose counters begin at cnt;
+//            first + n <= slots, and channel 0 of slot `slots - 1` is zero when it is among them
+constexpr uint32_t kConsCell = 10, kConsLay = 8;
+constexpr bool kConsStagedDefault = true;   // which write pass a consensus takes unless MTSV_CONS_WRITE says so: profiles/README.md
+void launch_cons_call(hipStream_t s, const uint32_t* cnt, uint32_t n_slots, uint32_t tile, const uint32_t* tile_pre, const uint32_t* ref_off, uint32_t n_refs,
+                      const uint8_t* ref, uint32_t md, uint32_t min_frac_ppm, uint32_t fill, uint8_t* call, uint32_t* tile_cnt, uint32_t* ref_pre,
+                      uint32_t* cells);
+void launch_cons_layout(hipStream_t s, const uint32_t* cells, const uint32_t* ref_off, const uint64_t* ref_key, uint32_t n_refs, const uint32_t* ref_pre,
+                        const uint32_t* tile_off, uint32_t tile, uint32_t min_breadth_ppm, uint32_t line_width, uint32_t* lay, uint64_t* total);
+void launch_cons_write(hipStream_t s, const uint8_t* call, uint32_t n_slots, uint32_t tile, const uint32_t* tile_off, const uint32_t* ref_off,
+                       const uint64_t* ref_key, uint32_t n_refs, const uint32_t* lay, uint32_t line_width, uint8_t* text, uint64_t text_bytes, bool staged);
+void launch_cons_add(hipStream_t s, uint32_t* cnt, uint32_t slots, uint32_t first, uint64_t n, const uint32_t* counts);
 
 }  // namespace mtsv

@@ -35,6 +35,7 @@ Pileup::Pileup(int device_, const uint32_t* taxa, uint64_t n_taxa) : device(devi
     require_device(device);
     refs.set_taxa(taxa, n_taxa);
     tile = tile_from_env("MTSV_PILE_TILE", kPileTile, 64, kPileTileMax);
+    if (const char* e = getenv("MTSV_CONS_WRITE")) cons_staged = std::string(e) == "staged" ? true : std::string(e) == "plain" ? false : cons_staged;
     trace = getenv("MTSV_TRACE") != nullptr;
     timing = getenv("MTSV_PILE_TIMING") != nullptr;
     HIP_CHECK(hipSetDevice(device));

@@ -31,7 +31,8 @@ struct Pileup {
     DevStream stream;
     bool trace = false, timing = false;
     uint32_t tile = kPileTile;  // MTSV_PILE_TILE, read at creation (tests)
-    DevEvents<6> ev;
+    bool cons_staged = kConsStagedDefault;  // MTSV_CONS_WRITE=plain|staged, read at creation (tests, tools/cons_ab.py)
+    DevEvents<10> ev;
     PileRefs refs;
     std::vector<std::unique_ptr<Segment>> segs;
     uint64_t hits_piled = 0, hits_skipped = 0;
@@ -42,6 +43,9 @@ struct Pileup {
     DevBuf<uint64_t> d_ctr, d_sums;
     DevBuf<uint32_t> d_tile_sum, d_tile_pre, d_tile_cnt, d_tile_off, d_dump;
     DevBuf<uint8_t> d_rows;
+    // of a consensus call (cons.hip)
+    DevBuf<uint8_t> d_call, d_text;
+    DevBuf<uint32_t> d_cells, d_ref_pre, d_lay, d_add;
 
     Pileup(int device, const uint32_t* taxa, uint64_t n_taxa);
     ~Pileup();
@@ -53,6 +57,10 @@ struct Pileup {
     void info(mtsv_pileup_info_t* out) const;
     void download(uint32_t tax_id, uint32_t gi, std::vector<uint32_t>& counts, std::vector<uint8_t>& ref);
     void sites(uint32_t min_depth, uint32_t min_alt, uint32_t min_alt_ppm, std::vector<mtsv_pile_site>& rows, float* device_ms);
+    // cons.hip.  fasta == nullptr: rows only, no layout and no write kernel
+    void consensus(uint32_t min_depth, uint32_t min_frac_ppm, uint32_t min_breadth_ppm, uint32_t fill, uint32_t line_width, std::vector<char>* fasta,
+                   std::vector<mtsv_cons_ref>& rows, float* device_ms);
+    void add_counts(uint32_t tax_id, uint32_t gi, uint32_t first_slot, uint64_t n_slots, const uint32_t* counts, uint64_t n_hits);
 
    private:
     std::unique_ptr<Segment> make_segment(Batch& b, const PileRefs::Plan& plan);
